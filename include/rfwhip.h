@@ -280,6 +280,44 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                  (a quarter of the terrain's groups).  "0": every record is read.  Never changes the image
  *   shadow_side  = "1" (default): that wave runs on the sub-batch's connection stream, beside the extension wave of depth 1;
  *                  "0": on the sub-batch's own stream, in front of it (per-stage timings)
+ *   denoise      = "0" (default) | "1": the presented FULL image is denoised (the reference's OptiX 6 DENOISE setting,
+ *                  OptiX6Context/src/OptiXContext.cpp:812-822, as a native filter) — rfwhip_read_framebuffer / _device of a world-1
+ *                  context, the group's image after every gather (rfwhip_group_gather / read_framebuffer / framebuffer_device /
+ *                  present_async: on the root's device and stream), the root's image after rfwhip_comm_gather (the ROOT's setting
+ *                  decides).  Strip-local reads (rfwhip_read_local_framebuffer_*, rfwhip_deinterleave_*) are never denoised.  Only
+ *                  output is filtered: the accumulator keeps the raw samples (CONVERGE goes on accumulating them) and "0" gives the
+ *                  raw image back bit for bit.  Buffers of the full image, allocated when the setting is first turned on and freed
+ *                  by rfwhip_cleanup / rfwhip_init: guides 2 x 16 B, irradiance 2 x 16 B, variance 2 x 4 B per pixel (1080p: 149 MB).
+ *                  The algorithm, term by term (csrc/denoise.h, DESIGN.md "Denoiser"):
+ *                  GUIDES: one ray per pixel from the pixel centre and the lens centre, the path tracer's closest-hit traversal; at
+ *                  the hit the shade kernel's surface, material colour and texture layers: albedo = material colour after textures,
+ *                  normal = shading normal after normal maps, flipped to face the camera (octahedral, 2 x snorm16), z = distance
+ *                  along the ray, grad z = central differences of z in x and y (one-sided at borders / next to invalid pixels).
+ *                  A pixel is INVALID when its ray misses, meets an emitter (a colour component > 1) or passes more than 8
+ *                  alpha-tested layers (pass-through as in the path tracer: on from I + 1e-5 D).  The guides are recomputed only
+ *                  when the camera of the last render (by value), the scene (any rfwhip_update) or the target size changed.
+ *                  Reads with "1": before the first rfwhip_render (since init) the empty image is returned unfiltered; when the
+ *                  guides are stale AND the scene has changed since the last rfwhip_update (set_* calls not yet committed), the
+ *                  read fails with RFWHIP_ERR_STATE, as a render would — current guides are used while such calls are pending.  A
+ *                  traversal-stack overflow of the guide pass fails rfwhip_read_framebuffer* / rfwhip_read_denoise_guides (its own
+ *                  counter: the render's statistics are not touched).
+ *                  FILTER (SVGF's spatial filter, Schied et al. HPG 2017, without the temporal part), valid pixels p:
+ *                    a_p = max(albedo_p, 1e-3) per channel, I_p = c_p / a_p, l = 0.2126 r + 0.7152 g + 0.0722 b of I;
+ *                    var_p = sum_q w_q (l_q - m)^2 / sum_q w_q, m = sum_q w_q l_q / sum_q w_q over the valid q of the 3 x 3
+ *                      neighbourhood, w_q = w_z(s = 1) w_n;
+ *                    pass i = 0 .. iterations - 1, s = 2^i, taps q = p + s (dx, dy), dx, dy in -2..2, valid and inside the image:
+ *                      w = h(dx) h(dy) w_z w_n w_l, h = (1, 4, 6, 4, 1) / 16,
+ *                      w_z = exp(-|z_p - z_q| / (sigma_depth |s (dx grad_x z_p + dy grad_y z_p)| + 1e-4)),
+ *                      w_n = max(0, n_p . n_q)^sigma_normal,
+ *                      w_l = exp(-|l_p - l_q| / (sigma_luminance sqrt(g_p) + 1e-10)), g_p = sum k(dx) k(dy) var_q / sum k(dx) k(dy)
+ *                        over the valid q of the 3 x 3 neighbourhood (step 1), k = (1, 2, 1) / 4;
+ *                      I'_p = sum w I_q / sum w, var'_p = sum w^2 var_q / (sum w)^2, l'_p = lum(I'_p);
+ *                    last pass: out_p = I'_p a_p, out_p.w = c_p.w.  Invalid pixels: out = c bit for bit, never a neighbour.
+ *                  Fixed tap order, no atomics, no communication between workgroups: the output depends on the image and the guides
+ *                  only — the same whichever rank, group or context produced the image
+ *   denoise_iterations = a-trous passes, 1..8 (default 5)
+ *   denoise_sigma_luminance / denoise_sigma_normal / denoise_sigma_depth = the filter's edge-stopping parameters (SVGF's defaults:
+ *                  4 / 128 / 1)
  *   rfwhip_get_setting also answers read-only keys: "textured" (the textured shade kernel variant is in use), "packet" (the
  *   pt primary wave can run in packet form), "world_tree" (triangles in the world tree of the last update; 0: none),
  *   "shadow_bins_per_run", "shadow_packets_on".
@@ -307,8 +345,17 @@ typedef struct rfwhip_counters
 RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, int reset);
 
 /* Accumulated hipEvent time (ms) and launch count per kernel family since the last reset; requires
- * stage_timing=1.  which: 0 generate, 1 extend, 2 shade, 3 connect, 4 finalize, 5 refit. */
+ * stage_timing=1.  which: 0 generate, 1 extend, 2 shade, 3 connect, 4 finalize, 5 refit, 6 denoise (a guide pass is two launches,
+ * guide rays + depth gradient; a filter is 1 + denoise_iterations launches: demodulation / variance, then the a-trous passes). */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
+
+/* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are
+ * stale.  albedo: W x H x 4 floats (rgb, w = 1 valid / 0 invalid); normal_depth: W x H x 4 floats (the unpacked normal, z; z = -1 for
+ * an invalid pixel).  Either pointer may be NULL.  World-1 contexts and the root of a group. */
+RFWHIP_API int rfwhip_read_denoise_guides(rfwhip_context *ctx, float *albedo, float *normal_depth);
+/* Filter a given W x H float4 image (host memory) with the current guides and the context's denoise_* knobs, whatever "denoise"
+ * says (the guide pass runs first if they are stale).  rgba_out may equal rgba_in. */
+RFWHIP_API int rfwhip_denoise_image(rfwhip_context *ctx, const float *rgba_in, float *rgba_out);
 
 /* Raw closest-hit records of the most recent primary wave (parity tests): per pixel of this rank's local image
  * t (1e34 = miss), primID, instID, u, v. Any pointer may be NULL. */

@@ -81,6 +81,8 @@ class CoreBinding:
                                   "read_local_framebuffer_device": (i32, [vp, vp]),
                                   "deinterleave_device": (i32, [vp, vp, vp]),
                                   "kat": (i32, [vp, i32, sz, vp, vp]),
+                                  "read_denoise_guides": (i32, [vp, vp, vp]),
+                                  "denoise_image": (i32, [vp, vp, vp]),
                                   "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32])}.items():
             if self._has(name):
                 f = self._fn(name)
@@ -291,6 +293,21 @@ class CoreBinding:
                                             prim.ctypes.data, inst.ctypes.data, u.ctypes.data, v.ctypes.data))
         return {"t": t, "prim": prim, "inst": inst, "u": u, "v": v}
 
+    def read_denoise_guides(self):
+        """The denoiser's guides of the full image for the camera of the last render (include/rfwhip.h, "denoise"):
+        {"albedo": H x W x 3, "valid": H x W bool, "normal": H x W x 3, "z": H x W (-1 where invalid)}."""
+        shp = (self.height, self.width, 4)
+        a, nd = np.empty(shp, np.float32), np.empty(shp, np.float32)
+        self._check(self._fn("read_denoise_guides")(self._ctx, a.ctypes.data, nd.ctypes.data))
+        return {"albedo": a[..., :3], "valid": a[..., 3] > 0.5, "normal": nd[..., :3], "z": nd[..., 3]}
+
+    def denoise_image(self, rgba):
+        """Filter an H x W x 4 float32 image with the current guides and the context's denoise_* settings."""
+        src = np.ascontiguousarray(rgba, dtype=np.float32).reshape(self.height, self.width, 4)
+        out = np.empty_like(src)
+        self._check(self._fn("denoise_image")(self._ctx, src.ctypes.data, out.ctypes.data))
+        return out
+
     # known-answer hook: RFWHIP_KAT_* (include/rfwhip_abi.h)
     KAT = {"bsdf_eval": 0, "bsdf_pdf": 1, "bsdf_sample": 2, "tangent_space": 3, "pack_normal": 4,
            "random_barycentrics": 5, "point_on_light": 6, "light_pick_prob": 7, "blue_noise": 8, "hash": 9, "half_to_float": 10, "fastdiv": 11, "tex_wrap": 12}
@@ -412,6 +429,10 @@ class RenderGroup:
 
     def get_stats(self):
         return [c.get_stats() for c in self.contexts]
+
+    def read_denoise_guides(self):
+        """The denoiser's guides: the root's (rank 0 computes them for the whole image)."""
+        return self.contexts[0].read_denoise_guides()
 
     def destroy(self):
         if self._g:

@@ -40,10 +40,11 @@ class RenderContext(CoreBinding):
 
     # ---- measurement hooks -------------------------------------------------------------------------------------------
     KERNELS = ("generate", "extend", "shade", "connect", "finalize", "refit")
+    DENOISE = 6  # kernel family of the denoiser (guide pass + filter), outside KERNELS: the render's stages
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 

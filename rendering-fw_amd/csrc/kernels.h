@@ -33,6 +33,19 @@ enum GenMode
 
 typedef void *stream_t; // hipStream_t
 
+// The denoiser's buffers and knobs (denoise.h): full image, W x H pixels, row-major
+struct DnView
+{
+	uint32_t W, H;
+	rt::f4 *ga, *gb;	  // guides: albedo | valid, octahedral normal | z | dz/dx | dz/dy
+	rt::f4 *in, *out;	  // the image to filter and where the result goes (may be the same buffer)
+	rt::f4 *img[2];		  // ping-pong demodulated irradiance (rgb, luminance)
+	float *var[2];		  // ping-pong variance of the luminance
+	float sigma_l, sigma_n, sigma_z;
+	uint32_t iterations;  // 1..8 passes, step 2^i
+	uint32_t *overflow;	  // the guide pass's own traversal-stack overflow counter (not the render's wave counters)
+};
+
 // capacity of the LDS top-of-tree cache the kernels were built with
 uint32_t max_lds_nodes();
 
@@ -60,6 +73,12 @@ void launch_resolve(const Params &p, stream_t s);
 void launch_kat(const Params &p, int function, const float *in, float *out, uint32_t n, stream_t s);
 // out: local layout (local_rows x W) when full == 0, else full image (H x W; world must be 1)
 void launch_present(const Params &p, rt::f4 *out, float scale, int full, stream_t s);
+// the denoiser's guide pass (p: scene, camera and FrameView of the full image) = guide kernel + depth-gradient kernel
+void launch_denoise_guides(const Params &p, const DnView &d, stream_t s);
+// demodulation + variance, d.iterations a-trous passes, remodulation into d.out: 1 + d.iterations launches
+void launch_denoise_filter(const DnView &d, stream_t s);
+// a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
+rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,
 						 uint32_t world, stream_t s);
 // bottom-up refit of one BLAS after its vertices changed: leaf_order[i] = original primitive of leaf slot i

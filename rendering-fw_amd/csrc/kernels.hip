@@ -890,6 +890,10 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 		mn[a] -= 2e-5f, mx[a] += 2e-5f;
 }
 
+// the denoiser of the presented image: guide pass + a-trous filter (work items shared with the emulation)
+#include "denoise.h"
+rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }
+
 // ================================================================================================================
 #if defined(RT_DEVICE_BUILD)
 // ================================================================================================================
@@ -2429,6 +2433,48 @@ void launch_deinterleave(const f4 *gathered, f4 *out, uint32_t W, uint32_t H, ui
 {
 	hipLaunchKernelGGL(k_deinterleave, dim3(persistent_grid(W * H, RT_GRID_BLOCKS_PER_CU, 8u)), dim3(BLOCK), 0, (hipStream_t)s, gathered, out, W, H,
 					   local_rows, world);
+}
+
+// ---- denoiser (denoise.h): one 8x8 tile per wave64, 2x2 tiles per 256-thread workgroup ------------------------------------------
+static_assert(BLOCK == 256 && DN_TILE_X == 2 * TILE && DN_TILE_Y == 2 * TILE, "denoiser workgroup = 2 x 2 tiles of 8 x 8");
+__global__ void __launch_bounds__(BLOCK) k_dn_guides(const Params p, const DnView d)
+{
+	RT_STACK_DECL_CLOSEST
+	ctx.stk.overflow = d.overflow; // (the pass may run on a gather stream beside the next frame: not the render's counters)
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_guide_item(p, d, i, ctx.stk);
+}
+__global__ void __launch_bounds__(BLOCK) k_dn_gradient(const DnView d)
+{
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_gradient_item(d, i);
+}
+__global__ void __launch_bounds__(BLOCK) k_dn_demod(const DnView d)
+{
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_demod_item(d, d.img[0], d.var[0], i);
+}
+__global__ void __launch_bounds__(BLOCK) k_dn_pass(const DnView d, uint32_t pass)
+{
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_pass_item(d, 1u << pass, pass + 1u == d.iterations, d.img[pass & 1u], d.var[pass & 1u], d.img[(pass + 1u) & 1u],
+					 d.var[(pass + 1u) & 1u], i);
+}
+static dim3 dn_grid(const DnView &d) { return dim3((d.W + DN_TILE_X - 1) / DN_TILE_X, (d.H + DN_TILE_Y - 1) / DN_TILE_Y); }
+void launch_denoise_guides(const Params &p, const DnView &d, stream_t s)
+{
+	hipLaunchKernelGGL(k_dn_guides, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d);
+	hipLaunchKernelGGL(k_dn_gradient, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
+}
+void launch_denoise_filter(const DnView &d, stream_t s)
+{
+	hipLaunchKernelGGL(k_dn_demod, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
+	for (uint32_t k = 0; k < d.iterations; k++)
+		hipLaunchKernelGGL(k_dn_pass, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d, k);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_skin_vertices(f4 *verts, f4 *vnormals, const f4 *base_verts, const f4 *base_normals,

@@ -357,6 +357,23 @@ void launch_deinterleave(const f4 *gathered, f4 *out, uint32_t W, uint32_t H, ui
 	for (uint32_t i = 0; i < W * H; i++)
 		deinterleave_item(gathered, out, W, H, local_rows, world, i);
 }
+void launch_denoise_guides(const Params &p, const DnView &d, stream_t)
+{
+	Ctx ctx(p);
+	ctx.stk.overflow = d.overflow;
+	for (uint32_t i = 0; i < d.W * d.H; i++)
+		dn_guide_item(p, d, i, ctx.stk);
+	for (uint32_t i = 0; i < d.W * d.H; i++)
+		dn_gradient_item(d, i);
+}
+void launch_denoise_filter(const DnView &d, stream_t)
+{
+	for (uint32_t i = 0; i < d.W * d.H; i++)
+		dn_demod_item(d, d.img[0], d.var[0], i);
+	for (uint32_t k = 0; k < d.iterations; k++)
+		for (uint32_t i = 0; i < d.W * d.H; i++)
+			dn_pass_item(d, 1u << k, k + 1u == d.iterations, d.img[k & 1u], d.var[k & 1u], d.img[(k + 1u) & 1u], d.var[(k + 1u) & 1u], i);
+}
 void launch_kat(const Params &p, int function, const float *in, float *out, uint32_t n, stream_t)
 {
 	float pot[POT_SLOTS];

@@ -373,7 +373,8 @@ enum KernelFamily
 	KF_CONNECT = 3,
 	KF_FINALIZE = 4,
 	KF_REFIT = 5,
-	KF_COUNT = 6
+	KF_DENOISE = 6, // the denoiser of the presented image: guide pass + filter (denoise.h)
+	KF_COUNT = 7
 };
 
 struct TimedSpan
@@ -457,6 +458,18 @@ struct rfwhip_context
 	uint32_t sgroup_last = 0; // log2 of the group the most recent render call used
 	int fuse = 1;	  // extension rays of depth d + 1 and shadow rays of depth d in one launch (kernels.hip: k_trace_fused)
 	int overlap = -1; // connection waves beside the next depth's stages on a second stream: 0 off, 1 on, -1 by launch size
+	// denoiser of the presented image (denoise.h): knobs, buffers of the full image, the guides' cache key
+	int denoise = 0;
+	int dn_iterations = 5;
+	float dn_sigma_l = 4.0f, dn_sigma_n = 128.0f, dn_sigma_z = 1.0f;
+	DevBuf d_dn_guides, d_dn_img, d_dn_var; // 2 x 16 B, 2 x 16 B, 2 x 4 B per pixel
+	bool guides_valid = false;				 // the guides were computed for guide_cam / guide_scene / guide_W x guide_H
+	rfwhip_camera guide_cam, last_cam;		 // ... and the camera of the most recent rfwhip_render
+	bool have_last_cam = false;
+	unsigned long long scene_version = 0, guide_scene = 0; // scene_version: rfwhip_update calls
+	uint32_t guide_W = 0, guide_H = 0;
+	dm::event_t ev_dn;	  // behind the last denoise enqueued on a caller's stream (the group / comm gather)
+	bool dn_pending = false;
 
 	// scene (host side)
 	std::vector<MeshRec> meshes;
@@ -499,8 +512,8 @@ struct rfwhip_context
 	std::vector<TimedSpan> spans;
 	std::vector<dm::event_t> event_pool;
 	size_t events_used = 0;
-	float kernel_ms[KF_COUNT] = {0, 0, 0, 0, 0, 0};
-	uint32_t kernel_launches[KF_COUNT] = {0, 0, 0, 0, 0, 0};
+	float kernel_ms[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+	uint32_t kernel_launches[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0};
 	rfwhip_render_stats stats;
 	std::chrono::steady_clock::time_point render_t0;
 	bool render_pending = false;
@@ -648,9 +661,10 @@ static void free_all(rfwhip_context *c)
 					  &c->d_thr[1], &c->d_hit, &c->d_hit_inst, &c->d_hit0, &c->d_hit0_inst, &c->d_hit0_done, &c->d_sh_org[0], &c->d_sh_org[1],
 					  &c->d_sh_dir[0], &c->d_sh_dir[1], &c->d_sh_rad[0], &c->d_sh_rad[1], &c->d_rad[0], &c->d_rad[1],
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
-					  &c->d_present};
+					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var};
 	for (DevBuf *b : bufs)
 		b->free_();
+	c->guides_valid = false;
 	for (auto &e : c->event_pool)
 		dm::event_destroy(e);
 	c->event_pool.clear();
@@ -661,14 +675,14 @@ static void free_all(rfwhip_context *c)
 		dm::event_destroy(c->ev_prologue);
 		for (int r = 0; r < rfwhip_context::MAX_RING; r++)
 			dm::event_destroy(c->ev_resolve[r]);
-		dm::event_destroy(c->ev_present_in), dm::event_destroy(c->ev_present_out);
+		dm::event_destroy(c->ev_present_in), dm::event_destroy(c->ev_present_out), dm::event_destroy(c->ev_dn);
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			dm::event_destroy(c->ev_sub_done[i]), dm::event_destroy(c->ev_conn_last[i]);
 			for (int d = 0; d < rt::MAX_DEPTH_SLOTS; d++)
 				dm::event_destroy(c->ev_shade[i][d]), dm::event_destroy(c->ev_conn[i][d]);
 		}
-		c->events_ready = false, c->present_pending = false;
+		c->events_ready = false, c->present_pending = false, c->dn_pending = false;
 	}
 	for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 	{
@@ -707,6 +721,8 @@ extern "C" void rfwhip_destroy(rfwhip_context *c)
 	delete c;
 }
 
+static int dn_ensure(rfwhip_context *c);
+
 #define CTX_ENTER(c)                                                                      \
 	if (!(c))                                                                             \
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null context");                    \
@@ -721,6 +737,10 @@ extern "C" int rfwhip_init(rfwhip_context *c, uint32_t width, uint32_t height)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_init: bad target size %ux%u", width, height);
 	RF_TRY(sync_all(c));
 	c->W = width, c->H = height;
+	c->d_dn_guides.free_(), c->d_dn_img.free_(), c->d_dn_var.free_(); // (re-allocated at the new size while denoise is on)
+	c->guides_valid = false;
+	if (c->denoise && c->rank == 0)
+		RF_TRY(dn_ensure(c));
 	const uint32_t lr = local_rows_of(c);
 	RF_TRY(c->d_acc.ensure((size_t)lr * width * sizeof(f4)));
 	RF_TRY(dm::zero(c->d_acc.p, (size_t)lr * width * sizeof(f4), c->stream));
@@ -1774,6 +1794,7 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 	sv.n_area = c->lc.areaLightCount, sv.n_point = c->lc.pointLightCount, sv.n_spot = c->lc.spotLightCount;
 	sv.n_dir = c->lc.directionalLightCount;
 	c->scene_dirty = false;
+	c->scene_version++; // (the denoiser's guides are recomputed)
 	c->depth_stats_valid = false;
 	c->shadow_packets_auto_on = true; // (another scene: the packet form of the depth-0 connection wave gets its chance again)
 	return RFWHIP_OK;
@@ -1968,6 +1989,11 @@ static int sync_all(rfwhip_context *c)
 		RF_TRY(dm::event_sync(c->ev_present_out));
 		c->present_pending = false;
 	}
+	if (c->dn_pending) // (a denoise on a gather stream reads the scene and the guides)
+	{
+		RF_TRY(dm::event_sync(c->ev_dn));
+		c->dn_pending = false;
+	}
 	return 0;
 }
 
@@ -1980,6 +2006,7 @@ static int ensure_sub_batches(rfwhip_context *c, int subs)
 			RF_TRY(dm::event_create(&c->ev_resolve[r]));
 		RF_TRY(dm::event_create(&c->ev_present_in));
 		RF_TRY(dm::event_create(&c->ev_present_out));
+		RF_TRY(dm::event_create(&c->ev_dn));
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			RF_TRY(dm::event_create(&c->ev_sub_done[i]));
@@ -2363,6 +2390,7 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	c->last_wave_off = alternate ? (paths + pad) * par : 0;
 	c->samples_done += (uint32_t)c->spp;
 	c->totals.samples += (uint64_t)c->W * c->H * (uint64_t)c->spp / (uint64_t)c->world;
+	c->last_cam = *cam, c->have_last_cam = true; // (the denoiser's guide pass traces this camera's centre rays)
 	return RFWHIP_OK;
 }
 
@@ -2376,6 +2404,11 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 	{
 		RF_TRY(dm::event_sync(c->ev_present_out));
 		c->present_pending = false;
+	}
+	if (c->dn_pending && c->stage_timing) // (the denoiser's timed spans on a gather stream are read below)
+	{
+		RF_TRY(dm::event_sync(c->ev_dn));
+		c->dn_pending = false;
 	}
 	// wave counters of the last frame, summed over its sub-batches.  A sub-batch's connection wave of depth d ran only
 	// if its depth d + 1 had extension rays (k_connect / k_trace_stream: connection_count)
@@ -2523,6 +2556,89 @@ static int present(rfwhip_context *c, f4 *dst_device, int full)
 	return 0;
 }
 
+// ---- denoiser of the presented image (setting "denoise"; work items: denoise.h) -------------------------------------------------
+static int dn_ensure(rfwhip_context *c)
+{
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(c->d_dn_guides.ensure_exact(2 * px * sizeof(f4) + sizeof(f4))); // (+ the guide pass's stack-overflow counter)
+	RF_TRY(c->d_dn_img.ensure_exact(2 * px * sizeof(f4)));
+	RF_TRY(c->d_dn_var.ensure_exact(2 * px * sizeof(float)));
+	return 0;
+}
+
+static rtk::DnView dn_view(rfwhip_context *c, f4 *in, f4 *out)
+{
+	rtk::DnView d;
+	const size_t px = (size_t)c->W * c->H;
+	d.W = c->W, d.H = c->H;
+	d.ga = c->d_dn_guides.as<f4>(), d.gb = d.ga + px;
+	d.in = in, d.out = out;
+	d.img[0] = c->d_dn_img.as<f4>(), d.img[1] = d.img[0] + px;
+	d.var[0] = c->d_dn_var.as<float>(), d.var[1] = d.var[0] + px;
+	d.sigma_l = c->dn_sigma_l, d.sigma_n = c->dn_sigma_n, d.sigma_z = c->dn_sigma_z;
+	d.iterations = (uint32_t)c->dn_iterations;
+	d.overflow = (uint32_t *)(d.gb + px);
+	return d;
+}
+
+// the guides of the full image for the camera of the last render, unless they are current (camera by value, scene, size)
+static int dn_guides(rfwhip_context *c, void *stream)
+{
+	if (!c->have_last_cam)
+		return set_error(RFWHIP_ERR_STATE, "denoise: no frame has been rendered (the guides need the camera of a render)");
+	RF_TRY(dn_ensure(c));
+	// (current guides belong to the scene of the last rfwhip_update — the one the image was rendered with — even while set_* calls
+	// since then wait for the next update)
+	if (c->guides_valid && c->guide_scene == c->scene_version && c->guide_W == c->W && c->guide_H == c->H &&
+		!memcmp(&c->guide_cam, &c->last_cam, sizeof(rfwhip_camera)))
+		return 0;
+	if (c->scene_dirty)
+		return set_error(RFWHIP_ERR_STATE, "denoise: the guides must be traced, but the scene changed since the last rfwhip_update()");
+	rtk::Params p;
+	fill_params(c, &c->last_cam, p);
+	const rtk::DnView d = dn_view(c, nullptr, nullptr);
+	RF_TRY(dm::zero(d.overflow, sizeof(uint32_t), stream));
+	StageTimer t(c, KF_DENOISE, -1, stream);
+	rtk::launch_denoise_guides(p, d, stream);
+	t.stop(2);
+	RF_TRY(dm::last_launch_error());
+	c->guides_valid = true, c->guide_cam = c->last_cam, c->guide_scene = c->scene_version, c->guide_W = c->W, c->guide_H = c->H;
+	return 0;
+}
+
+// the guide pass's traversal-stack overflow counter (synchronises the context's stream)
+static int dn_check_overflow(rfwhip_context *c)
+{
+	uint32_t n = 0;
+	RF_TRY(dm::d2h(&n, dn_view(c, nullptr, nullptr).overflow, sizeof(n), c->stream));
+	if (n)
+		return set_error(RFWHIP_ERR_STATE, "denoise: traversal stack overflow in the guide pass: %u entries dropped (the guides are wrong)", n);
+	return 0;
+}
+
+// filter the full image `in` (W x H float4 on this context's device) into `out` (may be `in`), enqueued on `stream`
+static int dn_filter(rfwhip_context *c, f4 *in, f4 *out, void *stream)
+{
+	RF_TRY(dn_guides(c, stream));
+	StageTimer t(c, KF_DENOISE, -1, stream);
+	rtk::launch_denoise_filter(dn_view(c, in, out), stream);
+	t.stop(1 + c->dn_iterations);
+	return dm::last_launch_error();
+}
+
+// the root's side of a group / comm gather (rfwhip_group.cpp): the full image on `hip_stream`, in place, when denoise is on
+int rfwhip_internal_denoise_stream(rfwhip_context *c, void *rgba_device, void *hip_stream)
+{
+	CTX_ENTER(c);
+	if (!c->denoise || !c->have_last_cam) // (nothing rendered yet: the accumulator is empty)
+		return RFWHIP_OK;
+	RF_TRY(ensure_sub_batches(c, 1)); // creates the hand-off events
+	RF_TRY(dn_filter(c, (f4 *)rgba_device, (f4 *)rgba_device, hip_stream));
+	RF_TRY(dm::event_record(c->ev_dn, hip_stream));
+	c->dn_pending = true;
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_read_framebuffer_device(rfwhip_context *c, void *rgba_device)
 {
 	CTX_ENTER(c);
@@ -2534,6 +2650,11 @@ extern "C" int rfwhip_read_framebuffer_device(rfwhip_context *c, void *rgba_devi
 	if (!c->W)
 		return set_error(RFWHIP_ERR_STATE, "no render target");
 	RF_TRY(present(c, (f4 *)rgba_device, 1));
+	if (c->denoise && c->have_last_cam) // (before the first render the accumulator is empty: nothing to filter, no camera to trace)
+	{
+		RF_TRY(dn_filter(c, (f4 *)rgba_device, (f4 *)rgba_device, c->stream));
+		RF_TRY(dn_check_overflow(c));
+	}
 	return dm::sync(c->stream);
 }
 
@@ -2654,7 +2775,7 @@ extern "C" int rfwhip_get_stats(rfwhip_context *c, rfwhip_render_stats *stats)
 	return RFWHIP_OK;
 }
 
-static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags"};
+static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth"};
 
 extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char *value)
 {
@@ -2781,6 +2902,29 @@ extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char
 			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "streams must be in [1, %d]", (int)rfwhip_context::MAX_SUB);
 		c->streams = n;
 	}
+	else if (k == "denoise")
+	{
+		if (v != "0" && v != "1")
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise must be \"0\" or \"1\"");
+		if (v == "1" && c->W && c->rank == 0) // (the root filters the gathered image; other ranks never do)
+			RF_TRY(dn_ensure(c)); // (buffers of the full image: allocated when the setting is first turned on)
+		c->denoise = v == "1";
+	}
+	else if (k == "denoise_iterations")
+	{
+		const int n = atoi(value);
+		if (n < 1 || n > 8)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_iterations must be in [1, 8]");
+		c->dn_iterations = n;
+	}
+	else if (k == "denoise_sigma_luminance" || k == "denoise_sigma_normal" || k == "denoise_sigma_depth")
+	{
+		char *end = nullptr;
+		const float f = strtof(value, &end);
+		if (!end || *end || !(f >= 0.0f) || !(f < 1e30f))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be a finite number >= 0", key);
+		(k == "denoise_sigma_luminance" ? c->dn_sigma_l : k == "denoise_sigma_normal" ? c->dn_sigma_n : c->dn_sigma_z) = f;
+	}
 	else
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "unknown setting \"%s\"", key);
 	return RFWHIP_OK;
@@ -2847,6 +2991,16 @@ extern "C" int rfwhip_get_setting(rfwhip_context *c, const char *key, char *valu
 		snprintf(value, cap, "%d", (c->packet_ok && (c->refill & 8)) ? 1 : 0);
 	else if (k == "world_tree") // triangles in the world tree of the last rfwhip_update (0: none)
 		snprintf(value, cap, "%zu", c->wtree.valid ? c->wtree.tris : (size_t)0);
+	else if (k == "denoise")
+		snprintf(value, cap, "%d", c->denoise);
+	else if (k == "denoise_iterations")
+		snprintf(value, cap, "%d", c->dn_iterations);
+	else if (k == "denoise_sigma_luminance")
+		snprintf(value, cap, "%g", c->dn_sigma_l);
+	else if (k == "denoise_sigma_normal")
+		snprintf(value, cap, "%g", c->dn_sigma_n);
+	else if (k == "denoise_sigma_depth")
+		snprintf(value, cap, "%g", c->dn_sigma_z);
 	else
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "unknown setting \"%s\"", key);
 	return RFWHIP_OK;
@@ -2914,6 +3068,53 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	if (reset)
 		c->kernel_ms[which] = 0.0f, c->kernel_launches[which] = 0;
 	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_denoise_guides(rfwhip_context *c, float *albedo, float *normal_depth)
+{
+	CTX_ENTER(c);
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	if (c->world != 1 && c->rank != 0)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_denoise_guides: the guides live on the root (rank 0)");
+	RF_TRY(sync_all(c));
+	RF_TRY(dn_guides(c, c->stream));
+	RF_TRY(dn_check_overflow(c));
+	const size_t px = (size_t)c->W * c->H;
+	std::vector<f4> g(2 * px);
+	RF_TRY(dm::d2h(g.data(), c->d_dn_guides.p, 2 * px * sizeof(f4), c->stream));
+	for (size_t i = 0; i < px; i++)
+	{
+		if (albedo)
+			for (int k = 0; k < 4; k++)
+				albedo[4 * i + k] = (&g[i].x)[k];
+		if (normal_depth)
+		{
+			uint32_t e;
+			memcpy(&e, &g[px + i].x, 4);
+			const rt::f3 n = rtk::dn_normal(e);
+			normal_depth[4 * i] = n.x, normal_depth[4 * i + 1] = n.y, normal_depth[4 * i + 2] = n.z, normal_depth[4 * i + 3] = g[px + i].y;
+		}
+	}
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_denoise_image(rfwhip_context *c, const float *rgba_in, float *rgba_out)
+{
+	CTX_ENTER(c);
+	if (!rgba_in || !rgba_out)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null image");
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	if (c->world != 1 && c->rank != 0)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_denoise_image: the guides live on the root (rank 0)");
+	RF_TRY(sync_all(c));
+	const size_t bytes = (size_t)c->W * c->H * sizeof(f4);
+	RF_TRY(c->d_present.ensure(bytes));
+	RF_TRY(dm::h2d(c->d_present.p, rgba_in, bytes, c->stream));
+	RF_TRY(dn_filter(c, c->d_present.as<f4>(), c->d_present.as<f4>(), c->stream));
+	RF_TRY(dm::d2h(rgba_out, c->d_present.p, bytes, c->stream));
+	return dm::sync(c->stream);
 }
 
 extern "C" int rfwhip_read_primary_hits(rfwhip_context *c, float *t, int32_t *prim, int32_t *inst, float *u, float *v)

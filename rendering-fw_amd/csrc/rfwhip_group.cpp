@@ -483,6 +483,10 @@ int gather(rfwhip_group *g, void *full_out)
 		}
 		else
 			GR_TRY(copy_async(full_out ? full_out : g->full, root->device, g->staging, root->device, (size_t)g->W * g->H * PIXEL_BYTES, root->stream));
+		// 4. the root's context denoises the full image when its "denoise" setting is on (the filter needs every strip's
+		//    neighbours: it runs once, here, on the root's device and stream; the guides come from the root's copy of the scene)
+		if (rfwhip_internal_denoise_stream(root->ctx, full_out ? full_out : g->full, root->stream))
+			return RFWHIP_ERR_STATE; // (the context's message stands)
 	}
 	return 0;
 }

@@ -415,6 +415,13 @@ RT_FN void pt_primary_ray(const CamView &cam, const FrameView &fr, uint32_t x, u
 	const float u = rounded(((float)x + r0) * fr.inv_w), v = rounded(((float)y + r1) * fr.inv_h); // (x (1.0f / (float)W): Kernels.cu:418-419)
 	D = normalize_r(madd2_r(cam.p1, cam.right, u, cam.up, v) - O);
 }
+// The centre form of the same ray (r0 = r1 = 0.5, lens centre): the denoiser's guide pass (denoise.h)
+RT_FN void pt_center_ray(const CamView &cam, const FrameView &fr, uint32_t x, uint32_t y, f3 &O, f3 &D)
+{
+	O = cam.pos;
+	const float u = rounded(((float)x + 0.5f) * fr.inv_w), v = rounded(((float)y + 0.5f) * fr.inv_h);
+	D = normalize_r(madd2_r(cam.p1, cam.right, u, cam.up, v) - O);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // traversal

@@ -1,0 +1,78 @@
+"""Time the denoiser (setting "denoise", csrc/denoise.h) on the 1920 x 1080 terrain (BASELINE config 3's scene), 1 spp per frame,
+with hipEvents (stage_timing=1, kernel family 6).  One JSON line per variant:
+  filter   a still camera: the guides are computed once, every present runs demodulation + the a-trous passes
+  guides   the camera moves a little every frame: every present runs the guide pass too
+  frame    wall time of a 1-spp frame (render + wait + present into device memory) with denoise off and on
+Usage: python tools/denoise_time.py [frames=200] [iterations=5]"""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402  (first: torch's HIP runtime before librfwhip.so)
+
+from __graft_entry__ import load_package  # noqa: E402
+
+W, H = 1920, 1080
+PIXELS = W * H
+# bytes a pass names per pixel: 25 taps x (irradiance 16 + variance 4 + guide 16) + 9 variance taps + centre albedo 16 + input 16,
+# written: irradiance 16 + variance 4 (the last pass: the image, 16).  Unique per pass: the five planes once.
+TAP_BYTES = 25 * 36 + 9 * 4 + 16 + 16 + 20
+UNIQUE_BYTES = 16 + 4 + 16 + 16 + 16 + 20
+
+
+def main():
+    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+    iterations = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    pkg = load_package()
+    scene = pkg.scenes.terrain(width=W, height_px=H)
+    ctx = pkg.RenderContext(device=0)
+    ctx.init(W, H)
+    scene.upload(ctx)
+    for k, v in dict(integrator="pt", spp=1, stage_timing=1, denoise=1, denoise_iterations=iterations).items():
+        ctx.set_setting(k, v)
+    out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda:0")
+    cam = scene.camera
+
+    def run(n, moving):
+        for f in range(n):
+            if moving:  # a camera that differs by value every frame: the guides are stale at every present
+                cam.clampValue = 10.0 + 1e-3 * (f % 2 + 1)
+            ctx.render_frame(cam, pkg.RESET if moving else pkg.CONVERGE)
+            ctx.read_framebuffer_device(out.data_ptr())
+        ctx.wait()  # (the last present's spans are resolved by the next wait)
+
+    results = {}
+    for variant, moving in (("filter", False), ("guides", True)):
+        run(10, moving)
+        ctx.get_kernel_time("denoise", reset=True)
+        run(frames, moving)
+        ms, launches = ctx.get_kernel_time("denoise", reset=True)
+        results[variant] = ms / frames
+        line = {"variant": variant, "frames": frames, "iterations": iterations, "launches": launches,
+                "denoise_ms_per_frame": round(ms / frames, 4)}
+        if variant == "filter":
+            line["ms_per_pass"] = round(ms / frames / (iterations + 1), 4)
+            line["bytes_per_pass_taps"] = PIXELS * TAP_BYTES
+            line["bytes_per_pass_unique"] = PIXELS * UNIQUE_BYTES
+            line["tap_GBps"] = round(PIXELS * TAP_BYTES / (ms / frames / (iterations + 1)) / 1e6, 1)
+        else:
+            line["guide_pass_ms"] = round(ms / frames - results["filter"], 4)
+        print(json.dumps(line), flush=True)
+    ctx.set_setting("stage_timing", 0)
+    for dn in (0, 1):
+        ctx.set_setting("denoise", dn)
+        run(10, False)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(frames, False)
+        torch.cuda.synchronize()
+        print(json.dumps({"variant": "frame", "denoise": dn, "frames": frames,
+                          "ms_per_frame": round((time.perf_counter() - t0) * 1e3 / frames, 4)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
