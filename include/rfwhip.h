@@ -377,6 +377,26 @@ RFWHIP_API int rfwhip_kat(rfwhip_context *ctx, int function, size_t n, const flo
 RFWHIP_API int rfwhip_get_bvh(rfwhip_context *ctx, size_t mesh_index, rfwhip_bvh_node *nodes, size_t node_cap,
 							  uint32_t *prim_indices, size_t prim_cap, size_t *node_count, size_t *prim_count);
 
+/* What rfwhip_get_bvh4 reports about a resident mesh's slice of the traversal tables (32 B). */
+typedef struct rfwhip_bvh4_info
+{
+	uint32_t n4_base, n4_count;	 /* its 4-wide nodes in the scene-wide table: [n4_base, n4_base + n4_count) */
+	uint32_t tri_base, tri_count; /* its leaf-ordered triangles: [tri_base, tri_base + tri_count) */
+	uint32_t node_base, node_count2; /* its BVH2 nodes (what src4 refers to, mesh-relative) */
+	int32_t stack_need;			  /* traversal-stack entries the mesh was admitted with (bvh::stack_need4) */
+	uint32_t device_built;		  /* 1: built by the device builder (builder=device), 0: by the host builder */
+} rfwhip_bvh4_info;
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_bvh4_info) == 32, "rfwhip_bvh4_info is 32 B");
+
+/* The TRAVERSED tree of mesh `index` as it sits on the device (a test hook like rfwhip_get_bvh, not part of the build path).
+ * Entries stay absolute.  nodes4c: n4_count compressed 4-wide nodes (64 B each, rt::Node4c), nodes4f: their float form
+ * (128 B each, rt::Node4f), src4: 4 x n4_count BVH2 node indices (mesh-relative, 0xFFFFFFFF = unused slot), tri_verts:
+ * 3 x tri_count float4 in leaf order (v0.w = primitive id bits, v1.w = 1, v2.w = determinant threshold).  At most node_cap
+ * nodes and tri_cap triangles are copied; any pointer may be NULL.  A mesh that is not resident (set again since the last
+ * rfwhip_update) fails with RFWHIP_ERR_STATE. */
+RFWHIP_API int rfwhip_get_bvh4(rfwhip_context *ctx, size_t mesh_index, void *nodes4c, void *nodes4f, uint32_t *src4,
+							   size_t node_cap, float *tri_verts, size_t tri_cap, rfwhip_bvh4_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,7 @@ class CoreBinding:
                                   "read_local_framebuffer_device": (i32, [vp, vp]),
                                   "deinterleave_device": (i32, [vp, vp, vp]),
                                   "kat": (i32, [vp, i32, sz, vp, vp]),
+                                  "get_bvh4": (i32, [vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(abi.Bvh4Info)]),
                                   "read_denoise_guides": (i32, [vp, vp, vp]),
                                   "denoise_image": (i32, [vp, vp, vp]),
                                   "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32])}.items():
@@ -333,6 +334,25 @@ class CoreBinding:
         self._check(self._fn("get_bvh")(self._ctx, int(mesh_index), nodes.ctypes.data, len(nodes), prims.ctypes.data,
                                         len(prims), C.byref(nn), C.byref(np_)))
         return nodes, prims
+
+    def get_bvh4(self, mesh_index):
+        """The traversed tree of a resident mesh as it sits on the device (entries absolute): {"nodes4c": NODE4C_DTYPE,
+        "nodes4f": NODE4F_DTYPE, "src4": n4 x 4 uint32, "tri_verts": tri_count x 3 x 4 float32, plus the fields of
+        abi.Bvh4Info (device_built as a bool)}."""
+        info = abi.Bvh4Info()
+        f = self._fn("get_bvh4")
+        self._check(f(self._ctx, int(mesh_index), None, None, None, 0, None, 0, C.byref(info)))
+        n4, nt = info.n4_count, info.tri_count
+        c4 = np.zeros(n4, abi.NODE4C_DTYPE)
+        f4 = np.zeros(n4, abi.NODE4F_DTYPE)
+        src = np.zeros((n4, 4), np.uint32)
+        tv = np.zeros((nt, 3, 4), np.float32)
+        self._check(f(self._ctx, int(mesh_index), c4.ctypes.data, f4.ctypes.data, src.ctypes.data, n4, tv.ctypes.data, nt,
+                      C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in abi.Bvh4Info._fields_}
+        out["device_built"] = bool(info.device_built)
+        out.update(nodes4c=c4, nodes4f=f4, src4=src, tri_verts=tv)
+        return out
 
 
 class RenderGroup:

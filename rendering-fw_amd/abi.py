@@ -60,6 +60,19 @@ assert DIRECTIONAL_LIGHT_DTYPE.itemsize == 32
 BVH_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left_first", "<i4"), ("count", "<i4")])
 assert BVH_NODE_DTYPE.itemsize == 32
 
+# the traversed 4-wide nodes (rfwhip_get_bvh4): compressed (rt::Node4c, rt_types.h) and their float form (rt::Node4f).
+# Compressed planes: byte k of qlo[a] / qhi[a] is child k's plane on axis a, decoded as fma(q, scale[a], org[a]).
+NODE4C_DTYPE = np.dtype([("org", "<f4", 3), ("scale_x", "<f4"), ("entry", "<u4", 4), ("qlo", "<u4", 3), ("qhi", "<u4", 3),
+                         ("scale_y", "<f4"), ("scale_z", "<f4")])
+assert NODE4C_DTYPE.itemsize == 64
+NODE4F_DTYPE = np.dtype([("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("entry", "<u4", 4), ("pad", "<u4", 4)])
+assert NODE4F_DTYPE.itemsize == 128
+ENTRY_LEAF = 0x80000000
+ENTRY_TLAS = 0x40000000
+ENTRY_EMPTY = 0xFFFFFFFC
+ENTRY_FIRST_MASK = 0x07FFFFFF   # 27 bits: first triangle of a leaf; bits 27..29: count - 1
+ENTRY_INDEX_MASK = 0x3FFFFFFF   # 30 bits: a 4-wide node
+
 # MatPropFlags, structs.h:67-83
 MAT_IS_DIELECTRIC = 0
 MAT_DIFFUSE_MAP_IS_HDR = 1
@@ -109,6 +122,12 @@ class CameraPOD(C.Structure):
 class CameraView(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("p1", C.c_float * 3), ("p2", C.c_float * 3), ("p3", C.c_float * 3),
                 ("aperture", C.c_float), ("spreadAngle", C.c_float)]
+
+
+class Bvh4Info(C.Structure):
+    _fields_ = [("n4_base", C.c_uint32), ("n4_count", C.c_uint32), ("tri_base", C.c_uint32), ("tri_count", C.c_uint32),
+                ("node_base", C.c_uint32), ("node_count2", C.c_uint32), ("stack_need", C.c_int32),
+                ("device_built", C.c_uint32)]
 
 
 class RenderStats(C.Structure):

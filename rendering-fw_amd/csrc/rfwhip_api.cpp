@@ -3334,3 +3334,49 @@ extern "C" int rfwhip_get_bvh(rfwhip_context *c, size_t mesh_index, rfwhip_bvh_n
 		memcpy(prim_indices, m.bvh.order.data(), std::min(prim_cap, m.bvh.order.size()) * 4);
 	return RFWHIP_OK;
 }
+
+extern "C" int rfwhip_get_bvh4(rfwhip_context *c, size_t mesh_index, void *nodes4c, void *nodes4f, uint32_t *src4, size_t node_cap,
+							   float *tri_verts, size_t tri_cap, rfwhip_bvh4_info *info)
+{
+	CTX_ENTER(c);
+	if (mesh_index >= c->meshes.size() || !c->meshes[mesh_index].used)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_get_bvh4: no mesh %zu", mesh_index);
+	const MeshRec &m = c->meshes[mesh_index];
+	if (!m.resident)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_get_bvh4: mesh %zu is not resident (rfwhip_update places it)", mesh_index);
+	if (info)
+	{
+		info->n4_base = m.n4_base, info->n4_count = m.n4_count, info->tri_base = m.tri_base, info->tri_count = (uint32_t)m.triCount;
+		info->node_base = m.node_base, info->node_count2 = m.node_count2;
+		info->stack_need = m.stack_need, info->device_built = m.device_built ? 1u : 0u;
+	}
+	RF_TRY(sync_all(c));
+	const size_t n4 = std::min<size_t>(node_cap, m.n4_count), nt = std::min<size_t>(tri_cap, m.triCount);
+	if (nodes4c && n4)
+		RF_TRY(dm::d2h(nodes4c, c->d_nodes4.as<rt::Node4c>() + m.n4_base, n4 * sizeof(rt::Node4c), c->stream));
+	if (src4 && n4)
+		RF_TRY(dm::d2h(src4, c->d_nodes4_src.as<uint32_t>() + 4ull * m.n4_base, 4 * n4 * sizeof(uint32_t), c->stream));
+	if (tri_verts && nt)
+		RF_TRY(dm::d2h(tri_verts, c->d_tri_verts.as<f4>() + 3ull * m.tri_base, 3 * nt * sizeof(f4), c->stream));
+	if (nodes4f && n4)
+	{
+		if (c->nodes4f_current)
+			RF_TRY(dm::d2h(nodes4f, c->d_nodes4f.as<rt::Node4f>() + m.n4_base, n4 * sizeof(rt::Node4f), c->stream));
+		else
+		{
+			// the float table is written only when the packet traversal can run: expand the slice with the same kernel
+			DevBuf tmp;
+			int rc = tmp.ensure(n4 * sizeof(rt::Node4f));
+			if (!rc)
+			{
+				rtk::launch_expand4(c->d_nodes4.as<rt::Node4c>() + m.n4_base, tmp.as<rt::Node4f>(), (uint32_t)n4, c->stream);
+				rc = dm::last_launch_error();
+			}
+			if (!rc)
+				rc = dm::d2h(nodes4f, tmp.p, n4 * sizeof(rt::Node4f), c->stream);
+			tmp.free_();
+			RF_TRY(rc);
+		}
+	}
+	return RFWHIP_OK;
+}

@@ -42,6 +42,11 @@ def test_pod_sizes(pkg):
     assert abi.AREA_LIGHT_DTYPE.itemsize == 96 and abi.POINT_LIGHT_DTYPE.itemsize == 32
     assert abi.SPOT_LIGHT_DTYPE.itemsize == 48 and abi.DIRECTIONAL_LIGHT_DTYPE.itemsize == 32
     assert C.sizeof(abi.CameraView) == 56 and C.sizeof(abi.RenderStats) == 48 and C.sizeof(abi.Mesh) == 56
+    # rfwhip_get_bvh4: its info record and the two node forms it copies (rt::Node4c, rt::Node4f)
+    assert C.sizeof(abi.Bvh4Info) == 32 and abi.NODE4C_DTYPE.itemsize == 64 and abi.NODE4F_DTYPE.itemsize == 128
+    c4, f4 = abi.NODE4C_DTYPE, abi.NODE4F_DTYPE
+    assert c4.fields["entry"][1] == 16 and c4.fields["qlo"][1] == 32 and c4.fields["qhi"][1] == 44 and c4.fields["scale_y"][1] == 56
+    assert f4.fields["hi"][1] == 48 and f4.fields["entry"][1] == 96
     # field offsets the kernels rely on (structs.h:35-60)
     t = abi.TRIANGLE_DTYPE
     assert t.fields["lightTriIdx"][1] == 12 and t.fields["material"][1] == 28 and t.fields["vN0"][1] == 32
