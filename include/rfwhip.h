@@ -301,7 +301,7 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                  read fails with RFWHIP_ERR_STATE, as a render would — current guides are used while such calls are pending.  A
  *                  traversal-stack overflow of the guide pass fails rfwhip_read_framebuffer* / rfwhip_read_denoise_guides (its own
  *                  counter: the render's statistics are not touched).
- *                  FILTER (SVGF's spatial filter, Schied et al. HPG 2017, without the temporal part), valid pixels p:
+ *                  FILTER (SVGF's spatial filter, Schied et al. HPG 2017; its temporal stage: "denoise_temporal"), valid pixels p:
  *                    a_p = max(albedo_p, 1e-3) per channel, I_p = c_p / a_p, l = 0.2126 r + 0.7152 g + 0.0722 b of I;
  *                    var_p = sum_q w_q (l_q - m)^2 / sum_q w_q, m = sum_q w_q l_q / sum_q w_q over the valid q of the 3 x 3
  *                      neighbourhood, w_q = w_z(s = 1) w_n;
@@ -318,6 +318,37 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   denoise_iterations = a-trous passes, 1..8 (default 5)
  *   denoise_sigma_luminance / denoise_sigma_normal / denoise_sigma_depth = the filter's edge-stopping parameters (SVGF's defaults:
  *                  4 / 128 / 1)
+ *   denoise_temporal = "0" (default) | "1": SVGF's temporal stage, a reprojected history of the presented frames.
+ *                  SAMPLE ORIGIN: with "1" a RESET render sets o = S mod 256, S = samples per pixel this context has rendered since
+ *                  rfwhip_init; the pt integrator's sample indices run o + samples_done + ... (with "0", o = 0: reset frames of one
+ *                  camera are identical).  Every rank renders the same counts: o, and so the image, is independent of the world size.
+ *                  The stage runs once per PRESENTED frame F: the first denoised world-1 read after a render, each group gather
+ *                  (frames in flight included), each rfwhip_comm_gather on the root.  Further reads of the same frame return the
+ *                  same bits (two history sets; a read runs the stage again from P's set into F's) while the scene is unchanged:
+ *                  an rfwhip_update after F was presented traces F's guides again against the new scene, and a further read of F
+ *                  (or rfwhip_read_denoise_history) then filters with those.  P = the previous presented
+ *                  frame.  The HISTORY IS USABLE when a frame P has been presented since the history was cleared, the size is
+ *                  P's, and a RESET render came after P (a CONVERGE accumulator holds P's samples).  Cleared by rfwhip_init,
+ *                  rfwhip_cleanup and by turning "denoise" or "denoise_temporal" on.  It follows the demodulation above:
+ *                    I_p = c_p / a_p, l_p = lum(I_p).  REPROJECTION: X = pos_F + z_p D_p (D_p the guide's centre ray); the ray
+ *                    pos_P -> X meets P's image plane (p1, right, up) at p1 + u right + v up, s > 0 (X in front of P);
+ *                    (x', y') = (u W - 0.5, v H - 0.5); the 4 bilinear taps q of (x', y'), each CONSISTENT when: its weight > 0,
+ *                    inside the image, P's guide at q valid, P's guide saw the same instance as p, that instance (transform,
+ *                    mesh, its rebuild / refit / pose / morph) unchanged by every rfwhip_update since P's guides,
+ *                    |z_P(q) - |X - pos_P|| <= 2 (|dz/dx_P(q)| + |dz/dy_P(q)|) + 0.01 |X - pos_P|, n_p . n_P(q) >= 0.9.  The
+ *                    consistent weights are renormalised; their sum < 0.01 (or no usable history): p is FRESH.
+ *                    BLEND, fresh: n = 1, I~ = I, mu1 = l, mu2 = l^2 (no history is read); else with the renormalised weights
+ *                    H, (m1, m2), n_P = sum w (history colour, moments, length) at q, n = min(n_P + 1, 64), a = max(alpha, 1 / n),
+ *                    I~ = (1 - a) H + a I, mu1 = (1 - a) m1 + a l, mu2 = (1 - a) m2 + a l^2.
+ *                    VARIANCE: n >= 3.99 (4, with a margin for the rounding of the weighted n_P): var = max(0, mu2 - mu1^2);
+ *                    else the 3 x 3 estimate above (from I).
+ *                    The passes above then run on (I~, lum(I~), var) unchanged.  HISTORY written: the demodulated output of
+ *                    pass 0 (the colour), (mu1, mu2), n, F's guides and instance ids, F's camera; invalid pixels store n = 0
+ *                    (and their output is c bit for bit, as above).  A fresh frame (the first, after a cut, any CONVERGE frame)
+ *                    is the spatial filter's output bit for bit.  Moving or deforming instances are not reprojected: they restart.
+ *                  Root-only buffers, allocated when the setting is turned on: 16 B (P's guides) + 2 x 4 B (instance ids) +
+ *                  2 x 28 B (history) per pixel.  rfwhip_denoise_image stays spatial-only.
+ *   denoise_alpha = SVGF's alpha in (0, 1] for colour and moments (default 0.2)
  *   rfwhip_get_setting also answers read-only keys: "textured" (the textured shade kernel variant is in use), "packet" (the
  *   pt primary wave can run in packet form), "world_tree" (triangles in the world tree of the last update; 0: none),
  *   "shadow_bins_per_run", "shadow_packets_on".
@@ -356,6 +387,13 @@ RFWHIP_API int rfwhip_read_denoise_guides(rfwhip_context *ctx, float *albedo, fl
 /* Filter a given W x H float4 image (host memory) with the current guides and the context's denoise_* knobs, whatever "denoise"
  * says (the guide pass runs first if they are stale).  rgba_out may equal rgba_in. */
 RFWHIP_API int rfwhip_denoise_image(rfwhip_context *ctx, const float *rgba_in, float *rgba_out);
+/* The temporal stage of the last presented frame (see "denoise_temporal"; world-1 contexts whose last render has been presented
+ * with denoise and denoise_temporal on): pre_rgbl = I~ and lum(I~), var = the variance the passes start from (W x H x 4 / W x H
+ * floats; 0 at invalid pixels), hist_rgbl = the stored colour history (pass 0's demodulated output, lum), moments = (mu1, mu2)
+ * (W x H x 2), length = n (W x H; 0 at invalid pixels).  Any pointer may be NULL.  It runs the stage of the frame again with the
+ * current guides and instance table: the presented frame's values while the scene is unchanged (no rfwhip_update since). */
+RFWHIP_API int rfwhip_read_denoise_history(rfwhip_context *ctx, float *pre_rgbl, float *var, float *hist_rgbl, float *moments,
+										   float *length);
 
 /* Raw closest-hit records of the most recent primary wave (parity tests): per pixel of this rank's local image
  * t (1e34 = miss), primID, instID, u, v. Any pointer may be NULL. */

@@ -84,6 +84,7 @@ class CoreBinding:
                                   "get_bvh4": (i32, [vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(abi.Bvh4Info)]),
                                   "read_denoise_guides": (i32, [vp, vp, vp]),
                                   "denoise_image": (i32, [vp, vp, vp]),
+                                  "read_denoise_history": (i32, [vp, vp, vp, vp, vp, vp]),
                                   "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32])}.items():
             if self._has(name):
                 f = self._fn(name)
@@ -307,6 +308,16 @@ class CoreBinding:
         src = np.ascontiguousarray(rgba, dtype=np.float32).reshape(self.height, self.width, 4)
         out = np.empty_like(src)
         self._check(self._fn("denoise_image")(self._ctx, src.ctypes.data, out.ctypes.data))
+        return out
+
+    def read_denoise_history(self):
+        """The temporal stage of the last presented frame (include/rfwhip.h, "denoise_temporal"; world-1 contexts):
+        {"pre": H x W x 4 (I~, lum), "var": H x W, "history": H x W x 4 (colour history, lum), "moments": H x W x 2,
+        "length": H x W (n; 0 at invalid pixels)} — abi.DENOISE_HISTORY_KEYS."""
+        h, w = self.height, self.width
+        out = dict(zip(abi.DENOISE_HISTORY_KEYS, (np.empty(s, np.float32) for s in
+                                                   ((h, w, 4), (h, w), (h, w, 4), (h, w, 2), (h, w)))))
+        self._check(self._fn("read_denoise_history")(self._ctx, *(out[k].ctypes.data for k in abi.DENOISE_HISTORY_KEYS)))
         return out
 
     # known-answer hook: RFWHIP_KAT_* (include/rfwhip_abi.h)

@@ -124,6 +124,10 @@ class CameraView(C.Structure):
                 ("aperture", C.c_float), ("spreadAngle", C.c_float)]
 
 
+# rfwhip_read_denoise_history's outputs, in argument order (include/rfwhip.h): I~ | lum, var, colour history | lum, (mu1, mu2), n
+DENOISE_HISTORY_KEYS = ("pre", "var", "history", "moments", "length")
+
+
 class Bvh4Info(C.Structure):
     _fields_ = [("n4_base", C.c_uint32), ("n4_count", C.c_uint32), ("tri_base", C.c_uint32), ("tri_count", C.c_uint32),
                 ("node_base", C.c_uint32), ("node_count2", C.c_uint32), ("stack_need", C.c_int32),

@@ -1,5 +1,5 @@
 // denoise.h — the work items of the denoiser of the presented image (setting "denoise", include/rfwhip.h): a guide pass and
-// SVGF's spatial filter (Schied et al., HPG 2017) without its temporal part.  Included by kernels.hip inside namespace rtk,
+// SVGF's filter (Schied et al., HPG 2017): the spatial a-trous passes and its temporal stage.  Included by kernels.hip inside namespace rtk,
 // after the other work items: the device kernels (kernels.hip) and the host emulation (kernels_emu.inc) run the same items.
 //
 // Guides, per pixel of the full W x H image (one centre ray from the lens centre, the closest-hit traversal of the path tracer):
@@ -16,11 +16,26 @@
 //               I' = sum w I_q / sum w, var' = sum w^2 var_q / (sum w)^2, l' = lum(I')
 //   remodulate  (last pass) out = I' max(albedo, 1e-3), out.w = c.w
 // Fixed tap order, no atomics: the output depends on the input image and the guides only.
+// Temporal stage (setting "denoise_temporal"; SVGF's reprojected history): dn_temporal_item follows the demodulation once per
+// presented frame F.  It reprojects p's guide point X = pos_F + z_p D_p into the previous presented frame P (bilinear taps, each
+// kept when it is consistent: inside, valid, the same unchanged instance, depth and normal within DN_T_*), blends I and the
+// luminance moments with the history (n = min(n_P + 1, 64), a = max(alpha, 1 / n)) and takes var = max(0, mu2 - mu1^2) once
+// n >= 4 (the 3x3 estimate before).  Pass 0 writes the colour history (its demodulated output).  A fresh pixel (no consistent
+// tap, or no usable history) reads no history and gives the spatial filter's values bit for bit.
 #pragma once
 
 constexpr int DN_MAX_ALPHA = 8;			// alpha-tested layers a guide ray passes before the pixel is called invalid
 constexpr float DN_ALBEDO_MIN = 1e-3f;	// demodulation floor per channel
 constexpr int DN_TILE_X = 16, DN_TILE_Y = 16; // pixels of a 256-thread workgroup: 2 x 2 tiles of 8 x 8, one per wave64
+// temporal stage (include/rfwhip.h "denoise_temporal" names the same constants)
+constexpr float DN_T_DEPTH_GRAD = 2.0f;	 // depth test: |z_P(q) - |X - pos_P|| <= 2 (|dz/dx| + |dz/dy|) + 0.01 |X - pos_P|
+constexpr float DN_T_DEPTH_REL = 0.01f;
+constexpr float DN_T_NORMAL = 0.9f;		 // normal test: n_p . n_P(q) >= 0.9
+constexpr float DN_T_MIN_WEIGHT = 0.01f; // a pixel whose consistent bilinear weights sum below this starts fresh
+constexpr float DN_T_MAX_N = 64.0f;		 // history length cap
+constexpr float DN_T_VAR_N = 3.99f;		 // from this history length on (4, less a margin for the rounding of the interpolated length:
+										 // n_P is a weighted sum), the variance comes from the moments
+constexpr uint32_t DN_NO_INST = 0xFFFFFFFFu; // instance id of an invalid guide pixel
 
 RT_FN float dn_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
@@ -68,6 +83,7 @@ RT_FN void dn_guide_item(const Params &p, const DnView &d, uint32_t i, const Tra
 	f3 albedo = mk3(0, 0, 0), n = mk3(0, 0, 1);
 	float z = 0.0f;
 	bool valid = false;
+	uint32_t inst = DN_NO_INST;
 	for (int layer = 0; layer <= DN_MAX_ALPHA; layer++)
 	{
 		Hit h;
@@ -96,11 +112,14 @@ RT_FN void dn_guide_item(const Params &p, const DnView &d, uint32_t i, const Tra
 			albedo = color;
 			n = iN * ((dot(D, sf.N) > 0.0f) ? -1.0f : 1.0f);
 			valid = true;
+			inst = (uint32_t)h.inst;
 		}
 		break;
 	}
 	d.ga[i] = mk4(albedo.x, albedo.y, albedo.z, valid ? 1.0f : 0.0f);
 	d.gb[i] = mk4(ubits(dn_oct_encode(n)), valid ? z : -1.0f, 0.0f, 0.0f);
+	if (d.id) // (the temporal stage's instance test)
+		d.id[i] = inst;
 }
 
 // screen-space depth gradient (a second kernel: it reads the neighbours' z); writes gb[i].z / .w only
@@ -171,6 +190,93 @@ RT_FN void dn_demod_item(const DnView &d, f4 *img, float *var, uint32_t i)
 	var[i] = v / sw;
 }
 
+// ---- temporal stage (after dn_demod_item when "denoise_temporal" is on) -----------------------------------------------------------
+// The demodulation has written I, l and the 3x3 variance into img / var; this reprojects pixel i into the previous presented frame,
+// blends with its history and chooses the variance, in place: img (I~, lum(I~)) / var; the moments and the history length into
+// t.mom_out / t.n_out.  A fresh pixel leaves img / var as the demodulation wrote them: the spatial filter's values, bit for bit.
+// Invalid pixels store n = 0.  (Reads and writes pixel i of img / var only.)
+RT_FN void dn_temporal_item(const DnView &d, const DnTemporal &t, f4 *img, float *var, uint32_t i)
+{
+	const f4 gp = d.gb[i];
+	if (gp.y < 0.0f)
+	{
+		d.hist[i] = mk4(0.0f, 0.0f, 0.0f, 0.0f); // (never read: P's guide at an invalid pixel fails every tap)
+		t.mom_out[2 * i] = 0.0f, t.mom_out[2 * i + 1] = 0.0f, t.n_out[i] = 0.0f;
+		return;
+	}
+	const uint32_t x = i % d.W, y = i / d.W;
+	const f4 I = img[i];
+	const float l = I.w;
+	// the consistent bilinear taps of X in P (fixed order: (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1))
+	float wq[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ws = 0.0f;
+	uint32_t qi[4] = {0u, 0u, 0u, 0u};
+	if (t.usable)
+	{
+		f3 O, D;
+		pt_center_ray(t.cam, t.fr, x, y, O, D);
+		const f3 X = O + D * gp.y, e = X - t.pcam.pos;
+		const f3 pn = cross(t.pcam.right, t.pcam.up);
+		const float s = dot(t.pcam.p1 - t.pcam.pos, pn) / dot(e, pn); // the ray pos_P -> X meets P's image plane at pos_P + s e
+		if (s > 0.0f)
+		{
+			const f3 Q = t.pcam.pos + e * s - t.pcam.p1, R = t.pcam.right, U = t.pcam.up;
+			const float rr = dot(R, R), ru = dot(R, U), uu = dot(U, U), qr = dot(Q, R), qu = dot(Q, U);
+			const float det = rr * uu - ru * ru;
+			const float xf = (qr * uu - qu * ru) / det * (float)d.W - 0.5f, yf = (qu * rr - qr * ru) / det * (float)d.H - 0.5f;
+			if (xf > -1.0f && xf < (float)d.W && yf > -1.0f && yf < (float)d.H) // (false for NaN)
+			{
+				const float fx0 = floorf(xf), fy0 = floorf(yf), fx = xf - fx0, fy = yf - fy0;
+				const int x0 = (int)fx0, y0 = (int)fy0;
+				const float dist = length(e);
+				const uint32_t id = t.id[i];
+				const bool same = id < t.n_inst && t.inst_ver[id] <= t.pscene; // (the instance has not changed since P)
+				const f3 np = dn_oct_decode(fbits(gp.x));
+				for (int k = 0; k < 4; k++)
+				{
+					const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
+					const float bw = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
+					if (!same || bw <= 0.0f || qx < 0 || qy < 0 || qx >= (int)d.W || qy >= (int)d.H)
+						continue;
+					const uint32_t q = (uint32_t)qy * d.W + (uint32_t)qx;
+					const f4 gq = t.pgb[q];
+					if (gq.y < 0.0f || t.pid[q] != id)
+						continue;
+					if (fabsf(gq.y - dist) > DN_T_DEPTH_GRAD * (fabsf(gq.z) + fabsf(gq.w)) + DN_T_DEPTH_REL * dist)
+						continue;
+					if (dot(np, dn_oct_decode(fbits(gq.x))) < DN_T_NORMAL)
+						continue;
+					wq[k] = bw, qi[k] = q, ws += bw;
+				}
+			}
+		}
+	}
+	if (!(ws >= DN_T_MIN_WEIGHT))
+	{
+		// fresh: no history is read, img / var stay the demodulation's
+		t.mom_out[2 * i] = l, t.mom_out[2 * i + 1] = l * l, t.n_out[i] = 1.0f;
+		return;
+	}
+	const float inv = 1.0f / ws;
+	float hr = 0.0f, hg = 0.0f, hb = 0.0f, h1 = 0.0f, h2 = 0.0f, hn = 0.0f;
+	for (int k = 0; k < 4; k++)
+	{
+		if (wq[k] == 0.0f)
+			continue;
+		const float w = wq[k] * inv;
+		const f4 hc = t.col_in[qi[k]];
+		hr += w * hc.x, hg += w * hc.y, hb += w * hc.z;
+		h1 += w * t.mom_in[2 * qi[k]], h2 += w * t.mom_in[2 * qi[k] + 1], hn += w * t.n_in[qi[k]];
+	}
+	const float n = fminf(hn + 1.0f, DN_T_MAX_N);
+	const float al = fmaxf(t.alpha, 1.0f / n), bl = 1.0f - al;
+	const float r = bl * hr + al * I.x, g = bl * hg + al * I.y, b = bl * hb + al * I.z;
+	const float m1 = bl * h1 + al * l, m2 = bl * h2 + al * (l * l);
+	img[i] = mk4(r, g, b, dn_lum(r, g, b));
+	if (n >= DN_T_VAR_N) // (before: the 3x3 estimate the demodulation wrote)
+		var[i] = fmaxf(0.0f, m2 - m1 * m1);
+	t.mom_out[2 * i] = m1, t.mom_out[2 * i + 1] = m2, t.n_out[i] = n;
+}
+
 // one a-trous pass of step `step`: src / vsrc -> dst / vdst, or (last) the remodulated image into d.out (may be d.in)
 RT_FN void dn_pass_item(const DnView &d, uint32_t step, bool last, const f4 *src, const float *vsrc, f4 *dst, float *vdst, uint32_t i)
 {
@@ -229,4 +335,6 @@ RT_FN void dn_pass_item(const DnView &d, uint32_t step, bool last, const f4 *src
 		dst[i] = mk4(r, g, b, dn_lum(r, g, b));
 		vdst[i] = sv * inv * inv;
 	}
+	if (step == 1u && d.hist) // (the temporal stage: pass 0's demodulated output is the colour history)
+		d.hist[i] = mk4(r, g, b, dn_lum(r, g, b));
 }

@@ -44,6 +44,25 @@ struct DnView
 	float sigma_l, sigma_n, sigma_z;
 	uint32_t iterations;  // 1..8 passes, step 2^i
 	uint32_t *overflow;	  // the guide pass's own traversal-stack overflow counter (not the render's wave counters)
+	uint32_t *id;		  // the guide pass's instance index per pixel (DN_NO_INST: invalid), or null (temporal stage off)
+	rt::f4 *hist;		  // where pass 0 writes its demodulated output (the temporal stage's colour history), or null
+};
+
+// The temporal stage of the denoiser (denoise.h dn_temporal_item): frame F's camera, the previous presented frame P's camera,
+// guides and instance ids, and the two history sets (read P's, write F's)
+struct DnTemporal
+{
+	rt::CamView cam, pcam;		 // F's and P's cameras (pos, p1, right, up)
+	rt::FrameView fr;			 // F's frame (1 / W, 1 / H of the centre rays)
+	const rt::f4 *pgb;			 // P's guides (normal | z | dz/dx | dz/dy)
+	const uint32_t *id, *pid;	 // F's and P's instance ids
+	const uint32_t *inst_ver;	 // per instance: the scene version of the update that last changed it
+	uint32_t n_inst, pscene;	 // instances, and the scene version of P's guides
+	const rt::f4 *col_in;		 // P's history: colour, moments (mu1, mu2), length
+	const float *mom_in, *n_in;
+	float *mom_out, *n_out;		 // F's moments and length (the colour goes through DnView::hist)
+	float alpha;
+	uint32_t usable;			 // 0: every pixel starts fresh (no history is read)
 };
 
 // capacity of the LDS top-of-tree cache the kernels were built with
@@ -75,8 +94,11 @@ void launch_kat(const Params &p, int function, const float *in, float *out, uint
 void launch_present(const Params &p, rt::f4 *out, float scale, int full, stream_t s);
 // the denoiser's guide pass (p: scene, camera and FrameView of the full image) = guide kernel + depth-gradient kernel
 void launch_denoise_guides(const Params &p, const DnView &d, stream_t s);
-// demodulation + variance, d.iterations a-trous passes, remodulation into d.out: 1 + d.iterations launches
-void launch_denoise_filter(const DnView &d, stream_t s);
+// demodulation + variance (with t, then the temporal stage), d.iterations a-trous passes, remodulation into d.out:
+// 1 (+ 1 with t) + d.iterations launches
+void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s);
+// demodulation + the temporal stage, into d.img[0] / d.var[0] (rfwhip_read_denoise_history): 2 launches
+void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t s);
 // a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
 rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,

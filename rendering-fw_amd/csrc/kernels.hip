@@ -2457,6 +2457,12 @@ __global__ void __launch_bounds__(BLOCK) k_dn_demod(const DnView d)
 	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
 		dn_demod_item(d, d.img[0], d.var[0], i);
 }
+__global__ void __launch_bounds__(BLOCK) k_dn_temporal(const DnView d, const DnTemporal t)
+{
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_temporal_item(d, t, d.img[0], d.var[0], i);
+}
 __global__ void __launch_bounds__(BLOCK) k_dn_pass(const DnView d, uint32_t pass)
 {
 	uint32_t i;
@@ -2470,9 +2476,17 @@ void launch_denoise_guides(const Params &p, const DnView &d, stream_t s)
 	hipLaunchKernelGGL(k_dn_guides, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d);
 	hipLaunchKernelGGL(k_dn_gradient, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
 }
-void launch_denoise_filter(const DnView &d, stream_t s)
+void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t s)
 {
 	hipLaunchKernelGGL(k_dn_demod, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
+	hipLaunchKernelGGL(k_dn_temporal, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d, t);
+}
+void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s)
+{
+	if (t)
+		launch_denoise_temporal(d, *t, s);
+	else
+		hipLaunchKernelGGL(k_dn_demod, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
 	for (uint32_t k = 0; k < d.iterations; k++)
 		hipLaunchKernelGGL(k_dn_pass, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d, k);
 }

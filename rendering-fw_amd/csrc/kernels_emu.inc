@@ -366,10 +366,20 @@ void launch_denoise_guides(const Params &p, const DnView &d, stream_t)
 	for (uint32_t i = 0; i < d.W * d.H; i++)
 		dn_gradient_item(d, i);
 }
-void launch_denoise_filter(const DnView &d, stream_t)
+void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t)
 {
 	for (uint32_t i = 0; i < d.W * d.H; i++)
 		dn_demod_item(d, d.img[0], d.var[0], i);
+	for (uint32_t i = 0; i < d.W * d.H; i++)
+		dn_temporal_item(d, t, d.img[0], d.var[0], i);
+}
+void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s)
+{
+	if (t)
+		launch_denoise_temporal(d, *t, s);
+	else
+		for (uint32_t i = 0; i < d.W * d.H; i++)
+			dn_demod_item(d, d.img[0], d.var[0], i);
 	for (uint32_t k = 0; k < d.iterations; k++)
 		for (uint32_t i = 0; i < d.W * d.H; i++)
 			dn_pass_item(d, 1u << k, k + 1u == d.iterations, d.img[k & 1u], d.var[k & 1u], d.img[(k + 1u) & 1u], d.var[(k + 1u) & 1u], i);

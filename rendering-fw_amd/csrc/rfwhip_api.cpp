@@ -319,6 +319,7 @@ struct MeshRec
 	bool refit_pending = false;
 	uint32_t generation = 0; // counts the (re)builds of this mesh (the world tree's cache key)
 	uint32_t refits = 0;	 // same-topology rfwhip_set_mesh calls since the last build: an animated mesh (never written into the world tree)
+	uint32_t edits = 0;		 // rebuilds, refits, poses and morphs (the denoiser's temporal stage: instance_versions)
 	// device skinning (rfwhip_set_mesh_skin / rfwhip_pose_mesh)
 	bool skinned = false, posed = false;
 	DevBuf d_base_verts, d_base_normals, d_joints, d_weights, d_vnormals, d_joint_mats;
@@ -344,6 +345,13 @@ struct InstRec
 	uint32_t moving = 0; // updates left before it may (re)join the world tree
 	uint32_t moves = 0;	 // times it has started to move out of stillness: the waiting time doubles with each (an object that moves now
 						 // and then would otherwise cost two rebuilds of the world tree — seconds for millions of triangles — per episode)
+	// the denoiser's temporal stage: what the instance was at the last rfwhip_update, and the scene version of the update that last
+	// changed it (instance_versions)
+	bool dn_used = false;
+	size_t dn_mesh = 0;
+	uint32_t dn_edits = 0;
+	float dn_transform[16];
+	unsigned long long dn_version = 0;
 };
 
 // The WORLD TREE (rfwhip_update): the triangles of the static instances written out in world space under ONE tree.
@@ -470,6 +478,27 @@ struct rfwhip_context
 	uint32_t guide_W = 0, guide_H = 0;
 	dm::event_t ev_dn;	  // behind the last denoise enqueued on a caller's stream (the group / comm gather)
 	bool dn_pending = false;
+	// ... its temporal stage (setting "denoise_temporal"): P = the last presented frame, F = the frame being presented
+	int dn_temporal = 0;
+	float dn_alpha = 0.2f;
+	DevBuf d_dn_prev, d_dn_ids, d_dn_hist, d_dn_inst_ver; // P's guides (16 B), ids of F | P (2 x 4 B), 2 history sets (2 x 28 B) per pixel
+	unsigned long long frame_serial = 0;	// rfwhip_render calls
+	unsigned long long samples_total = 0; // samples per pixel rendered since rfwhip_init (the sample origin of a RESET)
+	uint32_t sample_origin = 0;			// the pt integrator's sample indices start here (0 unless denoise_temporal)
+	bool dn_have_pres = false;				// a frame P has been presented since the history was last cleared
+	unsigned long long dn_pres_serial = 0;	// ... its render serial
+	rt::CamView dn_pres_cam{};				// ... its camera, the scene version and size of its guides
+	uint32_t dn_pres_scene = 0, dn_pres_W = 0, dn_pres_H = 0;
+	bool dn_guides_pres = false;			// d_dn_guides / ids still hold P's guides
+	bool dn_prev_ok = false;				// d_dn_prev / P's ids hold the guides of frame dn_saved_serial
+	unsigned long long dn_saved_serial = 0;
+	bool dn_reset_since = false;			// a RESET render since P was presented
+	int dn_hist_cur = 0;					// the history set P's stage wrote
+	bool dn_t_usable = false;				// the stage of the last presented frame: history usable, P's camera and scene version
+	rt::CamView dn_t_pcam{};
+	uint32_t dn_t_pscene = 0;
+	std::vector<uint32_t> dn_inst_ver;		// per instance: InstRec::dn_version (uploaded into d_dn_inst_ver)
+	bool dn_inst_ver_stale = true;			// d_dn_inst_ver is missing or older than dn_inst_ver: uploaded before the next stage
 
 	// scene (host side)
 	std::vector<MeshRec> meshes;
@@ -643,6 +672,12 @@ extern "C" int rfwhip_create(int device_ordinal, int rank, int world, rfwhip_con
 	return RFWHIP_OK;
 }
 
+// the denoiser's temporal stage forgets every presented frame: the next one starts fresh
+static void dn_clear_history(rfwhip_context *c)
+{
+	c->dn_have_pres = false, c->dn_guides_pres = false, c->dn_prev_ok = false, c->dn_reset_since = false;
+}
+
 static void free_all(rfwhip_context *c)
 {
 	for (auto &m : c->meshes)
@@ -661,10 +696,13 @@ static void free_all(rfwhip_context *c)
 					  &c->d_thr[1], &c->d_hit, &c->d_hit_inst, &c->d_hit0, &c->d_hit0_inst, &c->d_hit0_done, &c->d_sh_org[0], &c->d_sh_org[1],
 					  &c->d_sh_dir[0], &c->d_sh_dir[1], &c->d_sh_rad[0], &c->d_sh_rad[1], &c->d_rad[0], &c->d_rad[1],
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
-					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var};
+					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
+					  &c->d_dn_inst_ver};
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->guides_valid = false;
+	dn_clear_history(c);
+	c->dn_inst_ver_stale = true;
 	for (auto &e : c->event_pool)
 		dm::event_destroy(e);
 	c->event_pool.clear();
@@ -738,7 +776,10 @@ extern "C" int rfwhip_init(rfwhip_context *c, uint32_t width, uint32_t height)
 	RF_TRY(sync_all(c));
 	c->W = width, c->H = height;
 	c->d_dn_guides.free_(), c->d_dn_img.free_(), c->d_dn_var.free_(); // (re-allocated at the new size while denoise is on)
+	c->d_dn_prev.free_(), c->d_dn_ids.free_(), c->d_dn_hist.free_();
 	c->guides_valid = false;
+	dn_clear_history(c);
+	c->samples_total = 0, c->sample_origin = 0;
 	if (c->denoise && c->rank == 0)
 		RF_TRY(dn_ensure(c));
 	const uint32_t lr = local_rows_of(c);
@@ -949,7 +990,7 @@ extern "C" int rfwhip_set_mesh(rfwhip_context *c, size_t index, const rfwhip_mes
 	const f4 *V = (const f4 *)mesh->vertices;
 	if (same_topology)
 	{
-		m.refits++;
+		m.refits++, m.edits++;
 		// animated mesh: same counts => refit on the device (EmbreeRT/src/Mesh.cpp:33-35, top_level_bvh.cpp:26)
 		for (size_t i = 0; i < mesh->triangleCount; i++)
 		{
@@ -1002,7 +1043,7 @@ extern "C" int rfwhip_set_mesh(rfwhip_context *c, size_t index, const rfwhip_mes
 	// ... and until the build below has succeeded it describes NO tree (an error return leaves a mesh rfwhip_update() refuses,
 	// not the counts of the previous build beside freed or half-written arrays)
 	m.built = false, m.device_built = false, m.node_count2 = m.n4_count = 0, m.stack_need = 0;
-	m.generation++, m.refits = 0;
+	m.generation++, m.refits = 0, m.edits++;
 	const size_t n = mesh->triangleCount;
 	bool device_built = false;
 	if (c->builder == 1 && n > (size_t)BLAS_MAX_LEAF)
@@ -1208,7 +1249,7 @@ extern "C" int rfwhip_pose_mesh(rfwhip_context *c, size_t index, const float *jo
 		c->stats.animationTime = dm::event_ms(ea, eb);
 		dm::event_destroy(ea), dm::event_destroy(eb);
 	}
-	m.posed = true;
+	m.posed = true, m.edits++;
 	c->scene_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
 	return RFWHIP_OK;
 }
@@ -1298,7 +1339,7 @@ extern "C" int rfwhip_morph_mesh(rfwhip_context *c, size_t index, const float *w
 		c->stats.animationTime = dm::event_ms(ea, eb);
 		dm::event_destroy(ea), dm::event_destroy(eb);
 	}
-	m.posed = true;
+	m.posed = true, m.edits++;
 	c->scene_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
 	return RFWHIP_OK;
 }
@@ -1795,6 +1836,22 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 	sv.n_dir = c->lc.directionalLightCount;
 	c->scene_dirty = false;
 	c->scene_version++; // (the denoiser's guides are recomputed)
+	// which instances this update changed (transform, mesh, or the mesh's vertices): the temporal stage does not reproject them
+	c->dn_inst_ver.assign(c->instances.size(), 0u);
+	for (size_t i = 0; i < c->instances.size(); i++)
+	{
+		InstRec &in = c->instances[i];
+		const uint32_t edits = in.used && in.mesh < c->meshes.size() ? c->meshes[in.mesh].edits : 0u;
+		if (in.used != in.dn_used || (in.used && (in.mesh != in.dn_mesh || edits != in.dn_edits ||
+												  memcmp(in.transform, in.dn_transform, sizeof(in.transform)) != 0)))
+		{
+			in.dn_version = c->scene_version;
+			in.dn_used = in.used, in.dn_mesh = in.mesh, in.dn_edits = edits;
+			memcpy(in.dn_transform, in.transform, sizeof(in.transform));
+		}
+		c->dn_inst_ver[i] = (uint32_t)in.dn_version;
+	}
+	c->dn_inst_ver_stale = true; // (uploaded by the next temporal stage: whatever the order of update, init and the setting)
 	c->depth_stats_valid = false;
 	c->shadow_packets_auto_on = true; // (another scene: the packet form of the depth-0 connection wave gets its chance again)
 	return RFWHIP_OK;
@@ -1945,7 +2002,7 @@ static void fill_params(rfwhip_context *c, const rfwhip_camera *cam, rtk::Params
 	}
 	p.fr = c->fr;
 	p.fr.spp = (uint32_t)c->spp;
-	p.fr.sample_base = c->samples_done;
+	p.fr.sample_base = c->sample_origin + c->samples_done;
 	p.fr.probe_pixel = c->probe_y * c->W + c->probe_x;
 	p.max_depth = (uint32_t)c->max_depth;
 	p.parity_no_jitter = c->jitter == 1;
@@ -2173,6 +2230,10 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	{
 		RF_TRY(dm::zero(c->d_acc.p, (size_t)c->fr.local_rows * c->W * sizeof(f4), s0));
 		c->samples_done = 0;
+		// decorrelated reset frames for the denoiser's temporal stage: the sample indices go on where the last frame's ended
+		// (mod 256: the blue-noise sampler's table)
+		c->sample_origin = c->dn_temporal ? (uint32_t)(c->samples_total % 256u) : 0u;
+		c->dn_reset_since = true;
 	}
 	const uint32_t packets = (c->W / 4u) * (c->H / 2u);
 	if (c->integrator == 0 && c->jitter == 0)
@@ -2251,7 +2312,7 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		if (i > 0)
 			p.wv.counters = c->d_counters_sub[i].as<rt::WaveCounters>();
 		p.fr.spp = spp_i;
-		p.fr.sample_base = c->samples_done + s_begin;
+		p.fr.sample_base = c->sample_origin + c->samples_done + s_begin;
 		const uint32_t n = c->fr.slots * spp_i;
 		// packet form of the depth-0 connection wave: where the packet traversal can run (float node table, trees within its stack),
 		// a wave's shadow rays are neighbours (sample groups of >= 8) and the batch's slots leave room for the light's bin
@@ -2389,6 +2450,7 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	c->subs_last = subs, c->subs_first = first_slot;
 	c->last_wave_off = alternate ? (paths + pad) * par : 0;
 	c->samples_done += (uint32_t)c->spp;
+	c->samples_total += (uint64_t)c->spp, c->frame_serial++;
 	c->totals.samples += (uint64_t)c->W * c->H * (uint64_t)c->spp / (uint64_t)c->world;
 	c->last_cam = *cam, c->have_last_cam = true; // (the denoiser's guide pass traces this camera's centre rays)
 	return RFWHIP_OK;
@@ -2563,6 +2625,26 @@ static int dn_ensure(rfwhip_context *c)
 	RF_TRY(c->d_dn_guides.ensure_exact(2 * px * sizeof(f4) + sizeof(f4))); // (+ the guide pass's stack-overflow counter)
 	RF_TRY(c->d_dn_img.ensure_exact(2 * px * sizeof(f4)));
 	RF_TRY(c->d_dn_var.ensure_exact(2 * px * sizeof(float)));
+	if (c->dn_temporal)
+	{
+		RF_TRY(c->d_dn_prev.ensure_exact(px * sizeof(f4)));
+		RF_TRY(c->d_dn_ids.ensure_exact(2 * px * sizeof(uint32_t)));
+		RF_TRY(c->d_dn_hist.ensure_exact(2 * px * (sizeof(f4) + 3 * sizeof(float))));
+	}
+	return 0;
+}
+
+// per instance: the scene version of the update that last changed it (the temporal stage's instance test).  Uploaded on the
+// stage's stream in front of it whenever the device copy is missing or stale, so the kernel never reads a table that is not there
+// (the host copy changes only in rfwhip_update, after sync_all: no stage in flight still reads the device copy)
+static int dn_inst_ver_current(rfwhip_context *c, void *stream)
+{
+	if (!c->dn_inst_ver_stale && c->d_dn_inst_ver.p)
+		return 0;
+	const size_t n = c->dn_inst_ver.size();
+	RF_TRY(c->d_dn_inst_ver.ensure(std::max<size_t>(n, 1) * sizeof(uint32_t)));
+	RF_TRY(dm::h2d(c->d_dn_inst_ver.p, c->dn_inst_ver.data(), n * sizeof(uint32_t), stream));
+	c->dn_inst_ver_stale = false;
 	return 0;
 }
 
@@ -2578,7 +2660,41 @@ static rtk::DnView dn_view(rfwhip_context *c, f4 *in, f4 *out)
 	d.sigma_l = c->dn_sigma_l, d.sigma_n = c->dn_sigma_n, d.sigma_z = c->dn_sigma_z;
 	d.iterations = (uint32_t)c->dn_iterations;
 	d.overflow = (uint32_t *)(d.gb + px);
+	d.id = c->dn_temporal ? c->d_dn_ids.as<uint32_t>() : nullptr;
+	d.hist = nullptr;
 	return d;
+}
+
+// the temporal stage's view: F = the last render, P = the stage record of the last presented frame; history set rd -> wr
+static rtk::DnTemporal dn_temporal_view(rfwhip_context *c, const rtk::Params &p, int rd, int wr)
+{
+	rtk::DnTemporal t;
+	const size_t px = (size_t)c->W * c->H;
+	t.cam = p.cam, t.pcam = c->dn_t_pcam, t.fr = p.fr;
+	t.pgb = c->d_dn_prev.as<f4>();
+	t.id = c->d_dn_ids.as<uint32_t>(), t.pid = t.id + px;
+	t.inst_ver = c->d_dn_inst_ver.as<uint32_t>(), t.n_inst = (uint32_t)c->dn_inst_ver.size(), t.pscene = c->dn_t_pscene;
+	float *const mom = (float *)(c->d_dn_hist.as<f4>() + 2 * px), *const n = mom + 4 * px;
+	t.col_in = c->d_dn_hist.as<f4>() + (size_t)rd * px;
+	t.mom_in = mom + (size_t)rd * 2 * px, t.n_in = n + (size_t)rd * px;
+	t.mom_out = mom + (size_t)wr * 2 * px, t.n_out = n + (size_t)wr * px;
+	t.alpha = c->dn_alpha, t.usable = c->dn_t_usable ? 1u : 0u;
+	return t;
+}
+static f4 *dn_hist_colour(rfwhip_context *c, int set) { return c->d_dn_hist.as<f4>() + (size_t)set * c->W * c->H; }
+
+// P's guides (normal | z | gradient) and instance ids are kept before anything overwrites them for a new frame: only while a frame
+// rendered after P waits to be presented (a guide pass for P itself — after an rfwhip_update — is not P's history)
+static int dn_save_prev(rfwhip_context *c, void *stream)
+{
+	if (!c->dn_have_pres || !c->dn_guides_pres || c->frame_serial == c->dn_pres_serial ||
+		(c->dn_prev_ok && c->dn_saved_serial == c->dn_pres_serial))
+		return 0;
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(dm::d2d(c->d_dn_prev.p, c->d_dn_guides.as<f4>() + px, px * sizeof(f4), stream));
+	RF_TRY(dm::d2d(c->d_dn_ids.as<uint32_t>() + px, c->d_dn_ids.p, px * sizeof(uint32_t), stream));
+	c->dn_prev_ok = true, c->dn_saved_serial = c->dn_pres_serial;
+	return 0;
 }
 
 // the guides of the full image for the camera of the last render, unless they are current (camera by value, scene, size)
@@ -2594,6 +2710,8 @@ static int dn_guides(rfwhip_context *c, void *stream)
 		return 0;
 	if (c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "denoise: the guides must be traced, but the scene changed since the last rfwhip_update()");
+	if (c->dn_temporal)
+		RF_TRY(dn_save_prev(c, stream));
 	rtk::Params p;
 	fill_params(c, &c->last_cam, p);
 	const rtk::DnView d = dn_view(c, nullptr, nullptr);
@@ -2603,6 +2721,7 @@ static int dn_guides(rfwhip_context *c, void *stream)
 	t.stop(2);
 	RF_TRY(dm::last_launch_error());
 	c->guides_valid = true, c->guide_cam = c->last_cam, c->guide_scene = c->scene_version, c->guide_W = c->W, c->guide_H = c->H;
+	c->dn_guides_pres = false;
 	return 0;
 }
 
@@ -2616,14 +2735,49 @@ static int dn_check_overflow(rfwhip_context *c)
 	return 0;
 }
 
-// filter the full image `in` (W x H float4 on this context's device) into `out` (may be `in`), enqueued on `stream`
-static int dn_filter(rfwhip_context *c, f4 *in, f4 *out, void *stream)
+// filter the full image `in` (W x H float4 on this context's device) into `out` (may be `in`), enqueued on `stream`.  `presented`:
+// the image of the last render handed out (world-1 read, group / comm gather): the temporal stage runs when it is on — once per
+// frame with a new history set; a further read of the same frame runs it again from the same history into the same set
+static int dn_filter(rfwhip_context *c, f4 *in, f4 *out, void *stream, bool presented)
 {
+	if (!presented || !c->dn_temporal)
+	{
+		RF_TRY(dn_guides(c, stream));
+		StageTimer t(c, KF_DENOISE, -1, stream);
+		rtk::launch_denoise_filter(dn_view(c, in, out), nullptr, stream);
+		t.stop(1 + c->dn_iterations);
+		return dm::last_launch_error();
+	}
+	RF_TRY(dn_ensure(c));
+	const bool new_frame = !c->dn_have_pres || c->frame_serial != c->dn_pres_serial;
+	if (new_frame)
+		RF_TRY(dn_save_prev(c, stream)); // (before the guide pass of F may overwrite P's guides)
 	RF_TRY(dn_guides(c, stream));
+	rtk::Params p;
+	fill_params(c, &c->last_cam, p);
+	if (new_frame)
+	{
+		// the history is usable after a RESET since P, at P's size, with P's guides kept
+		c->dn_t_usable = c->dn_have_pres && c->dn_prev_ok && c->dn_saved_serial == c->dn_pres_serial && c->dn_reset_since &&
+						 c->dn_pres_W == c->W && c->dn_pres_H == c->H;
+		c->dn_t_pcam = c->dn_pres_cam, c->dn_t_pscene = c->dn_pres_scene;
+	}
+	const int rd = new_frame ? c->dn_hist_cur : c->dn_hist_cur ^ 1, wr = rd ^ 1;
+	RF_TRY(dn_inst_ver_current(c, stream));
+	rtk::DnView d = dn_view(c, in, out);
+	d.hist = dn_hist_colour(c, wr);
+	const rtk::DnTemporal tv = dn_temporal_view(c, p, rd, wr);
 	StageTimer t(c, KF_DENOISE, -1, stream);
-	rtk::launch_denoise_filter(dn_view(c, in, out), stream);
-	t.stop(1 + c->dn_iterations);
-	return dm::last_launch_error();
+	rtk::launch_denoise_filter(d, &tv, stream);
+	t.stop(2 + c->dn_iterations);
+	RF_TRY(dm::last_launch_error());
+	if (new_frame)
+	{
+		c->dn_hist_cur = wr, c->dn_have_pres = true, c->dn_pres_serial = c->frame_serial;
+		c->dn_pres_cam = p.cam, c->dn_pres_scene = (uint32_t)c->guide_scene, c->dn_pres_W = c->W, c->dn_pres_H = c->H;
+		c->dn_guides_pres = true, c->dn_reset_since = false;
+	}
+	return 0;
 }
 
 // the root's side of a group / comm gather (rfwhip_group.cpp): the full image on `hip_stream`, in place, when denoise is on
@@ -2633,7 +2787,7 @@ int rfwhip_internal_denoise_stream(rfwhip_context *c, void *rgba_device, void *h
 	if (!c->denoise || !c->have_last_cam) // (nothing rendered yet: the accumulator is empty)
 		return RFWHIP_OK;
 	RF_TRY(ensure_sub_batches(c, 1)); // creates the hand-off events
-	RF_TRY(dn_filter(c, (f4 *)rgba_device, (f4 *)rgba_device, hip_stream));
+	RF_TRY(dn_filter(c, (f4 *)rgba_device, (f4 *)rgba_device, hip_stream, true));
 	RF_TRY(dm::event_record(c->ev_dn, hip_stream));
 	c->dn_pending = true;
 	return RFWHIP_OK;
@@ -2652,7 +2806,7 @@ extern "C" int rfwhip_read_framebuffer_device(rfwhip_context *c, void *rgba_devi
 	RF_TRY(present(c, (f4 *)rgba_device, 1));
 	if (c->denoise && c->have_last_cam) // (before the first render the accumulator is empty: nothing to filter, no camera to trace)
 	{
-		RF_TRY(dn_filter(c, (f4 *)rgba_device, (f4 *)rgba_device, c->stream));
+		RF_TRY(dn_filter(c, (f4 *)rgba_device, (f4 *)rgba_device, c->stream, true));
 		RF_TRY(dn_check_overflow(c));
 	}
 	return dm::sync(c->stream);
@@ -2775,7 +2929,7 @@ extern "C" int rfwhip_get_stats(rfwhip_context *c, rfwhip_render_stats *stats)
 	return RFWHIP_OK;
 }
 
-static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth"};
+static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth", "denoise_temporal", "denoise_alpha"};
 
 extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char *value)
 {
@@ -2908,7 +3062,32 @@ extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char
 			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise must be \"0\" or \"1\"");
 		if (v == "1" && c->W && c->rank == 0) // (the root filters the gathered image; other ranks never do)
 			RF_TRY(dn_ensure(c)); // (buffers of the full image: allocated when the setting is first turned on)
+		if (v == "1" && !c->denoise)
+			dn_clear_history(c);
 		c->denoise = v == "1";
+	}
+	else if (k == "denoise_temporal")
+	{
+		if (v != "0" && v != "1")
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_temporal must be \"0\" or \"1\"");
+		if (v == "1" && !c->dn_temporal)
+		{
+			RF_TRY(sync_all(c)); // (a stage in flight may still read the buffers this reallocates)
+			c->dn_temporal = 1;
+			dn_clear_history(c);
+			c->guides_valid = false; // (traced again with the instance ids)
+			if (c->W && c->rank == 0)
+				RF_TRY(dn_ensure(c));
+		}
+		c->dn_temporal = v == "1";
+	}
+	else if (k == "denoise_alpha")
+	{
+		char *end = nullptr;
+		const float f = strtof(value, &end);
+		if (!end || *end || !(f > 0.0f) || !(f <= 1.0f))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_alpha must be in (0, 1]");
+		c->dn_alpha = f;
 	}
 	else if (k == "denoise_iterations")
 	{
@@ -3001,6 +3180,10 @@ extern "C" int rfwhip_get_setting(rfwhip_context *c, const char *key, char *valu
 		snprintf(value, cap, "%g", c->dn_sigma_n);
 	else if (k == "denoise_sigma_depth")
 		snprintf(value, cap, "%g", c->dn_sigma_z);
+	else if (k == "denoise_temporal")
+		snprintf(value, cap, "%d", c->dn_temporal);
+	else if (k == "denoise_alpha")
+		snprintf(value, cap, "%g", c->dn_alpha);
 	else
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "unknown setting \"%s\"", key);
 	return RFWHIP_OK;
@@ -3099,6 +3282,66 @@ extern "C" int rfwhip_read_denoise_guides(rfwhip_context *c, float *albedo, floa
 	return RFWHIP_OK;
 }
 
+extern "C" int rfwhip_read_denoise_history(rfwhip_context *c, float *pre_rgbl, float *var, float *hist_rgbl, float *moments, float *length)
+{
+	CTX_ENTER(c);
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	if (c->world != 1)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_denoise_history: world-1 contexts only (a group's root filters gathered images)");
+	if (!c->denoise || !c->dn_temporal || !c->dn_have_pres || c->frame_serial != c->dn_pres_serial)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_denoise_history: the last render has not been presented with denoise and "
+											"denoise_temporal on");
+	RF_TRY(sync_all(c));
+	// the stage of the presented frame once more, from the same history into the same set (the bits it wrote), for I~ and var
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
+	RF_TRY(present(c, c->d_present.as<f4>(), 1));
+	RF_TRY(dn_guides(c, c->stream));
+	rtk::Params p;
+	fill_params(c, &c->last_cam, p);
+	const int wr = c->dn_hist_cur, rd = wr ^ 1;
+	RF_TRY(dn_inst_ver_current(c, c->stream));
+	rtk::DnView d = dn_view(c, c->d_present.as<f4>(), c->d_present.as<f4>());
+	d.hist = dn_hist_colour(c, wr);
+	{
+		StageTimer t(c, KF_DENOISE, -1, c->stream);
+		rtk::launch_denoise_temporal(d, dn_temporal_view(c, p, rd, wr), c->stream);
+		t.stop(2);
+	}
+	RF_TRY(dm::last_launch_error());
+	const rtk::DnTemporal tv = dn_temporal_view(c, p, rd, wr);
+	std::vector<f4> img(px), col(px);
+	std::vector<float> v(px), mom(2 * px), n(px);
+	RF_TRY(dm::d2h(img.data(), d.img[0], px * sizeof(f4), c->stream));
+	RF_TRY(dm::d2h(v.data(), d.var[0], px * sizeof(float), c->stream));
+	RF_TRY(dm::d2h(col.data(), d.hist, px * sizeof(f4), c->stream));
+	RF_TRY(dm::d2h(mom.data(), tv.mom_out, 2 * px * sizeof(float), c->stream));
+	RF_TRY(dm::d2h(n.data(), tv.n_out, px * sizeof(float), c->stream));
+	RF_TRY(dm::sync(c->stream));
+	// (invalid pixels: the stage writes no I~ / var; 0 here)
+	std::vector<f4> gb(px);
+	RF_TRY(dm::d2h(gb.data(), c->d_dn_guides.as<f4>() + px, px * sizeof(f4), c->stream));
+	for (size_t i = 0; i < px; i++)
+	{
+		const bool valid = gb[i].y >= 0.0f;
+		for (int k = 0; k < 4; k++)
+		{
+			if (pre_rgbl)
+				pre_rgbl[4 * i + k] = valid ? (&img[i].x)[k] : 0.0f;
+			if (hist_rgbl)
+				hist_rgbl[4 * i + k] = (&col[i].x)[k];
+		}
+		if (var)
+			var[i] = valid ? v[i] : 0.0f;
+		if (moments)
+			moments[2 * i] = mom[2 * i], moments[2 * i + 1] = mom[2 * i + 1];
+		if (length)
+			length[i] = n[i];
+	}
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_denoise_image(rfwhip_context *c, const float *rgba_in, float *rgba_out)
 {
 	CTX_ENTER(c);
@@ -3112,7 +3355,7 @@ extern "C" int rfwhip_denoise_image(rfwhip_context *c, const float *rgba_in, flo
 	const size_t bytes = (size_t)c->W * c->H * sizeof(f4);
 	RF_TRY(c->d_present.ensure(bytes));
 	RF_TRY(dm::h2d(c->d_present.p, rgba_in, bytes, c->stream));
-	RF_TRY(dn_filter(c, c->d_present.as<f4>(), c->d_present.as<f4>(), c->stream));
+	RF_TRY(dn_filter(c, c->d_present.as<f4>(), c->d_present.as<f4>(), c->stream, false)); // (spatial only: not a presented frame)
 	RF_TRY(dm::d2h(rgba_out, c->d_present.p, bytes, c->stream));
 	return dm::sync(c->stream);
 }

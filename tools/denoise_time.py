@@ -3,7 +3,12 @@ with hipEvents (stage_timing=1, kernel family 6).  One JSON line per variant:
   filter   a still camera: the guides are computed once, every present runs demodulation + the a-trous passes
   guides   the camera moves a little every frame: every present runs the guide pass too
   frame    wall time of a 1-spp frame (render + wait + present into device memory) with denoise off and on
-Usage: python tools/denoise_time.py [frames=200] [iterations=5]"""
+With --temporal ("denoise_temporal" = 1) instead:
+  temporal the camera pans every frame, RESET every frame: every present runs the guide pass, the demodulation, the temporal
+           stage and the a-trous passes; TEMPORAL_BYTES is the stage's estimated traffic per pixel (the kernel's own time:
+           a rocprofv3 --kernel-trace --stats run of this tool, k_dn_temporal)
+  frame    wall time of such a frame with denoise off and with denoise + denoise_temporal on
+Usage: python tools/denoise_time.py [--temporal] [frames=200] [iterations=5]"""
 import json
 import os
 import sys
@@ -22,11 +27,44 @@ PIXELS = W * H
 # written: irradiance 16 + variance 4 (the last pass: the image, 16).  Unique per pass: the five planes once.
 TAP_BYTES = 25 * 36 + 9 * 4 + 16 + 16 + 20
 UNIQUE_BYTES = 16 + 4 + 16 + 16 + 16 + 20
+# bytes the temporal stage names per pixel: the demodulation's I 16, guide 16, id 4, and per bilinear tap P's guide 16 + id 4 + colour
+# 16 + moments 8 + length 4; written: I~ 16, var 4, moments 8, length 4, and pass 0's colour history 16
+TEMPORAL_BYTES = 16 + 16 + 4 + 4 * (16 + 4 + 16 + 8 + 4) + 16 + 4 + 8 + 4 + 16
+
+
+def temporal(pkg, ctx, scene, out, frames):
+    ctx.set_setting("denoise_temporal", 1)
+    base = scene.camera.position
+
+    def run(n):
+        for f in range(n):
+            scene.camera.position = (base[0] + 0.05 * (f % 40), base[1], base[2])  # a slow pan, RESET every frame
+            ctx.render_frame(scene.camera, pkg.RESET)
+            ctx.read_framebuffer_device(out.data_ptr())
+        ctx.wait()
+
+    run(10)
+    ctx.get_kernel_time("denoise", reset=True)
+    run(frames)
+    ms, launches = ctx.get_kernel_time("denoise", reset=True)
+    print(json.dumps({"variant": "temporal", "frames": frames, "launches": launches, "denoise_ms_per_frame": round(ms / frames, 4),
+                      "temporal_bytes_per_pixel_est": TEMPORAL_BYTES, "temporal_bytes_est": PIXELS * TEMPORAL_BYTES}), flush=True)
+    ctx.set_setting("stage_timing", 0)
+    for dn in (0, 1):
+        ctx.set_setting("denoise", dn)
+        run(10)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(frames)
+        torch.cuda.synchronize()
+        print(json.dumps({"variant": "frame", "denoise": dn, "denoise_temporal": dn, "frames": frames,
+                          "ms_per_frame": round((time.perf_counter() - t0) * 1e3 / frames, 4)}), flush=True)
 
 
 def main():
-    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    iterations = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    args = [a for a in sys.argv[1:] if a != "--temporal"]
+    frames = int(args[0]) if len(args) > 0 else 200
+    iterations = int(args[1]) if len(args) > 1 else 5
     pkg = load_package()
     scene = pkg.scenes.terrain(width=W, height_px=H)
     ctx = pkg.RenderContext(device=0)
@@ -35,6 +73,8 @@ def main():
     for k, v in dict(integrator="pt", spp=1, stage_timing=1, denoise=1, denoise_iterations=iterations).items():
         ctx.set_setting(k, v)
     out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda:0")
+    if "--temporal" in sys.argv[1:]:
+        return temporal(pkg, ctx, scene, out, frames)
     cam = scene.camera
 
     def run(n, moving):
