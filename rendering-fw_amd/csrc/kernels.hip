@@ -31,6 +31,7 @@
 // SIMD's turn each, tools/dev/micro/inst_rate5.hip) the packet kernels, HBM traffic the shade kernel.
 #include "kernels.h"
 #include "rt_core.h"
+#include "emu_streams.h" // (the deferred-stream variant of the emulation build; empty otherwise)
 
 #include <string.h>
 #include <algorithm>

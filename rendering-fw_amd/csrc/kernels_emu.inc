@@ -4,14 +4,29 @@
 // includes this file's contents.  Included by kernels.hip inside namespace rtk.
 // ================================================================================================================
 
+struct Rng4
+{
+	uint32_t v[4];
+};
+
 void set_device_cus(int) {}
 uint32_t max_lds_nodes() { return MAX_LDS_NODES; }
-void launch_init_counters(WaveCounters *c, uint32_t primary_count, stream_t) { init_counters_item(c, primary_count, 0u, 1u); }
-void launch_set_ext_count(WaveCounters *c, uint32_t depth, uint32_t count, stream_t) { c->ext[depth] = c->ext_n[depth] = count; }
+void launch_init_counters(WaveCounters *c, uint32_t primary_count, stream_t s)
+{
+	EMU_DEFER(s, launch_init_counters(c, primary_count, s));
+	init_counters_item(c, primary_count, 0u, 1u);
+}
+void launch_set_ext_count(WaveCounters *c, uint32_t depth, uint32_t count, stream_t s)
+{
+	EMU_DEFER(s, launch_set_ext_count(c, depth, count, s));
+	c->ext[depth] = c->ext_n[depth] = count;
+}
 
 void launch_rng_states(uint32_t *states, const uint32_t base_state[4], const uint32_t *jump_table,
-					   uint32_t packets_per_sample, uint32_t spp, stream_t)
+					   uint32_t packets_per_sample, uint32_t spp, stream_t s)
 {
+	const Rng4 base{{base_state[0], base_state[1], base_state[2], base_state[3]}}; // (a host array: taken at enqueue)
+	EMU_DEFER(s, launch_rng_states(states, base.v, jump_table, packets_per_sample, spp, s));
 	const uint32_t total = packets_per_sample * spp;
 	for (uint32_t r = 0; r < (total + RNG_RUN - 1) / RNG_RUN; r++)
 		rng_states_item(states, base_state, jump_table, total, r);
@@ -273,8 +288,9 @@ template <bool COUNT> void primary(const Params &p, uint32_t count)
 
 bool primary_packet_form(const Params &, uint32_t) { return false; } // (the emulation keeps no group flags: every record is read)
 
-void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t)
+void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s)
 {
+	EMU_DEFER(s, launch_extend(p, gen, count, max_items, s));
 	if (gen == GEN_PT && (p.refill & 8u) && (p.fr.sgroup_log2 >= 1u || max_items >= (16u << 20))) // (the device's rule)
 	{
 		count ? packet_emu::primary<true>(p, max_items) : packet_emu::primary<false>(p, max_items);
@@ -294,15 +310,17 @@ void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, str
 			count ? extend_item<GEN_PARITY, true>(p, i, true, ctx) : extend_item<GEN_PARITY, false>(p, i, true, ctx);
 	}
 }
-void launch_shade_parity(const Params &p, bool count, uint32_t max_items, stream_t)
+void launch_shade_parity(const Params &p, bool count, uint32_t max_items, stream_t s)
 {
+	EMU_DEFER(s, launch_shade_parity(p, count, max_items, s));
 	Ctx ctx(p);
 	for (uint32_t i = 0; i < max_items; i++)
 		count ? shade_parity_item<true>(p, i, true, ctx) : shade_parity_item<false>(p, i, true, ctx);
 }
 uint32_t queue_pad(uint32_t) { return 0u; }
-void launch_shade_pt(const Params &p, uint32_t, stream_t)
+void launch_shade_pt(const Params &p, uint32_t max_items, stream_t s)
 {
+	EMU_DEFER(s, launch_shade_pt(p, max_items, s));
 	Ctx ctx;
 	const uint32_t n = p.wv.counters->ext_n[p.depth];
 	const f4 *const hits = p.depth == 0 ? p.wv.hit0 : p.wv.hit;
@@ -326,8 +344,9 @@ void launch_shade_pt(const Params &p, uint32_t, stream_t)
 	}
 	p.wv.counters->ext[p.depth + 1] += ctx.q_ext.rays, p.wv.counters->shadow[p.depth] += ctx.q_shadow.rays;
 }
-void launch_connect(const Params &p, bool count, uint32_t, stream_t)
+void launch_connect(const Params &p, bool count, uint32_t max_items, stream_t s)
 {
+	EMU_DEFER(s, launch_connect(p, count, max_items, s));
 	Ctx ctx(p);
 	const uint32_t n = connection_count(p.wv.counters, p.depth);
 	if (n == 0u && p.depth == 0 && p.wv.rad_nee)
@@ -336,29 +355,41 @@ void launch_connect(const Params &p, bool count, uint32_t, stream_t)
 	for (uint32_t i = 0; i < n; i++)
 		count ? connect_item<true>(p, i, true, ctx) : connect_item<false>(p, i, true, ctx);
 }
-void launch_shadow_packets(const Params &p, bool count, uint32_t max_items, stream_t s) { launch_connect(p, count, max_items, s); } // (same answers per ray)
+void launch_shadow_packets(const Params &p, bool count, uint32_t max_items, stream_t s)
+{
+#if defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
+	if (emu_streams::deferring())
+		emu_streams::state().shadow_packet_launches++; // (rfwhip_emu_schedule_stats: the packet form really was chosen)
+#endif
+	launch_connect(p, count, max_items, s); // (same answers per ray)
+}
 void launch_trace_fused(const Params &pe, const Params &pa, bool count, uint32_t max_items, stream_t s)
 {
+	EMU_DEFER(s, launch_trace_fused(pe, pa, count, max_items, s)); // (one launch: its two waves run together)
 	launch_extend(pe, GEN_BUFFER, count, max_items, s);
 	launch_connect(pa, count, max_items, s);
 }
-void launch_resolve(const Params &p, stream_t)
+void launch_resolve(const Params &p, stream_t s)
 {
+	EMU_DEFER(s, launch_resolve(p, s));
 	for (uint32_t i = 0; i < p.fr.W * p.fr.local_rows; i++)
 		resolve_item(p, i);
 }
-void launch_present(const Params &p, f4 *out, float scale, int full, stream_t)
+void launch_present(const Params &p, f4 *out, float scale, int full, stream_t s)
 {
+	EMU_DEFER(s, launch_present(p, out, scale, full, s));
 	for (uint32_t i = 0; i < p.fr.W * p.fr.local_rows; i++)
 		present_item(p, out, scale, full, i);
 }
-void launch_deinterleave(const f4 *gathered, f4 *out, uint32_t W, uint32_t H, uint32_t local_rows, uint32_t world, stream_t)
+void launch_deinterleave(const f4 *gathered, f4 *out, uint32_t W, uint32_t H, uint32_t local_rows, uint32_t world, stream_t s)
 {
+	EMU_DEFER(s, launch_deinterleave(gathered, out, W, H, local_rows, world, s));
 	for (uint32_t i = 0; i < W * H; i++)
 		deinterleave_item(gathered, out, W, H, local_rows, world, i);
 }
-void launch_denoise_guides(const Params &p, const DnView &d, stream_t)
+void launch_denoise_guides(const Params &p, const DnView &d, stream_t s)
 {
+	EMU_DEFER(s, launch_denoise_guides(p, d, s));
 	Ctx ctx(p);
 	ctx.stk.overflow = d.overflow;
 	for (uint32_t i = 0; i < d.W * d.H; i++)
@@ -366,8 +397,9 @@ void launch_denoise_guides(const Params &p, const DnView &d, stream_t)
 	for (uint32_t i = 0; i < d.W * d.H; i++)
 		dn_gradient_item(d, i);
 }
-void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t)
+void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t s)
 {
+	EMU_DEFER(s, launch_denoise_temporal(d, t, s));
 	for (uint32_t i = 0; i < d.W * d.H; i++)
 		dn_demod_item(d, d.img[0], d.var[0], i);
 	for (uint32_t i = 0; i < d.W * d.H; i++)
@@ -375,6 +407,9 @@ void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t)
 }
 void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s)
 {
+	const DnTemporal tv = t ? *t : DnTemporal{}; // (a host record: taken at enqueue)
+	const bool has_t = t != nullptr;
+	EMU_DEFER(s, launch_denoise_filter(d, has_t ? &tv : nullptr, s));
 	if (t)
 		launch_denoise_temporal(d, *t, s);
 	else
@@ -384,47 +419,55 @@ void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s)
 		for (uint32_t i = 0; i < d.W * d.H; i++)
 			dn_pass_item(d, 1u << k, k + 1u == d.iterations, d.img[k & 1u], d.var[k & 1u], d.img[(k + 1u) & 1u], d.var[(k + 1u) & 1u], i);
 }
-void launch_kat(const Params &p, int function, const float *in, float *out, uint32_t n, stream_t)
+void launch_kat(const Params &p, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
+	EMU_DEFER(s, launch_kat(p, function, in, out, n, s));
 	float pot[POT_SLOTS];
 	for (uint32_t i = 0; i < n; i++)
 		kat_item(p, function, in, out, i, pot);
 }
 void launch_skin_vertices(f4 *verts, f4 *vnormals, const f4 *base_verts, const f4 *base_normals, const uint32_t *joints4,
-						  const f4 *weights4, const float *mats, uint32_t joint_count, uint32_t vertex_count, stream_t)
+						  const f4 *weights4, const float *mats, uint32_t joint_count, uint32_t vertex_count, stream_t s)
 {
+	EMU_DEFER(s, launch_skin_vertices(verts, vnormals, base_verts, base_normals, joints4, weights4, mats, joint_count, vertex_count, s));
 	for (uint32_t i = 0; i < vertex_count; i++)
 		skin_vertex_item(verts, vnormals, base_verts, base_normals, joints4, weights4, mats, joint_count, i);
 }
 void launch_morph_vertices(f4 *verts, f4 *vnormals, const f4 *base_verts, const f4 *base_normals, const f4 *tgt_pos,
-						   const f4 *tgt_nrm, const float *weights, uint32_t target_count, uint32_t vertex_count, stream_t)
+						   const f4 *tgt_nrm, const float *weights, uint32_t target_count, uint32_t vertex_count, stream_t s)
 {
+	EMU_DEFER(s, launch_morph_vertices(verts, vnormals, base_verts, base_normals, tgt_pos, tgt_nrm, weights, target_count, vertex_count, s));
 	for (uint32_t i = 0; i < vertex_count; i++)
 		morph_vertex_item(verts, vnormals, base_verts, base_normals, tgt_pos, tgt_nrm, weights, target_count, vertex_count, i);
 }
-void launch_skin_shade(TriShade *shade, const f4 *verts, const f4 *vnormals, const uint32_t *indices, uint32_t tri_count, stream_t)
+void launch_skin_shade(TriShade *shade, const f4 *verts, const f4 *vnormals, const uint32_t *indices, uint32_t tri_count, stream_t s)
 {
+	EMU_DEFER(s, launch_skin_shade(shade, verts, vnormals, indices, tri_count, s));
 	for (uint32_t i = 0; i < tri_count; i++)
 		skin_shade_item(shade, verts, vnormals, indices, i);
 }
-void launch_stamp_instance(f4 *tri_verts, uint32_t tri_count, uint32_t instance, stream_t)
+void launch_stamp_instance(f4 *tri_verts, uint32_t tri_count, uint32_t instance, stream_t s)
 {
+	EMU_DEFER(s, launch_stamp_instance(tri_verts, tri_count, instance, s));
 	for (uint32_t i = 0; i < tri_count; i++)
 		tri_verts[3ull * i + 1].w = ubits(instance);
 }
-void launch_refresh4(Node4c *nodes4, const uint32_t *src4, uint32_t count4, const Node *blas_nodes2, stream_t)
+void launch_refresh4(Node4c *nodes4, const uint32_t *src4, uint32_t count4, const Node *blas_nodes2, stream_t s)
 {
+	EMU_DEFER(s, launch_refresh4(nodes4, src4, count4, blas_nodes2, s));
 	for (uint32_t i = 0; i < count4; i++)
 		refresh4_item(nodes4, src4, blas_nodes2, i);
 }
-void launch_expand4(const Node4c *nodes4, Node4f *out, uint32_t count4, stream_t)
+void launch_expand4(const Node4c *nodes4, Node4f *out, uint32_t count4, stream_t s)
 {
+	EMU_DEFER(s, launch_expand4(nodes4, out, count4, s));
 	for (uint32_t i = 0; i < count4; i++)
 		expand4_item(nodes4, out, i);
 }
 void launch_refit(Node *all_nodes, uint32_t node_base, const int *parents, uint32_t node_count, f4 *tri_verts,
-				  uint32_t tri_base, const f4 *verts, const uint32_t *indices, uint32_t tri_count, uint32_t *flags, stream_t)
+				  uint32_t tri_base, const f4 *verts, const uint32_t *indices, uint32_t tri_count, uint32_t *flags, stream_t s)
 {
+	EMU_DEFER(s, launch_refit(all_nodes, node_base, parents, node_count, tri_verts, tri_base, verts, indices, tri_count, flags, s));
 	for (uint32_t i = 0; i < tri_count; i++)
 		refit_tris_item(tri_verts + 3ull * tri_base, verts, indices, i);
 	memset(flags, 0, sizeof(uint32_t) * node_count);

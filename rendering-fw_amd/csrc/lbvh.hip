@@ -21,6 +21,7 @@
 // The host builder of bvh_build.cpp stays the default; this one is for meshes whose topology changes.
 #include "kernels.h"
 #include "rt_core.h"
+#include "emu_streams.h" // (the deferred-stream variant of the emulation build; empty otherwise)
 
 #include <stdint.h>
 #include <string.h>
@@ -593,9 +594,26 @@ void launch_rebase(Node *nodes, uint32_t node_count, uint32_t node_base, Node4c 
 
 size_t device_build_scratch_bytes(uint32_t) { return 64; }
 
-int launch_device_build(const f4 *verts, const uint32_t *indices, uint32_t tri_count, void *, size_t, Node *nodes, int *parents,
-						uint32_t *flags, Node4c *nodes4, uint32_t *src4, f4 *tri_verts, DeviceBuildResult *out, stream_t)
+int launch_device_build(const f4 *verts, const uint32_t *indices, uint32_t tri_count, void *scratch, size_t scratch_bytes, Node *nodes,
+						int *parents, uint32_t *flags, Node4c *nodes4, uint32_t *src4, f4 *tri_verts, DeviceBuildResult *out, stream_t s)
 {
+#if defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
+	if (emu_streams::deferring())
+	{
+		// enqueued on `s` behind the uploads of its vertices; the record comes back to the host, so the call waits for it
+		auto rc = std::make_shared<int>(0);
+		auto res = std::make_shared<DeviceBuildResult>();
+		emu_streams::enqueue(s, [=]() {
+			*rc = launch_device_build(verts, indices, tri_count, scratch, scratch_bytes, nodes, parents, flags, nodes4, src4, tri_verts,
+									  res.get(), s);
+		});
+		emu_streams::sync(s);
+		*out = *res;
+		return *rc;
+	}
+#else
+	(void)scratch, (void)scratch_bytes, (void)s;
+#endif
 	const uint32_t n = tri_count;
 	if (n < 2u)
 		return 1;
@@ -683,8 +701,9 @@ int launch_device_build(const f4 *verts, const uint32_t *indices, uint32_t tri_c
 }
 
 void launch_rebase(Node *nodes, uint32_t node_count, uint32_t node_base, Node4c *nodes4, uint32_t n4_count, uint32_t n4_base,
-				   uint32_t tri_base, stream_t)
+				   uint32_t tri_base, stream_t s)
 {
+	EMU_DEFER(s, launch_rebase(nodes, node_count, node_base, nodes4, n4_count, n4_base, tri_base, s));
 	for (uint32_t i = 0; i < node_count; i++)
 		rebase_node_item(nodes, node_base, tri_base, i);
 	for (uint32_t i = 0; i < n4_count; i++)

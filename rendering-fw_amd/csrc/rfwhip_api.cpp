@@ -26,6 +26,7 @@
 #if !defined(RFWHIP_HOST_EMULATION)
 #include <hip/hip_runtime.h>
 #endif
+#include "emu_streams.h" // (the deferred-stream variant of the emulation build; empty otherwise)
 
 using rt::f4;
 
@@ -182,6 +183,93 @@ static int stream_wait_event(void *s, event_t e)
 static int event_sync(event_t e)
 {
 	DM_CHECK(hipEventSynchronize(e));
+	return 0;
+}
+#elif defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
+// ---- host emulation with deferred streams (tests/emu, the _streams variant): emu_streams.h schedules every operation ----
+static int init(int, int *cus)
+{
+	*cus = 1;
+	return 0;
+}
+static int use(int) { return 0; }
+static int alloc(void **p, size_t bytes)
+{
+	*p = calloc(bytes ? bytes : 16, 1);
+	return *p ? 0 : set_error(RFWHIP_ERR_HIP, "out of memory");
+}
+static void release(void *p)
+{
+	if (!p)
+		return;
+	emu_streams::sync_all(); // (hipFree synchronises the device)
+	free(p);
+}
+static void mem_info(size_t *free_b, size_t *total_b) { *free_b = *total_b = ~(size_t)0; }
+static int h2d(void *d, const void *h, size_t n, void *s)
+{
+	if (n)
+		emu_streams::h2d(d, h, n, s);
+	return 0;
+}
+static int d2h(void *h, const void *d, size_t n, void *s)
+{
+	if (n)
+	{
+		emu_streams::copy(h, d, n, s);
+		emu_streams::sync(s);
+	}
+	return 0;
+}
+static int d2d(void *dst, const void *src, size_t n, void *s)
+{
+	if (n)
+		emu_streams::copy(dst, src, n, s);
+	return 0;
+}
+static int zero(void *d, size_t n, void *s)
+{
+	if (n)
+		emu_streams::enqueue(s, [d, n]() { memset(d, 0, n); });
+	return 0;
+}
+static int sync(void *s)
+{
+	emu_streams::sync(s);
+	return 0;
+}
+static int stream_create(void **s)
+{
+	*s = emu_streams::stream_create();
+	return 0;
+}
+static void stream_destroy(void *s)
+{
+	if (s)
+		emu_streams::stream_destroy(s);
+}
+static int last_launch_error() { return 0; }
+typedef emu_streams::Event *event_t;
+static int event_create(event_t *e)
+{
+	*e = emu_streams::event_create();
+	return 0;
+}
+static void event_destroy(event_t e) { emu_streams::destroy_event(e); }
+static int event_record(event_t e, void *s)
+{
+	emu_streams::record(e, s);
+	return 0;
+}
+static float event_ms(event_t a, event_t b) { return emu_streams::elapsed_ms(a, b); }
+static int stream_wait_event(void *s, event_t e)
+{
+	emu_streams::wait_event(s, e);
+	return 0;
+}
+static int event_sync(event_t e)
+{
+	emu_streams::sync_event(e);
 	return 0;
 }
 #else
@@ -2412,6 +2500,11 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 						RF_TRY(dm::event_record(c->ev_shade[i][d], s));
 						RF_TRY(dm::stream_wait_event(sc, c->ev_shade[i][d]));
 					}
+					if (sp_side_pending) // (not fused: the depth-0 connection wave on the side stream zeroes slots this wave adds into,
+					{					 // and reads the parity-0 shadow buffers shade(d + 1) rewrites; extend / shade of depth 1 overlap it)
+						RF_TRY(dm::stream_wait_event(s, c->ev_conn[i][0]));
+						sp_side_pending = false;
+					}
 					p.group = 16u, p.queue = queue++;
 					StageTimer tc(c, KF_CONNECT, -1, sc);
 					rtk::launch_connect(p, count, depth_items(c, n, d + 1, false), sc);
@@ -3623,3 +3716,31 @@ extern "C" int rfwhip_get_bvh4(rfwhip_context *c, size_t mesh_index, void *nodes
 	}
 	return RFWHIP_OK;
 }
+
+#if defined(RFWHIP_HOST_EMULATION) && defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
+// ---- the deferred-stream emulation library only (tests/test_schedule.py): not declared in rfwhip.h, not in the product ----
+// policy: 0 = in enqueue order, 1 = latest ready operation first, 2 = seeded random, 3 = latest first over everything enqueued
+// (emu_streams.h).  Runs everything still pending (in enqueue order) first and resets the counters of rfwhip_emu_schedule_stats.
+extern "C" RFWHIP_API int rfwhip_emu_set_schedule(int policy, unsigned seed)
+{
+	if (policy < emu_streams::INORDER || policy > emu_streams::EAGER)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_emu_set_schedule: unknown policy %d", policy);
+	emu_streams::state().policy = emu_streams::INORDER; // (what is still pending runs as the host issued it)
+	emu_streams::set_schedule(policy, seed);
+	return RFWHIP_OK;
+}
+// since the last rfwhip_emu_set_schedule: the closures run, how many of them ran while an operation enqueued before them and
+// needed by the same sync point had not run yet, and the launches of the packet form of the depth-0 connection wave
+extern "C" RFWHIP_API int rfwhip_emu_schedule_stats(unsigned long long *ran, unsigned long long *out_of_order,
+												   unsigned long long *shadow_packet_launches)
+{
+	const emu_streams::State &S = emu_streams::state();
+	if (ran)
+		*ran = S.ran;
+	if (out_of_order)
+		*out_of_order = S.out_of_order;
+	if (shadow_packet_launches)
+		*shadow_packet_launches = S.shadow_packet_launches;
+	return RFWHIP_OK;
+}
+#endif

@@ -33,6 +33,7 @@
 #else
 #include <stdlib.h>
 #endif
+#include "emu_streams.h" // (the deferred-stream variant of the emulation build; empty otherwise)
 
 #define GR_TRY(x)            \
 	do                       \
@@ -210,6 +211,79 @@ Rccl g_rccl;
 			return rfwhip_internal_set_error(RFWHIP_ERR_HIP, "RCCL: %s failed: %s (%s:%d)", #x, g_rccl.err(r_), __FILE__, __LINE__); \
 	} while (0)
 typedef ncclComm_t comm_t;
+#elif defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
+// host emulation with deferred streams (emu_streams.h): the same model as the contexts' streams
+int dev_use(int) { return 0; }
+int dev_alloc(void **p, size_t bytes)
+{
+	*p = calloc(bytes ? bytes : 16, 1);
+	return *p ? 0 : rfwhip_internal_set_error(RFWHIP_ERR_HIP, "out of memory");
+}
+void dev_free(void *p)
+{
+	if (!p)
+		return;
+	emu_streams::sync_all(); // (hipFree synchronises the device)
+	free(p);
+}
+int stream_create(void **s)
+{
+	*s = emu_streams::stream_create();
+	return 0;
+}
+void stream_destroy(void *s)
+{
+	if (s)
+		emu_streams::stream_destroy(s);
+}
+int stream_sync(void *s)
+{
+	emu_streams::sync(s);
+	return 0;
+}
+typedef emu_streams::Event *event_t;
+int event_create(event_t *e)
+{
+	*e = emu_streams::event_create();
+	return 0;
+}
+void event_destroy(event_t e) { emu_streams::destroy_event(e); }
+int event_record(event_t e, void *s)
+{
+	emu_streams::record(e, s);
+	return 0;
+}
+int stream_wait(void *s, event_t e)
+{
+	emu_streams::wait_event(s, e);
+	return 0;
+}
+int copy_async(void *dst, int, const void *src, int, size_t bytes, void *s)
+{
+	emu_streams::copy(dst, src, bytes, s);
+	return 0;
+}
+int copy_to_host(void *dst, const void *src, size_t bytes, void *s)
+{
+	emu_streams::copy(dst, src, bytes, s);
+	emu_streams::sync(s);
+	return 0;
+}
+int host_alloc(void **p, size_t bytes) { return dev_alloc(p, bytes); }
+void host_free(void *p) { dev_free(p); }
+int copy_to_host_async(void *dst, const void *src, size_t bytes, void *s)
+{
+	emu_streams::copy(dst, src, bytes, s);
+	return 0;
+}
+int event_sync(event_t e)
+{
+	emu_streams::sync_event(e);
+	return 0;
+}
+int device_count() { return 1 << 20; }
+void enable_peer(int, int) {}
+typedef void *comm_t;
 #else
 int dev_use(int) { return 0; }
 int dev_alloc(void **p, size_t bytes)

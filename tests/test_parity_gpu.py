@@ -566,16 +566,30 @@ def test_image_is_independent_of_how_calls_are_scheduled_gpu(pkg, make_hip, inte
     scene = pkg.scenes.cornell(480, 272)
     base = {"integrator": integrator, "spp": 4, "max_depth": 2}
     ref = _pipelined(pkg, make_hip(), scene, 480, 272, dict(base, ring=1, streams=1), 8, 1)
-    for extra, wait_every in (({"ring": 2}, 0), ({"ring": 4}, 0), ({"ring": 4}, 3), ({"ring": 4, "overlap": 1}, 0),
+    # the packet form of the depth-0 connection wave (sample groups >= 8, shadow_packets = 1): fused or not, on the connection
+    # stream or not, waited / pipelined / sub-batches / overlap; spp 32 for four sub-batches (8 samples each)
+    packet_rows = [] if integrator != "pt" else [
+        (dict(extra, spp=spp, max_depth=max_depth, shadow_packets=1, fuse=fuse, shadow_side=shadow_side), wait_every)
+        for fuse in (0, 1) for shadow_side in (0, 1) for max_depth in (2, 3)
+        for extra, wait_every, spp in (({"ring": 1}, 1, 16), ({"ring": 2}, 0, 16), ({"ring": 4}, 0, 16),
+                                       ({"streams": 2, "sub_batch_paths": 1}, 0, 16), ({"streams": 4, "sub_batch_paths": 1}, 1, 32),
+                                       ({"overlap": 0}, 1, 16), ({"overlap": 0, "ring": 4}, 0, 16), ({"overlap": 1, "ring": 2}, 0, 16))]
+    refs = {(base["spp"], base["max_depth"], None): ref}
+    for extra, wait_every in [({"ring": 2}, 0), ({"ring": 4}, 0), ({"ring": 4}, 3), ({"ring": 4, "overlap": 1}, 0),
                               ({"streams": 4, "sub_batch_paths": 1}, 0), ({"streams": 3, "sub_batch_paths": 1, "overlap": 1}, 2),
                               ({"sample_group": 1}, 0), ({"sample_group": 2, "ring": 2}, 0), ({"sample_group": 64}, 1),
                               ({"sample_group": 4, "streams": 2, "sub_batch_paths": 1}, 0),
                               # round 4: one launch per depth or two;
                               # the primary wave per lane instead of as a packet
                               ({"fuse": 0}, 0), ({"fuse": 0, "ring": 4, "overlap": 1}, 0), ({"fuse": 0, "ring": 2}, 2),
-                              ({"refill": 7, "sample_group": 64}, 0), ({"refill": 0}, 0)):
-        img = _pipelined(pkg, make_hip(), scene, 480, 272, dict(base, **extra), 8, wait_every)
-        assert np.array_equal(img, ref), (extra, wait_every)
+                              ({"refill": 7, "sample_group": 64}, 0), ({"refill": 0}, 0)] + packet_rows:
+        settings = dict(base, **extra)
+        key = (settings["spp"], settings["max_depth"], settings.get("shadow_packets"))
+        if key not in refs:  # (one ring entry, one stream, every call waited for)
+            plain = {k: settings[k] for k in ("integrator", "spp", "max_depth", "shadow_packets")}
+            refs[key] = _pipelined(pkg, make_hip(), scene, 480, 272, dict(plain, ring=1, streams=1), 8, 1)
+        img = _pipelined(pkg, make_hip(), scene, 480, 272, settings, 8, wait_every)
+        assert np.array_equal(img, refs[key]), (extra, wait_every)
 
 
 @pytest.mark.parametrize("name,jitter", [("cornell96x64_center", "center"), ("cornell96x64_xor128", "xor128"), ("cards96x64_center", "center"), ("lens96x64_xor128", "xor128")])
