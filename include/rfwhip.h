@@ -349,9 +349,31 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                  Root-only buffers, allocated when the setting is turned on: 16 B (P's guides) + 2 x 4 B (instance ids) +
  *                  2 x 28 B (history) per pixel.  rfwhip_denoise_image stays spatial-only.
  *   denoise_alpha = SVGF's alpha in (0, 1] for colour and moments (default 0.2)
+ *   sky_sampling = "0" (default: the sky is found only by BSDF-sampled rays that miss) | "1": the pt integrator's next-event
+ *                  estimation importance-samples the sky.  The table is built by rfwhip_update, or by the next render after the
+ *                  setting changed, from the sky of the last update, when the sky or the setting changed; it is allocated only
+ *                  while the setting is on (8 B per texel).  The parity integrator ignores it and sky_pick.
+ *                  TEXELS, as the pt integrator reads the sky: column i of W covers phi in [-pi + 2 pi i / W, -pi + 2 pi (i + 1) / W),
+ *                    phi = atan2(D.x, -D.z); row j of H covers theta in [pi j / H, pi (j + 1) / H), theta = acos(D.y);
+ *                    Omega_ij = (2 pi / W) (cos theta_j - cos theta_{j+1}); lum_ij = max(0, 0.2126 r + 0.7152 g + 0.0722 b)
+ *                    (NaN and negative texels weigh 0); S = sum lum_ij Omega_ij (in double); P_ij = lum_ij Omega_ij / S.
+ *                  DENSITY per steradian: pdf_sky(D) = lum(texel(D)) / S — 0 for a black texel and for a direction the
+ *                    integrator reads as black.
+ *                  SAMPLE: a texel (i, j) with probability P_ij (Walker / Vose alias table), then a, b uniform:
+ *                    phi = -pi + 2 pi (i + a) / W, cos theta = cos theta_j - b (cos theta_j - cos theta_{j+1}),
+ *                    D = (sin theta sin phi, cos theta, -sin theta cos phi).
+ *                  ESTIMATOR, p = the sky's share (sky_pick), at a non-specular vertex with throughput T and survival factor
+ *                    s = min(1, max(T)) (the one its BSDF continuation divides by): q1 < p samples the sky with (q0, q1 / p)
+ *                    (the bucket's row and column; the alias coin and a, b come from the path's hash state), else a light with
+ *                    (q0, (q1 - p) / (1 - p)) and pick probability (1 - p) pick;
+ *                    sky term = T f(L) Lsky(L) (N.L) / ((bsdf_pdf(L) + p pdf_sky(L)) s), shadow ray to t = 1e34;
+ *                    a BSDF-sampled miss after a non-specular vertex (depth >= 1) adds T Lsky(D) / (bsdfPdf + p pdf_sky(D));
+ *                    an emitter hit's light pdf takes the factor 1 - p.  After a specular vertex and at depth 0 nothing changes.
+ *                  p = 0 (sky_pick "0", no sky, or a sky whose S is 0) runs the default kernels: bit-identical to "0".
+ *   sky_pick = "-1" (default: auto, p = 1 when the scene has no lights, 0.5 otherwise) | a probability p in [0, 1]
  *   rfwhip_get_setting also answers read-only keys: "textured" (the textured shade kernel variant is in use), "packet" (the
  *   pt primary wave can run in packet form), "world_tree" (triangles in the world tree of the last update; 0: none),
- *   "shadow_bins_per_run", "shadow_packets_on".
+ *   "shadow_bins_per_run", "shadow_packets_on", "sky" (the last update left p > 0: the shade waves run the sky variant).
  * Returns the number of keys; fills up to cap pointers with static strings. */
 RFWHIP_API int rfwhip_set_setting(rfwhip_context *ctx, const char *key, const char *value);
 RFWHIP_API int rfwhip_get_setting(rfwhip_context *ctx, const char *key, char *value, size_t cap);

@@ -271,7 +271,11 @@ enum rfwhip_kat_function
 	RFWHIP_KAT_HASH = 9,			   /* tools.h:218-235, [0] = seed -> WangHash bits, RandomFloat, state bits */
 	RFWHIP_KAT_FASTDIV = 11,		   /* the slot -> pixel mapping's division by per-frame constants (rt_types.h: fast_div): [0..7] = four (n, d) pairs, n < 2^31, 0 < d < 2^31 (ints) -> four quotients (ints) */
 	RFWHIP_KAT_TEX_WRAP = 12,		   /* the wrap of a texel coordinate (getShadingData.h:33-41: `% width`, `% height`; rt_core.h: tex_wrap): [0..7] = four (x, w) pairs, 0 <= x < 2^31, 1 <= w < 2^31 (ints) -> four remainders (ints) */
-	RFWHIP_KAT_HALF_TO_FLOAT = 10	   /* half -> float as the shade kernels read materials (structs.h:88-117): [0..7] = 8 half bit patterns (ints) -> 8 floats */
+	RFWHIP_KAT_HALF_TO_FLOAT = 10,	   /* half -> float as the shade kernels read materials (structs.h:88-117): [0..7] = 8 half bit patterns (ints) -> 8 floats */
+	/* sky sampling on the table of the last rfwhip_update() with sky_sampling=1 (rt_core.h: sky_sample / sky_eval).  Both answer
+	 * [0..2] = the direction, [3] = the sampling density per steradian (lum / S), [4..6] = the radiance, [7] = the texel (int, -1: none) */
+	RFWHIP_KAT_SKY_SAMPLE = 13,		   /* [0..4] = u0, u1 (the bucket's row, column), coin (texel or alias), a, b (position in phi, cos theta) -> the texel drawn and a direction in it */
+	RFWHIP_KAT_SKY_PDF = 14			   /* [0..2] = D -> what pt_sky reads for D and the density there */
 };
 
 #ifdef __cplusplus

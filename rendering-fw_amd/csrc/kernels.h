@@ -80,7 +80,9 @@ void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, str
 bool primary_packet_form(const Params &p, uint32_t max_items); // the pt primary wave of such a launch fills WaveView::hit0_done
 void launch_shade_parity(const Params &p, bool count, uint32_t max_items, stream_t s);
 uint32_t queue_pad(uint32_t max_items); // extra slots per queue and launch for the void entries of unfinished blocks
-void launch_shade_pt(const Params &p, uint32_t max_items, stream_t s);
+// sky.pick > 0 (setting sky_sampling): the sky variant k_shade_pt_sky, which takes the table as an argument of its own (Params, and
+// with it every other kernel's code, stays what it was)
+void launch_shade_pt(const Params &p, const rt::SkyView &sky, uint32_t max_items, stream_t s);
 void launch_connect(const Params &p, bool count, uint32_t max_items, stream_t s);
 // the connection wave of depth 0 in packet form: runs of the shadow queue sorted by the chosen light's bin (FrameView::shadow_bins),
 // one wave-uniform occlusion traversal per 64 rays of the sorted order
@@ -89,7 +91,7 @@ void launch_shadow_packets(const Params &p, bool count, uint32_t max_items, stre
 void launch_trace_fused(const Params &pe, const Params &pa, bool count, uint32_t max_items, stream_t s);
 void launch_resolve(const Params &p, stream_t s);
 // rfwhip_kat: `function` (RFWHIP_KAT_*) on n records of 24 floats -> n records of 8 floats (device pointers)
-void launch_kat(const Params &p, int function, const float *in, float *out, uint32_t n, stream_t s);
+void launch_kat(const Params &p, const rt::SkyView &sky, int function, const float *in, float *out, uint32_t n, stream_t s);
 // out: local layout (local_rows x W) when full == 0, else full image (H x W; world must be 1)
 void launch_present(const Params &p, rt::f4 *out, float scale, int full, stream_t s);
 // the denoiser's guide pass (p: scene, camera and FrameView of the full image) = guide kernel + depth-gradient kernel

@@ -400,7 +400,7 @@ struct ShadeSink
 
 // One entry of the wave of depth p.depth.  `active` = the lane holds a path (the device kernel's scan has checked that the entry is
 // a path's: not void, at depth 0 a real pixel's slot); h4 / hi = its hit record (the device kernel's scan has read them already).
-template <bool TEX> RT_FN void shade_pt_item(const Params &p, uint32_t i, bool active, const f4 &h4, int hi, Ctx &ctx RT_ITEM_CLK)
+template <bool TEX, bool SKY> RT_FN void shade_pt_item(const Params &p, const SkyView &sky, uint32_t i, bool active, const f4 &h4, int hi, Ctx &ctx RT_ITEM_CLK)
 {
 	RT_ITEM_TICK(0);
 	const uint32_t b = p.depth & 1u, nb = b ^ 1u;
@@ -433,7 +433,7 @@ template <bool TEX> RT_FN void shade_pt_item(const Params &p, uint32_t i, bool a
 	}
 	const uint32_t slot = in.slot;
 	ShadeSink sink{p, ctx, slot};
-	pt_shade<TEX>(p.sc, p.cam, p.fr, p.max_depth, active, in, h, out, ctx.pot, sink RT_CLK_ARG);
+	pt_shade<TEX, SKY>(p.sc, sky, p.cam, p.fr, p.max_depth, active, in, h, out, ctx.pot, sink RT_CLK_ARG);
 	if (active)
 	{
 		// depth 0 initialises the slot (no clear pass); later depths accumulate.  One path per slot => no race.
@@ -527,7 +527,7 @@ RT_FN void connect_item(const Params &p, uint32_t i, bool active, Ctx &ctx)
 }
 
 // rfwhip_kat: one of the shade kernel's functions on one record (rfwhip_abi.h: RFWHIP_KAT_*)
-RT_FN void kat_item(const Params &p, int function, const float *in, float *out, uint32_t i, float *pot_cache)
+RT_FN void kat_item(const Params &p, const SkyView &sky, int function, const float *in, float *out, uint32_t i, float *pot_cache)
 {
 	const float *r = in + (size_t)i * KAT_IN;
 	float *o = out + (size_t)i * KAT_OUT;
@@ -612,6 +612,25 @@ RT_FN void kat_item(const Params &p, int function, const float *in, float *out, 
 		for (int k = 0; k < 4; k++)
 			o[k] = ubits((uint32_t)tex_wrap((int)fbits(r[2 * k]), (int)fbits(r[2 * k + 1])));
 		break;
+	case 13: // sky_sample on the context's table: [0..4] = u0, u1, coin, a, b -> D, pdf and radiance of the texel drawn, the texel
+	{
+		uint32_t texel = 0u;
+		const f3 D = sky_sample(p.sc, sky, r[0], r[1], r[2], r[3], r[4], texel);
+		const f3 c = xyz(p.sc.sky[texel]);
+		o[0] = D.x, o[1] = D.y, o[2] = D.z, o[3] = sky_lum(c) * sky.inv_total;
+		o[4] = c.x, o[5] = c.y, o[6] = c.z, o[7] = ubits(texel);
+		break;
+	}
+	case 14: // sky_eval: [0..2] = D -> D, pdf, radiance, the texel (-1: none)
+	{
+		float pdf = 0.0f;
+		int texel = -1;
+		const f3 D = mk3(r[0], r[1], r[2]);
+		const f3 c = sky_eval(p.sc, sky, D, pdf, texel);
+		o[0] = D.x, o[1] = D.y, o[2] = D.z, o[3] = pdf;
+		o[4] = c.x, o[5] = c.y, o[6] = c.z, o[7] = ubits((uint32_t)texel);
+		break;
+	}
 	default:
 		break;
 	}
@@ -1870,172 +1889,16 @@ __global__ void __launch_bounds__(BLOCK, RT_TRAVERSAL_WAVES) k_shade_parity(cons
 
 template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt(const Params p)
 {
-	static_assert(BLOCK == POT_STRIDE, "potential cache layout is pot[light][thread]");
-	__shared__ float s_pot[POT_SLOTS * BLOCK];
-	Ctx ctx;
-	ctx.stk.lds = nullptr, ctx.stk.spill = nullptr, ctx.stk.top = nullptr, ctx.stk.top_first = 0, ctx.stk.top_count = 0;
-	ctx.stk.overflow = nullptr, ctx.stk.stride = 0;
-	ctx.pot = s_pot + threadIdx.x;
-	const uint32_t count = p.wv.counters->ext_n[p.depth];
-	// Hits and misses cost two orders of magnitude apart (sky lookup vs. BSDF + light sampling) and are mixed lane by lane
-	// on the bounce waves.  Every WAVE keeps its own queues of hit paths and of misses in LDS: it walks 64-path chunks and appends
-	// every entry to its queue; whenever 64 of a kind are queued it shades them as one full wave (hits first).
-	// No workgroup barrier anywhere (round 1's per-256 compaction parked the waves without hits at a barrier, holding
-	// their SIMD slots, while the others shaded), and the expensive path always runs with all lanes.  Which lane shades a
-	// path does not affect its result.
-	// Round 6: the queues are RINGS of 128 entries (nothing moves down when a wave of entries leaves), and a queued hit keeps the hit
-	// record and instance the scan has read beside its entry — the scan's loads are coalesced and fetched the whole records' lines
-	// anyway; the shading then starts at "instance -> shading record" instead of at a second, gathered read of both.
-	constexpr uint32_t QN = 128u, QM = QN - 1u;
-	__shared__ f4 s_qhit[BLOCK / 64][QN];
-	__shared__ uint32_t s_qidx[BLOCK / 64][QN];
-	__shared__ int s_qinst[BLOCK / 64][QN];
-	__shared__ uint32_t s_qmiss[BLOCK / 64][QN];
-	// (Round 6, built on this state, bit-identical, and the same speed to 1 %: (a) the scan's records asked for one scan ahead by LDS-DMA —
-	// global_load_lds_dwordx4 / _dword into staging rows of the wave, no register in flight: 7.89 against 7.93 ms per sub-batch; (b) the
-	// scan of the next chunk issued with the loads of the batch being shaded, one round trip for both, the hit's shading index looked up
-	// by the scan so that the shading record is asked for with the path records: 7.88 against 7.94; (c) hits sorted by material on
-	// textured scenes — plain variant for the hits on untextured materials, textured variant over a list of the others: atrium shade
-	// 16.7 against 15.2 ms.  A wave's time between two items is vmcnt(0) — on gfx9 one counter for loads AND stores — and what the
-	// kernel as a whole is bound by is not the length of a wave's chain of round trips.  DESIGN_LOG.md, round 6.)
-	// The wave index as a scalar (readfirstlane): the four ring bases are SGPRs, not a VGPR each — with it the kernel spills nothing.
-	const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-	f4 *const qhit = s_qhit[wave];
-	uint32_t *const qidx = s_qidx[wave], *const qmiss = s_qmiss[wave];
-	int *const qinst = s_qinst[wave];
-	const f4 *const hits = p.depth == 0 ? p.wv.hit0 : p.wv.hit;
-	const int *const insts = p.depth == 0 ? p.wv.hit0_inst : p.wv.hit_inst;
-	const uint32_t nchunks = (count + 63u) / 64u;
-	const uint32_t nwaves = gridDim.x * (BLOCK / 64u);
-	// queue block: QUEUE_BLOCK slots for big launches; a launch so small that a wave would leave most of a block empty
-	// reserves exactly what each call emits instead (no void entries; the atomics are few then)
-	{
-		const uint32_t per_wave = count / (nwaves * 4u);
-		ctx.q_block = per_wave > QUEUE_BLOCK ? QUEUE_BLOCK : (per_wave < 64u ? 0u : per_wave);
-	}
-#if defined(RT_DIAG_SHADE_CLOCK)
-	__shared__ unsigned long long s_clk[BLOCK / 64][32];
-	if (lane < 32u)
-		s_clk[wave][lane] = 0ull;
-	ClkProbe clk;
-	clk.last = __builtin_readcyclecounter(), clk.acc = s_clk[wave];
-#endif
-#ifndef RT_SHADE_RUN
-#define RT_SHADE_RUN 32u
-#endif
-#ifndef RT_SHADE_FRESH_PARAMS
-#define RT_SHADE_FRESH_PARAMS 1
-#endif
-	// a wave walks RUNS of consecutive chunks (fewer when the launch has less than four runs per wave)
-	uint32_t srun = nchunks / (nwaves * 4u);
-	srun = srun > RT_SHADE_RUN ? RT_SHADE_RUN : (srun ? srun : 1u);
-	uint32_t c = (blockIdx.x * (BLOCK / 64u) + wave) * srun; // this wave's next chunk
-	uint32_t c_left = srun;									 // chunks left of the wave's run
-	uint32_t hq = 0, nq = 0;						// hit queue: first entry, entries (wave-uniform)
-	uint32_t mq = 0, nm = 0;						// miss queue
-	uint32_t nshaded = 0;							// hits shaded by this wave (statistics: the gathers of the roofline's byte count)
-	// depth 0 behind the packet form of the primary wave: which 64-slot groups of the wave's run are finished already
-	// (WaveView::hit0_done; one coalesced byte load and a ballot per run)
-	static_assert(RT_SHADE_RUN <= 32u, "run_done is a 32-bit mask");
-	const unsigned char *const done = p.depth == 0 ? p.wv.hit0_done : nullptr;
-	uint32_t run_done = 0;
-#pragma nounroll
-	for (;;)
-	{
-		uint32_t idx = 0;
-		bool act = false;
-		f4 h4 = mk4(0, 0, 0, ubits((uint32_t)-1));
-		int hi = -1;
-		const bool drain = c >= nchunks;
-		const bool take_hits = nq >= 64u || (drain && nq > 0u);
-		if (take_hits)
-		{
-			const uint32_t n = nq < 64u ? nq : 64u, e = (hq + lane) & QM;
-			nshaded += n;
-			act = lane < n;
-			idx = qidx[e], h4 = qhit[e], hi = qinst[e];
-			hq = (hq + n) & QM, nq -= n;
-		}
-		else if (nm >= 64u || (drain && nm > 0u))
-		{
-			const uint32_t n = nm < 64u ? nm : 64u;
-			act = lane < n;
-			idx = qmiss[(mq + lane) & QM];
-			mq = (mq + n) & QM, nm -= n;
-		}
-		else if (!drain)
-		{
-			if (done && c_left == srun) // a run begins
-				run_done = (uint32_t)__ballot(lane < srun && c + lane < nchunks && done[c + lane] != 0);
-			const bool skip = (run_done >> (srun - c_left)) & 1u;
-			idx = c * 64u + lane;
-			if (--c_left)
-				c++;
-			else
-				c += (nwaves - 1u) * srun + 1u, c_left = srun;
-			if (skip)
-				continue;
-			bool valid = idx < count;
-			if (p.depth == 0 && valid)
-				valid = slot_to_pixel(p.fr, idx).valid;
-			if (valid)
-				h4 = hits[idx], hi = insts[idx];
-			const int prim = valid ? (int)fbits(h4.w) : HIT_VOID;
-			const bool is_hit = prim >= 0;
-			const unsigned long long m = __ballot(is_hit);
-			if (is_hit)
-			{
-				const uint32_t e = (hq + nq + wave_prefix(m)) & QM;
-				qidx[e] = idx, qhit[e] = h4, qinst[e] = hi;
-			}
-			nq += (uint32_t)__popcll(m);
-			// a miss; HIT_VOID entries (unfilled queue slots) and HIT_MISS_SHADED ones (finished by the primary kernel) are nobody's
-			// path.  The misses of a bounce wave are mixed lane by lane with its hits: they wait for a full wave too.
-			const bool is_miss = prim == -1;
-			const unsigned long long mm = __ballot(is_miss);
-			if (is_miss)
-				qmiss[(mq + nm + wave_prefix(mm)) & QM] = idx;
-			nm += (uint32_t)__popcll(mm);
-#if defined(RT_DIAG_SHADE_CLOCK)
-			clk_tick(clk, 14); // (a scan: from the end of the last item or scan to here)
-#endif
-			continue;
-		}
-		else
-			break;
-		__builtin_amdgcn_wave_barrier();
-#if defined(RT_DIAG_SHADE_CLOCK)
-		shade_pt_item<TEX>(p, idx, act, h4, hi, ctx, &clk);
-#else
-#if RT_SHADE_FRESH_PARAMS
-		// (the kernel's arguments read again from the kernarg segment — scalar loads — instead of staying live across the loop: with
-		// ~150 wave-uniform words of scene, wave buffers, camera and frame the compiler parks them in VGPR lanes, a v_readlane per use)
-		shade_pt_item<TEX>(fresh_params(), idx, act, h4, hi, ctx);
-#else
-		shade_pt_item<TEX>(p, idx, act, h4, hi, ctx);
-#endif
-#endif
-	}
-#if defined(RT_DIAG_SHADE_CLOCK)
-	if (lane < 32u)
-		atomicAdd(g_shade_clk + lane, s_clk[wave][lane]);
-#endif
-	// what is left of this wave's last queue blocks becomes void entries; the ray counts go to the statistics
-	WaveCounters *const wc = p.wv.counters;
-	const uint32_t nb = (p.depth & 1u) ^ 1u;
-	for (uint32_t s = ctx.q_ext.pos + lane; s < ctx.q_ext.end; s += 64u)
-		p.wv.org[nb][s] = mk4(0, 0, 0, ubits(RAY_VOID));
-	for (uint32_t s = ctx.q_shadow.pos + lane; s < ctx.q_shadow.end; s += 64u)
-		p.wv.sh_org[s] = mk4(0, 0, 0, ubits(RAY_VOID));
-	if (lane == 0u)
-	{
-		if (ctx.q_ext.rays)
-			atomicAdd(&wc->ext[p.depth + 1], ctx.q_ext.rays);
-		if (ctx.q_shadow.rays)
-			atomicAdd(&wc->shadow[p.depth], ctx.q_shadow.rays);
-		if (nshaded)
-			atomicAdd(&wc->shaded, (unsigned long long)nshaded);
-	}
+	constexpr bool SKY = false;
+	const SkyView sky{};
+#include "shade_pt_body.h"
+}
+// Sky sampling: the same kernel with the sky's next-event estimation (pt_shade<TEX, true>).  A kernel of its own, not a template
+// argument of k_shade_pt: the measurements look the default kernels up by their names.
+template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt_sky(const Params p, const SkyView sky)
+{
+	constexpr bool SKY = true;
+#include "shade_pt_body.h"
 }
 
 template <bool COUNT>
@@ -2082,17 +1945,17 @@ __global__ void __launch_bounds__(BLOCK) k_deinterleave(const f4 *gathered, f4 *
 		deinterleave_item(gathered, out, W, H, local_rows, world, i);
 }
 
-__global__ void __launch_bounds__(BLOCK) k_kat(const Params p, int function, const float *in, float *out, uint32_t n)
+__global__ void __launch_bounds__(BLOCK) k_kat(const Params p, const SkyView sky, int function, const float *in, float *out, uint32_t n)
 {
 	__shared__ float s_pot[POT_SLOTS * BLOCK];
 	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
 	if (i < n)
-		kat_item(p, function, in, out, i, s_pot + threadIdx.x);
+		kat_item(p, sky, function, in, out, i, s_pot + threadIdx.x);
 }
-void launch_kat(const Params &p, int function, const float *in, float *out, uint32_t n, stream_t s)
+void launch_kat(const Params &p, const SkyView &sky, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
 	if (n)
-		hipLaunchKernelGGL(k_kat, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, function, in, out, n);
+		hipLaunchKernelGGL(k_kat, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, function, in, out, n);
 }
 
 __global__ void k_init_counters(WaveCounters *c, uint32_t primary_count)
@@ -2338,7 +2201,7 @@ uint32_t queue_pad(uint32_t max_items)
 	return std::max(persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(false)), persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(true))) * (BLOCK / 64u) * QUEUE_BLOCK;
 }
 
-void launch_shade_pt(const Params &p, uint32_t max_items, stream_t s)
+void launch_shade_pt(const Params &p, const SkyView &sky, uint32_t max_items, stream_t s)
 {
 #if defined(RT_DIAG_SHADE_CLOCK)
 	static int launches = 0;
@@ -2355,7 +2218,14 @@ void launch_shade_pt(const Params &p, uint32_t max_items, stream_t s)
 		fprintf(stderr, "\n");
 	}
 #endif
-	if (p.textured)
+	if (sky.pick > 0.0f) // (sky sampling: the variant with the sky's next-event estimation)
+	{
+		if (p.textured)
+			hipLaunchKernelGGL(k_shade_pt_sky<true>, dim3(persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(true))), dim3(BLOCK), 0, (hipStream_t)s, p, sky);
+		else
+			hipLaunchKernelGGL(k_shade_pt_sky<false>, dim3(persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(false))), dim3(BLOCK), 0, (hipStream_t)s, p, sky);
+	}
+	else if (p.textured)
 		hipLaunchKernelGGL(k_shade_pt<true>, dim3(persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(true))), dim3(BLOCK), 0, (hipStream_t)s, p);
 	else
 		hipLaunchKernelGGL(k_shade_pt<false>, dim3(persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(false))), dim3(BLOCK), 0, (hipStream_t)s, p);

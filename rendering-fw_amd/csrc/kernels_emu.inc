@@ -318,9 +318,9 @@ void launch_shade_parity(const Params &p, bool count, uint32_t max_items, stream
 		count ? shade_parity_item<true>(p, i, true, ctx) : shade_parity_item<false>(p, i, true, ctx);
 }
 uint32_t queue_pad(uint32_t) { return 0u; }
-void launch_shade_pt(const Params &p, uint32_t max_items, stream_t s)
+void launch_shade_pt(const Params &p, const SkyView &sky, uint32_t max_items, stream_t s)
 {
-	EMU_DEFER(s, launch_shade_pt(p, max_items, s));
+	EMU_DEFER(s, launch_shade_pt(p, sky, max_items, s));
 	Ctx ctx;
 	const uint32_t n = p.wv.counters->ext_n[p.depth];
 	const f4 *const hits = p.depth == 0 ? p.wv.hit0 : p.wv.hit;
@@ -337,9 +337,16 @@ void launch_shade_pt(const Params &p, uint32_t max_items, stream_t s)
 #if defined(RT_DIAG_SHADE_CLOCK)
 		ClkProbe clk0;
 		clk0.last = 0, clk0.acc = nullptr;
-		p.textured ? shade_pt_item<true>(p, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false>(p, i, true, h4, insts[i], ctx, &clk0);
+		if (sky.pick > 0.0f)
+			p.textured ? shade_pt_item<true, true>(p, sky, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, true>(p, sky, i, true, h4, insts[i], ctx, &clk0);
+		else
+			p.textured ? shade_pt_item<true, false>(p, sky, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, false>(p, sky, i, true, h4, insts[i], ctx, &clk0);
 #else
-		p.textured ? shade_pt_item<true>(p, i, true, h4, insts[i], ctx) : shade_pt_item<false>(p, i, true, h4, insts[i], ctx);
+		// (sky sampling: what k_shade_pt_sky runs)
+		if (sky.pick > 0.0f)
+			p.textured ? shade_pt_item<true, true>(p, sky, i, true, h4, insts[i], ctx) : shade_pt_item<false, true>(p, sky, i, true, h4, insts[i], ctx);
+		else
+			p.textured ? shade_pt_item<true, false>(p, sky, i, true, h4, insts[i], ctx) : shade_pt_item<false, false>(p, sky, i, true, h4, insts[i], ctx);
 #endif
 	}
 	p.wv.counters->ext[p.depth + 1] += ctx.q_ext.rays, p.wv.counters->shadow[p.depth] += ctx.q_shadow.rays;
@@ -419,12 +426,12 @@ void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s)
 		for (uint32_t i = 0; i < d.W * d.H; i++)
 			dn_pass_item(d, 1u << k, k + 1u == d.iterations, d.img[k & 1u], d.var[k & 1u], d.img[(k + 1u) & 1u], d.var[(k + 1u) & 1u], i);
 }
-void launch_kat(const Params &p, int function, const float *in, float *out, uint32_t n, stream_t s)
+void launch_kat(const Params &p, const SkyView &sky, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
-	EMU_DEFER(s, launch_kat(p, function, in, out, n, s));
+	EMU_DEFER(s, launch_kat(p, sky, function, in, out, n, s));
 	float pot[POT_SLOTS];
 	for (uint32_t i = 0; i < n; i++)
-		kat_item(p, function, in, out, i, pot);
+		kat_item(p, sky, function, in, out, i, pot);
 }
 void launch_skin_vertices(f4 *verts, f4 *vnormals, const f4 *base_verts, const f4 *base_normals, const uint32_t *joints4,
 						  const f4 *weights4, const float *mats, uint32_t joint_count, uint32_t vertex_count, stream_t s)

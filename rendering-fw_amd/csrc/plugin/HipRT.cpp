@@ -270,9 +270,9 @@ class Context final : public rfw::RenderContext
 	rfw::AvailableRenderSettings get_settings() const override
 	{
 		rfw::AvailableRenderSettings s;
-		s.settingKeys = {"integrator", "jitter", "spp", "max_depth", "DENOISE", "DENOISE_TEMPORAL"};
+		s.settingKeys = {"integrator", "jitter", "spp", "max_depth", "DENOISE", "DENOISE_TEMPORAL", "sky_sampling"};
 		s.settingValues = {{"pt", "parity"}, {"xor128", "center"}, {"1", "2", "4", "8", "16"}, {"0", "1", "2", "3", "4"}, {"0", "1"},
-						   {"0", "1"}};
+						   {"0", "1"}, {"0", "1"}};
 		return s;
 	}
 

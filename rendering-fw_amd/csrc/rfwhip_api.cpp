@@ -12,6 +12,7 @@
 #include "internal.h"
 #include "kernels.h"
 #include "rt_types.h"
+#include "sky_sampling.h"
 
 #include <algorithm>
 #include <chrono>
@@ -603,6 +604,15 @@ struct rfwhip_context
 	DevBuf d_materials, d_textures, d_tex_u32, d_tex_f4, d_sky, d_area, d_point, d_spot, d_dir;
 	uint32_t material_count = 0, texture_count = 0, sky_w = 0, sky_h = 0;
 	bool textured = false; // some material carries a map
+	// sky sampling (sky_sampling.h): the settings, and what the last rfwhip_update made of them
+	int sky_sampling = 0;
+	float sky_pick = -1.0f;		 // -1: auto (1 without lights, 0.5 with)
+	uint64_t sky_version = 0;	 // rfwhip_set_sky calls
+	uint64_t sky_table_of = ~0ull; // the sky_version d_sky_alias was built from (~0: none)
+	double sky_total = 0.0;		 // S of that table (0: no texel with a positive weight)
+	DevBuf d_sky_alias;			 // allocated only while sky_sampling is on
+	rt::SkyView sky_view{};		 // pick == 0: the default kernels run
+	bool sky_stale = false;		 // a sky setting changed since: the next render (or update) refreshes the view
 	uint32_t tlas_root_entry = 0, instance_count = 0;
 	rt::SceneView sv;
 
@@ -785,7 +795,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_sh_dir[0], &c->d_sh_dir[1], &c->d_sh_rad[0], &c->d_sh_rad[1], &c->d_rad[0], &c->d_rad[1],
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
-					  &c->d_dn_inst_ver};
+					  &c->d_dn_inst_ver, &c->d_sky_alias};
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->guides_valid = false;
@@ -900,6 +910,7 @@ extern "C" int rfwhip_set_sky(rfwhip_context *c, const float *rgb, size_t width,
 	RF_TRY(dm::h2d(c->d_sky.p, px.data(), px.size() * sizeof(f4), c->stream));
 	RF_TRY(dm::sync(c->stream));
 	c->sky_w = (uint32_t)width, c->sky_h = (uint32_t)height;
+	c->sky_version++;
 	c->scene_dirty = true;
 	return RFWHIP_OK;
 }
@@ -1597,6 +1608,52 @@ static int prepare_world(rfwhip_context *c, bool &changed)
 	return 0;
 }
 
+// sky_sampling: the alias table (rebuilt when the sky or the setting changed) and p (the lights may have changed).  Called by
+// rfwhip_update, and by a render or rfwhip_kat after a sky setting changed (they run on the scene of the last update).
+static int update_sky_sampling(rfwhip_context *c)
+{
+	c->sky_stale = false;
+	if (!c->sky_sampling)
+	{
+		if (c->d_sky_alias.p)
+			RF_TRY(sync_all(c)); // (frames in flight may still read the table)
+		c->d_sky_alias.free_(), c->sky_table_of = ~0ull, c->sky_total = 0.0;
+		c->sky_view = rt::SkyView{};
+		return RFWHIP_OK;
+	}
+	const size_t n = (size_t)c->sky_w * c->sky_h;
+	if (n >= (1ull << 31))
+		return set_error(RFWHIP_ERR_UNSUPPORTED, "sky_sampling: a sky of %u x %u texels is too large", c->sky_w, c->sky_h);
+	if (c->sky_table_of != c->sky_version)
+	{
+		RF_TRY(sync_all(c)); // (frames in flight may still read the table)
+		c->sky_total = 0.0;
+		std::vector<rt::SkyAlias> table;
+		if (n)
+		{
+			std::vector<f4> px(n);
+			RF_TRY(dm::d2h(px.data(), c->d_sky.p, n * sizeof(f4), c->stream));
+			RF_TRY(dm::sync(c->stream));
+			c->sky_total = skysamp::build_alias(px.data(), c->sky_w, c->sky_h, table);
+		}
+		if (table.empty())
+			c->d_sky_alias.free_();
+		else
+		{
+			RF_TRY(c->d_sky_alias.ensure(table.size() * sizeof(rt::SkyAlias)));
+			RF_TRY(dm::h2d(c->d_sky_alias.p, table.data(), table.size() * sizeof(rt::SkyAlias), c->stream));
+			RF_TRY(dm::sync(c->stream));
+		}
+		c->sky_table_of = c->sky_version;
+	}
+	// p: forced to 0 without a usable sky (the default kernels run: bit-identical to sky_sampling=0)
+	float pick = c->sky_pick >= 0.0f ? c->sky_pick : (total_light_count(c) ? 0.5f : 1.0f);
+	if (!(c->sky_total > 0.0))
+		pick = 0.0f;
+	c->sky_view = skysamp::view(c->sky_total > 0.0 ? c->d_sky_alias.as<rt::SkyAlias>() : nullptr, c->sky_total, pick, c->sky_w, c->sky_h);
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_update(rfwhip_context *c)
 {
 	CTX_ENTER(c);
@@ -1922,6 +1979,7 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 	sv.spot = c->d_spot.as<rt::SpotLight>(), sv.dir = c->d_dir.as<rt::DirectionalLight>();
 	sv.n_area = c->lc.areaLightCount, sv.n_point = c->lc.pointLightCount, sv.n_spot = c->lc.spotLightCount;
 	sv.n_dir = c->lc.directionalLightCount;
+	RF_TRY(update_sky_sampling(c));
 	c->scene_dirty = false;
 	c->scene_version++; // (the denoiser's guides are recomputed)
 	// which instances this update changed (transform, mesh, or the mesh's vertices): the temporal stage does not reproject them
@@ -2222,6 +2280,8 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_render before rfwhip_init");
 	if (c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_render: scene changed since the last rfwhip_update()");
+	if (c->sky_stale)
+		RF_TRY(update_sky_sampling(c));
 	if (c->sampler == 1 && !c->have_blue_noise)
 		return set_error(RFWHIP_ERR_STATE, "sampler=bluenoise needs rfwhip_set_blue_noise() first");
 	if (c->max_depth + 2 > rt::MAX_DEPTH_SLOTS)
@@ -2350,7 +2410,8 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	const uint32_t row_group = std::max(1u, (c->fr.tiles_x << sgroup_log2) / 4u); // primary wave: one row of 8x8 tiles per XCD group
 	const uint32_t par = c->call_slot;							 // buffer set of this call
 	const uint32_t prev = (par + (uint32_t)ring - 1u) % (uint32_t)ring; // ... and of the previous one
-	const bool connect = c->integrator == 1 && total_light_count(c) > 0 && c->max_depth > 0;
+	// (sky sampling: the sky is a light of its own — a scene without lights still has shadow rays then)
+	const bool connect = c->integrator == 1 && (total_light_count(c) > 0 || c->sky_view.pick > 0.0f) && c->max_depth > 0;
 	// Connection waves on a second stream hide the kernel tails of a call that runs alone (1 spp frames, wait after every
 	// call: 1.56 -> 1.43 ms).  When the caller pipelines its calls, the ring of buffer sets already keeps up to four launch
 	// chains in flight and the extra kernels only evict each other's working sets (1 spp: 1.17 ms without, 1.38 ms with the
@@ -2459,7 +2520,7 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 				if (side && d >= 2 && d < c->max_depth) // connect(d - 2) read the buffers shade(d) is about to write
 					RF_TRY(dm::stream_wait_event(s, c->ev_conn[i][d - 2]));
 				StageTimer ts(c, KF_SHADE, -1, s);
-				rtk::launch_shade_pt(p, n_shade, s);
+				rtk::launch_shade_pt(p, c->sky_view, n_shade, s);
 				ts.stop();
 				// The connection wave of depth d runs beside extend / shade of depth d + 1 on its own stream (it adds into
 				// rad_nee, they into rad).  The connections of the last shade call are never traced
@@ -3022,7 +3083,7 @@ extern "C" int rfwhip_get_stats(rfwhip_context *c, rfwhip_render_stats *stats)
 	return RFWHIP_OK;
 }
 
-static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth", "denoise_temporal", "denoise_alpha"};
+static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth", "denoise_temporal", "denoise_alpha", "sky_sampling", "sky_pick"};
 
 extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char *value)
 {
@@ -3197,6 +3258,22 @@ extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char
 			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be a finite number >= 0", key);
 		(k == "denoise_sigma_luminance" ? c->dn_sigma_l : k == "denoise_sigma_normal" ? c->dn_sigma_n : c->dn_sigma_z) = f;
 	}
+	else if (k == "sky_sampling")
+	{
+		if (v != "0" && v != "1")
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sky_sampling must be \"0\" or \"1\"");
+		c->sky_sampling = v == "1";
+		c->sky_stale = true; // (the next render builds the table, on the sky of the last rfwhip_update)
+	}
+	else if (k == "sky_pick")
+	{
+		char *end = nullptr;
+		const float f = strtof(value, &end);
+		if (!end || end == value || *end || !(f == -1.0f || (f >= 0.0f && f <= 1.0f)))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sky_pick must be -1 (auto) or a probability in [0, 1]");
+		c->sky_pick = f;
+		c->sky_stale = true;
+	}
 	else
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "unknown setting \"%s\"", key);
 	return RFWHIP_OK;
@@ -3277,6 +3354,16 @@ extern "C" int rfwhip_get_setting(rfwhip_context *c, const char *key, char *valu
 		snprintf(value, cap, "%d", c->dn_temporal);
 	else if (k == "denoise_alpha")
 		snprintf(value, cap, "%g", c->dn_alpha);
+	else if (k == "sky_sampling")
+		snprintf(value, cap, "%d", c->sky_sampling);
+	else if (k == "sky_pick")
+		snprintf(value, cap, "%g", c->sky_pick);
+	else if (k == "sky") // (read-only) p > 0: the pt shade waves run k_shade_pt_sky
+	{
+		if (c->sky_stale && !c->scene_dirty)
+			RF_TRY(update_sky_sampling(c));
+		snprintf(value, cap, "%d", c->sky_view.pick > 0.0f ? 1 : 0);
+	}
 	else
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "unknown setting \"%s\"", key);
 	return RFWHIP_OK;
@@ -3579,10 +3666,14 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 	CTX_ENTER(c);
 	if (n && (!in || !out))
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: null records");
-	if (function < 0 || function > RFWHIP_KAT_TEX_WRAP)
+	if (function < 0 || function > RFWHIP_KAT_SKY_PDF)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: unknown function %d", function);
 	if ((function == RFWHIP_KAT_POINT_ON_LIGHT || function == RFWHIP_KAT_LIGHT_PICK_PROB) && c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the light functions use the lights of the last rfwhip_update()");
+	if ((function == RFWHIP_KAT_SKY_SAMPLE || function == RFWHIP_KAT_SKY_PDF) && !c->scene_dirty && c->sky_stale)
+		RF_TRY(update_sky_sampling(c));
+	if ((function == RFWHIP_KAT_SKY_SAMPLE || function == RFWHIP_KAT_SKY_PDF) && (c->scene_dirty || !c->sky_view.table))
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the sky functions use the table of the last rfwhip_update() with sky_sampling=1 and a sky with light");
 	if (function == RFWHIP_KAT_BLUE_NOISE && !c->have_blue_noise)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: no blue-noise table (rfwhip_set_blue_noise)");
 	if (n == 0)
@@ -3601,7 +3692,7 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 		rtk::Params p;
 		fill_params(c, nullptr, p);
 		p.cam.blue_noise = c->have_blue_noise ? c->d_blue_noise.as<uint32_t>() : nullptr;
-		rtk::launch_kat(p, function, d_in.as<float>(), d_out.as<float>(), (uint32_t)n, c->stream);
+		rtk::launch_kat(p, c->sky_view, function, d_in.as<float>(), d_out.as<float>(), (uint32_t)n, c->stream);
 		rc = dm::last_launch_error();
 	}
 	if (!rc)

@@ -1736,6 +1736,60 @@ RT_FN f3 random_point_on_light(const SceneView &sc, float r0, float r1, f3 I, f3
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// sky sampling (setting sky_sampling; the table: sky_sampling.h; formulas: include/rfwhip.h)
+// ---------------------------------------------------------------------------------------------------------------
+// a texel's weight: its luminance, 0 for a negative or NaN one (the host's table and this must agree on which texels are black)
+RT_FN float sky_lum(f3 c)
+{
+	const float l = fmaf(c.z, 0.0722f, fmaf(c.y, 0.7152f, rounded(c.x * 0.2126f)));
+	return l > 0.0f ? l : 0.0f;
+}
+// pt_sky's radiance of direction D together with the texel it reads and the sky-sampling density there, lum(texel) / S per
+// steradian (0 for a black texel and for the out-of-range index pt_sky maps to black; texel -1 then).  The same index arithmetic
+// as pt_sky, operation for operation: the radiance is pt_sky's to the bit.  The miss branch and the sky's next-event estimation
+// both call this, so a direction gets its radiance and its pdf from one texel whichever way it was found.
+RT_FN f3 sky_eval(const SceneView &sc, const SkyView &sky, f3 D, float &pdf, int &texel)
+{
+	pdf = 0.0f, texel = -1;
+	if (!sc.sky_w || !sc.sky_h)
+		return mk3(0, 0, 0);
+	const float turns = rounded(m_atan2f(D.x, -D.z) * RT_INV_PI);
+	const uint32_t u = f2u_sat((float)sc.sky_w * 0.5f * (1.0f + turns));
+	const uint32_t v = f2u_sat((float)sc.sky_h * m_acosf(clampf(D.y, -1.0f, 1.0f)) * RT_INV_PI);
+	const unsigned long long idx = (unsigned long long)u + (unsigned long long)v * sc.sky_w;
+	if (idx >= (unsigned long long)sc.sky_w * sc.sky_h)
+		return mk3(0, 0, 0);
+	const f3 c = xyz(sc.sky[idx]);
+	texel = (int)idx;
+	pdf = sky_lum(c) * sky.inv_total;
+	return c;
+}
+// One draw of the sky distribution.  (u0, u1) pick a bucket of the alias table as a row and a column of a W x H grid (uniform over
+// the W * H buckets, and each number needs only the precision of one axis), `coin` keeps the bucket's texel or takes its alias,
+// (a, b) place the direction uniformly in (phi, cos theta) inside the texel (i, j):
+//     phi = -pi + 2 pi (i + a) / W,   cos theta = cos theta_j - b (cos theta_j - cos theta_{j+1}),   theta_j = pi j / H,
+//     D = (sin theta sin phi, cos theta, -sin theta cos phi)   (pt_sky: phi = atan2(D.x, -D.z), theta = acos(D.y)).
+// One dependent load (the bucket); the texel's row is a multiply-high.  texel = the texel drawn.
+RT_FN f3 sky_sample(const SceneView &sc, const SkyView &sky, float u0, float u1, float coin, float a, float b, uint32_t &texel)
+{
+	const uint32_t W = sc.sky_w, H = sc.sky_h;
+	uint32_t row = f2u_sat(u0 * (float)H), col = f2u_sat(u1 * (float)W);
+	row = row < H ? row : H - 1u;
+	col = col < W ? col : W - 1u;
+	const uint32_t k = row * W + col;
+	const SkyAlias e = sky.table[k];
+	texel = coin < e.keep ? k : e.alias;
+	const uint32_t j = fast_div(texel, sky.div_w), i = texel - j * W;
+	float sp, cp, s0, c0, s1, c1;
+	sincos_turns(rounded(((float)i + a) * sky.inv_w) - 0.5f, sp, cp);
+	sincos_turns((float)j * sky.inv_2h, s0, c0);
+	sincos_turns((float)(j + 1u) * sky.inv_2h, s1, c1);
+	const float ct = clampf(c0 - rounded(b * (c0 - c1)), -1.0f, 1.0f);
+	const float st = m_sqrtf(fmaxf(0.0f, 1.0f - rounded(ct * ct)));
+	return mk3(rounded(st * sp), ct, -rounded(st * cp));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // PATH-TRACING shade step for one path vertex: CUDART/src/Kernels.cu:571-794
 // ---------------------------------------------------------------------------------------------------------------
 struct PathIn
@@ -1851,9 +1905,13 @@ RT_FN void pt_textures(const SceneView &sc, const CamView &cam, f3 D, float t, c
 //      (re-read from the material for a back-facing hit of a transmissive one), SafeOrigin (the same point as the shadow ray's).
 // TEX = false: the scene has no material with a texture or normal map (the host knows: rfwhip_set_materials) — the texture
 // layers, their descriptors and the level-of-detail arithmetic are compiled out, which frees a fifth of the registers.
-template <bool TEX, class Sink>
-RT_FN void pt_shade(const SceneView &sc, const CamView &cam, const FrameView &fr, uint32_t max_depth, bool active, const PathIn &in,
-					const Hit &h, ShadeOut &out, float *pot_cache, Sink &sink RT_CLK_PARAM)
+// SKY = true (setting sky_sampling, sky.pick = p > 0): next-event estimation samples the sky with probability p, and the two ways of
+// finding the sky — that sample and a BSDF-sampled miss after a non-specular vertex — are weighted against each other (balance
+// heuristic); the lights' selection probability and the emitter hit's weight take the factor 1 - p.  Every line of it sits under
+// SKY: the default kernels (SKY = false) are the code they were.
+template <bool TEX, bool SKY, class Sink>
+RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const CamView &cam, const FrameView &fr, uint32_t max_depth, bool active,
+					const PathIn &in, const Hit &h, ShadeOut &out, float *pot_cache, Sink &sink RT_CLK_PARAM)
 {
 	out.radiance = mk3(0, 0, 0);
 	out.emit_shadow = false, out.emit_ext = false;
@@ -1876,7 +1934,18 @@ RT_FN void pt_shade(const SceneView &sc, const CamView &cam, const FrameView &fr
 	}
 	else if (h.prim < 0)
 	{
-		const f3 contribution = (T * m_rcp(in.bsdfPdf)) * pt_sky(sc, D);
+		f3 contribution;
+		if (SKY && in.depth >= 1u && (in.flags & 1u) == 0u)
+		{
+			// (after a non-specular vertex, whose next-event estimation could have drawn this direction from the sky with density
+			// p * pdf_sky)
+			float skyPdf;
+			int texel;
+			const f3 Ls = sky_eval(sc, sky, D, skyPdf, texel);
+			contribution = (T * m_rcp(in.bsdfPdf + sky.pick * skyPdf)) * Ls;
+		}
+		else
+			contribution = (T * m_rcp(in.bsdfPdf)) * pt_sky(sc, D);
 		if (!any_nan(contribution))
 			out.radiance = clamp_intensity(contribution, cam.clamp_value);
 		RT_TICK(2);
@@ -1930,8 +1999,10 @@ RT_FN void pt_shade(const SceneView &sc, const CamView &cam, const FrameView &fr
 					const float lightPdf = m_div(h.t * h.t, -dot(D, N) * sf.area); // lights.h:78-81
 					const int ltri = sf.ltri;
 					// the reference reads the material id as light index (device_structs.h:37,40); lightTriIdx is meant
-					const float pickProb =
+					float pickProb =
 						(ltri >= 0 && (uint32_t)ltri < sc.n_area) ? light_pick_prob(sc, ltri, in.O, lastN, I) : 0.0f;
+					if (SKY)
+						pickProb = pickProb * (1.0f - sky.pick);
 					if ((in.bsdfPdf + lightPdf * pickProb) <= 0)
 						drop = true;
 					else
@@ -1961,7 +2032,7 @@ RT_FN void pt_shade(const SceneView &sc, const CamView &cam, const FrameView &fr
 			// next-event estimation: Kernels.cu:702-755.  The connections of a shade call are traced by the NEXT iteration of the
 			// reference's host loop (CUDART/src/Context.cpp:109-120), so those of the last call (depth == max_depth) never are:
 			// they are not even computed here (the two random numbers they would consume are followed by no other draw).
-			if ((flags & 1u) == 0 && total_lights(sc) > 0 && in.depth < max_depth)
+			if ((flags & 1u) == 0 && (total_lights(sc) > 0 || (SKY && sky.pick > 0.0f)) && in.depth < max_depth)
 			{
 				const f3 wo = D * -1.0f;
 				f3 lightColor = mk3(0, 0, 0);
@@ -1975,10 +2046,32 @@ RT_FN void pt_shade(const SceneView &sc, const CamView &cam, const FrameView &fr
 				else
 					q0 = random_float(seed), q1 = random_float(seed);
 				uint32_t light = 0u;
-				f3 L = random_point_on_light(sc, q0, q1, I, iN, pickProb, lightPdf, lightColor, light, pot_cache RT_CLK_ARG) - I;
-				RT_TICK(12);
-				const float dist = length(L);
-				L = L * m_rcp(dist);
+				f3 L;
+				float dist;
+				// sky: q1 < p picks the sky, with (q0, q1 / p); a light is picked with (q0, (q1 - p) / (1 - p)) and probability 1 - p
+				const bool sky_nee = SKY && (q1 < sky.pick || sky.pick >= 1.0f);
+				float skyPdf = 0.0f;
+				if (sky_nee)
+				{
+					const float coin = random_float(seed), a = random_float(seed), b = random_float(seed);
+					uint32_t drawn;
+					L = sky_sample(sc, sky, q0, q1 * sky.inv_pick, coin, a, b, drawn);
+					int texel;
+					lightColor = sky_eval(sc, sky, L, skyPdf, texel);
+					lightPdf = skyPdf, dist = 1e34f;
+					light = 0xFFFFFFFFu; // (depth 0 with shadow bins: the last bin)
+				}
+				else
+				{
+					if (SKY)
+						q1 = (q1 - sky.pick) * sky.inv_rest;
+					L = random_point_on_light(sc, q0, q1, I, iN, pickProb, lightPdf, lightColor, light, pot_cache RT_CLK_ARG) - I;
+					if (SKY)
+						pickProb = pickProb * (1.0f - sky.pick);
+					RT_TICK(12);
+					dist = length(L);
+					L = L * m_rcp(dist);
+				}
 				const float NdotL = dot(L, iN);
 				if (NdotL > 0 && lightPdf > 0)
 				{
@@ -1986,7 +2079,10 @@ RT_FN void pt_shade(const SceneView &sc, const CamView &cam, const FrameView &fr
 					const float shadowPdf = bsdf_pdf(sd, iN, wo, L);
 					if (shadowPdf > 0)
 					{
-						f3 contribution = ((T * bs) * lightColor) * m_div(NdotL, shadowPdf + lightPdf * pickProb);
+						// the sky's term divides by the survival factor s that this vertex's BSDF continuation divides by (Kernels.cu:783):
+						// the same integral as the miss branch's
+						f3 contribution = sky_nee ? ((T * bs) * lightColor) * m_div(NdotL, (shadowPdf + sky.pick * skyPdf) * survival_probability(T))
+												  : ((T * bs) * lightColor) * m_div(NdotL, shadowPdf + lightPdf * pickProb);
 						contribution = clamp_intensity(contribution, cam.clamp_value);
 						if (!any_nan(contribution))
 						{
@@ -1997,7 +2093,7 @@ RT_FN void pt_shade(const SceneView &sc, const CamView &cam, const FrameView &fr
 							const uint32_t last_bin = (1u << fr.shadow_bins) - 1u;
 							const uint32_t bin = (fr.shadow_bins && in.depth == 0u) ? (light < last_bin ? light : last_bin) << shadow_slot_bits(fr.shadow_bins) : 0u;
 							so = mk4(o.x, o.y, o.z, ubits(in.slot | bin));
-							sdir = mk4(L.x, L.y, L.z, dist - 2.0f * 1e-5f);
+							sdir = mk4(L.x, L.y, L.z, sky_nee ? dist : dist - 2.0f * 1e-5f); // (the sky: the reference's 1e34)
 							se = mk4(contribution.x, contribution.y, contribution.z, 0.0f);
 						}
 					}

@@ -342,6 +342,24 @@ RT_FN uint32_t fast_div(uint32_t n, const FastDiv f)
 #endif
 }
 
+// Sky sampling (setting sky_sampling, sky_sampling.h): one alias-table entry per texel of the sky, row-major like SceneView::sky.
+// Bucket k keeps texel k with probability `keep` and hands out texel `alias` otherwise.
+struct SkyAlias
+{
+	float keep;
+	uint32_t alias;
+};
+// What the sky variant of the shade kernel (k_shade_pt_sky) needs beyond the scene: the table, the probability p of sampling the
+// sky at a next-event vertex, 1 / p and 1 / (1 - p) for rescaling the selection number, and 1 / S (S = sum of lum * solid angle).
+// pick == 0: the variant is not launched and nothing here is read.
+struct SkyView
+{
+	const SkyAlias *table;
+	float pick, inv_pick, inv_rest, inv_total;
+	float inv_w, inv_2h; // 1 / W, 1 / (2 H): a texel's edges in turns
+	FastDiv div_w;		 // texel index -> row
+};
+
 // Which image rows this rank owns, and how path slots map to pixels.
 struct FrameView
 {
