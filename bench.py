@@ -3,6 +3,11 @@
 
   python bench.py --gpus N --steps K --warmup W           (N > 1: launched by torch.distributed.run, one rank per GPU)
   python bench.py ... --dump-outputs DIR                  (also writes the image of the last timed step: DIR/framebuffer.npy)
+  python bench.py ... --full                              (also everything below the headline: counters, roofline, CPU baselines)
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line; roofline, sampler_bluenoise,
+cpu_baseline, cpu_baseline_parity, parity_vs_cpu_baseline and, for N > 1, ranks.gather_enqueue_to_done_ms are null in it.
+--full measures and checks them as well, outside the timed region (a minute or more at the default size).
 
 Workload (BASELINE.json configs[2]): synthetic ~1 M-triangle displaced grid (1 002 528 triangles, seed 0x5EED) +
 synthetic HDR sky + 8 emissive light triangles + 2 point lights, 1920x1080, wavefront path-tracing integrator
@@ -13,7 +18,7 @@ there (rfwhip_comm_*: RCCL send / recv issued by the library itself; torch.distr
 communicator id, the barriers and the max-over-ranks of the elapsed time).  Inputs (scene, BVH, path buffers) are
 resident in HBM before the timed region starts.
 
-The JSON line carries, besides the driver contract fields:
+The JSON line of a --full run carries, besides the driver contract fields:
   roofline      the kernel that dominates the default command by time — k_trace_fused: the bounce and shadow waves of a depth in
                 one launch — in the units of what binds it (bound "valu": achieved = VALU wave-instructions per second of the launch,
                 peak = 1024 SIMDs x 2.4 GHz / 2, frac = achieved / peak, lane_weighted_frac beside it; its bytes — algorithmic per
@@ -132,7 +137,7 @@ def csrc_hash():
     return h.hexdigest()[:16]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -167,14 +172,19 @@ def parse():
     ap.add_argument("--pipeline", type=int, default=1,
                     help="N > 1, --gather torch: 1 = stream-ordered present/gather/de-interleave overlapping the next step's "
                          "kernels; 0 = host-synchronous gather per step (reports gather_ms_per_step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: the counter passes (--pmc), "
+                         "the roofline and its per-stage table, the blue-noise sampler, the CPU baselines and the GPU image against "
+                         "the CPU oracle's, and for N > 1 the gather of a finished frame alone.  Off: the run sets up, warms up, "
+                         "times the steps, writes --dump-outputs and prints the result line with those fields null")
     ap.add_argument("--stage-rates", action="store_true",
-                    help="also report Mrays/s per stage of the serialised frame, the way the reference's stats window shows them")
+                    help="--full: also report Mrays/s per stage of the serialised frame, the way the reference's stats window shows them")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="extra rendercore setting(s) for A/B runs, e.g. --set sample_group=1 (recorded in config.settings)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"],
                     help="hardware counters of THIS run for the roofline: separate `rocprofv3 --pmc` passes (FETCH_SIZE; WRITE_SIZE; VALU "
                          "instructions / lanes; VALU instruction classes) of a short child run of this script.  auto: when rocprofv3 is on the "
-                         "PATH (N = 1, pt integrator, roofline on; RFWHIP_BENCH_PMC=0 switches it off); otherwise — and when a pass fails — the "
+                         "PATH (--full, N = 1, pt integrator, roofline on; RFWHIP_BENCH_PMC=0 switches it off); otherwise — and when a pass fails — the "
                          "committed profiles/stage_counters.json is used if it belongs to the running sources")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -185,9 +195,15 @@ def parse():
                     help="after the timed steps, write what the timed path computed in its last step — the presented image a "
                          "caller reads back (height x width x 4 float32) — as DIR/framebuffer.npy; the inputs are seeded, so two "
                          "builds run with the same arguments can be compared output for output")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        # (asked for explicitly, they would otherwise be dropped without a word)
+        if args.stage_rates:
+            ap.error("--stage-rates is part of the roofline: add --full")
+        if args.pmc == "on":
+            ap.error("--pmc on takes counters for the roofline: add --full")
     return args
 
 
@@ -342,7 +358,7 @@ def main_group(args):
         dump_outputs(args.dump_outputs, {"framebuffer": img})
     out = {"metric": "Msamples/sec at 1920x1080, 1M-tri scene; 1/2/4/8-GPU tile scaling", "value": round(float(args.width) * args.height * args.spp * args.steps / elapsed / 1e6, 3),
            "unit": "Msamples/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
            "config": {"workload": "%s: %d triangles, %dx%d, %s integrator depth %d, %d spp per step" % (scene.name, scene.triangle_count(), args.width, args.height, args.integrator, args.max_depth, args.spp),
                       "parallelism": "ONE process / one host thread drives %d contexts (rfwhip_group_*): image strips of 8 rows interleaved over the ranks, one gather per step into rank 0's HBM" % n,
                       "gather": "group:%s%s" % (g.transport, " (all contexts on device 0: development aid, the number means nothing)" if one_device else ""),
@@ -399,7 +415,7 @@ def main():
     # ---- the run's own hardware counters, BEFORE this process takes the device's memory (a 256-spp step holds 140 GB of path state,
     # and every counter pass is a child process that renders the same workload)
     own_pm, own_source, own_note = None, None, "--pmc off"
-    want_pmc = (not args.no_roofline and rank == 0 and args.integrator == "pt" and
+    want_pmc = (args.full and not args.no_roofline and rank == 0 and args.integrator == "pt" and
                 (args.pmc == "on" or (args.pmc == "auto" and world == 1 and os.environ.get("RFWHIP_BENCH_PMC", "1") != "0")))
     if want_pmc:
         t_pmc = time.time()
@@ -550,7 +566,7 @@ def main():
         dist.all_reduce(own, op=dist.ReduceOp.SUM)
         own = [round(float(x), 4) for x in own.tolist()]
         probe = None
-        if comm is not None:
+        if comm is not None and args.full:
             # the gather of a finished frame, enqueue to done, with nothing else in flight: present + send on every rank,
             # world - 1 receives + the de-interleave on the root (xGMI: 33 MB / world per peer link)
             times = []
@@ -582,7 +598,7 @@ def main():
     roofline, stage_rates = None, None
     subs = max(1, min(args.streams, args.spp))
     sub_spp = max(1, args.spp // subs)
-    if not args.no_roofline and rank == 0 and args.integrator == "pt":
+    if args.full and not args.no_roofline and rank == 0 and args.integrator == "pt":
         ext_ms, ext_launches = kernel_times["extend"]
 
         def instrumented(frames, depth):
@@ -949,7 +965,7 @@ def main():
     # table of the reference's LAYOUT filled with our own numbers (scenes.synthetic_blue_noise: the published table belongs to
     # the reference tree and reaches the core through rfwhip_set_blue_noise) — same fetches, same arithmetic, other values.
     bluenoise = None
-    if not args.no_roofline and rank == 0 and world == 1 and args.integrator == "pt":
+    if args.full and not args.no_roofline and rank == 0 and world == 1 and args.integrator == "pt":
         ctx.set_blue_noise(pkg.scenes.synthetic_blue_noise())
         ctx.set_setting("sampler", "bluenoise")
         ctx.set_setting("stage_timing", 0)
@@ -972,7 +988,7 @@ def main():
 
     # ---- CPU baselines: the oracle (a port, not the reference build) on this box's host cores ---------------------------
     cpu_baseline, parity, cpu_parity = None, None, None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         from __graft_entry__ import load_oracle
         orc = load_oracle()
         cores = usable_cores()
@@ -1062,7 +1078,7 @@ def main():
                        "Msamples/sec at 1920x1080, Sponza-scale instanced textured scene (BASELINE config 4); tile scaling"),
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "%s: %d triangles, %dx%d, %s integrator depth %d, %d spp per step, %d area-light "
                                    "triangles + %d point lights, synthetic 2048x1024 HDR sky"
                                    % (scene.name, scene.triangle_count(), W, H, args.integrator, args.max_depth, args.spp,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/evidence.sh <tag>   (on the GPU box)  — the per-round evidence set:
-#   gpurun_out/<tag>_bench.json          python bench.py (default flags)
+#   <tag>_bench.json, beside the files below: python bench.py --full --stage-rates
 #   gpurun_out/<tag>_kernel_stats.md     rocprofv3 --kernel-trace --stats of the same command
 #   gpurun_out/<tag>_pmc_{fetch,write,tcc,tcp,sq_issue,sq_lanes}.md   one rocprofv3 --pmc pass each (no trace flags)
 #   gpurun_out/<tag>_traffic_extend.json HBM / L2 bytes per extend launch derived from the passes (-> profiles/traffic_extend.json)
@@ -38,10 +38,11 @@ export VALU_CALIB_DB=$cal
 (cd $R && python profiles/summarize.py traffic 256 4 terrain_1002k "$tag" $f $w $t $p $q $l > gpurun_out/${tag}_traffic_extend.json; cp gpurun_out/${tag}_traffic_extend.json profiles/traffic_extend.json)
 h=$(cd $R && python -c "import bench; print(bench.csrc_hash())")
 (cd $R && python profiles/summarize.py stages 256 4 terrain_1002k "$tag" $h $f $w $t $q $l $m > gpurun_out/${tag}_stage_counters.json; cat gpurun_out/${tag}_stage_counters.json; cp gpurun_out/${tag}_stage_counters.json profiles/stage_counters.json)
-cd $R && timeout 900 python bench.py --stage-rates > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+out=${dc%/*}  # the folder the files above went to
+cd $R && timeout 900 python bench.py --full --stage-rates > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 1500 gpurun_out/${tag}_bench.json
 d=$R/gpurun_out/${tag}_stats; rm -rf $d
-(cd $R && timeout 900 rocprofv3 --kernel-trace --stats -d $d -- python bench.py > $d.log 2>&1)
+(cd $R && timeout 900 rocprofv3 --kernel-trace --stats -d $d -- python bench.py --full > $d.log 2>&1)
 (cd $R && python profiles/summarize.py stats $(find $d -name "*.db" | head -1) > gpurun_out/${tag}_kernel_stats.md; head -12 gpurun_out/${tag}_kernel_stats.md)
 # config 4 (atrium: instanced, textured — the k_shade_pt<true> variant) under the same protocol: kernel stats + three PMC passes
 if [ -n "$EVIDENCE_ATRIUM" ]; then
@@ -55,7 +56,7 @@ if [ -n "$EVIDENCE_ATRIUM" ]; then
   apass write WRITE_SIZE
   apass sq_lanes SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE
   d=$R/gpurun_out/${tag}_atrium_stats; rm -rf $d
-  (cd $R && timeout 900 rocprofv3 --kernel-trace --stats -d $d -- python bench.py --workload atrium --no-cpu-baseline > $d.log 2>&1)
+  (cd $R && timeout 900 rocprofv3 --kernel-trace --stats -d $d -- python bench.py --full --workload atrium --no-cpu-baseline > $d.log 2>&1)
   (cd $R && python profiles/summarize.py stats $(find $d -name "*.db" | head -1) > gpurun_out/${tag}_atrium_kernel_stats.md; head -8 gpurun_out/${tag}_atrium_kernel_stats.md)
-  (cd $R && timeout 600 python bench.py --workload atrium --no-cpu-baseline --stage-rates > gpurun_out/${tag}_atrium_bench.json 2>/dev/null; tail -c 400 gpurun_out/${tag}_atrium_bench.json)
+  (cd $R && timeout 600 python bench.py --full --workload atrium --no-cpu-baseline --stage-rates > $out/${tag}_atrium_bench.json 2>/dev/null; tail -c 400 $out/${tag}_atrium_bench.json)
 fi
