@@ -345,10 +345,50 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                    The passes above then run on (I~, lum(I~), var) unchanged.  HISTORY written: the demodulated output of
  *                    pass 0 (the colour), (mu1, mu2), n, F's guides and instance ids, F's camera; invalid pixels store n = 0
  *                    (and their output is c bit for bit, as above).  A fresh frame (the first, after a cut, any CONVERGE frame)
- *                    is the spatial filter's output bit for bit.  Moving or deforming instances are not reprojected: they restart.
+ *                    is the spatial filter's output bit for bit.  Moving or deforming instances are not reprojected: they restart,
+ *                    unless "denoise_motion".
  *                  Root-only buffers, allocated when the setting is turned on: 16 B (P's guides) + 2 x 4 B (instance ids) +
  *                  2 x 28 B (history) per pixel.  rfwhip_denoise_image stays spatial-only.
  *   denoise_alpha = SVGF's alpha in (0, 1] for colour and moments (default 0.2)
+ *   denoise_motion = "0" (default) | "1", meaningful with denoise = 1 and denoise_temporal = 1 (inert otherwise): a pixel whose
+ *                  instance moved or deformed since P is reprojected through the previous position of its own surface point
+ *                  instead of restarting.  "0": every image, every history value and the kernels launched are those of
+ *                  denoise_temporal alone.  Turning it on clears the history (as "denoise" and "denoise_temporal" do).
+ *                  For the stage of a new presented frame F the host puts every instance into one of three STATES:
+ *                    STILL: unchanged by every rfwhip_update since P's guides (the test above).  Its pixels take the path above,
+ *                      X = pos_F + z_p D_p: a frame in which nothing moved has the bits of "0".
+ *                    MOVED: changed, and all of: used at P's guides and at F's; the same mesh index; the mesh's build is the one
+ *                      P's guides saw (no rebuild since: refits, poses and morphs keep it.  As rfwhip_set_mesh's refit path does,
+ *                      equal vertex and triangle counts are taken to mean the same triangles: vertex j of triangle k now is
+ *                      vertex j of triangle k then, and the indices are read as they are now); the history is usable; P's
+ *                      transform is known (P's guide pass ran with the setting on); the current vertices are the ones F's guide
+ *                      pass traced; P's vertex positions are available: either the mesh was not edited between the two guide
+ *                      passes (they are the current ones), or the context's ONE snapshot of the mesh is P's.  The snapshot
+ *                      (16 B per vertex, root only, only for meshes edited in place) is copied on the context's stream in front
+ *                      of the first rfwhip_pose_mesh / rfwhip_morph_mesh / same-topology rfwhip_set_mesh that follows a
+ *                      presented frame, when the vertices are still the ones that frame's guide pass traced, and is tagged with
+ *                      that frame; nothing is copied or allocated while the setting is off.
+ *                    RESTART: anything else (a rebuilt mesh, another mesh, a new instance, a snapshot that is not P's).  Its
+ *                      pixels are fresh, as above.
+ *                  A pixel p of a MOVED instance, with the primitive k and barycentrics (u, v) of the hit the guide pass kept
+ *                  (after its alpha pass-through layers; w = 1 - u - v on vertex 0, u on vertex 1, v on vertex 2), a_j the current
+ *                  object-space vertices of triangle k, b_j the ones at P's guides, M_F / M_P the instance's transform at F's / P's
+ *                  guides:
+ *                    X_P = M_P (w b_0 + u b_1 + v b_2) replaces X in the REPROJECTION above (the intersection with P's image
+ *                      plane, the 4 taps, |X_P - pos_P| in the depth test); inside / valid / same-instance / depth tests unchanged;
+ *                    the normal test is n'_p . n_P(q) >= 0.9 with p's normal carried back by the triangle's own deformation:
+ *                      A_j = M_F a_j, B_j = M_P b_j, e_1 = A_1 - A_0, e_2 = A_2 - A_0, N_a = normalize(e_1 x e_2), f_1, f_2, N_b
+ *                      likewise from B, d = |f_1 x f_2|, c = (e_1 . n_p, e_2 . n_p, N_a . n_p),
+ *                      n'_p = normalize((c_1 (f_2 x N_b) + c_2 (N_b x f_1)) / d + c_3 N_b)  (= F^-T n_p for the linear map F
+ *                      taking (e_1, e_2, N_a) to (f_1, f_2, N_b); for a rigid motion, the rotation);
+ *                    a degenerate current or previous triangle (d = 0, |e_1 x e_2| = 0, anything not finite): p is fresh.
+ *                  Blend, variance, history writes and the passes are unchanged.  Lighting that moves with the object (shadows,
+ *                  reflections) is left to alpha and the luminance moments, as in SVGF.
+ *                  A FURTHER READ of F uses F's table again while neither an rfwhip_update nor a mesh edit (set_mesh, pose,
+ *                  morph) followed F's presentation; after one, every instance that is not STILL restarts in such a read (the
+ *                  current vertices and the snapshot may belong to another frame; they are never read then).
+ *                  Root-only buffers: 16 B per pixel (primitive, u, v of the guide pass; allocated when the setting is turned on
+ *                  with denoise_temporal, freed with the other denoiser buffers), 144 B per instance (the stage's table).
  *   sky_sampling = "0" (default: the sky is found only by BSDF-sampled rays that miss) | "1": the pt integrator's next-event
  *                  estimation importance-samples the sky.  The table is built by rfwhip_update, or by the next render after the
  *                  setting changed, from the sky of the last update, when the sky or the setting changed; it is allocated only
@@ -406,6 +446,13 @@ RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms,
  * stale.  albedo: W x H x 4 floats (rgb, w = 1 valid / 0 invalid); normal_depth: W x H x 4 floats (the unpacked normal, z; z = -1 for
  * an invalid pixel).  Either pointer may be NULL.  World-1 contexts and the root of a group. */
 RFWHIP_API int rfwhip_read_denoise_guides(rfwhip_context *ctx, float *albedo, float *normal_depth);
+/* The motion part of the temporal stage of the last presented frame (see "denoise_motion"; world-1 contexts whose last render has
+ * been presented with denoise, denoise_temporal and denoise_motion on).  Runs the stage of the frame again, as
+ * rfwhip_read_denoise_history does.  state: W x H int32, 0 invalid pixel, 1 its instance is STILL, 2 MOVED, 3 RESTART (every valid
+ * pixel while the history is not usable); prev_position: W x H x 3, X_P for state 2, X for state 1, 0 otherwise; prev_normal:
+ * W x H x 3, n'_p for state 2, n_p for state 1, 0 otherwise (a pixel on a degenerate triangle reports X and n_p and is fresh).
+ * Any pointer may be NULL. */
+RFWHIP_API int rfwhip_read_denoise_motion(rfwhip_context *ctx, int32_t *state, float *prev_position, float *prev_normal);
 /* Filter a given W x H float4 image (host memory) with the current guides and the context's denoise_* knobs, whatever "denoise"
  * says (the guide pass runs first if they are stale).  rgba_out may equal rgba_in. */
 RFWHIP_API int rfwhip_denoise_image(rfwhip_context *ctx, const float *rgba_in, float *rgba_out);

@@ -85,6 +85,7 @@ class CoreBinding:
                                   "read_denoise_guides": (i32, [vp, vp, vp]),
                                   "denoise_image": (i32, [vp, vp, vp]),
                                   "read_denoise_history": (i32, [vp, vp, vp, vp, vp, vp]),
+                                  "read_denoise_motion": (i32, [vp, vp, vp, vp]),
                                   "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32])}.items():
             if self._has(name):
                 f = self._fn(name)
@@ -319,6 +320,15 @@ class CoreBinding:
                                                    ((h, w, 4), (h, w), (h, w, 4), (h, w, 2), (h, w)))))
         self._check(self._fn("read_denoise_history")(self._ctx, *(out[k].ctypes.data for k in abi.DENOISE_HISTORY_KEYS)))
         return out
+
+    def read_denoise_motion(self):
+        """The motion part of the temporal stage of the last presented frame (include/rfwhip.h, "denoise_motion"; world-1
+        contexts): {"state": H x W int32 (0 invalid, 1 still, 2 moved, 3 restart), "position": H x W x 3 (X_P),
+        "normal": H x W x 3 (n'_p)}."""
+        h, w = self.height, self.width
+        state, pos, nrm = np.empty((h, w), np.int32), np.empty((h, w, 3), np.float32), np.empty((h, w, 3), np.float32)
+        self._check(self._fn("read_denoise_motion")(self._ctx, state.ctypes.data, pos.ctypes.data, nrm.ctypes.data))
+        return {"state": state, "position": pos, "normal": nrm}
 
     # known-answer hook: RFWHIP_KAT_* (include/rfwhip_abi.h)
     KAT = {"bsdf_eval": 0, "bsdf_pdf": 1, "bsdf_sample": 2, "tangent_space": 3, "pack_normal": 4,

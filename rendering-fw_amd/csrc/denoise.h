@@ -22,6 +22,10 @@
 // luminance moments with the history (n = min(n_P + 1, 64), a = max(alpha, 1 / n)) and takes var = max(0, mu2 - mu1^2) once
 // n >= 4 (the 3x3 estimate before).  Pass 0 writes the colour history (its demodulated output).  A fresh pixel (no consistent
 // tap, or no usable history) reads no history and gives the spatial filter's values bit for bit.
+// Motion (setting "denoise_motion"; dn_temporal_motion_item, the same body): a pixel of an instance that moved or deformed since P
+// and whose previous vertices are known (DnMotionInst::state == DN_M_MOVED) is reprojected through the previous position of its own
+// surface point, X_P = M_P (w b_0 + u b_1 + v b_2), and its normal is carried back by the triangle's own deformation before the
+// normal test.  The guide pass's variant dn_guide_surf_item keeps the hit's primitive and barycentrics for it (DnMotion::surf).
 #pragma once
 
 constexpr int DN_MAX_ALPHA = 8;			// alpha-tested layers a guide ray passes before the pixel is called invalid
@@ -77,49 +81,16 @@ RT_FN bool dn_pixel(uint32_t bx, uint32_t by, uint32_t t, uint32_t W, uint32_t H
 // ---- guide pass ---------------------------------------------------------------------------------------------------------
 RT_FN void dn_guide_item(const Params &p, const DnView &d, uint32_t i, const TravStack &stk)
 {
-	const uint32_t x = i % d.W, y = i / d.W;
-	f3 O, D;
-	pt_center_ray(p.cam, p.fr, x, y, O, D);
-	f3 albedo = mk3(0, 0, 0), n = mk3(0, 0, 1);
-	float z = 0.0f;
-	bool valid = false;
-	uint32_t inst = DN_NO_INST;
-	for (int layer = 0; layer <= DN_MAX_ALPHA; layer++)
-	{
-		Hit h;
-		TStat st;
-		st.inner = 0, st.tris = 0, st.lds = 0;
-		trace<false, false>(p.sc, O, D, 1e-5f, 1e34f, h, stk, st);
-		if (h.prim < 0)
-			break;
-		Surface sf;
-		pt_surface(p.sc, h, sf);
-		f3 color = material_color(*sf.mat), iN = sf.iN;
-		bool alpha_skip = false;
-		if (p.textured && pt_has_textures(p.sc, sf))
-			pt_textures(p.sc, p.cam, D, h.t, sf, color, iN, alpha_skip);
-		z += h.t;
-		if (alpha_skip)
-		{
-			// the path tracer's pass-through (pt_shade): on from I + 1e-5 D in the same direction
-			const f3 I = O + D * h.t;
-			O = I + D * 1e-5f;
-			z += 1e-5f;
-			continue;
-		}
-		if (!(color.x > 1.0f || color.y > 1.0f || color.z > 1.0f)) // (an emitter ends the path: pt_shade)
-		{
-			albedo = color;
-			n = iN * ((dot(D, sf.N) > 0.0f) ? -1.0f : 1.0f);
-			valid = true;
-			inst = (uint32_t)h.inst;
-		}
-		break;
-	}
-	d.ga[i] = mk4(albedo.x, albedo.y, albedo.z, valid ? 1.0f : 0.0f);
-	d.gb[i] = mk4(ubits(dn_oct_encode(n)), valid ? z : -1.0f, 0.0f, 0.0f);
-	if (d.id) // (the temporal stage's instance test)
-		d.id[i] = inst;
+#define DN_BODY_SURF 0
+#include "denoise_guide_body.h"
+#undef DN_BODY_SURF
+}
+// "denoise_motion": the same item, which also keeps the hit's primitive and barycentrics (surf[i] = (prim, u, v, 0))
+RT_FN void dn_guide_surf_item(const Params &p, const DnView &d, f4 *surf, uint32_t i, const TravStack &stk)
+{
+#define DN_BODY_SURF 1
+#include "denoise_guide_body.h"
+#undef DN_BODY_SURF
 }
 
 // screen-space depth gradient (a second kernel: it reads the neighbours' z); writes gb[i].z / .w only
@@ -195,86 +166,61 @@ RT_FN void dn_demod_item(const DnView &d, f4 *img, float *var, uint32_t i)
 // blends with its history and chooses the variance, in place: img (I~, lum(I~)) / var; the moments and the history length into
 // t.mom_out / t.n_out.  A fresh pixel leaves img / var as the demodulation wrote them: the spatial filter's values, bit for bit.
 // Invalid pixels store n = 0.  (Reads and writes pixel i of img / var only.)
+// Motion ("denoise_motion", dn_temporal_motion_item): a pixel whose instance changed since P and is DN_M_MOVED in m.inst takes X_P
+// and n'_p below in place of X and n_p; every other pixel runs the code of the stage unchanged.
+// m.dump (rfwhip_read_denoise_motion; null in a presented frame's stage): 8 floats per pixel, state | X_P | n'_p | 0.
+RT_FN void dn_motion_dump(const DnMotion &m, uint32_t i, uint32_t state, f3 X, f3 n)
+{
+	float *const o = m.dump + 8u * (size_t)i;
+	o[0] = (float)state, o[1] = X.x, o[2] = X.y, o[3] = X.z, o[4] = n.x, o[5] = n.y, o[6] = n.z, o[7] = 0.0f;
+}
+RT_FN f3 dn_xform(const float *M, f3 v) // rows 0..2 of a 4 x 4 matrix, 3 x 4 row-major
+{
+	return mk3(M[0] * v.x + M[1] * v.y + M[2] * v.z + M[3], M[4] * v.x + M[5] * v.y + M[6] * v.z + M[7],
+			   M[8] * v.x + M[9] * v.y + M[10] * v.z + M[11]);
+}
+// the previous position of the surface point (prim, u, v) of a MOVED instance and p's normal carried back to P; false: degenerate
+RT_FN bool dn_motion_point(const DnMotionInst &mi, const f4 sf, f3 &X, f3 &n)
+{
+	const uint32_t k = fbits(sf.x);
+	if (k >= mi.tri_count)
+		return false;
+	uint32_t i0 = 3u * k, i1 = 3u * k + 1u, i2 = 3u * k + 2u;
+	if (mi.indices)
+		i0 = mi.indices[3u * k], i1 = mi.indices[3u * k + 1u], i2 = mi.indices[3u * k + 2u];
+	if (i0 >= mi.vert_count || i1 >= mi.vert_count || i2 >= mi.vert_count)
+		return false;
+	const f4 a0 = mi.cur[i0], a1 = mi.cur[i1], a2 = mi.cur[i2], b0 = mi.prev[i0], b1 = mi.prev[i1], b2 = mi.prev[i2];
+	const float u = sf.y, v = sf.z, w = 1.0f - u - v;
+	const f3 A0 = dn_xform(mi.mf, xyz(a0)), B0 = dn_xform(mi.mp, xyz(b0));
+	const f3 e1 = dn_xform(mi.mf, xyz(a1)) - A0, e2 = dn_xform(mi.mf, xyz(a2)) - A0;
+	const f3 f1 = dn_xform(mi.mp, xyz(b1)) - B0, f2 = dn_xform(mi.mp, xyz(b2)) - B0;
+	const f3 ca = cross(e1, e2), cb = cross(f1, f2);
+	const float la = length(ca), dd = length(cb);
+	if (!(la > 0.0f && la < 1e30f && dd > 0.0f && dd < 1e30f))
+		return false;
+	const f3 Na = ca * (1.0f / la), Nb = cb * (1.0f / dd);
+	const float c1 = dot(e1, n), c2 = dot(e2, n), c3 = dot(Na, n);
+	const f3 r = (cross(f2, Nb) * c1 + cross(Nb, f1) * c2) * (1.0f / dd) + Nb * c3;
+	const float lr = length(r);
+	if (!(lr > 0.0f && lr < 1e30f))
+		return false;
+	n = r * (1.0f / lr);
+	X = dn_xform(mi.mp, xyz(b0) * w + xyz(b1) * u + xyz(b2) * v);
+	return true;
+}
+
 RT_FN void dn_temporal_item(const DnView &d, const DnTemporal &t, f4 *img, float *var, uint32_t i)
 {
-	const f4 gp = d.gb[i];
-	if (gp.y < 0.0f)
-	{
-		d.hist[i] = mk4(0.0f, 0.0f, 0.0f, 0.0f); // (never read: P's guide at an invalid pixel fails every tap)
-		t.mom_out[2 * i] = 0.0f, t.mom_out[2 * i + 1] = 0.0f, t.n_out[i] = 0.0f;
-		return;
-	}
-	const uint32_t x = i % d.W, y = i / d.W;
-	const f4 I = img[i];
-	const float l = I.w;
-	// the consistent bilinear taps of X in P (fixed order: (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1))
-	float wq[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ws = 0.0f;
-	uint32_t qi[4] = {0u, 0u, 0u, 0u};
-	if (t.usable)
-	{
-		f3 O, D;
-		pt_center_ray(t.cam, t.fr, x, y, O, D);
-		const f3 X = O + D * gp.y, e = X - t.pcam.pos;
-		const f3 pn = cross(t.pcam.right, t.pcam.up);
-		const float s = dot(t.pcam.p1 - t.pcam.pos, pn) / dot(e, pn); // the ray pos_P -> X meets P's image plane at pos_P + s e
-		if (s > 0.0f)
-		{
-			const f3 Q = t.pcam.pos + e * s - t.pcam.p1, R = t.pcam.right, U = t.pcam.up;
-			const float rr = dot(R, R), ru = dot(R, U), uu = dot(U, U), qr = dot(Q, R), qu = dot(Q, U);
-			const float det = rr * uu - ru * ru;
-			const float xf = (qr * uu - qu * ru) / det * (float)d.W - 0.5f, yf = (qu * rr - qr * ru) / det * (float)d.H - 0.5f;
-			if (xf > -1.0f && xf < (float)d.W && yf > -1.0f && yf < (float)d.H) // (false for NaN)
-			{
-				const float fx0 = floorf(xf), fy0 = floorf(yf), fx = xf - fx0, fy = yf - fy0;
-				const int x0 = (int)fx0, y0 = (int)fy0;
-				const float dist = length(e);
-				const uint32_t id = t.id[i];
-				const bool same = id < t.n_inst && t.inst_ver[id] <= t.pscene; // (the instance has not changed since P)
-				const f3 np = dn_oct_decode(fbits(gp.x));
-				for (int k = 0; k < 4; k++)
-				{
-					const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
-					const float bw = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-					if (!same || bw <= 0.0f || qx < 0 || qy < 0 || qx >= (int)d.W || qy >= (int)d.H)
-						continue;
-					const uint32_t q = (uint32_t)qy * d.W + (uint32_t)qx;
-					const f4 gq = t.pgb[q];
-					if (gq.y < 0.0f || t.pid[q] != id)
-						continue;
-					if (fabsf(gq.y - dist) > DN_T_DEPTH_GRAD * (fabsf(gq.z) + fabsf(gq.w)) + DN_T_DEPTH_REL * dist)
-						continue;
-					if (dot(np, dn_oct_decode(fbits(gq.x))) < DN_T_NORMAL)
-						continue;
-					wq[k] = bw, qi[k] = q, ws += bw;
-				}
-			}
-		}
-	}
-	if (!(ws >= DN_T_MIN_WEIGHT))
-	{
-		// fresh: no history is read, img / var stay the demodulation's
-		t.mom_out[2 * i] = l, t.mom_out[2 * i + 1] = l * l, t.n_out[i] = 1.0f;
-		return;
-	}
-	const float inv = 1.0f / ws;
-	float hr = 0.0f, hg = 0.0f, hb = 0.0f, h1 = 0.0f, h2 = 0.0f, hn = 0.0f;
-	for (int k = 0; k < 4; k++)
-	{
-		if (wq[k] == 0.0f)
-			continue;
-		const float w = wq[k] * inv;
-		const f4 hc = t.col_in[qi[k]];
-		hr += w * hc.x, hg += w * hc.y, hb += w * hc.z;
-		h1 += w * t.mom_in[2 * qi[k]], h2 += w * t.mom_in[2 * qi[k] + 1], hn += w * t.n_in[qi[k]];
-	}
-	const float n = fminf(hn + 1.0f, DN_T_MAX_N);
-	const float al = fmaxf(t.alpha, 1.0f / n), bl = 1.0f - al;
-	const float r = bl * hr + al * I.x, g = bl * hg + al * I.y, b = bl * hb + al * I.z;
-	const float m1 = bl * h1 + al * l, m2 = bl * h2 + al * (l * l);
-	img[i] = mk4(r, g, b, dn_lum(r, g, b));
-	if (n >= DN_T_VAR_N) // (before: the 3x3 estimate the demodulation wrote)
-		var[i] = fmaxf(0.0f, m2 - m1 * m1);
-	t.mom_out[2 * i] = m1, t.mom_out[2 * i + 1] = m2, t.n_out[i] = n;
+#define DN_BODY_MOTION 0
+#include "denoise_temporal_body.h"
+#undef DN_BODY_MOTION
+}
+RT_FN void dn_temporal_motion_item(const DnView &d, const DnTemporal &t, const DnMotion &m, f4 *img, float *var, uint32_t i)
+{
+#define DN_BODY_MOTION 1
+#include "denoise_temporal_body.h"
+#undef DN_BODY_MOTION
 }
 
 // one a-trous pass of step `step`: src / vsrc -> dst / vdst, or (last) the remodulated image into d.out (may be d.in)

@@ -65,6 +65,24 @@ struct DnTemporal
 	uint32_t usable;			 // 0: every pixel starts fresh (no history is read)
 };
 
+// Motion in the temporal stage (setting "denoise_motion"; denoise.h dn_temporal_motion_item).  Per instance: what the host decided
+// (DN_M_STILL / DN_M_MOVED / DN_M_RESTART) and, for MOVED, the transforms at P's guides and now (rows 0..2, row-major 3 x 4) and
+// the mesh's object-space vertices now and at P's guides (the same array for a mesh nobody edited since)
+constexpr uint32_t DN_M_INVALID = 0u, DN_M_STILL = 1u, DN_M_MOVED = 2u, DN_M_RESTART = 3u; // (rfwhip_read_denoise_motion's states)
+struct alignas(16) DnMotionInst
+{
+	float mp[12], mf[12];
+	const rt::f4 *cur, *prev;
+	const uint32_t *indices; // three per triangle, or null: triangle k has the vertices 3 k .. 3 k + 2
+	uint32_t state, tri_count, vert_count, pad;
+};
+struct DnMotion
+{
+	const DnMotionInst *inst; // DnTemporal::n_inst records
+	const rt::f4 *surf;		  // per pixel, from the guide pass: (primitive, u, v, 0)
+	float *dump;			  // rfwhip_read_denoise_motion: 8 floats per pixel (state, X_P, n'_p, 0), or null
+};
+
 // capacity of the LDS top-of-tree cache the kernels were built with
 uint32_t max_lds_nodes();
 
@@ -95,12 +113,14 @@ void launch_kat(const Params &p, const rt::SkyView &sky, int function, const flo
 // out: local layout (local_rows x W) when full == 0, else full image (H x W; world must be 1)
 void launch_present(const Params &p, rt::f4 *out, float scale, int full, stream_t s);
 // the denoiser's guide pass (p: scene, camera and FrameView of the full image) = guide kernel + depth-gradient kernel
-void launch_denoise_guides(const Params &p, const DnView &d, stream_t s);
+// surf != null ("denoise_motion"): the guide kernel's variant that also writes the surface record per pixel
+void launch_denoise_guides(const Params &p, const DnView &d, rt::f4 *surf, stream_t s);
 // demodulation + variance (with t, then the temporal stage), d.iterations a-trous passes, remodulation into d.out:
 // 1 (+ 1 with t) + d.iterations launches
-void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s);
+// m != null (with t): the stage's motion variant k_dn_temporal_motion
+void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion *m, stream_t s);
 // demodulation + the temporal stage, into d.img[0] / d.var[0] (rfwhip_read_denoise_history): 2 launches
-void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t s);
+void launch_denoise_temporal(const DnView &d, const DnTemporal &t, const DnMotion *m, stream_t s);
 // a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
 rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,

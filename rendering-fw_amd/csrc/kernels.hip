@@ -2316,6 +2316,14 @@ __global__ void __launch_bounds__(BLOCK) k_dn_guides(const Params p, const DnVie
 	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
 		dn_guide_item(p, d, i, ctx.stk);
 }
+__global__ void __launch_bounds__(BLOCK) k_dn_guides_surf(const Params p, const DnView d, f4 *surf)
+{
+	RT_STACK_DECL_CLOSEST
+	ctx.stk.overflow = d.overflow;
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_guide_surf_item(p, d, surf, i, ctx.stk);
+}
 __global__ void __launch_bounds__(BLOCK) k_dn_gradient(const DnView d)
 {
 	uint32_t i;
@@ -2334,6 +2342,12 @@ __global__ void __launch_bounds__(BLOCK) k_dn_temporal(const DnView d, const DnT
 	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
 		dn_temporal_item(d, t, d.img[0], d.var[0], i);
 }
+__global__ void __launch_bounds__(BLOCK) k_dn_temporal_motion(const DnView d, const DnTemporal t, const DnMotion m)
+{
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_temporal_motion_item(d, t, m, d.img[0], d.var[0], i);
+}
 __global__ void __launch_bounds__(BLOCK) k_dn_pass(const DnView d, uint32_t pass)
 {
 	uint32_t i;
@@ -2342,20 +2356,26 @@ __global__ void __launch_bounds__(BLOCK) k_dn_pass(const DnView d, uint32_t pass
 					 d.var[(pass + 1u) & 1u], i);
 }
 static dim3 dn_grid(const DnView &d) { return dim3((d.W + DN_TILE_X - 1) / DN_TILE_X, (d.H + DN_TILE_Y - 1) / DN_TILE_Y); }
-void launch_denoise_guides(const Params &p, const DnView &d, stream_t s)
+void launch_denoise_guides(const Params &p, const DnView &d, f4 *surf, stream_t s)
 {
-	hipLaunchKernelGGL(k_dn_guides, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d);
+	if (surf)
+		hipLaunchKernelGGL(k_dn_guides_surf, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d, surf);
+	else
+		hipLaunchKernelGGL(k_dn_guides, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d);
 	hipLaunchKernelGGL(k_dn_gradient, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
 }
-void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t s)
+void launch_denoise_temporal(const DnView &d, const DnTemporal &t, const DnMotion *m, stream_t s)
 {
 	hipLaunchKernelGGL(k_dn_demod, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
-	hipLaunchKernelGGL(k_dn_temporal, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d, t);
+	if (m)
+		hipLaunchKernelGGL(k_dn_temporal_motion, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d, t, *m);
+	else
+		hipLaunchKernelGGL(k_dn_temporal, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d, t);
 }
-void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s)
+void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion *m, stream_t s)
 {
 	if (t)
-		launch_denoise_temporal(d, *t, s);
+		launch_denoise_temporal(d, *t, m, s);
 	else
 		hipLaunchKernelGGL(k_dn_demod, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, d);
 	for (uint32_t k = 0; k < d.iterations; k++)

@@ -394,31 +394,40 @@ void launch_deinterleave(const f4 *gathered, f4 *out, uint32_t W, uint32_t H, ui
 	for (uint32_t i = 0; i < W * H; i++)
 		deinterleave_item(gathered, out, W, H, local_rows, world, i);
 }
-void launch_denoise_guides(const Params &p, const DnView &d, stream_t s)
+void launch_denoise_guides(const Params &p, const DnView &d, f4 *surf, stream_t s)
 {
-	EMU_DEFER(s, launch_denoise_guides(p, d, s));
+	EMU_DEFER(s, launch_denoise_guides(p, d, surf, s));
 	Ctx ctx(p);
 	ctx.stk.overflow = d.overflow;
 	for (uint32_t i = 0; i < d.W * d.H; i++)
-		dn_guide_item(p, d, i, ctx.stk);
+		if (surf)
+			dn_guide_surf_item(p, d, surf, i, ctx.stk);
+		else
+			dn_guide_item(p, d, i, ctx.stk);
 	for (uint32_t i = 0; i < d.W * d.H; i++)
 		dn_gradient_item(d, i);
 }
-void launch_denoise_temporal(const DnView &d, const DnTemporal &t, stream_t s)
+void launch_denoise_temporal(const DnView &d, const DnTemporal &t, const DnMotion *m, stream_t s)
 {
-	EMU_DEFER(s, launch_denoise_temporal(d, t, s));
+	const DnMotion mv = m ? *m : DnMotion{}; // (a host record: taken at enqueue)
+	const bool has_m = m != nullptr;
+	EMU_DEFER(s, launch_denoise_temporal(d, t, has_m ? &mv : nullptr, s));
 	for (uint32_t i = 0; i < d.W * d.H; i++)
 		dn_demod_item(d, d.img[0], d.var[0], i);
 	for (uint32_t i = 0; i < d.W * d.H; i++)
-		dn_temporal_item(d, t, d.img[0], d.var[0], i);
+		if (m)
+			dn_temporal_motion_item(d, t, *m, d.img[0], d.var[0], i);
+		else
+			dn_temporal_item(d, t, d.img[0], d.var[0], i);
 }
-void launch_denoise_filter(const DnView &d, const DnTemporal *t, stream_t s)
+void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion *m, stream_t s)
 {
-	const DnTemporal tv = t ? *t : DnTemporal{}; // (a host record: taken at enqueue)
-	const bool has_t = t != nullptr;
-	EMU_DEFER(s, launch_denoise_filter(d, has_t ? &tv : nullptr, s));
+	const DnTemporal tv = t ? *t : DnTemporal{}; // (host records: taken at enqueue)
+	const DnMotion mv = m ? *m : DnMotion{};
+	const bool has_t = t != nullptr, has_m = m != nullptr;
+	EMU_DEFER(s, launch_denoise_filter(d, has_t ? &tv : nullptr, has_m ? &mv : nullptr, s));
 	if (t)
-		launch_denoise_temporal(d, *t, s);
+		launch_denoise_temporal(d, *t, m, s);
 	else
 		for (uint32_t i = 0; i < d.W * d.H; i++)
 			dn_demod_item(d, d.img[0], d.var[0], i);

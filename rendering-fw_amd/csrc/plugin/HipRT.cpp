@@ -270,18 +270,19 @@ class Context final : public rfw::RenderContext
 	rfw::AvailableRenderSettings get_settings() const override
 	{
 		rfw::AvailableRenderSettings s;
-		s.settingKeys = {"integrator", "jitter", "spp", "max_depth", "DENOISE", "DENOISE_TEMPORAL", "sky_sampling"};
+		s.settingKeys = {"integrator", "jitter", "spp", "max_depth", "DENOISE", "DENOISE_TEMPORAL", "sky_sampling", "DENOISE_MOTION"};
 		s.settingValues = {{"pt", "parity"}, {"xor128", "center"}, {"1", "2", "4", "8", "16"}, {"0", "1", "2", "3", "4"}, {"0", "1"},
-						   {"0", "1"}, {"0", "1"}};
+						   {"0", "1"}, {"0", "1"}, {"0", "1"}};
 		return s;
 	}
 
 	void set_setting(const rfw::RenderSetting &setting) override
 	{
 		// the reference's OptiX 6 key (OptiXContext.cpp:812-822): the denoised image is what render_frame hands out
-		// ... and its temporal stage (the history follows the frames render_frame presents)
+		// ... and its temporal stage (the history follows the frames render_frame presents), with or without motion
 		const char *key = setting.name == "DENOISE"			 ? "denoise"
 						  : setting.name == "DENOISE_TEMPORAL" ? "denoise_temporal"
+						  : setting.name == "DENOISE_MOTION"   ? "denoise_motion"
 															   : setting.name.c_str();
 		HIPRT_CHECK(rfwhip_group_set_setting(m_Group, key, setting.value.c_str()));
 	}

@@ -409,6 +409,11 @@ struct MeshRec
 	uint32_t generation = 0; // counts the (re)builds of this mesh (the world tree's cache key)
 	uint32_t refits = 0;	 // same-topology rfwhip_set_mesh calls since the last build: an animated mesh (never written into the world tree)
 	uint32_t edits = 0;		 // rebuilds, refits, poses and morphs (the denoiser's temporal stage: instance_versions)
+	// "denoise_motion": `edits` as the last guide pass traced the mesh and as the last presented frame's guide pass did; ONE snapshot
+	// of d_verts, taken in front of the first in-place edit after a presented frame and tagged with that frame (dn_snapshot_mesh)
+	uint32_t dn_g_edits = 0, dn_p_edits = 0;
+	DevBuf d_dn_snap;
+	unsigned long long dn_snap_pres = 0; // rfwhip_context::dn_pres_id of the frame whose vertices it holds (0: none)
 	// device skinning (rfwhip_set_mesh_skin / rfwhip_pose_mesh)
 	bool skinned = false, posed = false;
 	DevBuf d_base_verts, d_base_normals, d_joints, d_weights, d_vnormals, d_joint_mats;
@@ -417,6 +422,15 @@ struct MeshRec
 	bool morphed = false;
 	DevBuf d_tgt_pos, d_tgt_nrm, d_morph_weights;
 	uint32_t target_count = 0;
+};
+
+// "denoise_motion": an instance as a guide pass traced it
+struct DnInstSnap
+{
+	bool used = false;
+	size_t mesh = 0;
+	uint32_t generation = 0, edits = 0;
+	float transform[16];
 };
 
 struct InstRec
@@ -588,6 +602,18 @@ struct rfwhip_context
 	uint32_t dn_t_pscene = 0;
 	std::vector<uint32_t> dn_inst_ver;		// per instance: InstRec::dn_version (uploaded into d_dn_inst_ver)
 	bool dn_inst_ver_stale = true;			// d_dn_inst_ver is missing or older than dn_inst_ver: uploaded before the next stage
+	// ... and its motion part (setting "denoise_motion"): the surface record of the current guides (16 B per pixel), the instances as
+	// the current guides (g) and P's guides (p) traced them, and the stage's per-instance table (host copy + device copy)
+	int dn_motion = 0;
+	DevBuf d_dn_surf, d_dn_minst;
+	std::vector<DnInstSnap> dn_g_rec, dn_p_rec;
+	bool dn_g_rec_ok = false, dn_p_rec_ok = false; // (recorded by a guide pass that ran with the setting on)
+	unsigned long long dn_pres_id = 1;		// counts presented frames: the tag of the meshes' vertex snapshots
+	unsigned long long dn_edit_count = 0;	// counts rfwhip_set_mesh / pose / morph calls
+	std::vector<rtk::DnMotionInst> dn_mtab; // the table of the last presented frame's stage ...
+	uint32_t dn_mtab_scene = 0;				// ... valid for a further read of that frame while no update and no mesh edit followed
+	unsigned long long dn_mtab_edits = 0;
+	bool dn_mtab_stale = true;
 
 	// scene (host side)
 	std::vector<MeshRec> meshes;
@@ -774,6 +800,23 @@ extern "C" int rfwhip_create(int device_ordinal, int rank, int world, rfwhip_con
 static void dn_clear_history(rfwhip_context *c)
 {
 	c->dn_have_pres = false, c->dn_guides_pres = false, c->dn_prev_ok = false, c->dn_reset_since = false;
+	c->dn_p_rec_ok = false, c->dn_mtab_stale = true;
+}
+
+// "denoise_motion": keep the vertices the last presented frame's guide pass traced, in front of the first in-place edit of the mesh
+// that follows it (called after sync_all, before the edit is enqueued on the context's stream).  No copy when the mesh has been
+// edited since that guide pass (the vertices are no longer P's: its instances restart) or the snapshot is P's already.
+static int dn_snapshot_mesh(rfwhip_context *c, MeshRec &m)
+{
+	c->dn_edit_count++;
+	if (!c->dn_motion || !c->dn_temporal || !c->denoise || c->rank != 0 || !c->dn_have_pres || !c->dn_p_rec_ok)
+		return 0;
+	if (m.dn_snap_pres == c->dn_pres_id || m.edits != m.dn_p_edits || !m.d_verts.p)
+		return 0;
+	RF_TRY(m.d_dn_snap.ensure(m.vertexCount * sizeof(f4)));
+	RF_TRY(dm::d2d(m.d_dn_snap.p, m.d_verts.p, m.vertexCount * sizeof(f4), c->stream));
+	m.dn_snap_pres = c->dn_pres_id;
+	return 0;
 }
 
 static void free_all(rfwhip_context *c)
@@ -782,7 +825,7 @@ static void free_all(rfwhip_context *c)
 	{
 		DevBuf *mb[] = {&m.d_verts, &m.d_indices, &m.d_parents, &m.d_flags, &m.d_base_verts, &m.d_base_normals, &m.d_joints,
 						&m.d_weights, &m.d_vnormals, &m.d_joint_mats, &m.d_tgt_pos, &m.d_tgt_nrm, &m.d_morph_weights,
-						&m.d_b_nodes, &m.d_b_nodes4, &m.d_b_src, &m.d_b_tri_verts};
+						&m.d_b_nodes, &m.d_b_nodes4, &m.d_b_src, &m.d_b_tri_verts, &m.d_dn_snap};
 		for (DevBuf *b : mb)
 			b->free_();
 	}
@@ -795,7 +838,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_sh_dir[0], &c->d_sh_dir[1], &c->d_sh_rad[0], &c->d_sh_rad[1], &c->d_rad[0], &c->d_rad[1],
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
-					  &c->d_dn_inst_ver, &c->d_sky_alias};
+					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias};
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->guides_valid = false;
@@ -874,7 +917,7 @@ extern "C" int rfwhip_init(rfwhip_context *c, uint32_t width, uint32_t height)
 	RF_TRY(sync_all(c));
 	c->W = width, c->H = height;
 	c->d_dn_guides.free_(), c->d_dn_img.free_(), c->d_dn_var.free_(); // (re-allocated at the new size while denoise is on)
-	c->d_dn_prev.free_(), c->d_dn_ids.free_(), c->d_dn_hist.free_();
+	c->d_dn_prev.free_(), c->d_dn_ids.free_(), c->d_dn_hist.free_(), c->d_dn_surf.free_();
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->samples_total = 0, c->sample_origin = 0;
@@ -1067,6 +1110,10 @@ extern "C" int rfwhip_set_mesh(rfwhip_context *c, size_t index, const rfwhip_mes
 	const bool same_topology = m.used && m.resident && !m.dirty && m.vertexCount == mesh->vertexCount &&
 							   m.triCount == mesh->triangleCount && m.indexed == (mesh->indices != nullptr);
 	RF_TRY(sync_all(c));
+	if (same_topology)
+		RF_TRY(dn_snapshot_mesh(c, m));
+	else
+		c->dn_edit_count++;
 	// vertices / indices always go to the device (the refit kernels read them there)
 	RF_TRY(m.d_verts.ensure(mesh->vertexCount * sizeof(f4)));
 	RF_TRY(dm::h2d(m.d_verts.p, mesh->vertices, mesh->vertexCount * sizeof(f4), c->stream));
@@ -1311,6 +1358,7 @@ extern "C" int rfwhip_pose_mesh(rfwhip_context *c, size_t index, const float *jo
 	if (!m.resident || m.dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_pose_mesh: mesh %zu is not resident yet (rfwhip_update first)", index);
 	RF_TRY(sync_all(c));
+	RF_TRY(dn_snapshot_mesh(c, m));
 	RF_TRY(m.d_joint_mats.ensure(joint_count * 64));
 	RF_TRY(dm::h2d(m.d_joint_mats.p, joint_matrices16, joint_count * 64, c->stream));
 	m.joint_count = (uint32_t)joint_count;
@@ -1405,6 +1453,7 @@ extern "C" int rfwhip_morph_mesh(rfwhip_context *c, size_t index, const float *w
 	if (!m.resident || m.dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_morph_mesh: mesh %zu is not resident yet (rfwhip_update first)", index);
 	RF_TRY(sync_all(c));
+	RF_TRY(dn_snapshot_mesh(c, m));
 	RF_TRY(dm::h2d(m.d_morph_weights.p, weights, weight_count * sizeof(float), c->stream));
 	dm::event_t ea, eb;
 	const bool timed = c->stage_timing != 0;
@@ -2784,6 +2833,8 @@ static int dn_ensure(rfwhip_context *c)
 		RF_TRY(c->d_dn_prev.ensure_exact(px * sizeof(f4)));
 		RF_TRY(c->d_dn_ids.ensure_exact(2 * px * sizeof(uint32_t)));
 		RF_TRY(c->d_dn_hist.ensure_exact(2 * px * (sizeof(f4) + 3 * sizeof(float))));
+		if (c->dn_motion)
+			RF_TRY(c->d_dn_surf.ensure_exact(px * sizeof(f4)));
 	}
 	return 0;
 }
@@ -2871,9 +2922,27 @@ static int dn_guides(rfwhip_context *c, void *stream)
 	const rtk::DnView d = dn_view(c, nullptr, nullptr);
 	RF_TRY(dm::zero(d.overflow, sizeof(uint32_t), stream));
 	StageTimer t(c, KF_DENOISE, -1, stream);
-	rtk::launch_denoise_guides(p, d, stream);
+	const bool motion = c->dn_temporal && c->dn_motion;
+	rtk::launch_denoise_guides(p, d, motion ? c->d_dn_surf.as<f4>() : nullptr, stream);
 	t.stop(2);
 	RF_TRY(dm::last_launch_error());
+	c->dn_g_rec_ok = motion;
+	if (motion)
+	{
+		// what this pass traced (no set_* call is pending: scene_dirty is false here)
+		c->dn_g_rec.assign(c->instances.size(), DnInstSnap());
+		for (size_t i = 0; i < c->instances.size(); i++)
+		{
+			const InstRec &in = c->instances[i];
+			DnInstSnap &r = c->dn_g_rec[i];
+			if (!in.used || in.mesh >= c->meshes.size())
+				continue;
+			r.used = true, r.mesh = in.mesh, r.generation = c->meshes[in.mesh].generation, r.edits = c->meshes[in.mesh].edits;
+			memcpy(r.transform, in.transform, sizeof(r.transform));
+		}
+		for (auto &m : c->meshes)
+			m.dn_g_edits = m.edits;
+	}
 	c->guides_valid = true, c->guide_cam = c->last_cam, c->guide_scene = c->scene_version, c->guide_W = c->W, c->guide_H = c->H;
 	c->dn_guides_pres = false;
 	return 0;
@@ -2889,6 +2958,71 @@ static int dn_check_overflow(rfwhip_context *c)
 	return 0;
 }
 
+// "denoise_motion": the stage's per-instance table.  For a new presented frame F it is built from P's record and the record of F's
+// guide pass, and kept; a further read of F uses it again while no rfwhip_update and no mesh edit followed — after one, the
+// current vertices and the snapshots may be another frame's, and every instance that is not STILL restarts.
+static void dn_rows(const float *M, float *rows) // column-major 4 x 4 -> rows 0..2, row-major 3 x 4
+{
+	for (int r = 0; r < 3; r++)
+		for (int k = 0; k < 4; k++)
+			rows[4 * r + k] = M[4 * k + r];
+}
+static int dn_motion_view(rfwhip_context *c, bool new_frame, void *stream, rtk::DnMotion &mv)
+{
+	const size_t n = c->dn_inst_ver.size();
+	if (new_frame)
+	{
+		c->dn_mtab.assign(n, rtk::DnMotionInst{});
+		for (size_t i = 0; i < n; i++)
+		{
+			rtk::DnMotionInst &e = c->dn_mtab[i];
+			e.state = rtk::DN_M_RESTART;
+			if (c->dn_inst_ver[i] <= c->dn_t_pscene)
+			{
+				e.state = rtk::DN_M_STILL;
+				continue;
+			}
+			if (!c->dn_t_usable || !c->dn_p_rec_ok || !c->dn_g_rec_ok || i >= c->dn_p_rec.size() || i >= c->dn_g_rec.size())
+				continue;
+			const DnInstSnap &P = c->dn_p_rec[i], &G = c->dn_g_rec[i];
+			if (!P.used || !G.used || P.mesh != G.mesh || P.generation != G.generation || G.mesh >= c->meshes.size())
+				continue;
+			const MeshRec &m = c->meshes[G.mesh];
+			// the current vertices must be the ones F's guide pass traced, and P's either the same or the snapshot taken of P
+			if (!m.used || !m.d_verts.p || m.generation != G.generation || m.edits != G.edits)
+				continue;
+			const f4 *prev = nullptr;
+			if (P.edits == G.edits)
+				prev = m.d_verts.as<f4>();
+			else if (m.dn_snap_pres == c->dn_pres_id && m.d_dn_snap.p)
+				prev = m.d_dn_snap.as<f4>();
+			if (!prev)
+				continue;
+			e.state = rtk::DN_M_MOVED;
+			dn_rows(P.transform, e.mp), dn_rows(G.transform, e.mf);
+			e.cur = m.d_verts.as<f4>(), e.prev = prev;
+			e.indices = m.indexed ? m.d_indices.as<uint32_t>() : nullptr;
+			e.tri_count = (uint32_t)m.triCount, e.vert_count = (uint32_t)m.vertexCount;
+		}
+		c->dn_mtab_scene = (uint32_t)c->scene_version, c->dn_mtab_edits = c->dn_edit_count, c->dn_mtab_stale = true;
+	}
+	else if (c->dn_mtab.size() != n || c->dn_mtab_scene != (uint32_t)c->scene_version || c->dn_mtab_edits != c->dn_edit_count)
+	{
+		c->dn_mtab.assign(n, rtk::DnMotionInst{});
+		for (size_t i = 0; i < n; i++)
+			c->dn_mtab[i].state = c->dn_inst_ver[i] <= c->dn_t_pscene ? rtk::DN_M_STILL : rtk::DN_M_RESTART;
+		c->dn_mtab_scene = (uint32_t)c->scene_version, c->dn_mtab_edits = c->dn_edit_count, c->dn_mtab_stale = true;
+	}
+	if (c->dn_mtab_stale || !c->d_dn_minst.p)
+	{
+		RF_TRY(c->d_dn_minst.ensure(std::max<size_t>(n, 1) * sizeof(rtk::DnMotionInst)));
+		RF_TRY(dm::h2d(c->d_dn_minst.p, c->dn_mtab.data(), n * sizeof(rtk::DnMotionInst), stream));
+		c->dn_mtab_stale = false;
+	}
+	mv.inst = c->d_dn_minst.as<rtk::DnMotionInst>(), mv.surf = c->d_dn_surf.as<f4>(), mv.dump = nullptr;
+	return 0;
+}
+
 // filter the full image `in` (W x H float4 on this context's device) into `out` (may be `in`), enqueued on `stream`.  `presented`:
 // the image of the last render handed out (world-1 read, group / comm gather): the temporal stage runs when it is on — once per
 // frame with a new history set; a further read of the same frame runs it again from the same history into the same set
@@ -2898,7 +3032,7 @@ static int dn_filter(rfwhip_context *c, f4 *in, f4 *out, void *stream, bool pres
 	{
 		RF_TRY(dn_guides(c, stream));
 		StageTimer t(c, KF_DENOISE, -1, stream);
-		rtk::launch_denoise_filter(dn_view(c, in, out), nullptr, stream);
+		rtk::launch_denoise_filter(dn_view(c, in, out), nullptr, nullptr, stream);
 		t.stop(1 + c->dn_iterations);
 		return dm::last_launch_error();
 	}
@@ -2921,12 +3055,24 @@ static int dn_filter(rfwhip_context *c, f4 *in, f4 *out, void *stream, bool pres
 	rtk::DnView d = dn_view(c, in, out);
 	d.hist = dn_hist_colour(c, wr);
 	const rtk::DnTemporal tv = dn_temporal_view(c, p, rd, wr);
+	rtk::DnMotion mv;
+	const bool motion = c->dn_motion != 0;
+	if (motion)
+		RF_TRY(dn_motion_view(c, new_frame, stream, mv));
 	StageTimer t(c, KF_DENOISE, -1, stream);
-	rtk::launch_denoise_filter(d, &tv, stream);
+	rtk::launch_denoise_filter(d, &tv, motion ? &mv : nullptr, stream);
 	t.stop(2 + c->dn_iterations);
 	RF_TRY(dm::last_launch_error());
 	if (new_frame)
 	{
+		if (motion)
+		{
+			// F becomes P: its guide pass's instances, and per mesh the edit count that pass traced
+			c->dn_p_rec = c->dn_g_rec, c->dn_p_rec_ok = c->dn_g_rec_ok;
+			for (auto &m : c->meshes)
+				m.dn_p_edits = m.dn_g_edits;
+		}
+		c->dn_pres_id++;
 		c->dn_hist_cur = wr, c->dn_have_pres = true, c->dn_pres_serial = c->frame_serial;
 		c->dn_pres_cam = p.cam, c->dn_pres_scene = (uint32_t)c->guide_scene, c->dn_pres_W = c->W, c->dn_pres_H = c->H;
 		c->dn_guides_pres = true, c->dn_reset_since = false;
@@ -3083,7 +3229,7 @@ extern "C" int rfwhip_get_stats(rfwhip_context *c, rfwhip_render_stats *stats)
 	return RFWHIP_OK;
 }
 
-static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth", "denoise_temporal", "denoise_alpha", "sky_sampling", "sky_pick"};
+static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth", "denoise_temporal", "denoise_alpha", "sky_sampling", "sky_pick", "denoise_motion"};
 
 extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char *value)
 {
@@ -3235,6 +3381,21 @@ extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char
 		}
 		c->dn_temporal = v == "1";
 	}
+	else if (k == "denoise_motion")
+	{
+		if (v != "0" && v != "1")
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_motion must be \"0\" or \"1\"");
+		if (v == "1" && !c->dn_motion)
+		{
+			RF_TRY(sync_all(c)); // (a stage in flight may still read the buffers this reallocates)
+			c->dn_motion = 1;
+			dn_clear_history(c);
+			c->guides_valid = false; // (traced again with the surface record)
+			if (c->W && c->rank == 0 && c->dn_temporal)
+				RF_TRY(dn_ensure(c));
+		}
+		c->dn_motion = v == "1";
+	}
 	else if (k == "denoise_alpha")
 	{
 		char *end = nullptr;
@@ -3354,6 +3515,8 @@ extern "C" int rfwhip_get_setting(rfwhip_context *c, const char *key, char *valu
 		snprintf(value, cap, "%d", c->dn_temporal);
 	else if (k == "denoise_alpha")
 		snprintf(value, cap, "%g", c->dn_alpha);
+	else if (k == "denoise_motion")
+		snprintf(value, cap, "%d", c->dn_motion);
 	else if (k == "sky_sampling")
 		snprintf(value, cap, "%d", c->sky_sampling);
 	else if (k == "sky_pick")
@@ -3484,9 +3647,12 @@ extern "C" int rfwhip_read_denoise_history(rfwhip_context *c, float *pre_rgbl, f
 	RF_TRY(dn_inst_ver_current(c, c->stream));
 	rtk::DnView d = dn_view(c, c->d_present.as<f4>(), c->d_present.as<f4>());
 	d.hist = dn_hist_colour(c, wr);
+	rtk::DnMotion mv;
+	if (c->dn_motion)
+		RF_TRY(dn_motion_view(c, false, c->stream, mv));
 	{
 		StageTimer t(c, KF_DENOISE, -1, c->stream);
-		rtk::launch_denoise_temporal(d, dn_temporal_view(c, p, rd, wr), c->stream);
+		rtk::launch_denoise_temporal(d, dn_temporal_view(c, p, rd, wr), c->dn_motion ? &mv : nullptr, c->stream);
 		t.stop(2);
 	}
 	RF_TRY(dm::last_launch_error());
@@ -3518,6 +3684,58 @@ extern "C" int rfwhip_read_denoise_history(rfwhip_context *c, float *pre_rgbl, f
 			moments[2 * i] = mom[2 * i], moments[2 * i + 1] = mom[2 * i + 1];
 		if (length)
 			length[i] = n[i];
+	}
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_denoise_motion(rfwhip_context *c, int32_t *state, float *prev_position, float *prev_normal)
+{
+	CTX_ENTER(c);
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	if (c->world != 1)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_denoise_motion: world-1 contexts only (a group's root filters gathered images)");
+	if (!c->denoise || !c->dn_temporal || !c->dn_motion || !c->dn_have_pres || c->frame_serial != c->dn_pres_serial)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_denoise_motion: the last render has not been presented with denoise, "
+											"denoise_temporal and denoise_motion on");
+	RF_TRY(sync_all(c));
+	// the stage of the presented frame once more, from the same history into the same set, with the per-pixel record written
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
+	RF_TRY(present(c, c->d_present.as<f4>(), 1));
+	RF_TRY(dn_guides(c, c->stream));
+	rtk::Params p;
+	fill_params(c, &c->last_cam, p);
+	const int wr = c->dn_hist_cur, rd = wr ^ 1;
+	RF_TRY(dn_inst_ver_current(c, c->stream));
+	rtk::DnView d = dn_view(c, c->d_present.as<f4>(), c->d_present.as<f4>());
+	d.hist = dn_hist_colour(c, wr);
+	rtk::DnMotion mv;
+	RF_TRY(dn_motion_view(c, false, c->stream, mv));
+	DevBuf dump;
+	RF_TRY(dump.ensure_exact(8 * px * sizeof(float)));
+	mv.dump = dump.as<float>();
+	rtk::launch_denoise_temporal(d, dn_temporal_view(c, p, rd, wr), &mv, c->stream);
+	int rc = dm::last_launch_error();
+	std::vector<float> rec(8 * px);
+	if (!rc)
+		rc = dm::d2h(rec.data(), dump.p, 8 * px * sizeof(float), c->stream);
+	if (!rc)
+		rc = dm::sync(c->stream);
+	dump.free_();
+	if (rc)
+		return rc;
+	for (size_t i = 0; i < px; i++)
+	{
+		if (state)
+			state[i] = (int32_t)rec[8 * i];
+		for (int k = 0; k < 3; k++)
+		{
+			if (prev_position)
+				prev_position[3 * i + k] = rec[8 * i + 1 + k];
+			if (prev_normal)
+				prev_normal[3 * i + k] = rec[8 * i + 4 + k];
+		}
 	}
 	return RFWHIP_OK;
 }

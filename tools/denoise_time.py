@@ -8,7 +8,15 @@ With --temporal ("denoise_temporal" = 1) instead:
            stage and the a-trous passes; TEMPORAL_BYTES is the stage's estimated traffic per pixel (the kernel's own time:
            a rocprofv3 --kernel-trace --stats run of this tool, k_dn_temporal)
   frame    wall time of such a frame with denoise off and with denoise + denoise_temporal on
-Usage: python tools/denoise_time.py [--temporal] [frames=200] [iterations=5]"""
+With --motion ("denoise_temporal" = 1, "denoise_motion" = 0 then 1) the scene is BASELINE config 5's: the skinned CesiumMan of
+tests/golden/asset_cesiumman.npz over a floor, 1920 x 1080, posed on the device before every frame (the fixture's three poses in
+turn), RESET every frame, a still camera:
+  motion   per setting: the denoiser's time per frame (guide pass with / without the surface record, demodulation, the stage's
+           kernel k_dn_temporal / k_dn_temporal_motion, the passes) and the pose + refit kernels' time per frame (kernel times of
+           their own: a rocprofv3 --kernel-trace --stats run of this tool)
+  frame    wall time of such a frame (pose, update, render, present) per setting; with "1" it includes the snapshot copy in front
+           of each pose (a device-to-device copy of 16 B per vertex outside the timed spans)
+Usage: python tools/denoise_time.py [--temporal | --motion] [frames=200] [iterations=5]"""
 import json
 import os
 import sys
@@ -61,11 +69,79 @@ def temporal(pkg, ctx, scene, out, frames):
                           "ms_per_frame": round((time.perf_counter() - t0) * 1e3 / frames, 4)}), flush=True)
 
 
+def rig_scene(pkg, fx):
+    """The fixture's mesh under its node transform on a floor, lit by a point light, an area light and a sky."""
+    import numpy as np
+    pos, t = fx["positions"], np.asarray(fx["node_transform"], np.float64)
+    s = pkg.scenes.Scene()
+    s.name = "cesiumman"
+    body = s.add_material(color=(0.75, 0.55, 0.35), roughness=0.6)
+    floor = s.add_material(color=(0.6, 0.6, 0.6), roughness=0.9)
+    s.add_instance(s.add_mesh(pos, fx["indices"], normals=fx["normals"], material=body), t)
+    lo = (t[:3, :3] @ pos.T.astype(np.float64)).T + t[:3, 3]
+    c, r = (lo.min(0) + lo.max(0)) / 2, float(np.linalg.norm(lo.max(0) - lo.min(0)))
+    y0 = float(lo[:, 1].min()) - 0.02 * r
+    fv = np.array([[c[0] - 2 * r, y0, c[2] - 2 * r], [c[0] + 2 * r, y0, c[2] - 2 * r], [c[0] + 2 * r, y0, c[2] + 2 * r],
+                   [c[0] - 2 * r, y0, c[2] + 2 * r]], np.float32)
+    s.add_instance(s.add_mesh(fv, np.array([[0, 2, 1], [0, 3, 2]], np.uint32), material=floor))
+    s.add_point_light((c[0] + r, c[1] + 1.5 * r, c[2] - 1.2 * r), (40.0 * r * r, 38.0 * r * r, 35.0 * r * r))
+    s.add_area_light_quad((0.0, -1.0, 0.0), (c[0], c[1] + 2.0 * r, c[2]), r, r, (10.0, 10.0, 10.0))
+    s.set_test_sky(64, 32)
+    cam = pkg.Camera(aperture=0.0, FOV=40.0)
+    cam.look_at((c[0] + 0.3 * r, c[1] + 0.2 * r, c[2] - 2.2 * r), tuple(c))
+    cam.resize(W, H)
+    s.camera = cam
+    return s
+
+
+def motion(pkg, frames, iterations):
+    import numpy as np
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "asset_cesiumman.npz"))
+    scene = rig_scene(pkg, fx)
+    out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda:0")
+    poses = fx["joint_matrices"]
+    for on in (0, 1):
+        ctx = pkg.RenderContext(device=0)
+        ctx.init(W, H)
+        scene.upload(ctx)
+        for k, v in dict(integrator="pt", spp=1, stage_timing=1, denoise=1, denoise_iterations=iterations, denoise_temporal=1,
+                         denoise_motion=on).items():
+            ctx.set_setting(k, v)
+        ctx.set_mesh_skin(0, fx["joints"], fx["weights"], fx["normals"])
+
+        def run(n):
+            for f in range(n):
+                ctx.pose_mesh(0, poses[f % len(poses)])
+                ctx.update()
+                ctx.render_frame(scene.camera, pkg.RESET)
+                ctx.read_framebuffer_device(out.data_ptr())
+            ctx.wait()
+
+        run(10)
+        ctx.get_kernel_time("denoise", reset=True), ctx.get_kernel_time("refit", reset=True)
+        run(frames)
+        ms, launches = ctx.get_kernel_time("denoise", reset=True)
+        rms, _ = ctx.get_kernel_time("refit", reset=True)
+        print(json.dumps({"variant": "motion", "denoise_motion": on, "frames": frames, "launches": launches,
+                          "denoise_ms_per_frame": round(ms / frames, 4), "pose_refit_ms_per_frame": round(rms / frames, 4)}), flush=True)
+        ctx.set_setting("stage_timing", 0)
+        run(10)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(frames)
+        torch.cuda.synchronize()
+        print(json.dumps({"variant": "frame", "denoise_motion": on, "frames": frames,
+                          "ms_per_frame": round((time.perf_counter() - t0) * 1e3 / frames, 4)}), flush=True)
+        ctx.destroy()
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--temporal"]
+    args = [a for a in sys.argv[1:] if a not in ("--temporal", "--motion")]
     frames = int(args[0]) if len(args) > 0 else 200
     iterations = int(args[1]) if len(args) > 1 else 5
     pkg = load_package()
+    if "--motion" in sys.argv[1:]:
+        return motion(pkg, frames, iterations)
     scene = pkg.scenes.terrain(width=W, height_px=H)
     ctx = pkg.RenderContext(device=0)
     ctx.init(W, H)
