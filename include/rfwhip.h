@@ -477,7 +477,9 @@ RFWHIP_API int rfwhip_trace_rays(rfwhip_context *ctx, size_t n, const float *org
 /* Known-answer hook: one of the path tracer's DEVICE functions (rt_core.h: BSDF, light sampling, packing, samplers — the
  * very functions the shade kernel calls) evaluated by a kernel on n records; functions and record layout: RFWHIP_KAT_* in
  * rfwhip_abi.h.  in: n x RFWHIP_KAT_IN floats, out: n x RFWHIP_KAT_OUT floats (host pointers).  The light functions use
- * the lights of the last rfwhip_update(), BLUE_NOISE the table of rfwhip_set_blue_noise. */
+ * the lights of the last rfwhip_update(), BLUE_NOISE the table of rfwhip_set_blue_noise, TEX_FETCH and SURFACE_LAYERS the
+ * textures, materials, meshes and instances of the last rfwhip_update(): a record that names a texture, instance or triangle
+ * the scene does not have is RFWHIP_ERR_INVALID_ARGUMENT. */
 RFWHIP_API int rfwhip_kat(rfwhip_context *ctx, int function, size_t n, const float *in, float *out);
 
 /* BVH of mesh `index` as built on the device side (bvh_node.h layout) + its primitive order. */

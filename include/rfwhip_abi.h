@@ -275,7 +275,11 @@ enum rfwhip_kat_function
 	/* sky sampling on the table of the last rfwhip_update() with sky_sampling=1 (rt_core.h: sky_sample / sky_eval).  Both answer
 	 * [0..2] = the direction, [3] = the sampling density per steradian (lum / S), [4..6] = the radiance, [7] = the texel (int, -1: none) */
 	RFWHIP_KAT_SKY_SAMPLE = 13,		   /* [0..4] = u0, u1 (the bucket's row, column), coin (texel or alias), a, b (position in phi, cos theta) -> the texel drawn and a direction in it */
-	RFWHIP_KAT_SKY_PDF = 14			   /* [0..2] = D -> what pt_sky reads for D and the density there */
+	RFWHIP_KAT_SKY_PDF = 14,		   /* [0..2] = D -> what pt_sky reads for D and the density there */
+	/* the texture sampler on the scene of the last rfwhip_update() (getShadingData.h:25-217; rt_core.h: fetch_texel, fetch_trilinear,
+	 * pt_surface, pt_textures).  An index outside the scene's tables is an error. */
+	RFWHIP_KAT_TEX_FETCH = 15,		   /* [0] = texture (int), [1] = form (int: 0 = the trilinear fetch of a colour layer, 1 = the bilinear fetch at level 0 of a normal-map layer), [2] = lambda, [3..4] = tu, tv, [5..6] = width, height as the material's map descriptor gives them (ints, 1..65536) -> rgba */
+	RFWHIP_KAT_SURFACE_LAYERS = 16	   /* [0] = instance, [1] = triangle (ints), [2..3] = barycentrics u, v (weights of vertex 1, 2), [4..6] = D, [7] = t, [8] = the camera's spread angle -> [0..2] = colour after the texture layers, [3..5] = shading normal after the normal maps, [6] = flags (int): bit 0 alpha pass-through, bit 1 the material is textured */
 };
 
 #ifdef __cplusplus

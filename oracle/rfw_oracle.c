@@ -1581,8 +1581,11 @@ static void fetch_texel(const otexture *tex, float tu, float tv, size_t o, int w
 			out[q] += p[q] * wt[k];
 	}
 }
+/* the side of the next mip level: halved, never below 1 */
+static int mip_side(int s) { return (s >> 1) > 1 ? (s >> 1) : 1; }
 /* getShadingData.h:61-98 — MIPLEVELCOUNT 5; a texture that carries fewer texels than the chain needs is sampled at
- * level 0 only (texelCount tells). */
+ * level 0 only (texelCount tells).  The chain keeps every side at 1 or more (64x1: 64, 32, 16, 8, 4 x 1), as the
+ * scene helpers lay it out; the reference gives a level whose side reaches 0 no texels and then takes `% 0`. */
 static void fetch_trilinear(const otexture *tex, float lambda, float tu, float tv, int width, int height,
 							float out[4])
 {
@@ -1590,7 +1593,7 @@ static void fetch_trilinear(const otexture *tex, float lambda, float tu, float t
 	{
 		int w = width, h = height;
 		for (int i = 0; i < 5; i++)
-			chain += (size_t)w * h, w >>= 1, h >>= 1;
+			chain += (size_t)w * h, w = mip_side(w), h = mip_side(h);
 	}
 	const int has_mips = tex->texelCount >= chain;
 	/* getShadingData.h:66-67: level0 = min(4, (int)lambda), level1 = min(4, level0 + 1) — NOT clamped at 0: for
@@ -1607,9 +1610,9 @@ static void fetch_trilinear(const otexture *tex, float lambda, float tu, float t
 	size_t o0 = 0, o1 = 0;
 	int w0 = width, h0 = height, w1 = width, h1 = height;
 	for (int i = 0; i < level0; i++)
-		o0 += (size_t)w0 * h0, w0 >>= 1, h0 >>= 1;
+		o0 += (size_t)w0 * h0, w0 = mip_side(w0), h0 = mip_side(h0);
 	for (int i = 0; i < level1; i++)
-		o1 += (size_t)w1 * h1, w1 >>= 1, h1 >>= 1;
+		o1 += (size_t)w1 * h1, w1 = mip_side(w1), h1 = mip_side(h1);
 	float p0[4], p1[4];
 	fetch_texel(tex, tu, tv, o0, w0 > 0 ? w0 : 1, h0 > 0 ? h0 : 1, p0);
 	fetch_texel(tex, tu, tv, o1, w1 > 0 ? w1 : 1, h1 > 0 ? h1 : 1, p1);
@@ -1630,6 +1633,71 @@ static v3 layer_normal(const rfwo_context *c, const rfwhip_map_desc *md, float t
 				half_to_float(md->vscale) * (half_to_float(md->voffs) + tv), 0, md->width > 0 ? md->width : 1,
 				md->height > 0 ? md->height : 1, p);
 	return vscale(vsub(V3(p[0], p[1], p[2]), V3(0.5f, 0.5f, 0.5f)), 2.0f);
+}
+
+/* getShadingData.h:100-217 at a hit: the normals, the tangent frame of the unperturbed shading normal, and the texture
+ * layers of a textured material on *pcolor (the material's colour on entry); its u, v, w there are the weights of v0, v1, v2.
+ * Returns the alpha pass-through decision. */
+static int surface_layers(const rfwo_context *c, float spreadAngle, const oinstance *in, const rfwhip_triangle *tri,
+						  const rfwhip_material *mat, v3 D, float t, float bu, float bv, v3 *pcolor, v3 *pN, v3 *piN,
+						  v3 *pTg, v3 *pBt, int *textured)
+{
+	const float bw0 = 1.0f - bu - bv, bw1 = bu, bw2 = bv;
+	v3 color = *pcolor;
+	v3 N = V3(tri->Nx, tri->Ny, tri->Nz), iN = N;
+	if (mat_flag(mat, RFWHIP_MAT_HAS_SMOOTH_NORMALS))
+		iN = vnorm(vadd(vadd(vscale(v3p(tri->vN0), bw0), vscale(v3p(tri->vN1), bw1)), vscale(v3p(tri->vN2), bw2)));
+	N = vnorm(m3_mul(in->normal, N));
+	iN = vnorm(m3_mul(in->normal, iN));
+	v3 Tg, Bt;
+	*textured = 0;
+	create_tangent_space(iN, &Tg, &Bt);
+	int alpha_skip = 0;
+	if (mat_flag(mat, RFWHIP_MAT_HAS_DIFFUSE_MAP) && mat->map[0].addr < c->textureCount)
+	{
+		*textured = 1;
+		const float tu = bw0 * tri->u0 + bw1 * tri->u1 + bw2 * tri->u2;
+		const float tv = bw0 * tri->v0 + bw1 * tri->v1 + bw2 * tri->v2;
+		const float coneWidth = spreadAngle * t;
+		const float lambda = tri->LOD + log2f(coneWidth * (1.0f / fabsf(vdot(vscale(D, -1.0f), N))));
+		float texel[4];
+		layer_trilinear(c, &mat->map[0], lambda, tu, tv, texel);
+		if (mat_flag(mat, RFWHIP_MAT_HAS_ALPHA) && texel[3] < 0.5f)
+			alpha_skip = 1; /* getShadingData.h:145-149 */
+		else
+		{
+			color = vmul(color, V3(texel[0], texel[1], texel[2]));
+			/* additive second and third layers (getShadingData.h:153-166) */
+			if (mat_flag(mat, RFWHIP_MAT_HAS_2ND_DIFFUSE_MAP) && mat->map[1].addr < c->textureCount)
+			{
+				float l1[4];
+				layer_trilinear(c, &mat->map[1], lambda, tu, tv, l1);
+				color = vadd(color, V3(l1[0], l1[1], l1[2]));
+			}
+			if (mat_flag(mat, RFWHIP_MAT_HAS_3RD_DIFFUSE_MAP) && mat->map[2].addr < c->textureCount)
+			{
+				float l2[4];
+				layer_trilinear(c, &mat->map[2], lambda, tu, tv, l2);
+				color = vadd(color, V3(l2[0], l2[1], l2[2]));
+			}
+			/* normal maps at level 0 (getShadingData.h:169-200); layer 3 reads layer 2's descriptor (:189-196) */
+			if (mat_flag(mat, RFWHIP_MAT_HAS_NORMAL_MAP) && mat->map[3].addr < c->textureCount)
+			{
+				v3 sn = layer_normal(c, &mat->map[3], tu, tv);
+				if (mat_flag(mat, RFWHIP_MAT_HAS_2ND_NORMAL_MAP) && mat->map[4].addr < c->textureCount)
+					sn = vadd(sn, layer_normal(c, &mat->map[4], tu, tv));
+				if (mat_flag(mat, RFWHIP_MAT_HAS_3RD_NORMAL_MAP) && mat->map[4].addr < c->textureCount)
+					sn = vadd(sn, layer_normal(c, &mat->map[4], tu, tv));
+				sn = vnorm(sn);
+				/* tangentToWorld (tools.h:214) with the frame of the unperturbed normal */
+				iN = vnorm(vadd(vadd(vscale(Tg, sn.x), vscale(Bt, sn.y)), vscale(iN, sn.z)));
+			}
+			/* getShadingData.h:150 and :206 both multiply the colour by the texel */
+			color = vmul(color, V3(texel[0], texel[1], texel[2]));
+		}
+	}
+	*pcolor = color, *pN = N, *piN = iN, *pTg = Tg, *pBt = Bt;
+	return alpha_skip;
 }
 
 #define PT_MAX_DEPTHS 16
@@ -1717,63 +1785,15 @@ static void pt_path(rfwo_context *c, const rfwhip_camera_view *view, float clamp
 		const oinstance *in = &c->instances[inst];
 		const rfwhip_triangle *tri = &c->meshes[in->mesh].tris[prim];
 		const rfwhip_material *mat = &c->materials[tri->material];
-		/* ---- getShadingData (getShadingData.h:100-217); u,v,w there are the weights of v0,v1,v2 ---- */
-		const float bw0 = 1.0f - bu - bv, bw1 = bu, bw2 = bv;
+		/* ---- getShadingData (getShadingData.h:100-217) ---- */
 		oshading sd;
 		sd.color = mat_color(mat);
 		sd.absorption = V3(half_to_float(mat->transmittance[0]), half_to_float(mat->transmittance[1]),
 						   half_to_float(mat->transmittance[2]));
 		memcpy(sd.p, mat->parameters, 16);
-		v3 N = V3(tri->Nx, tri->Ny, tri->Nz), iN = N;
-		if (mat_flag(mat, RFWHIP_MAT_HAS_SMOOTH_NORMALS))
-			iN = vnorm(vadd(vadd(vscale(v3p(tri->vN0), bw0), vscale(v3p(tri->vN1), bw1)), vscale(v3p(tri->vN2), bw2)));
-		N = vnorm(m3_mul(in->normal, N));
-		iN = vnorm(m3_mul(in->normal, iN));
-		v3 Tg, Bt;
-		create_tangent_space(iN, &Tg, &Bt);
-		int alpha_skip = 0;
-		if (mat_flag(mat, RFWHIP_MAT_HAS_DIFFUSE_MAP) && mat->map[0].addr < c->textureCount)
-		{
-			const float tu = bw0 * tri->u0 + bw1 * tri->u1 + bw2 * tri->u2;
-			const float tv = bw0 * tri->v0 + bw1 * tri->v1 + bw2 * tri->v2;
-			const float coneWidth = view->spreadAngle * t;
-			const float lambda = tri->LOD + log2f(coneWidth * (1.0f / fabsf(vdot(vscale(D, -1.0f), N))));
-			float texel[4];
-			layer_trilinear(c, &mat->map[0], lambda, tu, tv, texel);
-			if (mat_flag(mat, RFWHIP_MAT_HAS_ALPHA) && texel[3] < 0.5f)
-				alpha_skip = 1; /* getShadingData.h:145-149 */
-			else
-			{
-				sd.color = vmul(sd.color, V3(texel[0], texel[1], texel[2]));
-				/* additive second and third layers (getShadingData.h:153-166) */
-				if (mat_flag(mat, RFWHIP_MAT_HAS_2ND_DIFFUSE_MAP) && mat->map[1].addr < c->textureCount)
-				{
-					float l1[4];
-					layer_trilinear(c, &mat->map[1], lambda, tu, tv, l1);
-					sd.color = vadd(sd.color, V3(l1[0], l1[1], l1[2]));
-				}
-				if (mat_flag(mat, RFWHIP_MAT_HAS_3RD_DIFFUSE_MAP) && mat->map[2].addr < c->textureCount)
-				{
-					float l2[4];
-					layer_trilinear(c, &mat->map[2], lambda, tu, tv, l2);
-					sd.color = vadd(sd.color, V3(l2[0], l2[1], l2[2]));
-				}
-				/* normal maps at level 0 (getShadingData.h:169-200); layer 3 reads layer 2's descriptor (:189-196) */
-				if (mat_flag(mat, RFWHIP_MAT_HAS_NORMAL_MAP) && mat->map[3].addr < c->textureCount)
-				{
-					v3 sn = layer_normal(c, &mat->map[3], tu, tv);
-					if (mat_flag(mat, RFWHIP_MAT_HAS_2ND_NORMAL_MAP) && mat->map[4].addr < c->textureCount)
-						sn = vadd(sn, layer_normal(c, &mat->map[4], tu, tv));
-					if (mat_flag(mat, RFWHIP_MAT_HAS_3RD_NORMAL_MAP) && mat->map[4].addr < c->textureCount)
-						sn = vadd(sn, layer_normal(c, &mat->map[4], tu, tv));
-					sn = vnorm(sn);
-					/* tangentToWorld (tools.h:214) with the frame of the unperturbed normal */
-					iN = vnorm(vadd(vadd(vscale(Tg, sn.x), vscale(Bt, sn.y)), vscale(iN, sn.z)));
-				}
-				/* getShadingData.h:150 and :206 both multiply the colour by the texel */
-				sd.color = vmul(sd.color, V3(texel[0], texel[1], texel[2]));
-			}
-		}
+		v3 N, iN, Tg, Bt;
+		int textured;
+		const int alpha_skip = surface_layers(c, view->spreadAngle, in, tri, mat, D, t, bu, bv, &sd.color, &N, &iN, &Tg, &Bt, &textured);
 		if (pathLength == 0 && pixel == c->probe_y * W + c->probe_x)
 			res->probe_hit = 1, res->probe_inst = inst, res->probe_prim = prim, res->probe_t = t;
 
@@ -1970,6 +1990,34 @@ int rfwo_kat(rfwo_context *c, int function, size_t n, const float *in, float *ou
 			memcpy(&o[0], &st, 4);
 			o[1] = random_float(&st);
 			memcpy(&o[2], &st, 4);
+			break;
+		}
+		case RFWHIP_KAT_TEX_FETCH:
+		{
+			if (ub[0] >= c->textureCount)
+				return fail("rfwo_kat: no such texture");
+			const int w = (int)ub[5], h = (int)ub[6];
+			if (ub[1])
+				fetch_texel(&c->textures[ub[0]], r[3], r[4], 0, w > 0 ? w : 1, h > 0 ? h : 1, o);
+			else
+				fetch_trilinear(&c->textures[ub[0]], r[2], r[3], r[4], w, h, o);
+			break;
+		}
+		case RFWHIP_KAT_SURFACE_LAYERS:
+		{
+			if (ub[0] >= c->instanceCount || !c->instances[ub[0]].used)
+				return fail("rfwo_kat: no such instance");
+			const oinstance *in = &c->instances[ub[0]];
+			if (in->mesh >= c->meshCount || ub[1] >= c->meshes[in->mesh].triCount)
+				return fail("rfwo_kat: no such triangle");
+			const rfwhip_triangle *tri = &c->meshes[in->mesh].tris[ub[1]];
+			const rfwhip_material *mat = &c->materials[tri->material];
+			v3 color = mat_color(mat), sN, siN, Tg, Bt;
+			int textured = 0;
+			const uint32_t alpha_skip = (uint32_t)surface_layers(c, r[8], in, tri, mat, V3(r[4], r[5], r[6]), r[7], r[2], r[3], &color, &sN, &siN, &Tg, &Bt, &textured);
+			const uint32_t fl = alpha_skip | (textured ? 2u : 0u);
+			o[0] = color.x, o[1] = color.y, o[2] = color.z, o[3] = siN.x, o[4] = siN.y, o[5] = siN.z;
+			memcpy(&o[6], &fl, 4);
 			break;
 		}
 		default:

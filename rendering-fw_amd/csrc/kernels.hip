@@ -631,6 +631,35 @@ RT_FN void kat_item(const Params &p, const SkyView &sky, int function, const flo
 		o[4] = c.x, o[5] = c.y, o[6] = c.z, o[7] = ubits((uint32_t)texel);
 		break;
 	}
+	case 15: // tex_fetch on the context's textures: [0] = texture (int), [1] = form (int: 0 fetch_trilinear, 1 fetch_texel at level 0, as
+			 // the normal-map layers call it), [2] = lambda, [3..4] = tu, tv, [5..6] = the descriptor's width, height (ints) -> rgba
+	{
+		const TexDesc &td = p.sc.textures[fbits(r[0])];
+		const int w = (int)fbits(r[5]), h = (int)fbits(r[6]);
+		const f4 t = fbits(r[1]) != 0u ? fetch_texel(p.sc, td, r[3], r[4], 0u, w > 0 ? w : 1, h > 0 ? h : 1)
+									   : fetch_trilinear(p.sc, td, r[2], r[3], r[4], w, h);
+		o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = t.w;
+		break;
+	}
+	case 16: // surface_layers: pt_surface and, for a textured material, pt_textures on a hit of the context's scene: [0] = instance,
+			 // [1] = triangle (ints), [2..3] = the barycentrics u, v, [4..6] = D, [7] = t, [8] = the camera's spread angle
+			 // -> colour, shading normal, flags (int: bit 0 alpha pass-through, bit 1 textured)
+	{
+		Hit h;
+		h.inst = (int)fbits(r[0]), h.prim = (int)fbits(r[1]), h.u = r[2], h.v = r[3], h.t = r[7];
+		Surface sf;
+		pt_surface(p.sc, h, sf);
+		f3 color = material_color(*sf.mat), iN = sf.iN;
+		bool alpha_skip = false;
+		const bool textured = pt_has_textures(p.sc, sf);
+		CamView cam = p.cam;
+		cam.spread_angle = r[8];
+		if (textured)
+			pt_textures(p.sc, cam, mk3(r[4], r[5], r[6]), h.t, sf, color, iN, alpha_skip);
+		o[0] = color.x, o[1] = color.y, o[2] = color.z, o[3] = iN.x, o[4] = iN.y, o[5] = iN.z;
+		o[6] = ubits((alpha_skip ? 1u : 0u) | (textured ? 2u : 0u));
+		break;
+	}
 	default:
 		break;
 	}

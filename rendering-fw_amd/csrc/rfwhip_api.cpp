@@ -3884,7 +3884,7 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 	CTX_ENTER(c);
 	if (n && (!in || !out))
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: null records");
-	if (function < 0 || function > RFWHIP_KAT_SKY_PDF)
+	if (function < 0 || function > RFWHIP_KAT_SURFACE_LAYERS)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: unknown function %d", function);
 	if ((function == RFWHIP_KAT_POINT_ON_LIGHT || function == RFWHIP_KAT_LIGHT_PICK_PROB) && c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the light functions use the lights of the last rfwhip_update()");
@@ -3894,6 +3894,27 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the sky functions use the table of the last rfwhip_update() with sky_sampling=1 and a sky with light");
 	if (function == RFWHIP_KAT_BLUE_NOISE && !c->have_blue_noise)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: no blue-noise table (rfwhip_set_blue_noise)");
+	if ((function == RFWHIP_KAT_TEX_FETCH || function == RFWHIP_KAT_SURFACE_LAYERS) && c->scene_dirty)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the texture functions use the scene of the last rfwhip_update()");
+	// (the kernel indexes the scene's tables with what the records name: every index is checked here)
+	for (size_t i = 0; i < n && (function == RFWHIP_KAT_TEX_FETCH || function == RFWHIP_KAT_SURFACE_LAYERS); i++)
+	{
+		uint32_t ub[7];
+		memcpy(ub, in + i * RFWHIP_KAT_IN, sizeof(ub));
+		if (function == RFWHIP_KAT_TEX_FETCH)
+		{
+			if (ub[0] >= c->texture_count)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: record %zu names texture %u of %u", i, ub[0], c->texture_count);
+			if (ub[1] > 1u || ub[5] < 1u || ub[5] > 65536u || ub[6] < 1u || ub[6] > 65536u)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: record %zu: form %u, size %u x %u", i, ub[1], ub[5], ub[6]);
+			continue;
+		}
+		if (ub[0] >= c->instances.size() || !c->instances[ub[0]].used || c->instances[ub[0]].mesh >= c->meshes.size() ||
+			!c->meshes[c->instances[ub[0]].mesh].used)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: record %zu names instance %u", i, ub[0]);
+		if (ub[1] >= c->meshes[c->instances[ub[0]].mesh].triCount)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: record %zu names triangle %u of instance %u", i, ub[1], ub[0]);
+	}
 	if (n == 0)
 		return RFWHIP_OK;
 	if (n >= (1ull << 31))

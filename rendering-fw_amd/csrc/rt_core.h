@@ -1036,6 +1036,8 @@ RT_FN int tex_wrap(int x, int w)
 #endif
 	return x % w;
 }
+// the side of the next mip level: halved, never below 1
+RT_FN int mip_side(int s) { return (s >> 1) > 1 ? (s >> 1) : 1; }
 // getShadingData.h:25-60 — bilinear, wrap
 RT_FN f4 fetch_texel(const SceneView &sc, const TexDesc &td, float tu, float tv, uint32_t o, int w, int h)
 {
@@ -1053,14 +1055,17 @@ RT_FN f4 fetch_texel(const SceneView &sc, const TexDesc &td, float tu, float tv,
 	r.w = 0.0f + p0.w * w0 + p1.w * w1 + p2.w * w2 + p3.w * w3;
 	return r;
 }
-// getShadingData.h:61-98 — MIPLEVELCOUNT 5; a texture without the appended chain is read at level 0 only
+// getShadingData.h:61-98 — MIPLEVELCOUNT 5; a texture without the appended chain is read at level 0 only.  The chain is walked
+// with every side clamped at 1 (a 64x1 map has levels 64, 32, 16, 8, 4 x 1): the layout scenes.make_texture_rgba8 appends, for
+// thin and odd-sized maps too.  (The reference's construct_mipmaps gives a level whose side reaches 0 no texels and its FetchTexel
+// then takes `% 0`; such a map carries fewer texels than this chain and is read at level 0 only.)
 RT_FN f4 fetch_trilinear(const SceneView &sc, const TexDesc &td, float lambda, float tu, float tv, int width, int height)
 {
 	uint32_t chain = 0;
 	{
 		int w = width, h = height;
 		for (int i = 0; i < 5; i++)
-			chain += (uint32_t)w * h, w >>= 1, h >>= 1;
+			chain += (uint32_t)w * h, w = mip_side(w), h = mip_side(h);
 	}
 	const bool has_mips = td.texelCount >= chain;
 	// getShadingData.h:66-67: level0 = min(4, (int)lambda), level1 = min(4, level0 + 1) — NOT clamped at 0: for
@@ -1077,9 +1082,9 @@ RT_FN f4 fetch_trilinear(const SceneView &sc, const TexDesc &td, float lambda, f
 	uint32_t o0 = 0, o1 = 0;
 	int w0 = width, h0 = height, w1 = width, h1 = height;
 	for (int i = 0; i < level0; i++)
-		o0 += (uint32_t)w0 * h0, w0 >>= 1, h0 >>= 1;
+		o0 += (uint32_t)w0 * h0, w0 = mip_side(w0), h0 = mip_side(h0);
 	for (int i = 0; i < level1; i++)
-		o1 += (uint32_t)w1 * h1, w1 >>= 1, h1 >>= 1;
+		o1 += (uint32_t)w1 * h1, w1 = mip_side(w1), h1 = mip_side(h1);
 	const f4 p0 = fetch_texel(sc, td, tu, tv, o0, w0 > 0 ? w0 : 1, h0 > 0 ? h0 : 1);
 	const f4 p1 = fetch_texel(sc, td, tu, tv, o1, w1 > 0 ? w1 : 1, h1 > 0 ? h1 : 1);
 	return mk4((1.0f - f) * p0.x + f * p1.x, (1.0f - f) * p0.y + f * p1.y, (1.0f - f) * p0.z + f * p1.z,

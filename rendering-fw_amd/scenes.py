@@ -98,8 +98,12 @@ def pack_materials(host_materials, textures, faithful=False):
 
 
 def make_texture_rgba8(rgba_u8, mips=True):
-    """UINT texture: texel = r | g<<8 | b<<16 | a<<24 (texture.cpp:77-81) with MIPLEVELCOUNT(5) box-filtered levels
-    appended (texture.cpp:163-225 semantics: each level halves width and height)."""
+    """UINT texture: texel = r | g<<8 | b<<16 | a<<24 (texture.cpp:77-81) with the four further levels of MIPLEVELCOUNT(5) appended.
+    Every level halves width and height and keeps a side at 1 once it is there (a 64 x 1 map: 64, 32, 16, 8, 4 x 1) — the layout
+    rt_core.h's fetch_trilinear walks.  A level's texel is the mean of the 2 x 2 texels under it (2 x 1 / 1 x 2 along a side of 1;
+    an odd last row or column is dropped), all four channels alike, rounded to nearest; the means are carried unrounded from level
+    to level.  This is NOT the filter of the reference's construct_mipmaps (texture.cpp:163-225), which truncates the channel sums
+    (`>> 2`) and takes the MINIMUM alpha of the four texels, and which gives a level whose side reaches 0 no texels at all."""
     img = np.ascontiguousarray(rgba_u8, dtype=np.uint8)
     h, w, _ = img.shape
     levels = [img]
@@ -107,7 +111,8 @@ def make_texture_rgba8(rgba_u8, mips=True):
         cur = img.astype(np.float32)
         for _ in range(4):
             hh, ww = max(1, cur.shape[0] // 2), max(1, cur.shape[1] // 2)
-            cur = cur[: hh * 2, : ww * 2].reshape(hh, 2, ww, 2, 4).mean(axis=(1, 3)) if cur.shape[0] >= 2 and cur.shape[1] >= 2 else cur[:hh, :ww]
+            fy, fx = min(2, cur.shape[0]), min(2, cur.shape[1])  # (a side of 1 is kept and filtered along the other)
+            cur = cur[: hh * fy, : ww * fx].reshape(hh, fy, ww, fx, 4).mean(axis=(1, 3))
             levels.append(np.clip(np.rint(cur), 0, 255).astype(np.uint8))
     flat = np.concatenate([l.reshape(-1, 4) for l in levels]).astype(np.uint32)
     data = flat[:, 0] | (flat[:, 1] << 8) | (flat[:, 2] << 16) | (flat[:, 3] << 24)

@@ -650,11 +650,23 @@ def fetch_texel(tex, tcx, tcy, o, w, h):  # getShadingData.h:28-61, BILINEAR 1; 
     return (((p0 * w0[:, None] + p1 * w1[:, None]) + p2 * w2[:, None]) + p3 * w3[:, None]).astype(f32)
 
 
+def mip_levels(width, height):
+    """(offset, width, height) of the MIPLEVELCOUNT levels of a width x height map: every side is halved and never falls below 1
+    (rt_core.h: mip_side), so a 64 x 1 map has levels 64, 32, 16, 8, 4 x 1.  The last entry's offset is the chain's texel count."""
+    out, o, w, h = [], 0, int(width), int(height)
+    for _ in range(MIPLEVELCOUNT):
+        out.append((o, w, h))
+        o, w, h = o + w * h, max(w >> 1, 1), max(h >> 1, 1)
+    return out, o
+
+
 def fetch_trilinear(tex, lam, tcx, tcy, width, height):  # getShadingData.h:63-98
     n = len(lam)
     ilam = np.trunc(lam).astype(np.int64)  # (int)lambda
     level0 = np.minimum(MIPLEVELCOUNT - 1, ilam)
     level1 = np.minimum(MIPLEVELCOUNT - 1, level0 + 1)
+    if len(tex["data"]) < mip_levels(width, height)[1]:  # a texture without the appended chain is read at level 0 only
+        level0, level1 = np.zeros_like(level0), np.zeros_like(level1)
     f = (lam - np.floor(lam)).astype(f32)
     def select(level):  # `for (i = 0; i < level; i++)`: a level <= 0 leaves offset, width and height alone
         o = np.zeros(n, np.int64)
@@ -663,14 +675,54 @@ def fetch_trilinear(tex, lam, tcx, tcy, width, height):  # getShadingData.h:63-9
         for i in range(MIPLEVELCOUNT - 1):
             step = level > i
             o = np.where(step, o + w * h, o)
-            w = np.where(step, w >> 1, w)
-            h = np.where(step, h >> 1, h)
+            w = np.where(step, np.maximum(w >> 1, 1), w)
+            h = np.where(step, np.maximum(h >> 1, 1), h)
         return o, np.maximum(w, 1), np.maximum(h, 1)
     o0, w0, h0 = select(level0)
     o1, w1, h1 = select(level1)
     p0 = fetch_texel(tex, tcx, tcy, o0, w0, h0)
     p1 = fetch_texel(tex, tcx, tcy, o1, w1, h1)
     return ((f32(1) - f)[:, None] * p0 + f[:, None] * p1).astype(f32)
+
+
+# The same sums in float64, for the known-answer tests of the fetches (tests/test_texture_fetch.py).  The one step of a fetch where
+# a legal rounding changes a discrete decision is the texel coordinate `(t + 1000) * side - 0.5`: a compiler may contract it into one
+# fused multiply-add (one rounding) or not (two).  texel_coordinate gives either form, exactly as float32 arithmetic rounds it;
+# everything after it (the texel indices, the weights, the weighted sums) is evaluated without rounding error worth the name.
+def texel_coordinate(t, side, fused):
+    a = np.maximum((np.asarray(t, f32) + f32(1000)).astype(f32), f32(0)).astype(np.float64)
+    prod = a * np.asarray(side, np.float64)  # exact: 24 bits times at most 17
+    if not fused:
+        prod = prod.astype(f32).astype(np.float64)
+    return (prod - 0.5).astype(f32).astype(np.float64)  # (prod - 0.5 is exact in float64; the cast is the float32 rounding)
+
+
+def texels64(tex, i):
+    i = np.minimum(i, len(tex["data"]) - 1)
+    return (tex["data"][i] if tex["float4"] else uchar4_to_float4(tex["data"][i])).astype(np.float64)
+
+
+def fetch_texel64(tex, fx, fy, o, w, h):
+    """FetchTexel from the texel coordinates fx, fy (texel_coordinate) in float64; o, w, h: per-lane int64 arrays."""
+    iu, iv = np.trunc(fx).astype(np.int64) % w, np.trunc(fy).astype(np.int64) % h
+    fu, fv = fx - np.floor(fx), fy - np.floor(fy)
+    iu1, iv1 = (iu + 1) % w, (iv + 1) % h
+    p0, p1 = texels64(tex, o + iu + iv * w), texels64(tex, o + iu1 + iv * w)
+    p2, p3 = texels64(tex, o + iu + iv1 * w), texels64(tex, o + iu1 + iv1 * w)
+    return (p0 * ((1 - fu) * (1 - fv))[:, None] + p1 * (fu * (1 - fv))[:, None]) + (p2 * ((1 - fu) * fv)[:, None] + p3 * (fu * fv)[:, None])
+
+
+def trilinear_levels(tex, lam, width, height):
+    """The two levels FetchTexelTrilinear blends and the weight of the second: (o0, w0, h0), (o1, w1, h1), f; per-lane arrays."""
+    lam = np.asarray(lam, f32)
+    levels, chain = mip_levels(width, height)
+    level0 = np.clip(np.minimum(MIPLEVELCOUNT - 1, np.trunc(lam).astype(np.int64)), 0, None)  # (a level below 0 walks no step)
+    level1 = np.clip(np.minimum(MIPLEVELCOUNT - 1, np.minimum(MIPLEVELCOUNT - 1, np.trunc(lam).astype(np.int64)) + 1), 0, None)
+    if len(tex["data"]) < chain:
+        level0, level1 = np.zeros_like(level0), np.zeros_like(level1)
+    tab = np.asarray(levels, np.int64)
+    f = lam.astype(np.float64) - np.floor(lam.astype(np.float64))
+    return tuple(tab[level0].T), tuple(tab[level1].T), f
 
 
 class PathTracer:
@@ -737,7 +789,10 @@ class PathTracer:
         out[ok] = self.sky[idx[ok]]
         return out
 
-    def shading_data(self, D, bu, bv, inst, prim, t):  # getShadingData.h:100-217
+    def shading_data(self, D, bu, bv, inst, prim, t, w=None, probe=None):  # getShadingData.h:100-217
+        # w: the third weight where the caller has it.  probe: a dict that receives what a known-answer test holds its bounds against
+        # (lam, tu, tv, matid, texel0 = the first layer's texel, color / iN = the layers' result without the alpha decision, iN0 = the
+        # unperturbed shading normal)
         n = len(D)
         texu = np.zeros((n, 3), f32)
         texv = np.zeros((n, 3), f32)
@@ -747,7 +802,7 @@ class PathTracer:
         matid = np.zeros(n, np.int64)
         area = np.zeros(n, f32)
         ltri = np.full(n, -1, np.int64)
-        w = (f32(1) - bu - bv).astype(f32)
+        w = (f32(1) - bu - bv).astype(f32) if w is None else np.asarray(w, f32)
         for ii, g in enumerate(self.geo.inst):
             sel = inst == ii
             if not sel.any():
@@ -771,12 +826,17 @@ class PathTracer:
         alpha = np.zeros(n, bool)
         flag = lambda bit: ((self.mat_flags[matid] >> u32(bit)) & u32(1)).astype(bool)  # noqa: E731  structs.h:67-83
         has_diffuse = flag(2)
+        if probe is not None:
+            probe.update(matid=matid, lam=np.zeros(n, f32), tu=np.zeros(n, f32), tv=np.zeros(n, f32), texel0=np.zeros((n, 4), f32),
+                         color=sd.color.copy(), iN=iN.copy(), iN0=iN.copy())
         if has_diffuse.any():
             color = sd.color.copy()
             tu = ((bu * texu[:, 0] + bv * texu[:, 1]) + w * texu[:, 2]).astype(f32)
             tv = ((bu * texv[:, 0] + bv * texv[:, 1]) + w * texv[:, 2]).astype(f32)
             coneWidth = (self.spread_angle * t).astype(f32)
             lam = (lod + np.log2(coneWidth * (f32(1) / np.abs(dot(-D, N)))).astype(f32)).astype(f32)  # eq. 26
+            if probe is not None:
+                probe.update(lam=lam, tu=tu, tv=tv)
             for mi in np.unique(matid[has_diffuse]):
                 sel = np.nonzero(has_diffuse & (matid == mi))[0]
                 maps = self.mat_maps[mi]
@@ -800,6 +860,8 @@ class PathTracer:
                 if (fl >> 12) & 1:  # HasAlpha: the rest of the surface is not evaluated
                     a = texel[:, 3] < f32(0.5)
                 alpha[sel] = a
+                if probe is not None:
+                    probe["texel0"][sel] = texel
                 c = (color[sel] * texel[:, :3]).astype(f32)
                 if (fl >> 9) & 1:   # Has2ndDiffuseMap: additive
                     c = (c + layer(1)[:, :3]).astype(f32)
@@ -813,8 +875,12 @@ class PathTracer:
                         sn = (sn + nlayer(4)).astype(f32)
                     sn = normalize(sn)
                     wn = normalize(((T[sel] * sn[:, 0:1] + B[sel] * sn[:, 1:2]) + iN[sel] * sn[:, 2:3]).astype(f32))  # tangentToWorld
+                    if probe is not None:
+                        probe["iN"][sel] = wn
                     iN[sel] = np.where(a[:, None], iN[sel], wn)
                 c = (c * texel[:, :3]).astype(f32)  # :206, the second multiplication by the texel
+                if probe is not None:
+                    probe["color"][sel] = c
                 color[sel] = np.where(a[:, None], color[sel], c)
             sd.color = color
         return sd, N, iN, T, B, area, ltri, alpha
