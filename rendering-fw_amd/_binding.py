@@ -86,7 +86,11 @@ class CoreBinding:
                                   "denoise_image": (i32, [vp, vp, vp]),
                                   "read_denoise_history": (i32, [vp, vp, vp, vp, vp, vp]),
                                   "read_denoise_motion": (i32, [vp, vp, vp, vp]),
-                                  "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32])}.items():
+                                  "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32]),
+                                  "get_kernel_time": (i32, [vp, i32, C.POINTER(fp), C.POINTER(u32), i32]),
+                                  "get_setting": (i32, [vp, C.c_char_p, C.c_char_p, sz]),
+                                  "get_settings": (i32, [vp, C.POINTER(C.c_char_p), sz]),
+                                  "version": (C.c_char_p, [])}.items():
             if self._has(name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -329,6 +333,29 @@ class CoreBinding:
         state, pos, nrm = np.empty((h, w), np.int32), np.empty((h, w, 3), np.float32), np.empty((h, w, 3), np.float32)
         self._check(self._fn("read_denoise_motion")(self._ctx, state.ctypes.data, pos.ctypes.data, nrm.ctypes.data))
         return {"state": state, "position": pos, "normal": nrm}
+
+    # ---- measurement hooks -------------------------------------------------------------------------------------------
+    KERNELS = ("generate", "extend", "shade", "connect", "finalize", "refit")
+    DENOISE = 6  # kernel family of the denoiser (guide pass + filter), outside KERNELS: the render's stages
+
+    def get_kernel_time(self, which, reset=False):
+        ms, n = C.c_float(), C.c_uint32()
+        idx = self.DENOISE if which == "denoise" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
+
+    def get_setting(self, key):
+        buf = C.create_string_buffer(128)
+        self._check(self._fn("get_setting")(self._ctx, str(key).encode(), buf, 128))
+        return buf.value.decode()
+
+    def get_settings(self):
+        keys = (C.c_char_p * 32)()
+        n = self._fn("get_settings")(self._ctx, keys, 32)
+        return {keys[i].decode(): self.get_setting(keys[i].decode()) for i in range(n)}
+
+    def version(self):
+        return self._fn("version")().decode()
 
     # known-answer hook: RFWHIP_KAT_* (include/rfwhip_abi.h)
     KAT = {"bsdf_eval": 0, "bsdf_pdf": 1, "bsdf_sample": 2, "tangent_space": 3, "pack_normal": 4,

@@ -9,6 +9,7 @@
 #include "rfwhip.h"
 
 #include "bvh_build.h"
+#include "device_layer.h"
 #include "internal.h"
 #include "kernels.h"
 #include "rt_types.h"
@@ -24,25 +25,12 @@
 #include <string>
 #include <vector>
 
-#if !defined(RFWHIP_HOST_EMULATION)
-#include <hip/hip_runtime.h>
-#endif
-#include "emu_streams.h" // (the deferred-stream variant of the emulation build; empty otherwise)
-
 using rt::f4;
 
 // =================================================================================================================
 // error reporting
 // =================================================================================================================
 static thread_local char g_error[1024] = "";
-static int set_error(int code, const char *fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(g_error, sizeof(g_error), fmt, ap);
-	va_end(ap);
-	return code;
-}
 int rfwhip_internal_set_error(int code, const char *fmt, ...)
 {
 	va_list ap;
@@ -51,6 +39,7 @@ int rfwhip_internal_set_error(int code, const char *fmt, ...)
 	va_end(ap);
 	return code;
 }
+#define set_error rfwhip_internal_set_error // (this file's short name for it)
 extern "C" const char *rfwhip_last_error(void) { return g_error; }
 extern "C" const char *rfwhip_version(void)
 {
@@ -60,275 +49,6 @@ extern "C" const char *rfwhip_version(void)
 	return "rfwhip 0.1 (gfx950 HIP)";
 #endif
 }
-
-// =================================================================================================================
-// device memory / stream abstraction
-// =================================================================================================================
-namespace dm
-{
-#if !defined(RFWHIP_HOST_EMULATION)
-#define DM_CHECK(x)                                                                                      \
-	do                                                                                                   \
-	{                                                                                                    \
-		hipError_t e_ = (x);                                                                             \
-		if (e_ != hipSuccess)                                                                            \
-			return set_error(RFWHIP_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-	} while (0)
-
-static int init(int device, int *cus)
-{
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-		return set_error(RFWHIP_ERR_NO_DEVICE, "no HIP device visible: the rendercore has no CPU path");
-	if (device < 0 || device >= n)
-		return set_error(RFWHIP_ERR_NO_DEVICE, "device ordinal %d out of range (%d devices)", device, n);
-	DM_CHECK(hipSetDevice(device));
-	hipDeviceProp_t prop;
-	DM_CHECK(hipGetDeviceProperties(&prop, device));
-	*cus = prop.multiProcessorCount;
-	return 0;
-}
-static int use(int device)
-{
-	DM_CHECK(hipSetDevice(device));
-	return 0;
-}
-static int alloc(void **p, size_t bytes)
-{
-	DM_CHECK(hipMalloc(p, bytes ? bytes : 16));
-	return 0;
-}
-static void release(void *p)
-{
-	if (p)
-		(void)hipFree(p);
-}
-static void mem_info(size_t *free_b, size_t *total_b)
-{
-	if (hipMemGetInfo(free_b, total_b) != hipSuccess)
-		*free_b = *total_b = ~(size_t)0;
-}
-static int h2d(void *d, const void *h, size_t n, void *s)
-{
-	if (n)
-		DM_CHECK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, (hipStream_t)s));
-	return 0;
-}
-static int d2h(void *h, const void *d, size_t n, void *s)
-{
-	if (n)
-	{
-		DM_CHECK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, (hipStream_t)s));
-		DM_CHECK(hipStreamSynchronize((hipStream_t)s));
-	}
-	return 0;
-}
-static int d2d(void *dst, const void *src, size_t n, void *s)
-{
-	if (n)
-		DM_CHECK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, (hipStream_t)s));
-	return 0;
-}
-static int zero(void *d, size_t n, void *s)
-{
-	if (n)
-		DM_CHECK(hipMemsetAsync(d, 0, n, (hipStream_t)s));
-	return 0;
-}
-static int sync(void *s)
-{
-	DM_CHECK(hipStreamSynchronize((hipStream_t)s));
-	return 0;
-}
-static int stream_create(void **s)
-{
-	hipStream_t st;
-	DM_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-	*s = st;
-	return 0;
-}
-static void stream_destroy(void *s)
-{
-	if (s)
-		(void)hipStreamDestroy((hipStream_t)s);
-}
-static int last_launch_error()
-{
-	DM_CHECK(hipGetLastError());
-	return 0;
-}
-typedef hipEvent_t event_t;
-static int event_create(event_t *e)
-{
-	DM_CHECK(hipEventCreate(e));
-	return 0;
-}
-static void event_destroy(event_t e) { (void)hipEventDestroy(e); }
-static int event_record(event_t e, void *s)
-{
-	DM_CHECK(hipEventRecord(e, (hipStream_t)s));
-	return 0;
-}
-static float event_ms(event_t a, event_t b)
-{
-	float ms = 0;
-	if (hipEventElapsedTime(&ms, a, b) != hipSuccess)
-		return 0.0f;
-	return ms;
-}
-static int stream_wait_event(void *s, event_t e)
-{
-	DM_CHECK(hipStreamWaitEvent((hipStream_t)s, e, 0));
-	return 0;
-}
-static int event_sync(event_t e)
-{
-	DM_CHECK(hipEventSynchronize(e));
-	return 0;
-}
-#elif defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
-// ---- host emulation with deferred streams (tests/emu, the _streams variant): emu_streams.h schedules every operation ----
-static int init(int, int *cus)
-{
-	*cus = 1;
-	return 0;
-}
-static int use(int) { return 0; }
-static int alloc(void **p, size_t bytes)
-{
-	*p = calloc(bytes ? bytes : 16, 1);
-	return *p ? 0 : set_error(RFWHIP_ERR_HIP, "out of memory");
-}
-static void release(void *p)
-{
-	if (!p)
-		return;
-	emu_streams::sync_all(); // (hipFree synchronises the device)
-	free(p);
-}
-static void mem_info(size_t *free_b, size_t *total_b) { *free_b = *total_b = ~(size_t)0; }
-static int h2d(void *d, const void *h, size_t n, void *s)
-{
-	if (n)
-		emu_streams::h2d(d, h, n, s);
-	return 0;
-}
-static int d2h(void *h, const void *d, size_t n, void *s)
-{
-	if (n)
-	{
-		emu_streams::copy(h, d, n, s);
-		emu_streams::sync(s);
-	}
-	return 0;
-}
-static int d2d(void *dst, const void *src, size_t n, void *s)
-{
-	if (n)
-		emu_streams::copy(dst, src, n, s);
-	return 0;
-}
-static int zero(void *d, size_t n, void *s)
-{
-	if (n)
-		emu_streams::enqueue(s, [d, n]() { memset(d, 0, n); });
-	return 0;
-}
-static int sync(void *s)
-{
-	emu_streams::sync(s);
-	return 0;
-}
-static int stream_create(void **s)
-{
-	*s = emu_streams::stream_create();
-	return 0;
-}
-static void stream_destroy(void *s)
-{
-	if (s)
-		emu_streams::stream_destroy(s);
-}
-static int last_launch_error() { return 0; }
-typedef emu_streams::Event *event_t;
-static int event_create(event_t *e)
-{
-	*e = emu_streams::event_create();
-	return 0;
-}
-static void event_destroy(event_t e) { emu_streams::destroy_event(e); }
-static int event_record(event_t e, void *s)
-{
-	emu_streams::record(e, s);
-	return 0;
-}
-static float event_ms(event_t a, event_t b) { return emu_streams::elapsed_ms(a, b); }
-static int stream_wait_event(void *s, event_t e)
-{
-	emu_streams::wait_event(s, e);
-	return 0;
-}
-static int event_sync(event_t e)
-{
-	emu_streams::sync_event(e);
-	return 0;
-}
-#else
-// ---- host emulation (tests/emu): plain heap memory, "streams" are immediate ----
-static int init(int, int *cus)
-{
-	*cus = 1;
-	return 0;
-}
-static int use(int) { return 0; }
-static int alloc(void **p, size_t bytes)
-{
-	*p = calloc(bytes ? bytes : 16, 1);
-	return *p ? 0 : set_error(RFWHIP_ERR_HIP, "out of memory");
-}
-static void release(void *p) { free(p); }
-static void mem_info(size_t *free_b, size_t *total_b) { *free_b = *total_b = ~(size_t)0; }
-static int h2d(void *d, const void *h, size_t n, void *)
-{
-	memcpy(d, h, n);
-	return 0;
-}
-static int d2h(void *h, const void *d, size_t n, void *)
-{
-	memcpy(h, d, n);
-	return 0;
-}
-static int d2d(void *dst, const void *src, size_t n, void *)
-{
-	memmove(dst, src, n);
-	return 0;
-}
-static int zero(void *d, size_t n, void *)
-{
-	memset(d, 0, n);
-	return 0;
-}
-static int sync(void *) { return 0; }
-static int stream_create(void **s)
-{
-	*s = nullptr;
-	return 0;
-}
-static void stream_destroy(void *) {}
-static int last_launch_error() { return 0; }
-typedef std::chrono::steady_clock::time_point event_t;
-static int event_create(event_t *) { return 0; }
-static void event_destroy(event_t) {}
-static int event_record(event_t &e, void *)
-{
-	e = std::chrono::steady_clock::now();
-	return 0;
-}
-static float event_ms(event_t a, event_t b) { return std::chrono::duration<float, std::milli>(b - a).count(); }
-static int stream_wait_event(void *, event_t) { return 0; }
-static int event_sync(event_t) { return 0; }
-#endif
-} // namespace dm
 
 #define RF_TRY(x)            \
 	do                       \
@@ -1091,6 +811,75 @@ constexpr int BLAS_STACK_BUDGET = 48;
 constexpr int TLAS_STACK_BUDGET = rt::STACK_CAPACITY - 1 - BLAS_STACK_BUDGET;
 static_assert(TLAS_STACK_BUDGET >= (3 * TLAS_DEPTH_LIMIT) / 2 && BLAS_STACK_BUDGET >= (3 * BLAS_DEPTH_LIMIT) / 2, "traversal stack too small for the builders' depth limits");
 
+// ---- refit of a resident mesh from its device vertices -------------------------------------------------------------------
+// The chain on c->stream: the shading records of a posed mesh (skin_shade), the 2-wide tree bottom-up (refit), the compressed
+// 4-wide nodes from it (refresh4).  skin_shade goes first wherever it runs: it writes d_tri_shade from d_verts / d_vnormals,
+// which the other two only read, and nothing else of theirs — on one stream its place in the chain changes no result.
+static int launch_refit_chain(rfwhip_context *c, MeshRec &m, bool shade)
+{
+	const uint32_t *indices = m.indexed ? m.d_indices.as<uint32_t>() : nullptr;
+	if (shade)
+		rtk::launch_skin_shade(c->d_tri_shade.as<rt::TriShade>() + m.shade_base, m.d_verts.as<f4>(), m.d_vnormals.as<f4>(), indices,
+							   (uint32_t)m.triCount, c->stream);
+	rtk::launch_refit(c->d_nodes.as<rt::Node>(), m.node_base, m.d_parents.as<int>(), m.node_count2, c->d_tri_verts.as<f4>(), m.tri_base,
+					  m.d_verts.as<f4>(), indices, (uint32_t)m.triCount, m.d_flags.as<uint32_t>(), c->stream);
+	rtk::launch_refresh4(c->d_nodes4.as<rt::Node4c>() + m.n4_base, c->d_nodes4_src.as<uint32_t>() + 4ull * m.n4_base, m.n4_count,
+						 c->d_nodes.as<rt::Node>() + m.node_base, c->stream);
+	return dm::last_launch_error();
+}
+
+// "stage_timing" of a refit: the events exist only when the setting is on, bracket what is enqueued on c->stream between the
+// constructor and stop(), and are destroyed on every path out of the scope.  add() after the stream has been synchronised.
+struct RefitTimer
+{
+	rfwhip_context *c;
+	const bool timed;
+	dm::event_t ea{}, eb{};
+	explicit RefitTimer(rfwhip_context *c) : c(c), timed(c->stage_timing != 0)
+	{
+		if (timed)
+		{
+			dm::event_create(&ea), dm::event_create(&eb);
+			dm::event_record(ea, c->stream);
+		}
+	}
+	RefitTimer(const RefitTimer &) = delete;
+	~RefitTimer()
+	{
+		if (timed)
+			dm::event_destroy(ea), dm::event_destroy(eb);
+	}
+	void stop()
+	{
+		if (timed)
+			dm::event_record(eb, c->stream);
+	}
+	void add(uint32_t launches)
+	{
+		if (!timed)
+			return;
+		c->kernel_ms[KF_REFIT] += dm::event_ms(ea, eb);
+		c->kernel_launches[KF_REFIT] += launches;
+		c->stats.animationTime = dm::event_ms(ea, eb);
+	}
+};
+
+// rfwhip_pose_mesh / rfwhip_morph_mesh behind their vertex launch: the chain, the new mesh bounds, the bookkeeping
+static int refit_deformed(rfwhip_context *c, MeshRec &m, RefitTimer &timer)
+{
+	RF_TRY(launch_refit_chain(c, m, true));
+	timer.stop();
+	// the instance boxes of the TLAS come from the mesh bounds = the refitted root (its two children's union)
+	rt::Node root;
+	RF_TRY(dm::d2h(&root, c->d_nodes.as<rt::Node>() + m.node_base, sizeof(rt::Node), c->stream)); // (synchronises the stream)
+	for (int a = 0; a < 3; a++)
+		m.bounds_min[a] = root.bmin[a] - 2e-5f, m.bounds_max[a] = root.bmax[a] + 2e-5f;
+	timer.add(5);
+	m.posed = true, m.edits++;
+	c->scene_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_set_mesh(rfwhip_context *c, size_t index, const rfwhip_mesh *mesh)
 {
 	CTX_ENTER(c);
@@ -1155,30 +944,11 @@ extern "C" int rfwhip_set_mesh(rfwhip_context *c, size_t index, const rfwhip_mes
 			m.bounds_min[a] -= 2e-5f, m.bounds_max[a] += 2e-5f;
 		RF_TRY(dm::h2d(c->d_tri_shade.as<rt::TriShade>() + m.shade_base, m.shade.data(), m.shade.size() * sizeof(rt::TriShade), c->stream));
 		RF_TRY(dm::h2d(c->d_tri_uv.as<rt::TriUV>() + m.shade_base, m.uv.data(), m.uv.size() * sizeof(rt::TriUV), c->stream));
-		dm::event_t ea, eb;
-		const bool timed = c->stage_timing != 0;
-		if (timed)
-		{
-			dm::event_create(&ea), dm::event_create(&eb);
-			dm::event_record(ea, c->stream);
-		}
-		rtk::launch_refit(c->d_nodes.as<rt::Node>(), m.node_base, m.d_parents.as<int>(), m.node_count2,
-						  c->d_tri_verts.as<f4>(), m.tri_base, m.d_verts.as<f4>(),
-						  m.indexed ? m.d_indices.as<uint32_t>() : nullptr, (uint32_t)m.triCount, m.d_flags.as<uint32_t>(),
-						  c->stream);
-		rtk::launch_refresh4(c->d_nodes4.as<rt::Node4c>() + m.n4_base, c->d_nodes4_src.as<uint32_t>() + 4ull * m.n4_base,
-							 m.n4_count, c->d_nodes.as<rt::Node>() + m.node_base, c->stream);
-		RF_TRY(dm::last_launch_error());
-		if (timed)
-			dm::event_record(eb, c->stream);
+		RefitTimer timer(c);
+		RF_TRY(launch_refit_chain(c, m, false));
+		timer.stop();
 		RF_TRY(dm::sync(c->stream));
-		if (timed)
-		{
-			c->kernel_ms[KF_REFIT] += dm::event_ms(ea, eb);
-			c->kernel_launches[KF_REFIT] += 3;
-			c->stats.animationTime = dm::event_ms(ea, eb);
-			dm::event_destroy(ea), dm::event_destroy(eb);
-		}
+		timer.add(3);
 		c->scene_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
 		return RFWHIP_OK;
 	}
@@ -1362,43 +1132,11 @@ extern "C" int rfwhip_pose_mesh(rfwhip_context *c, size_t index, const float *jo
 	RF_TRY(m.d_joint_mats.ensure(joint_count * 64));
 	RF_TRY(dm::h2d(m.d_joint_mats.p, joint_matrices16, joint_count * 64, c->stream));
 	m.joint_count = (uint32_t)joint_count;
-	dm::event_t ea, eb;
-	const bool timed = c->stage_timing != 0;
-	if (timed)
-	{
-		dm::event_create(&ea), dm::event_create(&eb);
-		dm::event_record(ea, c->stream);
-	}
+	RefitTimer timer(c);
 	rtk::launch_skin_vertices(m.d_verts.as<f4>(), m.d_vnormals.as<f4>(), m.d_base_verts.as<f4>(), m.d_base_normals.as<f4>(),
 							  m.d_joints.as<uint32_t>(), m.d_weights.as<f4>(), m.d_joint_mats.as<float>(), m.joint_count,
 							  (uint32_t)m.vertexCount, c->stream);
-	rtk::launch_skin_shade(c->d_tri_shade.as<rt::TriShade>() + m.shade_base, m.d_verts.as<f4>(), m.d_vnormals.as<f4>(),
-						   m.indexed ? m.d_indices.as<uint32_t>() : nullptr, (uint32_t)m.triCount, c->stream);
-	rtk::launch_refit(c->d_nodes.as<rt::Node>(), m.node_base, m.d_parents.as<int>(), m.node_count2,
-					  c->d_tri_verts.as<f4>(), m.tri_base, m.d_verts.as<f4>(), m.indexed ? m.d_indices.as<uint32_t>() : nullptr,
-					  (uint32_t)m.triCount, m.d_flags.as<uint32_t>(), c->stream);
-	rtk::launch_refresh4(c->d_nodes4.as<rt::Node4c>() + m.n4_base, c->d_nodes4_src.as<uint32_t>() + 4ull * m.n4_base,
-						 m.n4_count, c->d_nodes.as<rt::Node>() + m.node_base, c->stream);
-	RF_TRY(dm::last_launch_error());
-	if (timed)
-		dm::event_record(eb, c->stream);
-	// the instance boxes of the TLAS come from the mesh bounds = the refitted root (its two children's union)
-	rt::Node root[2];
-	const rt::Node *dn = c->d_nodes.as<rt::Node>() + m.node_base;
-	RF_TRY(dm::d2h(&root[0], dn, sizeof(rt::Node), c->stream));
-	RF_TRY(dm::sync(c->stream));
-	for (int a = 0; a < 3; a++)
-		m.bounds_min[a] = root[0].bmin[a] - 2e-5f, m.bounds_max[a] = root[0].bmax[a] + 2e-5f;
-	if (timed)
-	{
-		c->kernel_ms[KF_REFIT] += dm::event_ms(ea, eb);
-		c->kernel_launches[KF_REFIT] += 5;
-		c->stats.animationTime = dm::event_ms(ea, eb);
-		dm::event_destroy(ea), dm::event_destroy(eb);
-	}
-	m.posed = true, m.edits++;
-	c->scene_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
-	return RFWHIP_OK;
+	return refit_deformed(c, m, timer);
 }
 
 // float 4-wide node of the collapse -> the compressed node the rays fetch (entries as they are)
@@ -1455,41 +1193,11 @@ extern "C" int rfwhip_morph_mesh(rfwhip_context *c, size_t index, const float *w
 	RF_TRY(sync_all(c));
 	RF_TRY(dn_snapshot_mesh(c, m));
 	RF_TRY(dm::h2d(m.d_morph_weights.p, weights, weight_count * sizeof(float), c->stream));
-	dm::event_t ea, eb;
-	const bool timed = c->stage_timing != 0;
-	if (timed)
-	{
-		dm::event_create(&ea), dm::event_create(&eb);
-		dm::event_record(ea, c->stream);
-	}
+	RefitTimer timer(c);
 	rtk::launch_morph_vertices(m.d_verts.as<f4>(), m.d_vnormals.as<f4>(), m.d_base_verts.as<f4>(), m.d_base_normals.as<f4>(),
 							   m.d_tgt_pos.as<f4>(), m.d_tgt_nrm.as<f4>(), m.d_morph_weights.as<float>(), m.target_count,
 							   (uint32_t)m.vertexCount, c->stream);
-	rtk::launch_skin_shade(c->d_tri_shade.as<rt::TriShade>() + m.shade_base, m.d_verts.as<f4>(), m.d_vnormals.as<f4>(),
-						   m.indexed ? m.d_indices.as<uint32_t>() : nullptr, (uint32_t)m.triCount, c->stream);
-	rtk::launch_refit(c->d_nodes.as<rt::Node>(), m.node_base, m.d_parents.as<int>(), m.node_count2,
-					  c->d_tri_verts.as<f4>(), m.tri_base, m.d_verts.as<f4>(), m.indexed ? m.d_indices.as<uint32_t>() : nullptr,
-					  (uint32_t)m.triCount, m.d_flags.as<uint32_t>(), c->stream);
-	rtk::launch_refresh4(c->d_nodes4.as<rt::Node4c>() + m.n4_base, c->d_nodes4_src.as<uint32_t>() + 4ull * m.n4_base,
-						 m.n4_count, c->d_nodes.as<rt::Node>() + m.node_base, c->stream);
-	RF_TRY(dm::last_launch_error());
-	if (timed)
-		dm::event_record(eb, c->stream);
-	rt::Node root;
-	RF_TRY(dm::d2h(&root, c->d_nodes.as<rt::Node>() + m.node_base, sizeof(rt::Node), c->stream));
-	RF_TRY(dm::sync(c->stream));
-	for (int a = 0; a < 3; a++)
-		m.bounds_min[a] = root.bmin[a] - 2e-5f, m.bounds_max[a] = root.bmax[a] + 2e-5f;
-	if (timed)
-	{
-		c->kernel_ms[KF_REFIT] += dm::event_ms(ea, eb);
-		c->kernel_launches[KF_REFIT] += 5;
-		c->stats.animationTime = dm::event_ms(ea, eb);
-		dm::event_destroy(ea), dm::event_destroy(eb);
-	}
-	m.posed = true, m.edits++;
-	c->scene_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
-	return RFWHIP_OK;
+	return refit_deformed(c, m, timer);
 }
 
 // The float copy of the traversal nodes (rt::Node4f) — written only when its one reader, the packet form of the pt primary wave,
@@ -1850,19 +1558,7 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 			if (!m.used)
 				continue;
 			if (m.resident && !m.dirty)
-			{
-				rtk::launch_refit(c->d_nodes.as<rt::Node>(), m.node_base, m.d_parents.as<int>(), m.node_count2,
-								  c->d_tri_verts.as<f4>(), m.tri_base, m.d_verts.as<f4>(),
-								  m.indexed ? m.d_indices.as<uint32_t>() : nullptr, (uint32_t)m.triCount,
-								  m.d_flags.as<uint32_t>(), c->stream);
-				rtk::launch_refresh4(c->d_nodes4.as<rt::Node4c>() + m.n4_base, c->d_nodes4_src.as<uint32_t>() + 4ull * m.n4_base,
-									 m.n4_count, c->d_nodes.as<rt::Node>() + m.node_base, c->stream);
-				if (m.posed) // the host copy of the shading records is the bind pose
-					rtk::launch_skin_shade(c->d_tri_shade.as<rt::TriShade>() + m.shade_base, m.d_verts.as<f4>(),
-										   m.d_vnormals.as<f4>(), m.indexed ? m.d_indices.as<uint32_t>() : nullptr,
-										   (uint32_t)m.triCount, c->stream);
-				RF_TRY(dm::last_launch_error());
-			}
+				RF_TRY(launch_refit_chain(c, m, m.posed)); // (posed: the host copy of the shading records is the bind pose)
 			m.resident = true, m.dirty = false;
 		}
 		RF_TRY(dm::sync(c->stream));
@@ -3229,215 +2925,231 @@ extern "C" int rfwhip_get_stats(rfwhip_context *c, rfwhip_render_stats *stats)
 	return RFWHIP_OK;
 }
 
-static const char *const k_setting_keys[] = {"integrator", "spp", "max_depth", "jitter", "stage_timing", "count_traversal", "lds_nodes", "refill", "streams", "sampler", "builder", "overlap", "sub_batch_paths", "ring", "sample_group", "flat_instances", "flatten_bytes", "fuse", "shadow_packets", "shadow_side", "group_flags", "denoise", "denoise_iterations", "denoise_sigma_luminance", "denoise_sigma_normal", "denoise_sigma_depth", "denoise_temporal", "denoise_alpha", "sky_sampling", "sky_pick", "denoise_motion"};
+// =================================================================================================================
+// settings: one row per key — how a value is parsed and stored (nothing: read-only), how it is printed, whether
+// rfwhip_get_settings lists it.  rfwhip_set_setting / rfwhip_get_setting / rfwhip_get_settings are lookups in k_settings.
+// =================================================================================================================
+struct Setting
+{
+	const char *key;
+	int (*set)(rfwhip_context *c, const char *key, const char *value); // nullptr: read-only, a set answers "unknown setting"
+	int (*get)(rfwhip_context *c, char *out, size_t cap);
+	bool listed;
+};
+
+// ---- the recurring row kinds (lenient ones parse with atoi: "abc" is 0) ----
+static int set_enum2(int &dst, const char *key, const char *value, const char *name0, const char *name1)
+{
+	if (strcmp(value, name0) && strcmp(value, name1))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be \"%s\" or \"%s\"", key, name0, name1);
+	dst = !strcmp(value, name1);
+	return RFWHIP_OK;
+}
+static int set_flag(int &dst, const char *value)
+{
+	dst = atoi(value) != 0;
+	return RFWHIP_OK;
+}
+static int set_int_in(int &dst, const char *key, const char *value, int lo, int hi)
+{
+	const int n = atoi(value);
+	if (n < lo || n > hi)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be in [%d, %d]", key, lo, hi);
+	dst = n;
+	return RFWHIP_OK;
+}
+static int parse_01(const char *key, const char *value, bool *on) // strict: exactly "0" or "1"
+{
+	if (strcmp(value, "0") && strcmp(value, "1"))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be \"0\" or \"1\"", key);
+	*on = value[0] == '1';
+	return RFWHIP_OK;
+}
+// strict: the whole of `value` is one number that `ok` accepts ("" reads as 0 unless the row refuses it); `must` completes
+// "<key> must ..."
+static int set_float(float &dst, const char *key, const char *value, bool (*ok)(float), const char *must, bool empty_is_zero = true)
+{
+	char *end = nullptr;
+	const float f = strtof(value, &end);
+	if (!end || *end || (end == value && !empty_is_zero) || !ok(f))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must %s", key, must);
+	dst = f;
+	return RFWHIP_OK;
+}
+static int set_sigma(float &dst, const char *key, const char *value)
+{
+	return set_float(dst, key, value, [](float f) { return f >= 0.0f && f < 1e30f; }, "be a finite number >= 0");
+}
+// denoise_temporal / denoise_motion: turning one on clears the history, traces the guides again with what the stage needs
+// and, where `ensure` says the stage will run, (re)allocates its buffers
+static int set_denoise_stage(rfwhip_context *c, int &stage, const char *key, const char *value, bool (*ensure)(const rfwhip_context *))
+{
+	bool on;
+	RF_TRY(parse_01(key, value, &on));
+	if (on && !stage)
+	{
+		RF_TRY(sync_all(c)); // (a stage in flight may still read the buffers this reallocates)
+		stage = 1;
+		dn_clear_history(c);
+		c->guides_valid = false;
+		if (ensure(c))
+			RF_TRY(dn_ensure(c));
+	}
+	stage = on;
+	return RFWHIP_OK;
+}
+static int put(char *out, size_t cap, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+static int put(char *out, size_t cap, const char *fmt, ...)
+{
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(out, cap, fmt, ap);
+	va_end(ap);
+	return RFWHIP_OK;
+}
+
+#define SET [](rfwhip_context * c, const char *key, const char *value) -> int
+#define GET [](rfwhip_context * c, char *out, size_t cap) -> int
+#define GET_INT(member) GET { return put(out, cap, "%d", c->member); }
+#define ENUM2(member, name0, name1) SET { return set_enum2(c->member, key, value, name0, name1); }, GET { return put(out, cap, "%s", c->member ? name1 : name0); }
+#define FLAG(member) SET { return set_flag(c->member, value); }, GET_INT(member)
+#define INT_IN(member, lo, hi) SET { return set_int_in(c->member, key, value, lo, hi); }, GET_INT(member)
+#define SIGMA(member) SET { return set_sigma(c->member, key, value); }, GET { return put(out, cap, "%g", c->member); }
+static const Setting k_settings[] = {
+	// ---- listed by rfwhip_get_settings, in this order ----
+	{"integrator", SET {
+		 if (set_enum2(c->integrator, key, value, "parity", "pt"))
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "integrator must be \"parity\" or \"pt\", got \"%s\"", value);
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%s", c->integrator ? "pt" : "parity"); }, true},
+	{"spp", INT_IN(spp, 1, 4096), true},
+	{"max_depth", INT_IN(max_depth, 0, rt::MAX_DEPTH_SLOTS - 2), true},
+	{"jitter", ENUM2(jitter, "xor128", "center"), true},
+	{"stage_timing", FLAG(stage_timing), true},
+	{"count_traversal", FLAG(count_traversal), true},
+	{"lds_nodes", SET { c->lds_nodes = std::max(-1, atoi(value)); return RFWHIP_OK; }, GET_INT(lds_nodes), true},
+	{"refill", SET { c->refill = atoi(value) & 15; return RFWHIP_OK; }, GET_INT(refill), true},
+	{"streams", INT_IN(streams, 1, rfwhip_context::MAX_SUB), true},
+	{"sampler", ENUM2(sampler, "hash", "bluenoise"), true},
+	{"builder", ENUM2(builder, "host", "device"), true},
+	{"overlap", SET {
+		 if (set_int_in(c->overlap, key, value, -1, 1))
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "overlap must be -1 (by launch size), 0 or 1");
+		 return RFWHIP_OK; },
+	 GET_INT(overlap), true},
+	{"sub_batch_paths", SET {
+		 const long long n = atoll(value);
+		 if (n < 1)
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sub_batch_paths must be >= 1");
+		 c->sub_batch_paths = n;
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%lld", c->sub_batch_paths); }, true},
+	{"ring", INT_IN(ring, 1, rfwhip_context::MAX_RING), true},
+	{"sample_group", SET {
+		 const int n = atoi(value);
+		 if (n < 1 || n > 64 || (n & (n - 1)))
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sample_group must be a power of two in [1, 64]");
+		 c->sample_group = n;
+		 return RFWHIP_OK; },
+	 GET_INT(sample_group), true},
+	{"flat_instances", SET {
+		 c->scene_dirty = true; // takes effect with the next rfwhip_update()
+		 return set_flag(c->flat_instances, value); },
+	 GET_INT(flat_instances), true},
+	{"flatten_bytes", SET {
+		 c->flatten_bytes = std::max(0ll, atoll(value));
+		 c->scene_dirty = true;
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%lld", c->flatten_bytes); }, true},
+	{"fuse", FLAG(fuse), true},
+	{"shadow_packets", SET {
+		 const int v = atoi(value);
+		 c->shadow_packets = v < 0 ? -1 : (v != 0);
+		 c->shadow_packets_auto_on = true;
+		 return RFWHIP_OK; },
+	 GET_INT(shadow_packets), true},
+	{"shadow_side", FLAG(shadow_side), true},
+	{"group_flags", FLAG(group_flags), true},
+	{"denoise", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 if (on && c->W && c->rank == 0) // (the root filters the gathered image; other ranks never do)
+			 RF_TRY(dn_ensure(c)); // (buffers of the full image: allocated when the setting is first turned on)
+		 if (on && !c->denoise)
+			 dn_clear_history(c);
+		 c->denoise = on;
+		 return RFWHIP_OK; },
+	 GET_INT(denoise), true},
+	{"denoise_iterations", INT_IN(dn_iterations, 1, 8), true},
+	{"denoise_sigma_luminance", SIGMA(dn_sigma_l), true},
+	{"denoise_sigma_normal", SIGMA(dn_sigma_n), true},
+	{"denoise_sigma_depth", SIGMA(dn_sigma_z), true},
+	{"denoise_temporal", SET { // (guides: traced again with the instance ids)
+		 return set_denoise_stage(c, c->dn_temporal, key, value, [](const rfwhip_context *c) { return c->W && c->rank == 0; }); },
+	 GET_INT(dn_temporal), true},
+	{"denoise_alpha", SET { return set_float(c->dn_alpha, key, value, [](float f) { return f > 0.0f && f <= 1.0f; }, "be in (0, 1]"); },
+	 GET { return put(out, cap, "%g", c->dn_alpha); }, true},
+	{"sky_sampling", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 c->sky_sampling = on;
+		 c->sky_stale = true; // (the next render builds the table, on the sky of the last rfwhip_update)
+		 return RFWHIP_OK; },
+	 GET_INT(sky_sampling), true},
+	{"sky_pick", SET {
+		 RF_TRY(set_float(c->sky_pick, key, value, [](float f) { return f == -1.0f || (f >= 0.0f && f <= 1.0f); },
+						  "be -1 (auto) or a probability in [0, 1]", false));
+		 c->sky_stale = true;
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%g", c->sky_pick); }, true},
+	{"denoise_motion", SET { // (guides: traced again with the surface record)
+		 return set_denoise_stage(c, c->dn_motion, key, value, [](const rfwhip_context *c) { return c->W && c->rank == 0 && c->dn_temporal; }); },
+	 GET_INT(dn_motion), true},
+	// ---- unlisted ----
+	// (self-arming primary kernels: round 4's switch, removed with the variant in round 5 — accepted and ignored, like refill bit 2)
+	{"arm", SET { return RFWHIP_OK; }, GET { return put(out, cap, "0"); }, false},
+	// read-only: would the next large pt call take the packet form of the depth-0 connection wave?
+	{"shadow_packets_on", nullptr, GET { return put(out, cap, "%d", (c->shadow_packets > 0 || (c->shadow_packets < 0 && c->shadow_packets_auto_on)) && c->packet_ok && c->nodes4f_current && (c->refill & 8) ? 1 : 0); }, false},
+	// read-only: light bins per sorted run of the last waited frames, see shadow_packets
+	{"shadow_bins_per_run", nullptr, GET { return put(out, cap, "%.3f", c->shadow_bins_per_run); }, false},
+	// read-only: which kernel variants the render calls launch (for hosts that label their measurements: bench.py)
+	{"textured", nullptr, GET { return put(out, cap, "%d", c->textured ? 1 : 0); }, false}, // some material carries a texture / normal map: k_shade_pt<true>
+	// the pt primary wave runs in packet form (k_primary_packet) for sample groups >= 2 or large launches
+	{"packet", nullptr, GET { return put(out, cap, "%d", (c->packet_ok && (c->refill & 8)) ? 1 : 0); }, false},
+	// triangles in the world tree of the last rfwhip_update (0: none)
+	{"world_tree", nullptr, GET { return put(out, cap, "%zu", c->wtree.valid ? c->wtree.tris : (size_t)0); }, false},
+	// read-only: p > 0, the pt shade waves run k_shade_pt_sky
+	{"sky", nullptr, GET {
+		 if (c->sky_stale && !c->scene_dirty)
+			 RF_TRY(update_sky_sampling(c));
+		 return put(out, cap, "%d", c->sky_view.pick > 0.0f ? 1 : 0); },
+	 false},
+};
+#undef SET
+#undef GET
+#undef GET_INT
+#undef ENUM2
+#undef FLAG
+#undef INT_IN
+#undef SIGMA
+
+static const Setting *find_setting(const char *key)
+{
+	for (const Setting &s : k_settings)
+		if (!strcmp(s.key, key))
+			return &s;
+	return nullptr;
+}
 
 extern "C" int rfwhip_set_setting(rfwhip_context *c, const char *key, const char *value)
 {
 	CTX_ENTER(c);
 	if (!key || !value)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null key/value");
-	const std::string k(key), v(value);
-	if (k == "integrator")
-	{
-		if (v == "parity")
-			c->integrator = 0;
-		else if (v == "pt")
-			c->integrator = 1;
-		else
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "integrator must be \"parity\" or \"pt\", got \"%s\"", value);
-	}
-	else if (k == "spp")
-	{
-		const int n = atoi(value);
-		if (n < 1 || n > 4096)
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "spp must be in [1, 4096]");
-		c->spp = n;
-	}
-	else if (k == "max_depth")
-	{
-		const int n = atoi(value);
-		if (n < 0 || n + 2 > rt::MAX_DEPTH_SLOTS)
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "max_depth must be in [0, %d]", rt::MAX_DEPTH_SLOTS - 2);
-		c->max_depth = n;
-	}
-	else if (k == "jitter")
-	{
-		if (v == "xor128")
-			c->jitter = 0;
-		else if (v == "center")
-			c->jitter = 1;
-		else
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "jitter must be \"xor128\" or \"center\"");
-	}
-	else if (k == "builder")
-	{
-		if (!strcmp(value, "host"))
-			c->builder = 0;
-		else if (!strcmp(value, "device"))
-			c->builder = 1;
-		else
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "builder must be \"host\" or \"device\"");
-	}
-	else if (k == "sampler")
-	{
-		if (!strcmp(value, "hash"))
-			c->sampler = 0;
-		else if (!strcmp(value, "bluenoise"))
-			c->sampler = 1;
-		else
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sampler must be \"hash\" or \"bluenoise\"");
-	}
-	else if (k == "stage_timing")
-		c->stage_timing = atoi(value) != 0;
-	else if (k == "count_traversal")
-		c->count_traversal = atoi(value) != 0;
-	else if (k == "lds_nodes")
-		c->lds_nodes = std::max(-1, atoi(value));
-	else if (k == "refill")
-		c->refill = atoi(value) & 15;
-	else if (k == "arm")
-	{
-		// (self-arming primary kernels: round 4's switch, removed with the variant in round 5 — accepted and ignored, like refill bit 2)
-	}
-	else if (k == "fuse")
-		c->fuse = atoi(value) != 0;
-	else if (k == "shadow_side")
-		c->shadow_side = atoi(value) != 0;
-	else if (k == "group_flags")
-		c->group_flags = atoi(value) != 0;
-	else if (k == "shadow_packets")
-	{
-		const int v = atoi(value);
-		c->shadow_packets = v < 0 ? -1 : (v != 0);
-		c->shadow_packets_auto_on = true;
-	}
-	else if (k == "flatten_bytes")
-	{
-		c->flatten_bytes = std::max(0ll, atoll(value));
-		c->scene_dirty = true;
-	}
-	else if (k == "sub_batch_paths")
-	{
-		const long long n = atoll(value);
-		if (n < 1)
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sub_batch_paths must be >= 1");
-		c->sub_batch_paths = n;
-	}
-	else if (k == "ring")
-	{
-		const int n = atoi(value);
-		if (n < 1 || n > rfwhip_context::MAX_RING)
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "ring must be in [1, %d]", (int)rfwhip_context::MAX_RING);
-		c->ring = n;
-	}
-	else if (k == "flat_instances")
-	{
-		c->flat_instances = atoi(value) != 0;
-		c->scene_dirty = true; // takes effect with the next rfwhip_update()
-	}
-	else if (k == "sample_group")
-	{
-		const int n = atoi(value);
-		if (n < 1 || n > 64 || (n & (n - 1)))
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sample_group must be a power of two in [1, 64]");
-		c->sample_group = n;
-	}
-	else if (k == "overlap")
-	{
-		const int n = atoi(value);
-		if (n < -1 || n > 1)
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "overlap must be -1 (by launch size), 0 or 1");
-		c->overlap = n;
-	}
-	else if (k == "streams")
-	{
-		const int n = atoi(value);
-		if (n < 1 || n > rfwhip_context::MAX_SUB)
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "streams must be in [1, %d]", (int)rfwhip_context::MAX_SUB);
-		c->streams = n;
-	}
-	else if (k == "denoise")
-	{
-		if (v != "0" && v != "1")
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise must be \"0\" or \"1\"");
-		if (v == "1" && c->W && c->rank == 0) // (the root filters the gathered image; other ranks never do)
-			RF_TRY(dn_ensure(c)); // (buffers of the full image: allocated when the setting is first turned on)
-		if (v == "1" && !c->denoise)
-			dn_clear_history(c);
-		c->denoise = v == "1";
-	}
-	else if (k == "denoise_temporal")
-	{
-		if (v != "0" && v != "1")
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_temporal must be \"0\" or \"1\"");
-		if (v == "1" && !c->dn_temporal)
-		{
-			RF_TRY(sync_all(c)); // (a stage in flight may still read the buffers this reallocates)
-			c->dn_temporal = 1;
-			dn_clear_history(c);
-			c->guides_valid = false; // (traced again with the instance ids)
-			if (c->W && c->rank == 0)
-				RF_TRY(dn_ensure(c));
-		}
-		c->dn_temporal = v == "1";
-	}
-	else if (k == "denoise_motion")
-	{
-		if (v != "0" && v != "1")
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_motion must be \"0\" or \"1\"");
-		if (v == "1" && !c->dn_motion)
-		{
-			RF_TRY(sync_all(c)); // (a stage in flight may still read the buffers this reallocates)
-			c->dn_motion = 1;
-			dn_clear_history(c);
-			c->guides_valid = false; // (traced again with the surface record)
-			if (c->W && c->rank == 0 && c->dn_temporal)
-				RF_TRY(dn_ensure(c));
-		}
-		c->dn_motion = v == "1";
-	}
-	else if (k == "denoise_alpha")
-	{
-		char *end = nullptr;
-		const float f = strtof(value, &end);
-		if (!end || *end || !(f > 0.0f) || !(f <= 1.0f))
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_alpha must be in (0, 1]");
-		c->dn_alpha = f;
-	}
-	else if (k == "denoise_iterations")
-	{
-		const int n = atoi(value);
-		if (n < 1 || n > 8)
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "denoise_iterations must be in [1, 8]");
-		c->dn_iterations = n;
-	}
-	else if (k == "denoise_sigma_luminance" || k == "denoise_sigma_normal" || k == "denoise_sigma_depth")
-	{
-		char *end = nullptr;
-		const float f = strtof(value, &end);
-		if (!end || *end || !(f >= 0.0f) || !(f < 1e30f))
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be a finite number >= 0", key);
-		(k == "denoise_sigma_luminance" ? c->dn_sigma_l : k == "denoise_sigma_normal" ? c->dn_sigma_n : c->dn_sigma_z) = f;
-	}
-	else if (k == "sky_sampling")
-	{
-		if (v != "0" && v != "1")
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sky_sampling must be \"0\" or \"1\"");
-		c->sky_sampling = v == "1";
-		c->sky_stale = true; // (the next render builds the table, on the sky of the last rfwhip_update)
-	}
-	else if (k == "sky_pick")
-	{
-		char *end = nullptr;
-		const float f = strtof(value, &end);
-		if (!end || end == value || *end || !(f == -1.0f || (f >= 0.0f && f <= 1.0f)))
-			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "sky_pick must be -1 (auto) or a probability in [0, 1]");
-		c->sky_pick = f;
-		c->sky_stale = true;
-	}
-	else
+	const Setting *s = find_setting(key);
+	if (!s || !s->set)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "unknown setting \"%s\"", key);
-	return RFWHIP_OK;
+	return s->set(c, key, value);
 }
 
 extern "C" int rfwhip_get_setting(rfwhip_context *c, const char *key, char *value, size_t cap)
@@ -3445,99 +3157,23 @@ extern "C" int rfwhip_get_setting(rfwhip_context *c, const char *key, char *valu
 	CTX_ENTER(c);
 	if (!key || !value || !cap)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null key/value");
-	const std::string k(key);
-	if (k == "integrator")
-		snprintf(value, cap, "%s", c->integrator ? "pt" : "parity");
-	else if (k == "spp")
-		snprintf(value, cap, "%d", c->spp);
-	else if (k == "max_depth")
-		snprintf(value, cap, "%d", c->max_depth);
-	else if (k == "jitter")
-		snprintf(value, cap, "%s", c->jitter ? "center" : "xor128");
-	else if (k == "builder")
-		snprintf(value, cap, "%s", c->builder ? "device" : "host");
-	else if (k == "sampler")
-		snprintf(value, cap, "%s", c->sampler ? "bluenoise" : "hash");
-	else if (k == "stage_timing")
-		snprintf(value, cap, "%d", c->stage_timing);
-	else if (k == "count_traversal")
-		snprintf(value, cap, "%d", c->count_traversal);
-	else if (k == "lds_nodes")
-		snprintf(value, cap, "%d", c->lds_nodes);
-	else if (k == "refill")
-		snprintf(value, cap, "%d", c->refill);
-	else if (k == "arm")
-		snprintf(value, cap, "0"); // (retired: see rfwhip_set_setting)
-	else if (k == "fuse")
-		snprintf(value, cap, "%d", c->fuse);
-	else if (k == "shadow_packets")
-		snprintf(value, cap, "%d", c->shadow_packets);
-	else if (k == "shadow_side")
-		snprintf(value, cap, "%d", c->shadow_side);
-	else if (k == "group_flags")
-		snprintf(value, cap, "%d", c->group_flags);
-	else if (k == "shadow_packets_on") // (read-only: would the next large pt call take the packet form of the depth-0 connection wave?)
-		snprintf(value, cap, "%d", (c->shadow_packets > 0 || (c->shadow_packets < 0 && c->shadow_packets_auto_on)) && c->packet_ok && c->nodes4f_current && (c->refill & 8) ? 1 : 0);
-	else if (k == "shadow_bins_per_run") // (read-only: light bins per sorted run of the last waited frames, see shadow_packets)
-		snprintf(value, cap, "%.3f", c->shadow_bins_per_run);
-	else if (k == "streams")
-		snprintf(value, cap, "%d", c->streams);
-	else if (k == "flatten_bytes")
-		snprintf(value, cap, "%lld", c->flatten_bytes);
-	else if (k == "sub_batch_paths")
-		snprintf(value, cap, "%lld", c->sub_batch_paths);
-	else if (k == "ring")
-		snprintf(value, cap, "%d", c->ring);
-	else if (k == "overlap")
-		snprintf(value, cap, "%d", c->overlap);
-	else if (k == "sample_group")
-		snprintf(value, cap, "%d", c->sample_group);
-	else if (k == "flat_instances")
-		snprintf(value, cap, "%d", c->flat_instances);
-	// read-only: which kernel variants the render calls launch (for hosts that label their measurements: bench.py)
-	else if (k == "textured") // some material carries a texture / normal map: k_shade_pt<true>
-		snprintf(value, cap, "%d", c->textured ? 1 : 0);
-	else if (k == "packet") // the pt primary wave runs in packet form (k_primary_packet) for sample groups >= 2 or large launches
-		snprintf(value, cap, "%d", (c->packet_ok && (c->refill & 8)) ? 1 : 0);
-	else if (k == "world_tree") // triangles in the world tree of the last rfwhip_update (0: none)
-		snprintf(value, cap, "%zu", c->wtree.valid ? c->wtree.tris : (size_t)0);
-	else if (k == "denoise")
-		snprintf(value, cap, "%d", c->denoise);
-	else if (k == "denoise_iterations")
-		snprintf(value, cap, "%d", c->dn_iterations);
-	else if (k == "denoise_sigma_luminance")
-		snprintf(value, cap, "%g", c->dn_sigma_l);
-	else if (k == "denoise_sigma_normal")
-		snprintf(value, cap, "%g", c->dn_sigma_n);
-	else if (k == "denoise_sigma_depth")
-		snprintf(value, cap, "%g", c->dn_sigma_z);
-	else if (k == "denoise_temporal")
-		snprintf(value, cap, "%d", c->dn_temporal);
-	else if (k == "denoise_alpha")
-		snprintf(value, cap, "%g", c->dn_alpha);
-	else if (k == "denoise_motion")
-		snprintf(value, cap, "%d", c->dn_motion);
-	else if (k == "sky_sampling")
-		snprintf(value, cap, "%d", c->sky_sampling);
-	else if (k == "sky_pick")
-		snprintf(value, cap, "%g", c->sky_pick);
-	else if (k == "sky") // (read-only) p > 0: the pt shade waves run k_shade_pt_sky
-	{
-		if (c->sky_stale && !c->scene_dirty)
-			RF_TRY(update_sky_sampling(c));
-		snprintf(value, cap, "%d", c->sky_view.pick > 0.0f ? 1 : 0);
-	}
-	else
+	const Setting *s = find_setting(key);
+	if (!s)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "unknown setting \"%s\"", key);
-	return RFWHIP_OK;
+	return s->get(c, value, cap);
 }
 
 extern "C" int rfwhip_get_settings(rfwhip_context *c, const char **keys, size_t cap)
 {
 	(void)c;
-	const size_t n = sizeof(k_setting_keys) / sizeof(k_setting_keys[0]);
-	for (size_t i = 0; i < n && i < cap && keys; i++)
-		keys[i] = k_setting_keys[i];
+	size_t n = 0;
+	for (const Setting &s : k_settings)
+		if (s.listed)
+		{
+			if (keys && n < cap)
+				keys[n] = s.key;
+			n++;
+		}
 	return (int)n;
 }
 

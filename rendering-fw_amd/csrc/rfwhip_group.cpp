@@ -19,21 +19,18 @@
 // Built on the public C ABI of rfwhip.h only (no access to the context's internals); librccl is opened on first use.
 #include "rfwhip.h"
 
+#include "device_layer.h"
 #include "internal.h"
 
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
 #if !defined(RFWHIP_HOST_EMULATION)
-#include <stdlib.h>
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
-#else
-#include <stdlib.h>
 #endif
-#include "emu_streams.h" // (the deferred-stream variant of the emulation build; empty otherwise)
 
 #define GR_TRY(x)            \
 	do                       \
@@ -47,114 +44,7 @@ namespace
 {
 constexpr size_t PIXEL_BYTES = 16; // float4
 
-// ---- device layer: HIP, or heap memory in the host-emulation build of the tests ------------------------------------
 #if !defined(RFWHIP_HOST_EMULATION)
-#define GR_HIP(x)                                                                                                   \
-	do                                                                                                              \
-	{                                                                                                               \
-		const hipError_t e_ = (x);                                                                                  \
-		if (e_ != hipSuccess)                                                                                       \
-			return rfwhip_internal_set_error(RFWHIP_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-	} while (0)
-int dev_use(int device)
-{
-	GR_HIP(hipSetDevice(device));
-	return 0;
-}
-int dev_alloc(void **p, size_t bytes)
-{
-	GR_HIP(hipMalloc(p, bytes ? bytes : 16));
-	return 0;
-}
-void dev_free(void *p)
-{
-	if (p)
-		(void)hipFree(p);
-}
-int stream_create(void **s)
-{
-	hipStream_t st;
-	GR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-	*s = st;
-	return 0;
-}
-void stream_destroy(void *s)
-{
-	if (s)
-		(void)hipStreamDestroy((hipStream_t)s);
-}
-int stream_sync(void *s)
-{
-	GR_HIP(hipStreamSynchronize((hipStream_t)s));
-	return 0;
-}
-typedef hipEvent_t event_t;
-int event_create(event_t *e)
-{
-	GR_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-	return 0;
-}
-void event_destroy(event_t e) { (void)hipEventDestroy(e); }
-int event_record(event_t e, void *s)
-{
-	GR_HIP(hipEventRecord(e, (hipStream_t)s));
-	return 0;
-}
-int stream_wait(void *s, event_t e)
-{
-	GR_HIP(hipStreamWaitEvent((hipStream_t)s, e, 0));
-	return 0;
-}
-// dst on dst_device <- src on src_device, enqueued on `s` (a stream of the source device: the copy is pushed)
-int copy_async(void *dst, int dst_device, const void *src, int src_device, size_t bytes, void *s)
-{
-	if (dst_device == src_device)
-		GR_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-	else
-		GR_HIP(hipMemcpyPeerAsync(dst, dst_device, src, src_device, bytes, (hipStream_t)s));
-	return 0;
-}
-int copy_to_host(void *dst, const void *src, size_t bytes, void *s)
-{
-	GR_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)s));
-	GR_HIP(hipStreamSynchronize((hipStream_t)s));
-	return 0;
-}
-int host_alloc(void **p, size_t bytes) // pinned: the device-to-host copy of a presented frame runs asynchronously
-{
-	GR_HIP(hipHostMalloc(p, bytes ? bytes : 16, hipHostMallocDefault));
-	return 0;
-}
-void host_free(void *p)
-{
-	if (p)
-		(void)hipHostFree(p);
-}
-int copy_to_host_async(void *dst, const void *src, size_t bytes, void *s)
-{
-	GR_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)s));
-	return 0;
-}
-int event_sync(event_t e)
-{
-	GR_HIP(hipEventSynchronize(e));
-	return 0;
-}
-int device_count()
-{
-	int n = 0;
-	return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-void enable_peer(int a, int b) // best effort: without it hipMemcpyPeerAsync stages through the host
-{
-	int can = 0;
-	if (a == b || hipDeviceCanAccessPeer(&can, a, b) != hipSuccess || !can)
-		return;
-	if (hipSetDevice(a) == hipSuccess)
-		(void)hipDeviceEnablePeerAccess(b, 0); // (hipErrorPeerAccessAlreadyEnabled is fine)
-	(void)hipGetLastError();
-}
-
 // ---- RCCL, opened on first use (a single-GPU host never loads it) ----------------------------------------------------
 struct Rccl
 {
@@ -211,123 +101,7 @@ Rccl g_rccl;
 			return rfwhip_internal_set_error(RFWHIP_ERR_HIP, "RCCL: %s failed: %s (%s:%d)", #x, g_rccl.err(r_), __FILE__, __LINE__); \
 	} while (0)
 typedef ncclComm_t comm_t;
-#elif defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
-// host emulation with deferred streams (emu_streams.h): the same model as the contexts' streams
-int dev_use(int) { return 0; }
-int dev_alloc(void **p, size_t bytes)
-{
-	*p = calloc(bytes ? bytes : 16, 1);
-	return *p ? 0 : rfwhip_internal_set_error(RFWHIP_ERR_HIP, "out of memory");
-}
-void dev_free(void *p)
-{
-	if (!p)
-		return;
-	emu_streams::sync_all(); // (hipFree synchronises the device)
-	free(p);
-}
-int stream_create(void **s)
-{
-	*s = emu_streams::stream_create();
-	return 0;
-}
-void stream_destroy(void *s)
-{
-	if (s)
-		emu_streams::stream_destroy(s);
-}
-int stream_sync(void *s)
-{
-	emu_streams::sync(s);
-	return 0;
-}
-typedef emu_streams::Event *event_t;
-int event_create(event_t *e)
-{
-	*e = emu_streams::event_create();
-	return 0;
-}
-void event_destroy(event_t e) { emu_streams::destroy_event(e); }
-int event_record(event_t e, void *s)
-{
-	emu_streams::record(e, s);
-	return 0;
-}
-int stream_wait(void *s, event_t e)
-{
-	emu_streams::wait_event(s, e);
-	return 0;
-}
-int copy_async(void *dst, int, const void *src, int, size_t bytes, void *s)
-{
-	emu_streams::copy(dst, src, bytes, s);
-	return 0;
-}
-int copy_to_host(void *dst, const void *src, size_t bytes, void *s)
-{
-	emu_streams::copy(dst, src, bytes, s);
-	emu_streams::sync(s);
-	return 0;
-}
-int host_alloc(void **p, size_t bytes) { return dev_alloc(p, bytes); }
-void host_free(void *p) { dev_free(p); }
-int copy_to_host_async(void *dst, const void *src, size_t bytes, void *s)
-{
-	emu_streams::copy(dst, src, bytes, s);
-	return 0;
-}
-int event_sync(event_t e)
-{
-	emu_streams::sync_event(e);
-	return 0;
-}
-int device_count() { return 1 << 20; }
-void enable_peer(int, int) {}
-typedef void *comm_t;
 #else
-int dev_use(int) { return 0; }
-int dev_alloc(void **p, size_t bytes)
-{
-	*p = calloc(bytes ? bytes : 16, 1);
-	return *p ? 0 : rfwhip_internal_set_error(RFWHIP_ERR_HIP, "out of memory");
-}
-void dev_free(void *p) { free(p); }
-int stream_create(void **s)
-{
-	*s = nullptr;
-	return 0;
-}
-void stream_destroy(void *) {}
-int stream_sync(void *) { return 0; }
-typedef int event_t;
-int event_create(event_t *e)
-{
-	*e = 0;
-	return 0;
-}
-void event_destroy(event_t) {}
-int event_record(event_t, void *) { return 0; }
-int stream_wait(void *, event_t) { return 0; }
-int copy_async(void *dst, int, const void *src, int, size_t bytes, void *)
-{
-	memmove(dst, src, bytes);
-	return 0;
-}
-int copy_to_host(void *dst, const void *src, size_t bytes, void *)
-{
-	memcpy(dst, src, bytes);
-	return 0;
-}
-int host_alloc(void **p, size_t bytes) { return dev_alloc(p, bytes); }
-void host_free(void *p) { free(p); }
-int copy_to_host_async(void *dst, const void *src, size_t bytes, void *)
-{
-	memcpy(dst, src, bytes);
-	return 0;
-}
-int event_sync(event_t) { return 0; }
-int device_count() { return 1 << 20; }
-void enable_peer(int, int) {}
 typedef void *comm_t;
 #endif
 
@@ -339,7 +113,7 @@ struct Endpoint
 	void *stream = nullptr;	  // the gather chain of this device: present -> transfer (-> de-interleave on the root)
 	void *local_fb = nullptr; // [local_rows][width] float4: where this rank's present lands (ranks other than the root)
 	comm_t comm = nullptr;
-	event_t sent;			  // peer transport: the push of this rank's strips is enqueued up to here
+	dm::event_t sent;			  // peer transport: the push of this rank's strips is enqueued up to here
 	bool have_event = false;
 };
 
@@ -357,7 +131,7 @@ struct rfwhip_group
 	void *staging = nullptr, *full = nullptr; // on the root's device
 	// peer transport: recorded on the root's stream once a frame's de-interleave has read the staging image; every rank's next
 	// push waits for it (frames in flight: without it a fast rank overwrites its chunk while the root still waits for a slow one)
-	event_t staging_read;
+	dm::event_t staging_read;
 	bool staging_event = false, staging_read_valid = false;
 	bool poisoned = false; // a call failed half-way through the ranks: sample counts / ring slots diverge, re-init needed
 	int root_local = -1;					  // index of rank 0 in ep, -1 when another process owns it
@@ -366,7 +140,7 @@ struct rfwhip_group
 	void *host_img[SLOTS] = {};
 	void *slot_img[SLOTS] = {};	 // the de-interleaved image of each slot on the root's device (the copy's source)
 	void *copy_stream = nullptr; // the device-to-host copies run beside the gather chain, not inside it
-	event_t host_ready[SLOTS], slot_done[SLOTS];
+	dm::event_t host_ready[SLOTS], slot_done[SLOTS];
 	bool host_events = false, host_pending[SLOTS] = {};
 	size_t chunk_bytes() const { return (size_t)local_rows * W * PIXEL_BYTES; }
 };
@@ -382,20 +156,20 @@ void release_buffers(rfwhip_group *g)
 {
 	for (auto &e : g->ep)
 	{
-		(void)dev_use(e.device);
-		dev_free(e.local_fb), e.local_fb = nullptr;
+		(void)dm::use(e.device);
+		dm::release(e.local_fb), e.local_fb = nullptr;
 	}
 	if (g->root_local >= 0)
 	{
-		(void)dev_use(g->ep[g->root_local].device);
-		dev_free(g->staging), dev_free(g->full);
+		(void)dm::use(g->ep[g->root_local].device);
+		dm::release(g->staging), dm::release(g->full);
 	}
 	g->staging = g->full = nullptr;
 	g->staging_read_valid = false;
 	for (int k = 0; k < rfwhip_group::SLOTS; k++)
 	{
-		host_free(g->host_img[k]), g->host_img[k] = nullptr, g->host_pending[k] = false;
-		dev_free(g->slot_img[k]), g->slot_img[k] = nullptr;
+		dm::host_free(g->host_img[k]), g->host_img[k] = nullptr, g->host_pending[k] = false;
+		dm::release(g->slot_img[k]), g->slot_img[k] = nullptr;
 	}
 }
 
@@ -409,15 +183,15 @@ int size_buffers(rfwhip_group *g, uint32_t W, uint32_t H)
 	{
 		if (rfwhip_local_rows(e.ctx) != g->local_rows)
 			return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "ranks disagree about the padded strip rows");
-		GR_TRY(dev_use(e.device));
+		GR_TRY(dm::use(e.device));
 		if (e.rank != 0 || g->loopback)
-			GR_TRY(dev_alloc(&e.local_fb, g->chunk_bytes()));
+			GR_TRY(dm::alloc(&e.local_fb, g->chunk_bytes()));
 	}
 	if (g->root_local >= 0)
 	{
-		GR_TRY(dev_use(g->ep[g->root_local].device));
-		GR_TRY(dev_alloc(&g->staging, g->chunk_bytes() * (size_t)g->world));
-		GR_TRY(dev_alloc(&g->full, (size_t)W * H * PIXEL_BYTES));
+		GR_TRY(dm::use(g->ep[g->root_local].device));
+		GR_TRY(dm::alloc(&g->staging, g->chunk_bytes() * (size_t)g->world));
+		GR_TRY(dm::alloc(&g->full, (size_t)W * H * PIXEL_BYTES));
 	}
 	return 0;
 }
@@ -426,9 +200,9 @@ int make_streams(rfwhip_group *g)
 {
 	for (auto &e : g->ep)
 	{
-		GR_TRY(dev_use(e.device));
-		GR_TRY(stream_create(&e.stream));
-		GR_TRY(event_create(&e.sent));
+		GR_TRY(dm::use(e.device));
+		GR_TRY(dm::stream_create(&e.stream));
+		GR_TRY(dm::event_create(&e.sent, false));
 		e.have_event = true;
 	}
 	return 0;
@@ -442,7 +216,7 @@ int init_rccl(rfwhip_group *g, const ncclUniqueId &id)
 	const int rc_group = [&]() -> int {
 		for (auto &e : g->ep)
 		{
-			GR_TRY(dev_use(e.device));
+			GR_TRY(dm::use(e.device));
 			GR_NCCL(g_rccl.CommInitRank(&e.comm, g->world, id, e.rank));
 		}
 		return 0;
@@ -475,7 +249,7 @@ int gather(rfwhip_group *g, void *full_out)
 	{
 		// world 1 over RCCL: the one rank sends its strips to itself — same calls, same streams as the root's side of a real gather
 		const size_t count = chunk / sizeof(float);
-		GR_TRY(dev_use(root->device));
+		GR_TRY(dm::use(root->device));
 		GR_NCCL(g_rccl.GroupStart());
 		const ncclResult_t r_send = g_rccl.Send(root->local_fb, count, ncclFloat, 0, root->comm, (hipStream_t)root->stream);
 		const ncclResult_t r_recv = r_send == ncclSuccess ? g_rccl.Recv(g->staging, count, ncclFloat, 0, root->comm, (hipStream_t)root->stream) : r_send;
@@ -498,12 +272,12 @@ int gather(rfwhip_group *g, void *full_out)
 				for (auto &e : g->ep)
 					if (e.rank != 0)
 					{
-						GR_TRY(dev_use(e.device));
+						GR_TRY(dm::use(e.device));
 						GR_NCCL(g_rccl.Send(e.local_fb, count, ncclFloat, 0, e.comm, (hipStream_t)e.stream));
 					}
 				if (root)
 				{
-					GR_TRY(dev_use(root->device));
+					GR_TRY(dm::use(root->device));
 					for (int r = 1; r < g->world; r++)
 						GR_NCCL(g_rccl.Recv((char *)g->staging + (size_t)r * chunk, count, ncclFloat, r, root->comm, (hipStream_t)root->stream));
 				}
@@ -522,19 +296,19 @@ int gather(rfwhip_group *g, void *full_out)
 			for (auto &e : g->ep)
 				if (e.rank != 0)
 				{
-					GR_TRY(dev_use(e.device));
+					GR_TRY(dm::use(e.device));
 					// (the root's de-interleave of the PREVIOUS frame must have read this rank's chunk of the staging image before the
 					// push overwrites it: the event is recorded behind that de-interleave, step 3, and re-recorded only after this
 					// wait has been enqueued — with frames in flight the push of frame k + 1 would otherwise race the read of frame k)
 					if (g->staging_read_valid)
-						GR_TRY(stream_wait(e.stream, g->staging_read));
-					GR_TRY(copy_async((char *)g->staging + (size_t)e.rank * chunk, root->device, e.local_fb, e.device, chunk, e.stream));
-					GR_TRY(event_record(e.sent, e.stream));
+						GR_TRY(dm::stream_wait_event(e.stream, g->staging_read));
+					GR_TRY(dm::copy_async((char *)g->staging + (size_t)e.rank * chunk, root->device, e.local_fb, e.device, chunk, e.stream));
+					GR_TRY(dm::event_record(e.sent, e.stream));
 				}
-			GR_TRY(dev_use(root->device));
+			GR_TRY(dm::use(root->device));
 			for (auto &e : g->ep)
 				if (e.rank != 0)
-					GR_TRY(stream_wait(root->stream, e.sent));
+					GR_TRY(dm::stream_wait_event(root->stream, e.sent));
 		}
 	}
 	// 3. the root undoes the strip interleave
@@ -548,15 +322,15 @@ int gather(rfwhip_group *g, void *full_out)
 			{
 				if (!g->staging_event)
 				{
-					GR_TRY(event_create(&g->staging_read));
+					GR_TRY(dm::event_create(&g->staging_read, false));
 					g->staging_event = true;
 				}
-				GR_TRY(event_record(g->staging_read, root->stream));
+				GR_TRY(dm::event_record(g->staging_read, root->stream));
 				g->staging_read_valid = true;
 			}
 		}
 		else
-			GR_TRY(copy_async(full_out ? full_out : g->full, root->device, g->staging, root->device, (size_t)g->W * g->H * PIXEL_BYTES, root->stream));
+			GR_TRY(dm::copy_async(full_out ? full_out : g->full, root->device, g->staging, root->device, (size_t)g->W * g->H * PIXEL_BYTES, root->stream));
 		// 4. the root's context denoises the full image when its "denoise" setting is on (the filter needs every strip's
 		//    neighbours: it runs once, here, on the root's device and stream; the guides come from the root's copy of the scene)
 		if (rfwhip_internal_denoise_stream(root->ctx, full_out ? full_out : g->full, root->stream))
@@ -574,9 +348,9 @@ int wait_all(rfwhip_group *g)
 	{
 		if (rfwhip_wait(e.ctx) && !first)
 			first = RFWHIP_ERR_STATE;
-		int rc = dev_use(e.device);
+		int rc = dm::use(e.device);
 		if (!rc)
-			rc = stream_sync(e.stream);
+			rc = dm::sync(e.stream);
 		if (rc && !first)
 			first = rc;
 	}
@@ -584,8 +358,8 @@ int wait_all(rfwhip_group *g)
 		return first;
 	if (g->copy_stream && g->root_local >= 0)
 	{
-		GR_TRY(dev_use(g->ep[(size_t)g->root_local].device));
-		GR_TRY(stream_sync(g->copy_stream));
+		GR_TRY(dm::use(g->ep[(size_t)g->root_local].device));
+		GR_TRY(dm::sync(g->copy_stream));
 	}
 	return 0;
 }
@@ -594,38 +368,38 @@ void destroy_group(rfwhip_group *g)
 {
 	for (auto &e : g->ep)
 	{
-		(void)dev_use(e.device);
+		(void)dm::use(e.device);
 		if (e.stream)
-			(void)stream_sync(e.stream);
+			(void)dm::sync(e.stream);
 	}
 	if (g->copy_stream && g->root_local >= 0)
 	{
-		(void)dev_use(g->ep[(size_t)g->root_local].device);
-		(void)stream_sync(g->copy_stream);
+		(void)dm::use(g->ep[(size_t)g->root_local].device);
+		(void)dm::sync(g->copy_stream);
 	}
 	release_buffers(g);
 	for (auto &e : g->ep)
 	{
-		(void)dev_use(e.device);
+		(void)dm::use(e.device);
 #if !defined(RFWHIP_HOST_EMULATION)
 		if (e.comm && g_rccl.lib)
 			(void)g_rccl.CommDestroy(e.comm);
 #endif
 		if (e.have_event)
-			event_destroy(e.sent);
-		stream_destroy(e.stream);
+			dm::event_destroy(e.sent);
+		dm::stream_destroy(e.stream);
 		if (g->owns_contexts && e.ctx)
 			rfwhip_destroy(e.ctx);
 	}
 	if (g->host_events)
 	{
 		for (int k = 0; k < rfwhip_group::SLOTS; k++)
-			event_destroy(g->host_ready[k]), event_destroy(g->slot_done[k]);
+			dm::event_destroy(g->host_ready[k]), dm::event_destroy(g->slot_done[k]);
 		g->host_events = false;
 	}
 	if (g->staging_event)
-		event_destroy(g->staging_read), g->staging_event = false;
-	stream_destroy(g->copy_stream), g->copy_stream = nullptr;
+		dm::event_destroy(g->staging_read), g->staging_event = false;
+	dm::stream_destroy(g->copy_stream), g->copy_stream = nullptr;
 	g->ep.clear();
 }
 
@@ -665,7 +439,7 @@ extern "C" int rfwhip_group_create(const int *devices, int n, int transport, rfw
 	bool distinct = true;
 	for (int i = 0; i < n; i++)
 	{
-		if (devices[i] < 0 || devices[i] >= device_count())
+		if (devices[i] < 0 || devices[i] >= dm::device_count())
 			return rfwhip_internal_set_error(RFWHIP_ERR_NO_DEVICE, "rfwhip_group_create: device ordinal %d out of range", devices[i]);
 		for (int j = 0; j < i; j++)
 			distinct = distinct && devices[i] != devices[j];
@@ -693,7 +467,7 @@ extern "C" int rfwhip_group_create(const int *devices, int n, int transport, rfw
 	}
 	if (!rc && tr == RFWHIP_TRANSPORT_PEER)
 		for (int i = 1; i < n; i++)
-			enable_peer(devices[i], devices[0]), enable_peer(devices[0], devices[i]);
+			dm::enable_peer(devices[i], devices[0]), dm::enable_peer(devices[0], devices[i]);
 #endif
 	if (rc)
 	{
@@ -800,8 +574,8 @@ extern "C" int rfwhip_group_read_framebuffer(rfwhip_group *g, float *rgba_host)
 	GR_TRY(gather(g, nullptr));
 	GR_TRY(wait_all(g));
 	Endpoint &root = g->ep[(size_t)g->root_local];
-	GR_TRY(dev_use(root.device));
-	return copy_to_host(rgba_host, g->full, (size_t)g->W * g->H * PIXEL_BYTES, root.stream);
+	GR_TRY(dm::use(root.device));
+	return dm::d2h(rgba_host, g->full, (size_t)g->W * g->H * PIXEL_BYTES, root.stream);
 }
 
 // Pipelined presentation: frame k's image travels to the host while the next frames render.  present_async enqueues gather +
@@ -814,32 +588,32 @@ extern "C" int rfwhip_group_present_async(rfwhip_group *g, int slot)
 	if (g->root_local < 0 || !g->full)
 		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "no render target");
 	Endpoint &root = g->ep[(size_t)g->root_local];
-	GR_TRY(dev_use(root.device));
+	GR_TRY(dm::use(root.device));
 	const size_t bytes = (size_t)g->W * g->H * PIXEL_BYTES;
 	if (!g->host_events)
 	{
 		for (int k = 0; k < rfwhip_group::SLOTS; k++)
 		{
-			GR_TRY(event_create(&g->host_ready[k]));
-			GR_TRY(event_create(&g->slot_done[k]));
+			GR_TRY(dm::event_create(&g->host_ready[k], false));
+			GR_TRY(dm::event_create(&g->slot_done[k], false));
 		}
-		GR_TRY(stream_create(&g->copy_stream));
+		GR_TRY(dm::stream_create(&g->copy_stream));
 		g->host_events = true;
 	}
 	if (!g->host_img[slot])
-		GR_TRY(host_alloc(&g->host_img[slot], bytes));
+		GR_TRY(dm::host_alloc(&g->host_img[slot], bytes));
 	if (!g->slot_img[slot])
-		GR_TRY(dev_alloc(&g->slot_img[slot], bytes));
+		GR_TRY(dm::alloc(&g->slot_img[slot], bytes));
 	// the slot's device image is rewritten only after its previous copy to the host has read it
 	if (g->host_pending[slot])
-		GR_TRY(stream_wait(root.stream, g->host_ready[slot]));
+		GR_TRY(dm::stream_wait_event(root.stream, g->host_ready[slot]));
 	GR_TRY(gather(g, g->slot_img[slot]));
-	GR_TRY(dev_use(root.device));
-	GR_TRY(event_record(g->slot_done[slot], root.stream));
+	GR_TRY(dm::use(root.device));
+	GR_TRY(dm::event_record(g->slot_done[slot], root.stream));
 	// ... and the copy rides its own stream: the next frame's present / transfer / de-interleave do not queue behind 33 MB of PCIe
-	GR_TRY(stream_wait(g->copy_stream, g->slot_done[slot]));
-	GR_TRY(copy_to_host_async(g->host_img[slot], g->slot_img[slot], bytes, g->copy_stream));
-	GR_TRY(event_record(g->host_ready[slot], g->copy_stream));
+	GR_TRY(dm::stream_wait_event(g->copy_stream, g->slot_done[slot]));
+	GR_TRY(dm::d2h_async(g->host_img[slot], g->slot_img[slot], bytes, g->copy_stream));
+	GR_TRY(dm::event_record(g->host_ready[slot], g->copy_stream));
 	g->host_pending[slot] = true;
 	return RFWHIP_OK;
 }
@@ -852,8 +626,8 @@ extern "C" int rfwhip_group_present_wait(rfwhip_group *g, int slot, const float 
 		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "rfwhip_group_present_wait: nothing was presented into slot %d", slot);
 	if (g->host_pending[slot])
 	{
-		GR_TRY(dev_use(g->ep[(size_t)g->root_local].device));
-		GR_TRY(event_sync(g->host_ready[slot]));
+		GR_TRY(dm::use(g->ep[(size_t)g->root_local].device));
+		GR_TRY(dm::event_sync(g->host_ready[slot]));
 		g->host_pending[slot] = false;
 	}
 	*rgba_host = (const float *)g->host_img[slot];

@@ -1,7 +1,7 @@
 """Host-emulation build of the rendercore sources — TEST INFRASTRUCTURE ONLY.
 
 Compiles rendering-fw_amd/csrc/{rfwhip_api.cpp,bvh_build.cpp,kernels.hip,lbvh.hip} with g++ and -DRFWHIP_HOST_EMULATION into
-tests/_emu/librfwhip_emu.so: device memory becomes heap memory and every kernel launch becomes a plain loop over the
+tests/_emu/librfwhip_emu.so: device memory becomes heap memory (csrc/device_layer.h) and every kernel launch becomes a plain loop over the
 same per-ray / per-path functions (rt_core.h, the *_item functions of kernels.hip).  This lets the CPU test tier
 (-m "not gpu") check the host logic (BVH build, TLAS, packing, strip interleave, xor128 jump-ahead, counters) and
 the device arithmetic against the oracle without a GPU.  The product never loads this library:

@@ -12,7 +12,7 @@ import denoise_motion_model as MM
 import denoise_temporal_model as M
 from conftest import ROOT
 from test_assets import _rig_scene
-from test_denoise_temporal import _bits, _ctx, _get, _keys, check_frame
+from test_denoise_temporal import _bits, _ctx, check_frame
 
 W, H = 96, 64
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -354,12 +354,12 @@ def test_a_further_read_after_an_edit_restarts_instead_of_reading_another_frames
 def test_settings_keys_validation_and_clearing(pkg, make_emu, emu_lib):
     c = make_emu()
     c.init(16, 16)
-    assert "denoise_motion" in _keys(emu_lib, c) and _get(emu_lib, c, "denoise_motion") == "0"
+    assert "denoise_motion" in list(c.get_settings()) and c.get_setting("denoise_motion") == "0"
     for v in ("2", "", "x"):
         with pytest.raises(RuntimeError):
             c.set_setting("denoise_motion", v)
     c.set_setting("denoise_motion", "1")
-    assert _get(emu_lib, c, "denoise_motion") == "1"
+    assert c.get_setting("denoise_motion") == "1"
     scene = _cornell(pkg)
     c = _ctx(pkg, make_emu, scene, denoise=1, denoise_temporal=1)
     for f in range(2):

@@ -2,7 +2,6 @@
 host-emulation build runs the same work items as the HIP kernels.  Held to the numpy model of tests/denoise_temporal_model.py frame
 by frame, to the spatial filter bit for bit where the header promises it, to one context for groups, and to a converged render for
 quality."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -216,34 +215,18 @@ def test_groups_equal_one_context_over_a_moving_sequence(pkg, make_emu, emu_lib,
     g.destroy()
 
 
-def _get(emu_lib, c, key):
-    buf = ctypes.create_string_buffer(128)
-    f = emu_lib.rfwhip_get_setting
-    f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
-    assert f(c._ctx, key.encode(), buf, 128) == 0
-    return buf.value.decode()
-
-
-def _keys(emu_lib, c):
-    keys = (ctypes.c_char_p * 64)()
-    f = emu_lib.rfwhip_get_settings
-    f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t]
-    n = f(c._ctx, keys, 64)
-    return [keys[i].decode() for i in range(n)]
-
-
 def test_settings_keys_and_clearing(pkg, make_emu, emu_lib):
     c = make_emu()
     c.init(16, 16)
-    keys = _keys(emu_lib, c)
+    keys = list(c.get_settings())
     assert "denoise_temporal" in keys and "denoise_alpha" in keys
-    assert _get(emu_lib, c, "denoise_temporal") == "0" and float(_get(emu_lib, c, "denoise_alpha")) == pytest.approx(0.2)
+    assert c.get_setting("denoise_temporal") == "0" and float(c.get_setting("denoise_alpha")) == pytest.approx(0.2)
     for k, v in [("denoise_temporal", "2"), ("denoise_temporal", ""), ("denoise_alpha", "0"), ("denoise_alpha", "1.5"),
                  ("denoise_alpha", "-0.1"), ("denoise_alpha", "x"), ("denoise_alpha", "nan")]:
         with pytest.raises(RuntimeError):
             c.set_setting(k, v)
     c.set_setting("denoise_alpha", "1")
-    assert float(_get(emu_lib, c, "denoise_alpha")) == 1.0
+    assert float(c.get_setting("denoise_alpha")) == 1.0
     # the history is cleared by a re-init and by turning denoise or denoise_temporal on
     scene = _scene(pkg, "cornell")
     c = _ctx(pkg, make_emu, scene, denoise=1, denoise_temporal=1)

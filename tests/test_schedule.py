@@ -50,14 +50,6 @@ def _stats(lib):
     return {"ran": ran.value, "out_of_order": ooo.value, "shadow_packet_launches": sp.value}
 
 
-def _get(lib, c, key):
-    buf = ctypes.create_string_buffer(64)
-    f = lib.rfwhip_get_setting
-    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
-    assert f(c._ctx, key.encode(), buf, 64) == 0
-    return buf.value.decode()
-
-
 def _pipelined(pkg, ctx, scene, w, h, settings, calls, wait_every):
     ctx.init(w, h)
     scene.upload(ctx)
@@ -154,7 +146,7 @@ def test_shadow_packets_under_every_schedule(pkg, make_s, lib, fuse, policy):
                 st = _stats(lib)
                 row = "%s: %s, wait_every=%d" % (name, settings, wait_every)
                 assert np.array_equal(img, refs[spp, max_depth]), row
-                assert _get(lib, c, "shadow_packets_on") == "1", row
+                assert c.get_setting("shadow_packets_on") == "1", row
                 if _takes_packets(fuse, extra, wait_every):
                     assert st["shadow_packet_launches"] > 0, "%s: the packet form never ran %s" % (row, st)
                 else:

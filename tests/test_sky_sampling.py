@@ -2,7 +2,6 @@
 pt_shade<TEX, true>), CPU tier: the host-emulation build runs the same shade work items as k_shade_pt_sky.  The distribution is
 held to the numpy model of tests/sky_sampling_model.py through the known-answer hooks; the estimator to the default one (same
 expectation, less noise); the switch to the default kernels bit for bit wherever p is 0."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -75,22 +74,6 @@ def _ctx(pkg, make_emu, scene, spp=1, upload_sky=True, **settings):
     return c
 
 
-def _get(c, key):  # rfwhip_get_setting on an emulated context
-    buf = ctypes.create_string_buffer(128)
-    f = c._fn("get_setting")
-    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
-    c._check(f(c._ctx, key.encode(), buf, 128))
-    return buf.value.decode()
-
-
-def _keys(c):  # rfwhip_get_settings
-    keys = (ctypes.c_char_p * 64)()
-    f = c._fn("get_settings")
-    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t]
-    n = f(c._ctx, keys, 64)
-    return [keys[i].decode() for i in range(n)]
-
-
 def _render(pkg, c, scene, frames=1):
     for f in range(frames):
         c.render_frame(scene.camera, pkg.RESET if f == 0 else pkg.CONVERGE)
@@ -124,10 +107,10 @@ def _tile_z(fa, fb, t=8):
 # ---------------------------------------------------------------------------------------------------------------------------
 def test_settings_defaults_validation_and_keys(pkg, make_emu):
     c = make_emu()
-    assert _get(c, "sky_sampling") == "0"
-    assert _get(c, "sky_pick") == "-1"
-    assert _get(c, "sky") == "0"
-    keys = _keys(c)
+    assert c.get_setting("sky_sampling") == "0"
+    assert c.get_setting("sky_pick") == "-1"
+    assert c.get_setting("sky") == "0"
+    keys = list(c.get_settings())
     assert "sky_sampling" in keys and "sky_pick" in keys
     for bad in ("2", "-1", "yes", ""):
         with pytest.raises(Exception):
@@ -136,12 +119,12 @@ def test_settings_defaults_validation_and_keys(pkg, make_emu):
         with pytest.raises(Exception):
             c.set_setting("sky_pick", bad)
     c.set_setting("sky_pick", "0.25")
-    assert _get(c, "sky_pick") == "0.25"
+    assert c.get_setting("sky_pick") == "0.25"
     c.set_setting("sky_pick", "-1")
-    assert _get(c, "sky_pick") == "-1"
+    assert c.get_setting("sky_pick") == "-1"
     c.set_setting("sky_sampling", "1")
-    assert _get(c, "sky_sampling") == "1"
-    assert _get(c, "sky") == "0"  # (no sky yet)
+    assert c.get_setting("sky_sampling") == "1"
+    assert c.get_setting("sky") == "0"  # (no sky yet)
 
 
 def test_plugin_lists_the_key():
@@ -154,13 +137,13 @@ def test_plugin_lists_the_key():
 def test_sky_key_follows_the_scene(pkg, make_emu):
     scene = _open_scene(pkg)
     c = _ctx(pkg, make_emu, scene, sky_sampling=1)
-    assert _get(c, "sky") == "1"
+    assert c.get_setting("sky") == "1"
     c.set_setting("sky_pick", 0)
-    assert _get(c, "sky") == "0"
+    assert c.get_setting("sky") == "0"
     c.set_setting("sky_pick", -1)
-    assert _get(c, "sky") == "1"
+    assert c.get_setting("sky") == "1"
     c.set_setting("sky_sampling", 0)
-    assert _get(c, "sky") == "0"
+    assert c.get_setting("sky") == "0"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -175,7 +158,7 @@ def test_p_zero_is_bit_identical_to_the_default(pkg, make_emu, case):
     up = case != "no_sky"
     ref = _render(pkg, _ctx(pkg, make_emu, scene, spp=2, upload_sky=up, max_depth=3), scene, frames=2)
     c = _ctx(pkg, make_emu, scene, spp=2, upload_sky=up, max_depth=3, sky_sampling=1, **extra)
-    assert _get(c, "sky") == "0"
+    assert c.get_setting("sky") == "0"
     assert np.array_equal(_render(pkg, c, scene, frames=2), ref)
 
 
@@ -344,7 +327,7 @@ def test_closed_room_under_a_distant_lid_stays_black(pkg, make_emu):
     s.upload(c)
     for k, v_ in {"integrator": "pt", "spp": 16, "max_depth": 3, "sky_sampling": 1}.items():
         c.set_setting(k, v_)
-    assert _get(c, "sky") == "1"
+    assert c.get_setting("sky") == "1"
     img = _render(pkg, c, s)
     assert np.array_equal(img[..., :3], np.zeros_like(img[..., :3]))
 
