@@ -474,6 +474,47 @@ RFWHIP_API int rfwhip_read_primary_hits(rfwhip_context *ctx, float *t, int32_t *
 RFWHIP_API int rfwhip_trace_rays(rfwhip_context *ctx, size_t n, const float *org, const float *dir, float t_min,
 								 float t_max, float *t, int32_t *prim, int32_t *inst, float *u, float *v);
 
+/* Test entry: the caller's rays through ONE chosen form of the traversal — the product's own launchers (kernels.h), not copies.
+ * rfwhip_trace_rays reaches only the one-ray-per-lane closest-hit kernel; a render's incoherent waves run the other forms.
+ *
+ *   form                          launcher                                   rays read from                   result
+ *   RFWHIP_FORM_LANE_CLOSEST  0   launch_extend(GEN_RANGED), depth 1         org[1] / dir[1], w = (1e-5, 1e34)  hit records
+ *   RFWHIP_FORM_STREAM_CLOSEST 1  launch_extend(GEN_BUFFER), refill bit 0    org[1] / dir[1], org.w = tag       hit records
+ *   RFWHIP_FORM_LANE_ANY      2   launch_connect, refill bit 1 clear, depth 1  sh_org / sh_dir, sh_org.w = tag,   visibility
+ *   RFWHIP_FORM_STREAM_ANY    3   launch_connect, refill bit 1 set, depth 1      sh_dir.w = t_max
+ *   RFWHIP_FORM_FUSED         4   launch_trace_fused: the closest-hit set at depth 3 and the occlusion set at depth 2 in one
+ *                                 launch (either may be empty)                                                both
+ *   RFWHIP_FORM_PACKET_ANY    5   launch_shadow_packets, depth 0, FrameView::shadow_bins = bins, rad_nee present    visibility
+ *
+ * The closest-hit set: n rays (org / dir: n x 3 floats), interval (1e-5, 1e34) — the kernels' own.  tag: n words or NULL.  A tag
+ * is the word the queue entry carries in org.w: any value below 2^31, or 0xFFFFFFFF (RAY_VOID) for a void entry, whose record
+ * comes back with prim = -2 (HIT_VOID).  NULL: tag = ray index.  LANE_CLOSEST reads no tag and accepts no void entry.  Outputs
+ * t / u / v / prim / inst (n each, any may be NULL; prim = -1 and inst = -1 on a miss).
+ * The occlusion set: n_any rays, t_max_any per ray (interval (1e-5, t_max); t_max <= 1e-5 or negative: traced, hits nothing),
+ * tag_any: n_any words or NULL (= ray index).  A tag is the path slot the result is folded into, below n_any and UNIQUE within the
+ * call (connect_finish is a read-modify-write), or 0xFFFFFFFF for a void entry.  PACKET_ANY: tag = bin << (31 - bins) | slot with
+ * 1 <= bins <= 4 (the bin is every bit from 31 - bins to 30).  visible (n_any floats, indexed by SLOT): 1 = nothing inside the interval, 0 = occluded,
+ * RFWHIP_FORM_UNTOUCHED (-777) = a slot no entry of the queue named.  (LANE / STREAM / FUSED: sh_rad = (1, 0, 0) is added to a
+ * zeroed rad[slot] for a visible ray; PACKET: rad_nee[slot] starts at 1 and an occluded ray zeroes it.)
+ * grid_items is handed to the launcher as max_items: only the grid is derived from it, the queue lengths come from the counters,
+ * so a small ray count can reach every run length of the persistent-lane kernels (0: the ray count).
+ * Before the launch the hit records hold a sentinel (prim = RFWHIP_FORM_SENTINEL_PRIM, t = NaN): a record no kernel wrote is
+ * returned as such.  launch_counters (or NULL): 4 x uint64 of this launch, counted whatever count_traversal says — rays_extend,
+ * rays_shadow, sp_runs, stack_overflow.  A stack overflow is RFWHIP_ERR_STATE, as in rfwhip_trace_rays.
+ * In the host-emulation build the forms collapse to the per-item loops (kernels_emu.inc): LANE_* = STREAM_* = FUSED = PACKET. */
+#define RFWHIP_FORM_LANE_CLOSEST 0
+#define RFWHIP_FORM_STREAM_CLOSEST 1
+#define RFWHIP_FORM_LANE_ANY 2
+#define RFWHIP_FORM_STREAM_ANY 3
+#define RFWHIP_FORM_FUSED 4
+#define RFWHIP_FORM_PACKET_ANY 5
+#define RFWHIP_FORM_UNTOUCHED (-777.0f)
+#define RFWHIP_FORM_SENTINEL_PRIM 0x5E5E5E5E
+RFWHIP_API int rfwhip_trace_rays_form(rfwhip_context *ctx, int form, uint32_t grid_items, uint32_t bins, size_t n, const float *org,
+									  const float *dir, const uint32_t *tag, float *t, int32_t *prim, int32_t *inst, float *u, float *v,
+									  size_t n_any, const float *org_any, const float *dir_any, const float *t_max_any,
+									  const uint32_t *tag_any, float *visible, uint64_t *launch_counters);
+
 /* Known-answer hook: one of the path tracer's DEVICE functions (rt_core.h: BSDF, light sampling, packing, samplers — the
  * very functions the shade kernel calls) evaluated by a kernel on n records; functions and record layout: RFWHIP_KAT_* in
  * rfwhip_abi.h.  in: n x RFWHIP_KAT_IN floats, out: n x RFWHIP_KAT_OUT floats (host pointers).  The light functions use

@@ -81,6 +81,8 @@ class CoreBinding:
                                   "read_local_framebuffer_device": (i32, [vp, vp]),
                                   "deinterleave_device": (i32, [vp, vp, vp]),
                                   "kat": (i32, [vp, i32, sz, vp, vp]),
+                                  "trace_rays_form": (i32, [vp, i32, u32, u32, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp,
+                                                            vp, vp, vp]),
                                   "get_bvh4": (i32, [vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(abi.Bvh4Info)]),
                                   "read_denoise_guides": (i32, [vp, vp, vp]),
                                   "denoise_image": (i32, [vp, vp, vp]),
@@ -299,6 +301,50 @@ class CoreBinding:
         self._check(self._fn("trace_rays")(self._ctx, n, o.ctypes.data, d.ctypes.data, t_min, t_max, t.ctypes.data,
                                             prim.ctypes.data, inst.ctypes.data, u.ctypes.data, v.ctypes.data))
         return {"t": t, "prim": prim, "inst": inst, "u": u, "v": v}
+
+    FORMS = {"lane_closest": 0, "stream_closest": 1, "lane_any": 2, "stream_any": 3, "fused": 4, "packet_any": 5}
+    RAY_VOID = 0xFFFFFFFF        # tag of a void queue entry
+    HIT_VOID = -2                # prim of a void entry's hit record
+    FORM_UNTOUCHED = -777.0      # visibility of a slot no queue entry named
+    FORM_SENTINEL_PRIM = 0x5E5E5E5E  # prim of a hit record no kernel wrote
+
+    def trace_rays_form(self, form, org=None, dir=None, tag=None, org_any=None, dir_any=None, t_max_any=None, tag_any=None,
+                        bins=0, grid_items=0):
+        """The given rays through one form of the traversal, launched by the product's own launchers (include/rfwhip.h,
+        rfwhip_trace_rays_form).  form: a key of FORMS.  The closest-hit forms ("lane_closest", "stream_closest", "fused") take
+        org / dir (n x 3) and tag (n uint32 slot words below 2^31, RAY_VOID for a void entry; None: the ray index) and return
+        t / u / v / prim / inst; the occlusion forms ("lane_any", "stream_any", "fused", "packet_any") take org_any / dir_any /
+        t_max_any and tag_any (the slot, unique and below the ray count, RAY_VOID for void; "packet_any": bin << (31 - bins) |
+        slot) and return "visible", indexed by SLOT: 1 visible, 0 occluded, FORM_UNTOUCHED for a slot no entry named.
+        grid_items: what the launcher sizes its grid by (0: the ray count).  "counters": rays_extend, rays_shadow, sp_runs,
+        stack_overflow of this launch.  In the host-emulation build the forms collapse to the same per-item loops: the lane
+        and stream forms, "fused" and "packet_any" run identical code there."""
+        if form not in self.FORMS:
+            code = int(form)  # (an unknown number goes to the library, which refuses it)
+        else:
+            code = self.FORMS[form]
+        e_o = _f32(org if org is not None else np.zeros((0, 3))).reshape(-1, 3)
+        e_d = _f32(dir if dir is not None else np.zeros((0, 3))).reshape(-1, 3)
+        a_o = _f32(org_any if org_any is not None else np.zeros((0, 3))).reshape(-1, 3)
+        a_d = _f32(dir_any if dir_any is not None else np.zeros((0, 3))).reshape(-1, 3)
+        n, na = len(e_o), len(a_o)
+        if len(e_d) != n or len(a_d) != na:
+            raise ValueError("origins and directions differ in number")
+        a_t = _f32(np.full(na, 1e34) if t_max_any is None else t_max_any).reshape(-1)
+        e_tag = None if tag is None else np.ascontiguousarray(tag, np.uint32).reshape(-1)
+        a_tag = None if tag_any is None else np.ascontiguousarray(tag_any, np.uint32).reshape(-1)
+        if len(a_t) != na or (e_tag is not None and len(e_tag) != n) or (a_tag is not None and len(a_tag) != na):
+            raise ValueError("per-ray arrays differ in length")
+        t, u, v = (np.empty(n, np.float32) for _ in range(3))
+        prim, inst = np.empty(n, np.int32), np.empty(n, np.int32)
+        vis = np.empty(na, np.float32)
+        cnt = np.zeros(4, np.uint64)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        self._check(self._fn("trace_rays_form")(self._ctx, code, int(grid_items), int(bins), n, ptr(e_o), ptr(e_d), ptr(e_tag),
+                                                 ptr(t), ptr(prim), ptr(inst), ptr(u), ptr(v), na, ptr(a_o), ptr(a_d), ptr(a_t),
+                                                 ptr(a_tag), ptr(vis), ptr(cnt)))
+        return {"t": t, "prim": prim, "inst": inst, "u": u, "v": v, "visible": vis,
+                "counters": dict(zip(("rays_extend", "rays_shadow", "sp_runs", "stack_overflow"), (int(x) for x in cnt)))}
 
     def read_denoise_guides(self):
         """The denoiser's guides of the full image for the camera of the last render (include/rfwhip.h, "denoise"):

@@ -3454,63 +3454,228 @@ extern "C" int rfwhip_read_primary_hits(rfwhip_context *c, float *t, int32_t *pr
 	return RFWHIP_OK;
 }
 
+// The caller's rays through one form of the traversal (rfwhip.h: rfwhip_trace_rays_form): the product's launchers on the context's
+// own wave buffers, with the counters a render's shade stages would have left (queue lengths, "paths went on").
+struct FormRays
+{
+	size_t n = 0;
+	const float *org = nullptr, *dir = nullptr, *t_max = nullptr;
+	const uint32_t *tag = nullptr;
+};
+static int trace_form(rfwhip_context *c, const char *who, int form, uint32_t grid_items, uint32_t bins, const FormRays &e, float t_min, float t_max,
+					  float *t, int32_t *prim, int32_t *inst, float *u, float *v, const FormRays &a, float *visible, uint64_t *launch_counters)
+{
+	if (form < RFWHIP_FORM_LANE_CLOSEST || form > RFWHIP_FORM_PACKET_ANY)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: unknown form %d", who, form);
+	const bool closest = form == RFWHIP_FORM_LANE_CLOSEST || form == RFWHIP_FORM_STREAM_CLOSEST || form == RFWHIP_FORM_FUSED;
+	const bool any = form >= RFWHIP_FORM_LANE_ANY;
+	const size_t ne = closest ? e.n : 0, na = any ? a.n : 0;
+	if ((ne && (!e.org || !e.dir)) || (na && (!a.org || !a.dir || !a.t_max)))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: null rays", who);
+	if (c->scene_dirty)
+		return set_error(RFWHIP_ERR_STATE, "%s: scene changed since the last rfwhip_update()", who);
+	if (ne >= (1ull << 31) || na >= (1ull << 31))
+		return set_error(RFWHIP_ERR_UNSUPPORTED, "%s: too many rays", who);
+	const bool packet = form == RFWHIP_FORM_PACKET_ANY;
+	if (packet && (bins < 1u || bins > rt::SHADOW_BIN_BITS))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: %u bin bits (1..%u)", who, bins, rt::SHADOW_BIN_BITS);
+	if (form == RFWHIP_FORM_LANE_CLOSEST && e.tag)
+		for (size_t i = 0; i < ne; i++)
+			if (e.tag[i] == rt::RAY_VOID)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: the one-ray-per-lane closest-hit form has no void entries (ray %zu)", who, i);
+	for (size_t i = 0; i < ne && e.tag; i++)
+		if (e.tag[i] != rt::RAY_VOID && e.tag[i] >= (1u << 31))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: tag %zu is no slot word (below 2^31) and not void", who, i);
+	// occlusion set: the slot of every entry, unique and inside the visibility buffer
+	const uint32_t slot_bits = packet ? rt::shadow_slot_bits(bins) : 32u;
+	std::vector<uint32_t> slot_of(na, rt::RAY_VOID);
+	{
+		std::vector<uint8_t> taken(na, 0);
+		for (size_t i = 0; i < na; i++)
+		{
+			const uint32_t w = a.tag ? a.tag[i] : (uint32_t)i;
+			if (w == rt::RAY_VOID)
+				continue;
+			if (w >> 31)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: tag %zu of the occlusion set is no slot word (below 2^31: the bin ends at bit 30) and not void", who, i);
+			const uint32_t sl = packet ? w & ((1u << slot_bits) - 1u) : w;
+			if (sl >= na)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: slot %u of ray %zu outside the %zu slots of the call", who, sl, i, na);
+			if (taken[sl])
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: duplicate slot %u (ray %zu): the result is folded into its slot by a read-modify-write", who, sl, i);
+			taken[sl] = 1, slot_of[i] = sl;
+		}
+	}
+	if (ne + na == 0)
+		return RFWHIP_OK;
+	RF_TRY(sync_all(c)); // the wave buffers are shared with the sub-batch streams of a render in flight
+	const size_t cap = std::max(ne, na);
+	RF_TRY(ensure_wave_buffers(c, std::max(cap, c->wave_capacity), std::max(na, c->rad_capacity[0]), c->rad_capacity[1]));
+	void *s = c->stream;
+	if (packet)
+	{
+		RF_TRY(ensure_nodes4f(c));
+		if (!(c->packet_ok && c->nodes4f_current && (c->refill & 8)))
+			return set_error(RFWHIP_ERR_UNSUPPORTED, "%s: the packet traversal cannot run on this scene (its trees exceed the packet stack, or refill bit 3 is off)", who);
+	}
+	rtk::Params p;
+	fill_params(c, nullptr, p);
+	std::vector<f4> o4(cap), d4(cap);
+	const auto word = [](uint32_t wd) {
+		float f;
+		memcpy(&f, &wd, 4);
+		return f;
+	};
+	if (ne)
+	{
+		const bool ranged = form == RFWHIP_FORM_LANE_CLOSEST;
+		for (size_t i = 0; i < ne; i++)
+		{
+			o4[i] = f4{e.org[3 * i], e.org[3 * i + 1], e.org[3 * i + 2], ranged ? t_min : word(e.tag ? e.tag[i] : (uint32_t)i)};
+			d4[i] = f4{e.dir[3 * i], e.dir[3 * i + 1], e.dir[3 * i + 2], ranged ? t_max : 0.0f};
+		}
+		// the closest-hit waves of odd depth read the odd buffers: org/dir carry (origin, t_min | tag) and (direction, t_max | -)
+		RF_TRY(dm::h2d(c->d_org[1].p, o4.data(), ne * sizeof(f4), s));
+		RF_TRY(dm::h2d(c->d_dir2[1].p, d4.data(), ne * sizeof(f4), s));
+		// a record no kernel writes stays recognisable
+		std::vector<f4> h(ne, f4{NAN, NAN, NAN, word((uint32_t)RFWHIP_FORM_SENTINEL_PRIM)});
+		std::vector<int> hi(ne, (int)RFWHIP_FORM_SENTINEL_PRIM);
+		RF_TRY(dm::h2d(c->d_hit.p, h.data(), ne * sizeof(f4), s));
+		RF_TRY(dm::h2d(c->d_hit_inst.p, hi.data(), ne * 4, s));
+	}
+	f4 *const vis_buf = packet ? c->d_rad_nee[0].as<f4>() : c->d_rad[0].as<f4>();
+	if (na)
+	{
+		for (size_t i = 0; i < na; i++)
+		{
+			o4[i] = f4{a.org[3 * i], a.org[3 * i + 1], a.org[3 * i + 2], word(a.tag ? a.tag[i] : (uint32_t)i)};
+			d4[i] = f4{a.dir[3 * i], a.dir[3 * i + 1], a.dir[3 * i + 2], a.t_max[i]};
+		}
+		RF_TRY(dm::h2d(c->d_sh_org[0].p, o4.data(), na * sizeof(f4), s));
+		RF_TRY(dm::h2d(c->d_sh_dir[0].p, d4.data(), na * sizeof(f4), s));
+		std::vector<f4> one(na, f4{1.0f, 0.0f, 0.0f, 0.0f});
+		RF_TRY(dm::h2d(c->d_sh_rad[0].p, one.data(), na * sizeof(f4), s));
+		// the slots the queue names start at 0 (1 for the packet form, whose occluded rays zero theirs); every other slot holds the
+		// sentinel
+		std::vector<f4> vis(na, f4{RFWHIP_FORM_UNTOUCHED, 0.0f, 0.0f, 0.0f});
+		for (size_t i = 0; i < na; i++)
+			if (slot_of[i] != rt::RAY_VOID)
+				vis[slot_of[i]].x = packet ? 1.0f : 0.0f;
+		RF_TRY(dm::h2d(vis_buf, vis.data(), na * sizeof(f4), s));
+	}
+	// the counters as the shade stages of a render would have left them: queue lengths, and "paths went on" (connection_count)
+	const uint32_t de = form == RFWHIP_FORM_FUSED ? 3u : 1u, da = packet ? 0u : (form == RFWHIP_FORM_FUSED ? 2u : 1u);
+	rtk::launch_init_counters(p.wv.counters, 0, s);
+	RF_TRY(dm::last_launch_error());
+	rt::WaveCounters w0;
+	RF_TRY(dm::d2h(&w0, c->d_counters.p, sizeof(w0), s));
+	if (ne)
+		w0.ext[de] = w0.ext_n[de] = (uint32_t)ne;
+	if (na)
+	{
+		w0.shadow[da] = w0.shadow_n[da] = (uint32_t)na;
+		if (!w0.ext[da + 1])
+			w0.ext[da + 1] = 1u;
+	}
+	RF_TRY(dm::h2d(c->d_counters.p, &w0, sizeof(w0), s));
+	const bool count = launch_counters != nullptr || c->count_traversal != 0;
+	const uint32_t items = grid_items ? grid_items : (uint32_t)cap;
+	p.group = 16;
+	p.wv.sh_org = c->d_sh_org[0].as<f4>(), p.wv.sh_dir = c->d_sh_dir[0].as<f4>(), p.wv.sh_rad = c->d_sh_rad[0].as<f4>();
+	p.wv.rad = c->d_rad[0].as<f4>(), p.wv.rad_nee = nullptr;
+	switch (form)
+	{
+	case RFWHIP_FORM_LANE_CLOSEST:
+		p.depth = 1, p.queue = 0;
+		rtk::launch_extend(p, rtk::GEN_RANGED, count, items, s);
+		break;
+	case RFWHIP_FORM_STREAM_CLOSEST:
+		p.depth = 1, p.queue = 0, p.refill |= 1u;
+		rtk::launch_extend(p, rtk::GEN_BUFFER, count, items, s);
+		break;
+	case RFWHIP_FORM_LANE_ANY:
+		p.depth = 1, p.queue = 0, p.refill &= ~2u;
+		rtk::launch_connect(p, count, items, s);
+		break;
+	case RFWHIP_FORM_STREAM_ANY:
+		p.depth = 1, p.queue = 0, p.refill |= 2u;
+		rtk::launch_connect(p, count, items, s);
+		break;
+	case RFWHIP_FORM_FUSED:
+	{
+		p.refill |= 3u;
+		rtk::Params pa = p;
+		p.depth = 3, p.queue = 0;
+		pa.depth = 2, pa.queue = 1;
+		rtk::launch_trace_fused(p, pa, count, items, s);
+		break;
+	}
+	default:
+		p.depth = 0, p.queue = 0, p.fr.shadow_bins = bins, p.wv.rad_nee = c->d_rad_nee[0].as<f4>();
+		rtk::launch_shadow_packets(p, count, items, s);
+		break;
+	}
+	RF_TRY(dm::last_launch_error());
+	rt::WaveCounters wc;
+	RF_TRY(dm::d2h(&wc, c->d_counters.p, sizeof(wc), s));
+	if (launch_counters)
+	{
+		launch_counters[0] = wc.rays_extend - w0.rays_extend, launch_counters[1] = wc.rays_shadow - w0.rays_shadow;
+		launch_counters[2] = wc.sp_runs - w0.sp_runs, launch_counters[3] = wc.stack_overflow;
+	}
+	if (ne)
+	{
+		std::vector<f4> h(ne);
+		std::vector<int> hi(ne);
+		RF_TRY(dm::d2h(h.data(), c->d_hit.p, ne * sizeof(f4), s));
+		RF_TRY(dm::d2h(hi.data(), c->d_hit_inst.p, ne * 4, s));
+		for (size_t i = 0; i < ne; i++)
+		{
+			int pr;
+			memcpy(&pr, &h[i].w, 4);
+			if (t)
+				t[i] = h[i].x;
+			if (u)
+				u[i] = h[i].y;
+			if (v)
+				v[i] = h[i].z;
+			if (prim)
+				prim[i] = pr;
+			if (inst)
+				inst[i] = pr >= 0 ? hi[i] : -1;
+		}
+	}
+	if (na && visible)
+	{
+		std::vector<f4> vis(na);
+		RF_TRY(dm::d2h(vis.data(), vis_buf, na * sizeof(f4), s));
+		for (size_t i = 0; i < na; i++)
+			visible[i] = vis[i].x;
+	}
+	if (wc.stack_overflow)
+		return set_error(RFWHIP_ERR_STATE, "traversal stack overflow: %u entries dropped", wc.stack_overflow);
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_trace_rays(rfwhip_context *c, size_t n, const float *org, const float *dir, float t_min, float t_max,
 								 float *t, int32_t *prim, int32_t *inst, float *u, float *v)
 {
 	CTX_ENTER(c);
-	if (n && (!org || !dir))
-		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_trace_rays: null rays");
-	if (c->scene_dirty)
-		return set_error(RFWHIP_ERR_STATE, "rfwhip_trace_rays: scene changed since the last rfwhip_update()");
-	if (n == 0)
-		return RFWHIP_OK;
-	if (n >= (1ull << 31))
-		return set_error(RFWHIP_ERR_UNSUPPORTED, "rfwhip_trace_rays: too many rays");
-	RF_TRY(sync_all(c)); // the wave buffers are shared with the sub-batch streams of a render in flight
-	RF_TRY(ensure_wave_buffers(c, std::max(n, c->wave_capacity), c->rad_capacity[0], c->rad_capacity[1]));
-	std::vector<f4> o4(n), d4(n);
-	for (size_t i = 0; i < n; i++)
-	{
-		o4[i] = f4{org[3 * i], org[3 * i + 1], org[3 * i + 2], t_min};
-		d4[i] = f4{dir[3 * i], dir[3 * i + 1], dir[3 * i + 2], t_max};
-	}
-	void *s = c->stream;
-	// the generic-ray wave uses the odd buffers at depth 1: org/dir carry (origin, t_min) and (direction, t_max)
-	RF_TRY(dm::h2d(c->d_org[1].p, o4.data(), n * sizeof(f4), s));
-	RF_TRY(dm::h2d(c->d_dir2[1].p, d4.data(), n * sizeof(f4), s));
-	rtk::Params p;
-	fill_params(c, nullptr, p);
-	rtk::launch_init_counters(p.wv.counters, 0, s);
-	rtk::launch_set_ext_count(p.wv.counters, 1, (uint32_t)n, s);
-	p.depth = 1, p.queue = 0, p.group = 16;
-	rtk::launch_extend(p, rtk::GEN_RANGED, c->count_traversal != 0, (uint32_t)n, s);
-	RF_TRY(dm::last_launch_error());
-	std::vector<f4> h(n);
-	std::vector<int> hi(n);
-	RF_TRY(dm::d2h(h.data(), c->d_hit.p, n * sizeof(f4), s));
-	RF_TRY(dm::d2h(hi.data(), c->d_hit_inst.p, n * 4, s));
-	{
-		rt::WaveCounters wc;
-		RF_TRY(dm::d2h(&wc, c->d_counters.p, sizeof(wc), s));
-		if (wc.stack_overflow)
-			return set_error(RFWHIP_ERR_STATE, "traversal stack overflow: %u entries dropped", wc.stack_overflow);
-	}
-	for (size_t i = 0; i < n; i++)
-	{
-		int pr;
-		memcpy(&pr, &h[i].w, 4);
-		if (t)
-			t[i] = h[i].x;
-		if (u)
-			u[i] = h[i].y;
-		if (v)
-			v[i] = h[i].z;
-		if (prim)
-			prim[i] = pr;
-		if (inst)
-			inst[i] = pr >= 0 ? hi[i] : -1;
-	}
-	return RFWHIP_OK;
+	FormRays e;
+	e.n = n, e.org = org, e.dir = dir;
+	return trace_form(c, "rfwhip_trace_rays", RFWHIP_FORM_LANE_CLOSEST, 0u, 0u, e, t_min, t_max, t, prim, inst, u, v, FormRays(), nullptr, nullptr);
+}
+
+extern "C" int rfwhip_trace_rays_form(rfwhip_context *c, int form, uint32_t grid_items, uint32_t bins, size_t n, const float *org, const float *dir,
+									  const uint32_t *tag, float *t, int32_t *prim, int32_t *inst, float *u, float *v, size_t n_any,
+									  const float *org_any, const float *dir_any, const float *t_max_any, const uint32_t *tag_any,
+									  float *visible, uint64_t *launch_counters)
+{
+	CTX_ENTER(c);
+	FormRays e, a;
+	e.n = n, e.org = org, e.dir = dir, e.tag = tag;
+	a.n = n_any, a.org = org_any, a.dir = dir_any, a.t_max = t_max_any, a.tag = tag_any;
+	return trace_form(c, "rfwhip_trace_rays_form", form, grid_items, bins, e, 1e-5f, 1e34f, t, prim, inst, u, v, a, visible, launch_counters);
 }
 
 static_assert(RFWHIP_KAT_IN == 24 && RFWHIP_KAT_OUT == 8, "kat_item's record layout (kernels.hip)");
