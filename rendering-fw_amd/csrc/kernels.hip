@@ -67,13 +67,6 @@ constexpr int KAT_IN = 24, KAT_OUT = 8; // = RFWHIP_KAT_IN / RFWHIP_KAT_OUT (sta
 #ifndef RT_SHADE_WAVES
 #define RT_SHADE_WAVES 4 // the textured shade kernel: 128 registers
 #endif
-// the shade kernel's waves queue their misses as well as their hits (1), or shade every chunk's misses in place (0).
-// (Two queued misses per lane through a routine of their own — the loads of both in flight together, a miss being four dependent
-// round trips and a few dozen instructions — was built, is bit-identical, and loses: shade alone 8.57 -> 9.05 ms per sub-batch,
-// 4610 -> 4505 Msamples/s; the second code path costs the hit path registers.)
-#ifndef RT_MISS_QUEUE
-#define RT_MISS_QUEUE 1
-#endif
 // (Round 5: the scan's primitive ids asked for one chunk ahead with global_load_lds_dword — straight into the wave's LDS, no register
 // in flight — so that a scan is not a memory round trip with nothing beside it (13 % of a wave's time by the clock): bit-identical,
 // and slower, 8.22 -> 8.63 ms per sub-batch — the plain kernel went from 10 to 18 spilled registers.  Like every change to this
@@ -172,28 +165,19 @@ struct Ctx
 // ================================================================================================================
 // The end of primary ray `idx` of the pt integrator where the wave is converged when its rays end: the packet kernel (device:
 // k_primary_packet, emulation: packet_emu::primary) and the one-ray-per-lane kernel of small launches (extend_item<GEN_PT>).
-// A hit goes to the shade stage: direction record + hit record.  A MISS is finished here (RT_PRIMARY_MISS): the wave is converged,
-// all 64 samples of a sky pixel miss together, and what the shade stage would do for it — the sky along the ray into the slot
-// (pt_shade, h.prim < 0 at depth 0: throughput 1, pdf 1; shade_pt_item: alpha -1 = the path ends, no connection record) — needs
-// nothing the kernel does not hold.  The shade kernel then neither queues the path nor reads its direction (27 % of the bench
-// scene's primaries), and no direction record is written for it; its hit record says HIT_MISS_SHADED (read back as a miss).
-#ifndef RT_PRIMARY_INITS_RAD
-#define RT_PRIMARY_INITS_RAD 1
-#endif
-#ifndef RT_PRIMARY_MISS
-#define RT_PRIMARY_MISS 1
-#endif
-// Round 6: the primary wave writes NO ray record at all (0) — the shade kernel regenerates a primary ray from its pixel and sample
-// (pt_primary_ray has a fixed arithmetic shape: the same bits in every kernel) instead of reading 16 bytes the primary kernel wrote
-// for it: ~60 instructions in a kernel whose VALUs are busy 0.45 of the time against 32 bytes of HBM traffic per primary hit in the
-// kernel that is bound by it.  1: direction record per hit (+ origin record behind a lens), rounds 1-5.
-#ifndef RT_PRIMARY_RAY_RECORD
-#define RT_PRIMARY_RAY_RECORD 0
-#endif
+// A hit goes to the shade stage as its hit record alone.  A MISS is finished here: the wave is converged, all 64 samples of a sky
+// pixel miss together, and what the shade stage would do for it — the sky along the ray into the slot (pt_shade, h.prim < 0 at
+// depth 0: throughput 1, pdf 1; shade_pt_item: alpha -1 = the path ends, no connection record) — needs nothing the kernel does
+// not hold.  The shade kernel then does not queue the path (27 % of the bench scene's primaries); its hit record says
+// HIT_MISS_SHADED (read back as a miss).
+// The primary wave writes NO ray record — the shade kernel regenerates a primary ray from its pixel and sample (pt_primary_ray has
+// a fixed arithmetic shape: the same bits in every kernel) instead of reading 16 bytes the primary kernel wrote for it: ~60
+// instructions in a kernel whose VALUs are busy 0.45 of the time against 32 bytes of HBM traffic per primary hit in the kernel
+// that is bound by it.
 RT_FN void primary_finish_item(const Params &q, uint32_t idx, f3 D, const Hit &h)
 {
 	int prim = h.prim;
-	if (RT_PRIMARY_MISS && prim < 0)
+	if (prim < 0)
 	{
 		f3 radiance = mk3(0, 0, 0);
 		const f3 contribution = (mk3(1, 1, 1) * m_rcp(1.0f)) * pt_sky(q.sc, D);
@@ -202,14 +186,12 @@ RT_FN void primary_finish_item(const Params &q, uint32_t idx, f3 D, const Hit &h
 		q.wv.rad[idx] = mk4(radiance.x, radiance.y, radiance.z, q.wv.rad_nee ? -1.0f : 1.0f);
 		prim = HIT_MISS_SHADED;
 	}
-	else if (RT_PRIMARY_RAY_RECORD)
-		q.wv.dir[0][idx] = mk4(D.x, D.y, D.z, 0.0f);
 	q.wv.hit0[idx] = mk4(h.t, h.u, h.v, ubits((uint32_t)prim));
 	q.wv.hit0_inst[idx] = h.inst;
 	// a hit's slot starts as what most hits leave there — no radiance, a path that goes on — from here, where the stores of a
 	// wave are neighbours and the memory pipes idle; the shade kernel writes the slot of a path that adds light or ends only
 	// (after the hit record's stores: its registers are free then — in front of them the packet kernel spilled four)
-	if (RT_PRIMARY_INITS_RAD && prim >= 0)
+	if (prim >= 0)
 	{
 		float zero = 0.0f, one = 1.0f;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -282,14 +264,10 @@ RT_FN void extend_item(const Params &p, uint32_t i, bool active, Ctx &ctx)
 				parity_primary_ray(p.cam, p.fr, pr.x, pr.y, r0, r1, r2, r3, O, D);
 			}
 		}
-		if (active)
+		if (active && GEN != GEN_PT) // (pt: entry i of the primary wave is path slot i and the shade kernel regenerates its ray — no ray record)
 		{
-			// (pt, pinhole camera: every primary ray starts at the camera position and entry i of the primary wave is path slot
-			// i — the shade kernel needs no origin record: 16 bytes less written here and read there per primary ray)
-			if (GEN != GEN_PT || (RT_PRIMARY_RAY_RECORD && p.cam.aperture != 0.0f))
-				p.wv.org[0][i] = mk4(O.x, O.y, O.z, ubits((i << 1) | 1u));
-			if (GEN != GEN_PT) // (pt: written with the hit record, or not at all for a miss — primary_finish_item)
-				p.wv.dir[0][i] = mk4(D.x, D.y, D.z, 0.0f);
+			p.wv.org[0][i] = mk4(O.x, O.y, O.z, ubits((i << 1) | 1u));
+			p.wv.dir[0][i] = mk4(D.x, D.y, D.z, 0.0f);
 		}
 	}
 	Hit h;
@@ -410,7 +388,7 @@ template <bool TEX, bool SKY> RT_FN void shade_pt_item(const Params &p, const Sk
 	in.slot = 0, in.flags = 0, in.packedN = 0, in.depth = p.depth;
 	Hit h;
 	h.t = h4.x, h.u = h4.y, h.v = h4.z, h.prim = (int)fbits(h4.w), h.inst = hi;
-	if (active && p.depth == 0 && !RT_PRIMARY_RAY_RECORD)
+	if (active && p.depth == 0)
 	{
 		// (the primary wave: entry i IS path slot i, and its ray is a function of pixel and sample — regenerated, not read)
 		const PixelRef pr = slot_to_pixel(p.fr, i);
@@ -419,7 +397,8 @@ template <bool TEX, bool SKY> RT_FN void shade_pt_item(const Params &p, const Sk
 	}
 	else if (active)
 	{
-		// (depth 0 behind a pinhole camera: no origin record was written — the origin is the camera, the slot is the entry)
+		// VESTIGE: depth 0 is taken above, so the first arm is unreachable; it stays because dropping it changes the code objects
+		// of all four shade kernels (register assignment) — a performance change with its own measurement (DESIGN_LOG.md, round 7)
 		const f4 o4 = (p.depth == 0 && p.cam.aperture == 0.0f) ? mk4(p.cam.pos.x, p.cam.pos.y, p.cam.pos.z, ubits((i << 1) | 1u)) : p.wv.org[b][i];
 		const f4 d4 = p.wv.dir[b][i];
 		in.O = xyz(o4), in.D = xyz(d4);
@@ -444,7 +423,7 @@ template <bool TEX, bool SKY> RT_FN void shade_pt_item(const Params &p, const Sk
 			// 16 bytes less written here and 16 less read there for every such path (two in five on the terrain).
 			const bool ends = p.wv.rad_nee && !out.emit_shadow && !out.emit_ext;
 			// (a hit without light of its own that goes on: primary_finish_item has written exactly that)
-			if (!RT_PRIMARY_INITS_RAD || h.prim < 0 || ends || out.radiance.x != 0.0f || out.radiance.y != 0.0f || out.radiance.z != 0.0f)
+			if (h.prim < 0 || ends || out.radiance.x != 0.0f || out.radiance.y != 0.0f || out.radiance.z != 0.0f)
 				p.wv.rad[slot] = mk4(out.radiance.x, out.radiance.y, out.radiance.z, ends ? -1.0f : 1.0f);
 			// (a path with a shadow ray: ShadeSink::shadow has stored its connection term)  Paths that emit no shadow ray but go on
 			// start theirs at zero.
@@ -943,6 +922,14 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 #include "denoise.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }
 
+// Which launches of the pt primary wave take the packet form (the device's launchers and the emulation's driver): a single-sample
+// launch (sample groups of 1: a wave is an 8x8 tile of different pixels) only when it is large; small ones keep the
+// one-ray-per-lane kernel with its tile-row-to-XCD dealing (launch_extend)
+#ifndef RT_PRIMARY_PACKET_MIN
+#define RT_PRIMARY_PACKET_MIN (16u << 20)
+#endif
+#define RT_PRIMARY_PACKET_RULE(P, N) (((P).refill & 8u) && ((P).fr.sgroup_log2 >= 1u || (N) >= RT_PRIMARY_PACKET_MIN))
+
 // ================================================================================================================
 #if defined(RT_DEVICE_BUILD)
 // ================================================================================================================
@@ -1074,14 +1061,9 @@ __global__ void __launch_bounds__(BLOCK, RT_PRIMARY_WAVES) k_extend(const Params
 
 // the node phase of a wave ends early once this many of its lanes hold a leaf (64: only when none is on an inner node)
 #ifndef RT_LEAF_VOTE_EXT
-#define RT_LEAF_VOTE_EXT 40 // (of 64: the share of the wave's lanes WITH a ray that must hold a leaf, rt_core.h RT_VOTE_RELATIVE)
+#define RT_LEAF_VOTE_EXT 40 // (of 64: the share of the wave's lanes WITH a ray that must hold a leaf, Traverser::descend)
 #endif
-// a single-sample primary launch (sample groups of 1: a wave is an 8x8 tile of different pixels) takes the packet form only when
-// it is large; small ones keep the one-ray-per-lane kernel with its tile-row-to-XCD dealing (launch_extend)
-#ifndef RT_PRIMARY_PACKET_MIN
-#define RT_PRIMARY_PACKET_MIN (16u << 20)
-#endif
-// rays a wave takes from the launch's queue per atomic (0: one atomic per refill, exactly the idle lanes).  Round 5, per kernel
+// rays a wave takes from the launch's queue per atomic (a run; refills in between are wave-local).  Round 5, per kernel
 // (MI355X, serialised ms per 64-spp sub-batch at 128 / 256 / 512 / 1024): extension rays of depth 1 6.09 / 5.96 / 6.02 / 6.27, of
 // depth 2 1.72 / 1.72 / 1.75 / 1.76, shadow rays 9.24 / 7.49 / 7.72 / 7.88 — short runs spread a queue's neighbourhoods over more
 // waves while their nodes are still in the L2s, too short ones pay in atomics.  The packet kernel's runs are its own
@@ -1092,15 +1074,10 @@ __global__ void __launch_bounds__(BLOCK, RT_PRIMARY_WAVES) k_extend(const Params
 #ifndef RT_STREAM_CHUNK_ANY
 #define RT_STREAM_CHUNK_ANY RT_STREAM_CHUNK
 #endif
+static_assert(RT_STREAM_CHUNK >= 64 && RT_STREAM_CHUNK_ANY >= 64, "a run is at least one wave of rays");
 #ifndef RT_LEAF_VOTE_ANY
 #define RT_LEAF_VOTE_ANY 40
 #endif
-#ifndef RT_REFILL_PIN
-#define RT_REFILL_PIN 1
-#endif
-
-
-
 
 // MODE: where a lane's next ray comes from — the extension-ray buffers of this depth or the shadow-ray buffers.  (The pt
 // integrator's primary wave had a persistent-lane form of its own, k_primary_stream, until the packet form of round 4 replaced
@@ -1145,13 +1122,11 @@ template <int MODE, bool COUNT> __device__ __forceinline__ void stream_rays(cons
 	const uint32_t lane = __lane_id();
 	bool has_ray = false, exhausted = false;
 	uint32_t ray = 0, slot = 0;
-#if RT_STREAM_CHUNK
 	uint32_t q_next = 0, q_end = 0; // wave-uniform: the rest of the run this wave owns
 	// run length: RT_STREAM_CHUNK for big launches, down to 64 when the launch has fewer than ~4 runs per wave
 	uint32_t run = count / (gridDim.x * (blockDim.x / 64u) * 4u);
 	constexpr uint32_t RUN_MAX = MODE == STREAM_ANY ? (uint32_t)RT_STREAM_CHUNK_ANY : (uint32_t)RT_STREAM_CHUNK;
 	run = run > RUN_MAX ? RUN_MAX : (run < 64u ? 64u : run);
-#endif
 	uint32_t REFILL = MODE == STREAM_ANY ? RT_REFILL_IDLE_ANY : RT_REFILL_IDLE_EXT;
 	// Waves of near-identical rays — the slot layout's sample groups put >= 8 samples of a pixel side by side (rt_core.h), so a
 	// wave of the shadow rays the first vertices emit walks the same nodes in step — are refilled only as a whole: a partial
@@ -1169,7 +1144,6 @@ template <int MODE, bool COUNT> __device__ __forceinline__ void stream_rays(cons
 		const uint32_t nidle = (uint32_t)__popcll(idle_mask);
 		if (!exhausted && nidle >= REFILL)
 		{
-#if RT_STREAM_CHUNK
 			// the wave owns a run of consecutive rays at a time: one queue atomic per run, refills in between are wave-local
 			if (q_next == q_end)
 			{
@@ -1184,30 +1158,18 @@ template <int MODE, bool COUNT> __device__ __forceinline__ void stream_rays(cons
 			const uint32_t take = nidle < q_end - q_next ? nidle : q_end - q_next;
 			q_next += take;
 			const uint32_t limit = base + take;
-#else
-			const uint32_t leader = (uint32_t)__ffsll((long long)idle_mask) - 1u;
-			uint32_t base = 0;
-			if (lane == leader)
-				base = atomicAdd(head, nidle);
-			base = __shfl(base, (int)leader);
-			const uint32_t limit = count;
-#endif
 			if (!has_ray)
 			{
 				const uint32_t idx = base + wave_prefix(idle_mask);
 				if (idx < limit)
 				{
 					{
-#if RT_REFILL_PIN
 						// both records of the ray in ONE round trip: left alone, the compiler fetches the slot word first, tests it
 						// for RAY_VOID and only then asks for the rest — two dependent waits per refill for the whole wave
 						typedef float v4f_ __attribute__((ext_vector_type(4)));
 						v4f_ oa = *(const v4f_ *)(ray_o + idx), da = *(const v4f_ *)(ray_d + idx);
 						asm volatile("" : "+v"(oa), "+v"(da));
 						const f4 o4 = mk4(oa.x, oa.y, oa.z, oa.w), d4 = mk4(da.x, da.y, da.z, da.w);
-#else
-						const f4 o4 = ray_o[idx], d4 = ray_d[idx];
-#endif
 						// void entries (the unfilled rest of a shade wave's last queue block) are skipped
 						if (fbits(o4.w) == RAY_VOID)
 						{
@@ -1223,11 +1185,7 @@ template <int MODE, bool COUNT> __device__ __forceinline__ void stream_rays(cons
 					}
 				}
 			}
-#if RT_STREAM_CHUNK
 			exhausted = q_next >= count;
-#else
-			exhausted = base + nidle >= count;
-#endif
 		}
 		if (__ballot(has_ray) == 0ull)
 		{
@@ -1477,7 +1435,7 @@ struct PacketSpace
 	const char *row_n[3]; // wave-uniform: the node table offset to the near / far plane row of a Node4f per axis — a row is
 	const char *row_f[3]; // fetched as s_load_dwordx4 dst, row, node_byte_offset with no address arithmetic
 	uint32_t mixed;		  // 1: the lanes disagree about a direction sign on some axis (an integer in an SGPR: a wave-uniform bool lives in a lane mask)
-	// t_hit: the lane's hit distance — 1/d and -o/d are NORMALISED by k = norm_k(t_hit) (rt_core.h, RT_NORM_T: the interval a box
+	// t_hit: the lane's hit distance — 1/d and -o/d are NORMALISED by k = norm_k(t_hit) (rt_core.h: the interval a box
 	// must meet becomes [0, 1], which the clamp modifier of v_max3 / v_min3 folds into the slab test)
 	// off: this lane holds no ray and the caller does not mask its ballots — 1/d = -o/d = 0: every slab distance is 0, entry == exit,
 	// and no box is entered (0 < 0)
@@ -1485,9 +1443,7 @@ struct PacketSpace
 	{
 		o = o_, d = d_;
 		id = mk3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
-#if RT_NORM_T
 		id = id * norm_k(t_hit);
-#endif
 		noid = mk3(-(o.x * id.x), -(o.y * id.y), -(o.z * id.z));
 		const unsigned long long mx = __ballot(id.x < 0.0f) & act, my = __ballot(id.y < 0.0f) & act, mz = __ballot(id.z < 0.0f) & act;
 		if (off)
@@ -1542,9 +1498,9 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 			float tk[4];
 			pk_v4u ent;
 			unsigned long long m[4];
-			// per child: tmin = max3 of the near-plane distances, clamped at 0; tmax = min3 of the far-plane distances, capped by the
-			// lane's hit distance; the lane enters the child when tmin < tmax.  (Traverser::node_step accepts tmax > tmin && tmin <
-			// hit.t && tmax >= 0; a box whose far side passes through the origin exactly, tmax == 0, holds nothing beyond t_min.)
+			// per child, in normalised distances (norm_k): tmin = max3 of the near-plane distances, tmax = min3 of the far-plane
+			// distances, both clamped to [0, 1] = [the origin, the lane's hit distance]; the lane enters the child when tmin < tmax —
+			// Traverser::node_step's test.
 			if (!sp.mixed)
 			{
 				PacketRows r;
@@ -1553,16 +1509,9 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 #pragma unroll
 				for (int k = 0; k < 4; k++)
 				{
-#if RT_NORM_T
 					tk[k] = max3_clamp01(fmaf(r.nx[k], sp.id.x, sp.noid.x), fmaf(r.ny[k], sp.id.y, sp.noid.y), fmaf(r.nz[k], sp.id.z, sp.noid.z));
 					const float tmax = min3_clamp01(fmaf(r.fx[k], sp.id.x, sp.noid.x), fmaf(r.fy[k], sp.id.y, sp.noid.y), fmaf(r.fz[k], sp.id.z, sp.noid.z));
 					m[k] = __ballot(tk[k] < tmax);
-#else
-					const float tmin = fmaxf(fmaxf(fmaf(r.nx[k], sp.id.x, sp.noid.x), fmaf(r.ny[k], sp.id.y, sp.noid.y)), fmaf(r.nz[k], sp.id.z, sp.noid.z));
-					const float tmax = fminf(fminf(fmaf(r.fx[k], sp.id.x, sp.noid.x), fmaf(r.fy[k], sp.id.y, sp.noid.y)), fmaf(r.fz[k], sp.id.z, sp.noid.z));
-					tk[k] = fmaxf(tmin, 0.0f);
-					m[k] = __ballot(tk[k] < fminf(tmax, hit.t));
-#endif
 				}
 			}
 			else
@@ -1577,16 +1526,9 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 					const float ay = fmaf(ly[k], sp.id.y, sp.noid.y), by = fmaf(hy[k], sp.id.y, sp.noid.y);
 					const float az = fmaf(lz[k], sp.id.z, sp.noid.z), bz = fmaf(hz[k], sp.id.z, sp.noid.z);
 					// (min / max per plane pair turn the inverted box of an unused slot into a huge one: asked for by its entry)
-#if RT_NORM_T
 					tk[k] = max3_clamp01(fminf(ax, bx), fminf(ay, by), fminf(az, bz));
 					const float tmax = min3_clamp01(fmaxf(ax, bx), fmaxf(ay, by), fmaxf(az, bz));
 					m[k] = ent[k] != ENTRY_EMPTY ? __ballot(tk[k] < tmax) : 0ull;
-#else
-					const float tmin = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-					const float tmax = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-					tk[k] = fmaxf(tmin, 0.0f);
-					m[k] = ent[k] != ENTRY_EMPTY ? __ballot(tk[k] < fminf(tmax, hit.t)) : 0ull;
-#endif
 				}
 			}
 			if (COUNT)
@@ -1665,9 +1607,7 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 		{
 			const uint32_t first = cur & ENTRY_FIRST_MASK, count = ((cur >> 27) & 7u) + 1u;
 			const char *const tb = (const char *)sc.tri_verts + (size_t)first * 48u;
-#if RT_NORM_T
 			const float t_before = hit.t;
-#endif
 			for (uint32_t i = 0; i < count; i++)
 			{
 				const pk_v4f v0 = sload4(tb, i * 48u), v1 = sload4(tb, i * 48u + 16u), v2 = sload4(tb, i * 48u + 32u);
@@ -1689,13 +1629,11 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 					break;
 				ref_lane = __ffsll((long long)act) - 1;
 			}
-#if RT_NORM_T
 			if (!ANY && hit.t != t_before) // the lane's hit moved: rescale its normalised 1/d and -o/d (Traverser::renormalise)
 			{
 				const float r = norm_k(hit.t) * fast_rcp(norm_k(t_before)) * 0.99999952f;
 				sp.id = sp.id * r, sp.noid = sp.noid * r;
 			}
-#endif
 			cur = stk.pop();
 		}
 	}
@@ -1758,7 +1696,9 @@ __global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet
 					if (active)
 					{
 						pt_primary_ray(q.cam, q.fr, pr.x, pr.y, q.fr.sample_base + pr.sample, O, D);
-						if (q.cam.aperture != 0.0f) // (pinhole: no origin record, extend_item)
+						// VESTIGE: nothing reads this record (the shade kernel regenerates the primary ray); the store stays because dropping it
+						// changes this kernel's code object — a performance change with its own measurement (DESIGN_LOG.md, round 7)
+						if (q.cam.aperture != 0.0f)
 							q.wv.org[0][idx] = mk4(O.x, O.y, O.z, ubits((idx << 1) | 1u));
 					}
 				}
@@ -1768,11 +1708,10 @@ __global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet
 			trace_packet<COUNT>(fresh_params().sc, active, O, D, 1e-5f, h, st);
 			if (active)
 			{
-				primary_finish_item(fresh_params(), idx, D, h); // (direction + hit record, or the sky term of a miss)
+				primary_finish_item(fresh_params(), idx, D, h); // (hit record, or the sky term of a miss)
 				nrays++;
 			}
 			// a group without a hit is finished here (27 % of the terrain's): the shade kernel's scan passes it by
-			if (RT_PRIMARY_MISS)
 			{
 				unsigned char *const done = fresh_params().wv.hit0_done;
 				const bool none = __ballot(active && h.prim >= 0) == 0ull;
@@ -2131,6 +2070,9 @@ static inline uint32_t persistent_grid(uint32_t items, uint32_t per_cu = RT_GRID
 	return blocks ? blocks : 8u;
 }
 
+// the grid of the persistent-lane and packet kernels (workgroups of TRACE_BLOCK threads) beside g, the grid of BLOCK-thread workgroups
+static inline dim3 trace_grid(const dim3 &g) { return dim3(std::max(8u, g.x * BLOCK / TRACE_BLOCK)); }
+
 void launch_init_counters(WaveCounters *c, uint32_t primary_count, stream_t s)
 {
 	hipLaunchKernelGGL(k_init_counters, dim3(1), dim3(256), 0, (hipStream_t)s, c, primary_count);
@@ -2155,7 +2097,7 @@ void launch_rng_states(uint32_t *states, const uint32_t base_state[4], const uin
 // does the pt primary wave of this launch run in packet form?  (the host asks too: only that form fills WaveView::hit0_done)
 bool primary_packet_form(const Params &p, uint32_t max_items)
 {
-	return (p.refill & 8u) && (p.fr.sgroup_log2 >= 1u || max_items >= RT_PRIMARY_PACKET_MIN);
+	return RT_PRIMARY_PACKET_RULE(p, max_items);
 }
 
 void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s)
@@ -2165,7 +2107,7 @@ void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, str
 #define RT_EXT(G, C) hipLaunchKernelGGL((k_extend<G, C>), g, b, 0, st, p, max_items)
 	if (gen == GEN_BUFFER && (p.refill & 1u))
 	{
-		const dim3 gt(std::max(8u, g.x * BLOCK / TRACE_BLOCK)), bt(TRACE_BLOCK);
+		const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
 		if (count)
 			hipLaunchKernelGGL((k_trace_stream<false, true>), gt, bt, 0, st, p);
 		else
@@ -2192,7 +2134,7 @@ void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, str
 		// 5.52, 32: 8.45 / 5.15, 64: 7.27 / 4.92 — a wave of one pixel's samples reaches the same few leaves, a wave that is an 8x8
 		// tile of different pixels reaches 64 different ones and every lane tests them all.  Small launches of single samples (1-spp
 		// frames: 0.37 against 0.57 ms) keep the one-ray-per-lane kernel with its tile-row-to-XCD dealing.
-		const dim3 gt(std::max(8u, g.x * BLOCK / TRACE_BLOCK)), bt(TRACE_BLOCK);
+		const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
 		if (count)
 			hipLaunchKernelGGL((k_primary_packet<true>), gt, bt, 0, st, p, max_items);
 		else
@@ -2263,7 +2205,7 @@ void launch_shade_pt(const Params &p, const SkyView &sky, uint32_t max_items, st
 void launch_shadow_packets(const Params &p, bool count, uint32_t max_items, stream_t s)
 {
 	const dim3 g(persistent_grid(max_items));
-	const dim3 gt(std::max(8u, g.x * BLOCK / TRACE_BLOCK)), bt(TRACE_BLOCK);
+	const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
 	if (count)
 		hipLaunchKernelGGL((k_shadow_packet<true>), gt, bt, 0, (hipStream_t)s, p);
 	else
@@ -2275,7 +2217,7 @@ void launch_connect(const Params &p, bool count, uint32_t max_items, stream_t s)
 	const dim3 g(persistent_grid(max_items)), b(BLOCK);
 	if (p.refill & 2u)
 	{
-		const dim3 gt(std::max(8u, g.x * BLOCK / TRACE_BLOCK)), bt(TRACE_BLOCK);
+		const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
 		if (count)
 			hipLaunchKernelGGL((k_trace_stream<true, true>), gt, bt, 0, (hipStream_t)s, p);
 		else
@@ -2310,7 +2252,7 @@ void launch_trace_fused(const Params &pe, const Params &pa, bool count, uint32_t
 	}
 #endif
 	const dim3 g(persistent_grid(max_items));
-	const dim3 gt(std::max(8u, g.x * BLOCK / TRACE_BLOCK)), bt(TRACE_BLOCK);
+	const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
 	if (count)
 		hipLaunchKernelGGL((k_trace_fused<true>), gt, bt, 0, (hipStream_t)s, pe, pa);
 	else

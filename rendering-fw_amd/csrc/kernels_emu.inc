@@ -51,9 +51,7 @@ struct Space
 		{
 			o[l] = o_[l], d[l] = d_[l];
 			id[l] = mk3(slab_rcp(d[l].x), slab_rcp(d[l].y), slab_rcp(d[l].z));
-#if RT_NORM_T
 			id[l] = id[l] * norm_k(hit[l].t);
-#endif
 			noid[l] = mk3(-(o[l].x * id[l].x), -(o[l].y * id[l].y), -(o[l].z * id[l].z));
 			mx |= (unsigned long long)(id[l].x < 0.0f) << l, my |= (unsigned long long)(id[l].y < 0.0f) << l, mz |= (unsigned long long)(id[l].z < 0.0f) << l;
 		}
@@ -140,7 +138,6 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 						tmin = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
 						tmax = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
 					}
-#if RT_NORM_T
 					// (normalised distances: the interval a box must meet is [0, 1] — device: v_max3 / v_min3 with the clamp modifier)
 					const float tk = fminf(fmaxf(tmin, 0.0f), 1.0f);
 					tmax = fminf(fmaxf(tmax, 0.0f), 1.0f);
@@ -148,13 +145,6 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 						tk_ref[k] = tk;
 					if (tk < tmax && ((act >> l) & 1ull))
 						m[k] |= 1ull << l;
-#else
-					const float tk = fmaxf(tmin, 0.0f);
-					if (l == ref_lane)
-						tk_ref[k] = tk;
-					if (tk < fminf(tmax, hit[l].t))
-						m[k] |= 1ull << l;
-#endif
 				}
 				if (sp.mixed && nd.entry[k] == ENTRY_EMPTY)
 					m[k] = 0ull;
@@ -212,11 +202,9 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 		}
 		{
 			const uint32_t first = cur & ENTRY_FIRST_MASK, count = ((cur >> 27) & 7u) + 1u;
-#if RT_NORM_T
 			float t_before[WAVE];
 			for (int l = 0; l < WAVE; l++)
 				t_before[l] = hit[l].t;
-#endif
 			for (uint32_t i = 0; i < count; i++)
 			{
 				const f4 *tv = sc.tri_verts + 3u * (first + i);
@@ -230,14 +218,12 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 						hit[l].inst = tri_inst;
 					}
 			}
-#if RT_NORM_T
 			for (int l = 0; l < WAVE; l++)
 				if (hit[l].t != t_before[l])
 				{
 					const float r = norm_k(hit[l].t) * fast_rcp(norm_k(t_before[l])) * 0.99999952f;
 					sp.id[l] = sp.id[l] * r, sp.noid[l] = sp.noid[l] * r;
 				}
-#endif
 			cur = stk.pop();
 		}
 	}
@@ -264,7 +250,7 @@ template <bool COUNT> void primary(const Params &p, uint32_t count)
 				if (active[l])
 				{
 					pt_primary_ray(p.cam, p.fr, pr.x, pr.y, p.fr.sample_base + pr.sample, O[l], D[l]);
-					if (p.cam.aperture != 0.0f)
+					if (p.cam.aperture != 0.0f) // VESTIGE: unread, kept as k_primary_packet's twin (DESIGN_LOG.md, round 7)
 						p.wv.org[0][idx] = mk4(O[l].x, O[l].y, O[l].z, ubits((idx << 1) | 1u));
 				}
 			}
@@ -291,7 +277,7 @@ bool primary_packet_form(const Params &, uint32_t) { return false; } // (the emu
 void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s)
 {
 	EMU_DEFER(s, launch_extend(p, gen, count, max_items, s));
-	if (gen == GEN_PT && (p.refill & 8u) && (p.fr.sgroup_log2 >= 1u || max_items >= (16u << 20))) // (the device's rule)
+	if (gen == GEN_PT && RT_PRIMARY_PACKET_RULE(p, max_items)) // (the device's rule)
 	{
 		count ? packet_emu::primary<true>(p, max_items) : packet_emu::primary<false>(p, max_items);
 		return;

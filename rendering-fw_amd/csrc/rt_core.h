@@ -55,7 +55,7 @@ RT_FN void clk_tick(ClkProbe &c, int k)
 // division is 10 instructions around the same v_rcp_f32 (two v_div_scale, four fmas, v_div_fmas, v_div_fixup — ~46 issue
 // cycles against 18), a correctly rounded square root a dozen around v_sqrt_f32, and the plain shade kernel held 106 + 50 of
 // them.  The host build and the validation build (RT_STRICT_MATH) keep IEEE division and square root, like the oracle; ray
-// generation, traversal and the triangle test are not written with these (rounded(), safe_rcp).
+// generation, traversal and the triangle test are not written with these (rounded(), slab_rcp).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_STRICT_MATH)
 RT_FN float m_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 RT_FN float m_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
@@ -462,14 +462,6 @@ struct TravStack
 	uint32_t stride;	// entries between two stack levels of one lane (= workgroup size on the device)
 };
 
-// 1/d for the slab test.  A direction component of exactly 0 (it happens: jitter r0 == 1.0f puts a ray on the image's
-// centre line) would give inf, and inf * 0 = NaN in the fma form below makes the slab test ignore that axis — the ray
-// then visits every box along it.  Such components are replaced by +-1e-30, i.e. a finite 1e30.
-RT_FN float safe_rcp(float d)
-{
-	return 1.0f / (fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
-}
-
 RT_FN float fast_rcp(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_STRICT_MATH)
@@ -479,23 +471,18 @@ RT_FN float fast_rcp(float x)
 #endif
 }
 
-// RT_FAST_ID: 1/d of the slab test by v_rcp_f32 (1 ulp) instead of a correctly rounded division (ten instructions, three times
-// per ray and change of space).  1/d only feeds the box tests — which boxes a ray enters, never what it hits there: the
-// triangle test takes o and d — and the boxes carry a margin of 2e-5 plus the outward rounding of their quantisation.
-#ifndef RT_FAST_ID
-#define RT_FAST_ID 1
-#endif
+// 1/d for the slab test.  A direction component of exactly 0 (it happens: jitter r0 == 1.0f puts a ray on the image's
+// centre line) would give inf, and inf * 0 = NaN in the fma form of the node step makes the slab test ignore that axis — the
+// ray then visits every box along it.  Such components are replaced by +-1e-30, i.e. a finite 1e30.
+// The reciprocal is v_rcp_f32 (1 ulp), not a correctly rounded division (ten instructions, three times per ray and change of
+// space): 1/d only feeds the box tests — which boxes a ray enters, never what it hits there: the triangle test takes o and
+// d — and the boxes carry a margin of 2e-5 plus the outward rounding of their quantisation.
 RT_FN float slab_rcp(float d)
 {
-	const float c = fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d);
-#if RT_FAST_ID
-	return fast_rcp(c);
-#else
-	return 1.0f / c;
-#endif
+	return fast_rcp(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
 }
 
-// RT_NORM_T: the slab test in NORMALISED distances s = t * k with k = (1 - 2^-16) / hit.t (k = 2^-100 while the ray has no hit
+// The slab test runs in NORMALISED distances s = t * k with k = (1 - 2^-16) / hit.t (k = 2^-100 while the ray has no hit
 // and no bound): the interval a box must meet, [0, hit.t], becomes [0, 1] — exactly what the `clamp` output modifier of
 // v_max3_f32 / v_min3_f32 clamps to for free.  With near' = clamp(max3(..)), far' = clamp(min3(..)) the reference's three
 // conditions (aabb.cpp:39-77: tmax > tmin && tmin < t, plus tmax >= 0 here) are ONE compare, near' < far': per child
@@ -505,10 +492,6 @@ RT_FN float slab_rcp(float d)
 // 1 - 2^-16 keeps the far clamp conservative against the rounding of k and of the rescaling: a box is culled by distance only
 // when its entry lies beyond hit.t * (1 + 1.5e-5).  (A box that ENDS exactly at the ray's origin, tmax == 0, was entered before
 // and is not now; nothing in it can be hit: t > t_min = 1e-5.)
-#ifndef RT_NORM_T
-#define RT_NORM_T 1
-#endif
-
 RT_FN float norm_k(float t)
 {
 	// t >= 1e30: "no bound" (the integrators' 1e34): a power of two, so the scaling is exact; k <= 1e3 keeps o/d * k finite
@@ -536,20 +519,6 @@ RT_FN float min3_clamp01(float a, float b, float c)
 #else
 	return fminf(fmaxf(fminf(fminf(a, b), c), 0.0f), 1.0f);
 #endif
-}
-
-// Slab test (aabb.cpp:39-77) in fma form: t = b * (1/d) - o * (1/d).  a = bmin.xyz, bmax.x ; b = bmax.y, bmax.z, ...
-// The reference accepts tmax > tmin && tmin < t; boxes entirely behind the origin (tmax < 0) cannot contain an
-// accepted hit (t > t_min >= 0) and are culled as well.
-RT_FN bool slab(const f4 &a, const f4 &b, f3 id, f3 oid, float t, float &tnear)
-{
-	const float tx1 = fmaf(a.x, id.x, -oid.x), tx2 = fmaf(a.w, id.x, -oid.x);
-	const float ty1 = fmaf(a.y, id.y, -oid.y), ty2 = fmaf(b.x, id.y, -oid.y);
-	const float tz1 = fmaf(a.z, id.z, -oid.z), tz2 = fmaf(b.y, id.z, -oid.z);
-	const float tmin = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
-	const float tmax = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
-	tnear = tmin;
-	return tmax > tmin && tmin < t && tmax >= 0.0f;
 }
 
 // The four 16-byte rows of a compressed 4-wide node (rt::Node4c).
@@ -669,21 +638,17 @@ struct Traverser : TraverserWorld<WORLD>
 	{
 		o = o_, d = d_;
 		id = mk3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
-#if RT_NORM_T
-		id = id * norm_k(hit.t); // (id, oid hold the NORMALISED 1/d and o/d: see RT_NORM_T)
-#endif
+		id = id * norm_k(hit.t); // (id, oid hold the NORMALISED 1/d and o/d: see norm_k)
 		oid = o * id;
 		neg_x = id.x < 0.0f, neg_y = id.y < 0.0f, neg_z = id.z < 0.0f;
 	}
-	// RT_NORM_T: the closest hit moved from t_old to hit.t — rescale the normalised 1/d and o/d
+	// the closest hit moved from t_old to hit.t — rescale the normalised 1/d and o/d
 	RT_FN void renormalise(float t_old)
 	{
-#if RT_NORM_T
 		// (the last factor, 1 - 2^-21, outweighs the rounding of the line: however often a ray's hit moves, k only drifts DOWN —
 		// towards a looser far clamp — never past (1 - 2^-16) / hit.t)
 		const float r = norm_k(hit.t) * fast_rcp(norm_k(t_old)) * 0.99999952f;
 		id = id * r, oid = oid * r;
-#endif
 	}
 
 	RT_FN void begin(const SceneView &sc, f3 O_, f3 D_, float t_min_, float t_max)
@@ -704,8 +669,6 @@ struct Traverser : TraverserWorld<WORLD>
 					mk3(row_dir_r(in.inv, D), row_dir_r(in.inv + 4, D), row_dir_r(in.inv + 8, D)));
 	}
 	RT_FN bool done() const { return cur == ENTRY_DONE; }
-	// a triangle leaf (not a top-level leaf, the sentinel or ENTRY_DONE, which all carry the ENTRY_TLAS bit)
-	static RT_FN bool tri_leaf(uint32_t e) { return (e & (ENTRY_LEAF | ENTRY_TLAS)) == ENTRY_LEAF; }
 	// has this lane nothing left to do in the node phase?
 	RT_FN bool parked() const { return (cur & ENTRY_LEAF) != 0u; }
 
@@ -796,21 +759,12 @@ struct Traverser : TraverserWorld<WORLD>
 		const uint32_t nyq = neg_y ? hiy : loy, fyq = neg_y ? loy : hiy;
 		const uint32_t nzq = neg_z ? hiz : loz, fzq = neg_z ? loz : hiz;
 		const float INF = NODE_INF;
-#if RT_NORM_T
 #define RT_SLAB4(UB, OUT)                                                                                   \
 	{                                                                                                       \
 		const float tmin = max3_clamp01(fmaf(UB(nxq), Ax, Bx), fmaf(UB(nyq), Ay, By), fmaf(UB(nzq), Az, Bz)); \
 		const float tmax = min3_clamp01(fmaf(UB(fxq), Ax, Bx), fmaf(UB(fyq), Ay, By), fmaf(UB(fzq), Az, Bz)); \
 		OUT = tmax > tmin ? tmin : INF;                                                                     \
 	}
-#else
-#define RT_SLAB4(UB, OUT)                                                                                   \
-	{                                                                                                       \
-		const float tmin = fmaxf(fmaxf(fmaf(UB(nxq), Ax, Bx), fmaf(UB(nyq), Ay, By)), fmaf(UB(nzq), Az, Bz)); \
-		const float tmax = fminf(fminf(fmaf(UB(fxq), Ax, Bx), fmaf(UB(fyq), Ay, By)), fmaf(UB(fzq), Az, Bz)); \
-		OUT = (tmax > tmin && tmin < hit.t && tmax >= 0.0f) ? tmin : INF;                                   \
-	}
-#endif
 		RT_SLAB4(ub0, t0)
 		RT_SLAB4(ub1, t1)
 		RT_SLAB4(ub2, t2)
@@ -862,9 +816,6 @@ struct Traverser : TraverserWorld<WORLD>
 	// phase 1: walk 4-wide inner nodes until this lane holds a leaf entry (or ENTRY_DONE / ENTRY_SENTINEL)
 	// VOTE < 64 (wave kernels only): the wave leaves the node phase as soon as VOTE / 64 of its lanes with a ray hold a leaf,
 	// so that those lanes do not sit idle while the others finish a long descent (lanes still on an inner node skip visit()).
-#ifndef RT_VOTE_RELATIVE
-#define RT_VOTE_RELATIVE 1
-#endif
 	template <int VOTE = 64> RT_FN void descend(const SceneView &sc, const TravStack stk, TStat &st)
 	{
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -884,13 +835,8 @@ struct Traverser : TraverserWorld<WORLD>
 				// only the lanes still inside this loop execute the ballot: the lanes with work that are NOT counted here
 				// are the ones already waiting with a leaf (or with a finished ray to retire)
 				const int inner = __popcll(__ballot(!parked()));
-#if RT_VOTE_RELATIVE
 				if ((nwork - inner) * 64 >= nwork * VOTE) // VOTE / 64 of the lanes that HAVE a ray (idle lanes do not count)
 					break;
-#else
-				if (nwork - inner >= VOTE)
-					break;
-#endif
 			}
 #endif
 		}
@@ -933,9 +879,7 @@ struct Traverser : TraverserWorld<WORLD>
 		}
 		const uint32_t first = leaf & ENTRY_FIRST_MASK;
 		const uint32_t count = ((leaf >> 27) & 7u) + 1u;
-#if RT_NORM_T
 		const float t_before = hit.t;
-#endif
 		for (uint32_t i = 0; i < count; i++)
 		{
 			const f4 *tv = sc.tri_verts + 3u * (first + i);
@@ -957,10 +901,8 @@ struct Traverser : TraverserWorld<WORLD>
 				}
 			}
 		}
-#if RT_NORM_T
 		if (!ANY && hit.t != t_before)
 			renormalise(t_before);
-#endif
 		cur = pop(stk);
 	}
 };

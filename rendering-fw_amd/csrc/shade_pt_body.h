@@ -57,9 +57,6 @@
 #ifndef RT_SHADE_RUN
 #define RT_SHADE_RUN 32u
 #endif
-#ifndef RT_SHADE_FRESH_PARAMS
-#define RT_SHADE_FRESH_PARAMS 1
-#endif
 	// a wave walks RUNS of consecutive chunks (fewer when the launch has less than four runs per wave)
 	uint32_t srun = nchunks / (nwaves * 4u);
 	srun = srun > RT_SHADE_RUN ? RT_SHADE_RUN : (srun ? srun : 1u);
@@ -141,13 +138,9 @@
 #if defined(RT_DIAG_SHADE_CLOCK)
 		shade_pt_item<TEX, SKY>(p, sky, idx, act, h4, hi, ctx, &clk);
 #else
-#if RT_SHADE_FRESH_PARAMS
 		// (the kernel's arguments read again from the kernarg segment — scalar loads — instead of staying live across the loop: with
 		// ~150 wave-uniform words of scene, wave buffers, camera and frame the compiler parks them in VGPR lanes, a v_readlane per use)
 		shade_pt_item<TEX, SKY>(fresh_params(), sky, idx, act, h4, hi, ctx);
-#else
-		shade_pt_item<TEX, SKY>(p, sky, idx, act, h4, hi, ctx);
-#endif
 #endif
 	}
 #if defined(RT_DIAG_SHADE_CLOCK)

@@ -60,7 +60,7 @@ def check_traversal(pkg, core, oracle, n_random=20000):
     core.set_setting("count_traversal", 0)
     _compare(a, oracle.trace_rays(o, d), ties=True)
     assert cnt["rays_extend"] == len(o)
-    assert cnt["inner_extend"] / len(o) < 120, cnt    # was ~5800 per ray before safe_rcp (inf * 0 = NaN in the slab test)
+    assert cnt["inner_extend"] / len(o) < 120, cnt    # was ~5800 per ray before slab_rcp's clamp (inf * 0 = NaN in the slab test)
     # intervals: nothing before t_min, nothing beyond t_max
     full = core.trace_rays(o[:64], d[:64])
     hit = full["prim"] >= 0
