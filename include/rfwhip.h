@@ -413,7 +413,12 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   sky_pick = "-1" (default: auto, p = 1 when the scene has no lights, 0.5 otherwise) | a probability p in [0, 1]
  *   rfwhip_get_setting also answers read-only keys: "textured" (the textured shade kernel variant is in use), "packet" (the
  *   pt primary wave can run in packet form), "world_tree" (triangles in the world tree of the last update; 0: none),
- *   "shadow_bins_per_run", "shadow_packets_on", "sky" (the last update left p > 0: the shade waves run the sky variant).
+ *   "shadow_bins_per_run", "shadow_packets_on", "sky" (the last update left p > 0: the shade waves run the sky variant),
+ *   "light_tree" (nodes of the light tree the next render would use; 0: none, or light_sampling is not "tree").
+ *   Not listed by rfwhip_get_settings, but settable:
+ *   light_sampling = "reference" (default: the reference's estimator, the default kernels) | "linear" (its potentials, consistent
+ *                  weights) | "tree" (the light tree, O(log lights) per next-event vertex, the same weights): rfwhip_get_light_tree
+ *                  below has the formulas.  The parity integrator ignores it.
  * Returns the number of keys; fills up to cap pointers with static strings. */
 RFWHIP_API int rfwhip_set_setting(rfwhip_context *ctx, const char *key, const char *value);
 RFWHIP_API int rfwhip_get_setting(rfwhip_context *ctx, const char *key, char *value, size_t cap);
@@ -546,6 +551,31 @@ RFWHIP_STATIC_ASSERT(sizeof(rfwhip_bvh4_info) == 32, "rfwhip_bvh4_info is 32 B")
  * rfwhip_update) fails with RFWHIP_ERR_STATE. */
 RFWHIP_API int rfwhip_get_bvh4(rfwhip_context *ctx, size_t mesh_index, void *nodes4c, void *nodes4f, uint32_t *src4,
 							   size_t node_cap, float *tri_verts, size_t tri_cap, rfwhip_bvh4_info *info);
+
+/* The light tree of setting light_sampling=tree as the next render would use it (a test hook like rfwhip_get_bvh; built on the
+ * host at the setting, at rfwhip_set_lights and at rfwhip_update, downloaded here on demand).  Returns the node count — 0 when
+ * the mode is not `tree` or no area, point or spot light exists, 1 for one such light, 2 n for n >= 2 — or a negative error
+ * code.  At most node_cap nodes and light_cap paths (one per light of all four kinds, in the order area, point, spot,
+ * directional) are copied; either pointer may be NULL.
+ *
+ * light_sampling = reference (default) | linear | tree.  `reference` is the reference's estimator, untouched.  `linear` picks a
+ * light by the reference's potentials, `tree` by descending the tree; both weight consistently, so that they converge to the
+ * same image whatever the picking rule (q = the probability of the picked light, times 1 - p under sky sampling):
+ *   area light, next event:  T bs radiance NdotL / (shadowPdf + q p_w),   p_w = dist^2 / (area LNdotL)   (no 1 / |radiance|)
+ *   point, spot, directional: T bs radiance NdotL / (q lightPdf)        (lightPdf as the reference has it; no BSDF pdf)
+ *   emitter found by a BSDF ray: T colour / (bsdfPdf + p_w q),          q by the rule that picks.
+ * The tree: binary, over the area, point and spot lights; split at the median of the centroids along the longest axis of the
+ * centroid box, ties by light index; a leaf holds one light.  Directional lights form a flat list beside the root.  The
+ * importance of a node for a point I with normal N — c = (lo + hi) / 2, r = |hi - lo| / 2, v = I - c, d = |v| —
+ *   d <= r:  E / max(r^2, 1e-12)
+ *   else:    E cos(max(0, theta - theta_o - theta_u)) cos(max(0, theta_i - theta_u)) / d^2,
+ *            theta_u = asin(r / d), theta = angle(axis, v), theta_i = angle(N, -v),
+ * where a cosine c of a positive angle counts as max(0, c + 1e-5) (a margin for the rounding of the sine and cosine identities
+ * the kernel uses: a light with a positive potential must never lose a node on its path).  Selection: r1 chooses
+ * among [root by importance, directional 0 .. k - 1 by potential]; each level below picks a child in proportion to importance,
+ * left first, and rescales r1 into the child's interval; q is the product of the probabilities. */
+RFWHIP_API int rfwhip_get_light_tree(rfwhip_context *ctx, rfwhip_light_tree_node *nodes, size_t node_cap,
+									 rfwhip_light_tree_path *paths, size_t light_cap);
 
 #ifdef __cplusplus
 }

@@ -240,6 +240,24 @@ typedef struct rfwhip_bvh_node
 } rfwhip_bvh_node;
 RFWHIP_STATIC_ASSERT(sizeof(rfwhip_bvh_node) == 32, "BVHNode must be 32 B (bvh_node.cpp:10)");
 
+/* A node of the light tree (setting light_sampling=tree; rfwhip_get_light_tree; rfwhip.h has the formulas).  Node 0 is the root,
+ * node 1 is unused, the children of a node are `child` and `child + 1` with `child` even; child == 0: a leaf holding `light`. */
+typedef struct rfwhip_light_tree_node
+{
+	float lo[3], energy; /* box of the lights below; sum of their energies (a negative or NaN energy counts as 0) */
+	float hi[3], cos_o;	 /* cosine of the half angle of the cone of their normals; -1: every direction */
+	float axis[3];		 /* the cone's axis */
+	uint32_t child, light, count; /* count: lights below */
+	uint32_t pad[2];
+} rfwhip_light_tree_node;
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_light_tree_node) == 64, "light-tree node must be 64 B");
+/* A light's way down the tree: bit i of `bits` set = the right child at level i; `depth` levels (0, 0 for a directional light). */
+typedef struct rfwhip_light_tree_path
+{
+	uint32_t bits, depth;
+} rfwhip_light_tree_path;
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_light_tree_path) == 8, "light-tree path must be 8 B");
+
 /* context.h:19-23 */
 enum rfwhip_render_status
 {
@@ -279,7 +297,10 @@ enum rfwhip_kat_function
 	/* the texture sampler on the scene of the last rfwhip_update() (getShadingData.h:25-217; rt_core.h: fetch_texel, fetch_trilinear,
 	 * pt_surface, pt_textures).  An index outside the scene's tables is an error. */
 	RFWHIP_KAT_TEX_FETCH = 15,		   /* [0] = texture (int), [1] = form (int: 0 = the trilinear fetch of a colour layer, 1 = the bilinear fetch at level 0 of a normal-map layer), [2] = lambda, [3..4] = tu, tv, [5..6] = width, height as the material's map descriptor gives them (ints, 1..65536) -> rgba */
-	RFWHIP_KAT_SURFACE_LAYERS = 16	   /* [0] = instance, [1] = triangle (ints), [2..3] = barycentrics u, v (weights of vertex 1, 2), [4..6] = D, [7] = t, [8] = the camera's spread angle -> [0..2] = colour after the texture layers, [3..5] = shading normal after the normal maps, [6] = flags (int): bit 0 alpha pass-through, bit 1 the material is textured */
+	RFWHIP_KAT_SURFACE_LAYERS = 16,   /* [0] = instance, [1] = triangle (ints), [2..3] = barycentrics u, v (weights of vertex 1, 2), [4..6] = D, [7] = t, [8] = the camera's spread angle -> [0..2] = colour after the texture layers, [3..5] = shading normal after the normal maps, [6] = flags (int): bit 0 alpha pass-through, bit 1 the material is textured */
+	/* the light tree of light_sampling=tree (rt_core.h: lt_sample / lt_pick_prob); RFWHIP_ERR_STATE in any other mode */
+	RFWHIP_KAT_LT_SAMPLE = 17,		   /* [0..2] = I, [3..5] = N, [6] = r0, [7] = r1 -> [0..2] = P, [3] = q, [4] = lightPdf (area: dist^2 / (area LNdotL)), [5] = the light (int, -1: none), [6] = its rank in the order r1 walks through (int) */
+	RFWHIP_KAT_LT_PICK_PROB = 18 	   /* [0..2] = I, [3..5] = N, [8] = light (int) -> q, bit for bit what LT_SAMPLE gives when it draws that light */
 };
 
 #ifdef __cplusplus

@@ -84,6 +84,7 @@ class CoreBinding:
                                   "trace_rays_form": (i32, [vp, i32, u32, u32, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp,
                                                             vp, vp, vp]),
                                   "get_bvh4": (i32, [vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(abi.Bvh4Info)]),
+                                  "get_light_tree": (i32, [vp, vp, sz, vp, sz]),
                                   "read_denoise_guides": (i32, [vp, vp, vp]),
                                   "denoise_image": (i32, [vp, vp, vp]),
                                   "read_denoise_history": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -226,6 +227,7 @@ class CoreBinding:
         s, ps = prep(spot, abi.SPOT_LIGHT_DTYPE)
         d, pd = prep(directional, abi.DIRECTIONAL_LIGHT_DTYPE)
         self._check(self._fn("set_lights")(self._ctx, abi.LightCount(len(a), len(p), len(s), len(d)), pa, pp, ps, pd))
+        self._light_count = len(a) + len(p) + len(s) + len(d)
 
     def get_probe_results(self):
         inst, prim, dist = C.c_uint32(), C.c_uint32(), C.c_float()
@@ -406,7 +408,7 @@ class CoreBinding:
     # known-answer hook: RFWHIP_KAT_* (include/rfwhip_abi.h)
     KAT = {"bsdf_eval": 0, "bsdf_pdf": 1, "bsdf_sample": 2, "tangent_space": 3, "pack_normal": 4,
            "random_barycentrics": 5, "point_on_light": 6, "light_pick_prob": 7, "blue_noise": 8, "hash": 9, "half_to_float": 10, "fastdiv": 11, "tex_wrap": 12,
-           "sky_sample": 13, "sky_pdf": 14, "tex_fetch": 15, "surface_layers": 16}
+           "sky_sample": 13, "sky_pdf": 14, "tex_fetch": 15, "surface_layers": 16, "lt_sample": 17, "lt_pick_prob": 18}
 
     def kat(self, function, records):
         """One of the path tracer's functions on n records (n x 24 float32, integers as bit patterns) -> n x 8 float32."""
@@ -429,6 +431,23 @@ class CoreBinding:
         self._check(self._fn("get_bvh")(self._ctx, int(mesh_index), nodes.ctypes.data, len(nodes), prims.ctypes.data,
                                         len(prims), C.byref(nn), C.byref(np_)))
         return nodes, prims
+
+    def get_light_tree(self, lights=None):
+        """The light tree of light_sampling=tree as the next render would use it: (nodes LIGHT_TREE_NODE_DTYPE, paths
+        LIGHT_TREE_PATH_DTYPE — one per light of all four kinds; `lights`: how many the scene has, by default the count of
+        this binding's last set_lights).  No nodes: the mode is not tree, or no light has a position."""
+        if lights is None:
+            lights = getattr(self, "_light_count", 0)
+        f = self._fn("get_light_tree")
+        n = f(self._ctx, None, 0, None, 0)
+        if n < 0:
+            self._check(-n)
+        nodes = np.zeros(n, abi.LIGHT_TREE_NODE_DTYPE)
+        paths = np.zeros(int(lights), abi.LIGHT_TREE_PATH_DTYPE)
+        n = f(self._ctx, nodes.ctypes.data, len(nodes), paths.ctypes.data, len(paths))
+        if n < 0:
+            self._check(-n)
+        return nodes, paths
 
     def get_bvh4(self, mesh_index):
         """The traversed tree of a resident mesh as it sits on the device (entries absolute): {"nodes4c": NODE4C_DTYPE,

@@ -59,6 +59,12 @@ assert DIRECTIONAL_LIGHT_DTYPE.itemsize == 32
 
 BVH_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left_first", "<i4"), ("count", "<i4")])
 assert BVH_NODE_DTYPE.itemsize == 32
+# the light tree (rfwhip_get_light_tree; rfwhip_abi.h: rfwhip_light_tree_node / rfwhip_light_tree_path)
+LIGHT_TREE_NODE_DTYPE = np.dtype([("lo", "<f4", 3), ("energy", "<f4"), ("hi", "<f4", 3), ("cos_o", "<f4"), ("axis", "<f4", 3),
+                                  ("child", "<u4"), ("light", "<u4"), ("count", "<u4"), ("pad", "<u4", 2)])
+assert LIGHT_TREE_NODE_DTYPE.itemsize == 64
+LIGHT_TREE_PATH_DTYPE = np.dtype([("bits", "<u4"), ("depth", "<u4")])
+assert LIGHT_TREE_PATH_DTYPE.itemsize == 8
 
 # the traversed 4-wide nodes (rfwhip_get_bvh4): compressed (rt::Node4c, rt_types.h) and their float form (rt::Node4f).
 # Compressed planes: byte k of qlo[a] / qhi[a] is child k's plane on axis a, decoded as fma(q, scale[a], org[a]).

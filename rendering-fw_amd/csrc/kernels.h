@@ -101,6 +101,8 @@ uint32_t queue_pad(uint32_t max_items); // extra slots per queue and launch for 
 // sky.pick > 0 (setting sky_sampling): the sky variant k_shade_pt_sky, which takes the table as an argument of its own (Params, and
 // with it every other kernel's code, stays what it was)
 void launch_shade_pt(const Params &p, const rt::SkyView &sky, uint32_t max_items, stream_t s);
+// light_sampling = linear | tree: k_shade_pt_lt (lt.nodes null: linear); sky as above (pick == 0: no sky sampling)
+void launch_shade_pt_lt(const Params &p, const rt::SkyView &sky, const rt::LightTreeView &lt, uint32_t max_items, stream_t s);
 void launch_connect(const Params &p, bool count, uint32_t max_items, stream_t s);
 // the connection wave of depth 0 in packet form: runs of the shadow queue sorted by the chosen light's bin (FrameView::shadow_bins),
 // one wave-uniform occlusion traversal per 64 rays of the sorted order
@@ -109,7 +111,9 @@ void launch_shadow_packets(const Params &p, bool count, uint32_t max_items, stre
 void launch_trace_fused(const Params &pe, const Params &pa, bool count, uint32_t max_items, stream_t s);
 void launch_resolve(const Params &p, stream_t s);
 // rfwhip_kat: `function` (RFWHIP_KAT_*) on n records of 24 floats -> n records of 8 floats (device pointers)
-void launch_kat(const Params &p, const rt::SkyView &sky, int function, const float *in, float *out, uint32_t n, stream_t s);
+// (KAT_LT_*: the functions of k_kat_lt, RFWHIP_KAT_LT_* of rfwhip_abi.h; every other function runs in k_kat)
+constexpr int KAT_LT_SAMPLE = 17, KAT_LT_PICK_PROB = 18;
+void launch_kat(const Params &p, const rt::SkyView &sky, const rt::LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s);
 // out: local layout (local_rows x W) when full == 0, else full image (H x W; world must be 1)
 void launch_present(const Params &p, rt::f4 *out, float scale, int full, stream_t s);
 // the denoiser's guide pass (p: scene, camera and FrameView of the full image) = guide kernel + depth-gradient kernel

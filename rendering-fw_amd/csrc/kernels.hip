@@ -378,7 +378,7 @@ struct ShadeSink
 
 // One entry of the wave of depth p.depth.  `active` = the lane holds a path (the device kernel's scan has checked that the entry is
 // a path's: not void, at depth 0 a real pixel's slot); h4 / hi = its hit record (the device kernel's scan has read them already).
-template <bool TEX, bool SKY> RT_FN void shade_pt_item(const Params &p, const SkyView &sky, uint32_t i, bool active, const f4 &h4, int hi, Ctx &ctx RT_ITEM_CLK)
+template <bool TEX, bool SKY, bool LT> RT_FN void shade_pt_item(const Params &p, const SkyView &sky, const LightTreeView &lt, uint32_t i, bool active, const f4 &h4, int hi, Ctx &ctx RT_ITEM_CLK)
 {
 	RT_ITEM_TICK(0);
 	const uint32_t b = p.depth & 1u, nb = b ^ 1u;
@@ -412,7 +412,7 @@ template <bool TEX, bool SKY> RT_FN void shade_pt_item(const Params &p, const Sk
 	}
 	const uint32_t slot = in.slot;
 	ShadeSink sink{p, ctx, slot};
-	pt_shade<TEX, SKY>(p.sc, sky, p.cam, p.fr, p.max_depth, active, in, h, out, ctx.pot, sink RT_CLK_ARG);
+	pt_shade<TEX, SKY, LT>(p.sc, sky, lt, p.cam, p.fr, p.max_depth, active, in, h, out, ctx.pot, sink RT_CLK_ARG);
 	if (active)
 	{
 		// depth 0 initialises the slot (no clear pass); later depths accumulate.  One path per slot => no race.
@@ -506,7 +506,8 @@ RT_FN void connect_item(const Params &p, uint32_t i, bool active, Ctx &ctx)
 }
 
 // rfwhip_kat: one of the shade kernel's functions on one record (rfwhip_abi.h: RFWHIP_KAT_*)
-RT_FN void kat_item(const Params &p, const SkyView &sky, int function, const float *in, float *out, uint32_t i, float *pot_cache)
+// (LT: the light-tree functions, which k_kat_lt alone runs — k_kat's arguments stay what they were)
+template <bool LT> RT_FN void kat_item(const Params &p, const SkyView &sky, const LightTreeView &lt, int function, const float *in, float *out, uint32_t i, float *pot_cache)
 {
 	const float *r = in + (size_t)i * KAT_IN;
 	float *o = out + (size_t)i * KAT_OUT;
@@ -639,6 +640,26 @@ RT_FN void kat_item(const Params &p, const SkyView &sky, int function, const flo
 		o[6] = ubits((alpha_skip ? 1u : 0u) | (textured ? 2u : 0u));
 		break;
 	}
+	case KAT_LT_SAMPLE: // lt_sample on the context's light tree: [0..2] = I, [3..5] = N, [6] = r0, [7] = r1 -> P, q, lightPdf, the light (int: -1
+			 // none), its rank in r1's order (int)
+		if (LT)
+		{
+			const f3 I = mk3(r[0], r[1], r[2]), N = mk3(r[3], r[4], r[5]);
+			uint32_t light = 0u, rank = 0u;
+			float q = 0.0f, pdf = 0.0f;
+			f3 P = mk3(0, 0, 0), col = mk3(0, 0, 0);
+			bool delta = false;
+			const bool found = lt_sample(p.sc, lt, r[7], I, N, light, q, rank);
+			if (found)
+				P = lt_point_on_light(p.sc, light, random_barycentrics(r[6]), I, N, pdf, col, delta);
+			o[0] = P.x, o[1] = P.y, o[2] = P.z, o[3] = q, o[4] = pdf;
+			o[5] = ubits(found ? light : 0xFFFFFFFFu), o[6] = ubits(rank);
+		}
+		break;
+	case KAT_LT_PICK_PROB: // lt_pick_prob: [0..2] = I, [3..5] = N, [8] = light (int; the host has checked it) -> q
+		if (LT)
+			o[0] = lt_pick_prob(p.sc, lt, fbits(r[8]), mk3(r[0], r[1], r[2]), mk3(r[3], r[4], r[5]));
+		break;
 	default:
 		break;
 	}
@@ -1857,15 +1878,25 @@ __global__ void __launch_bounds__(BLOCK, RT_TRAVERSAL_WAVES) k_shade_parity(cons
 
 template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt(const Params p)
 {
-	constexpr bool SKY = false;
+	constexpr bool SKY = false, LT = false;
 	const SkyView sky{};
+	const LightTreeView lt{};
 #include "shade_pt_body.h"
 }
 // Sky sampling: the same kernel with the sky's next-event estimation (pt_shade<TEX, true>).  A kernel of its own, not a template
 // argument of k_shade_pt: the measurements look the default kernels up by their names.
 template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt_sky(const Params p, const SkyView sky)
 {
-	constexpr bool SKY = true;
+	constexpr bool SKY = true, LT = false;
+	const LightTreeView lt{};
+#include "shade_pt_body.h"
+}
+// light_sampling = linear | tree: the same kernel with lt_random_point_on_light and the consistent weights (pt_shade<TEX, SKY, true>).
+// One kernel serves both modes: lt.nodes is null in linear, a wave-uniform branch.  SKY as in the two kernels above (sky.pick == 0:
+// SKY = false is launched and `sky` is unread).
+template <bool TEX, bool SKY> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt_lt(const Params p, const SkyView sky, const LightTreeView lt)
+{
+	constexpr bool LT = true;
 #include "shade_pt_body.h"
 }
 
@@ -1918,12 +1949,7 @@ __global__ void __launch_bounds__(BLOCK) k_kat(const Params p, const SkyView sky
 	__shared__ float s_pot[POT_SLOTS * BLOCK];
 	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
 	if (i < n)
-		kat_item(p, sky, function, in, out, i, s_pot + threadIdx.x);
-}
-void launch_kat(const Params &p, const SkyView &sky, int function, const float *in, float *out, uint32_t n, stream_t s)
-{
-	if (n)
-		hipLaunchKernelGGL(k_kat, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, function, in, out, n);
+		kat_item<false>(p, sky, LightTreeView{}, function, in, out, i, s_pot + threadIdx.x);
 }
 
 __global__ void k_init_counters(WaveCounters *c, uint32_t primary_count)
@@ -2411,6 +2437,40 @@ void launch_refit(Node *nodes, uint32_t node_base, const int *parents, uint32_t 
 					   verts, indices, tri_count);
 	hipLaunchKernelGGL(k_refit_nodes, dim3((node_count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, nodes, node_base, parents,
 					   node_count, tri_verts, flags);
+}
+
+// ---- light_sampling = linear | tree.  Last in the file: the kernels above keep their places in the code object. ----
+void launch_shade_pt_lt(const Params &p, const SkyView &sky, const LightTreeView &lt, uint32_t max_items, stream_t s)
+{
+	const dim3 g(persistent_grid(max_items, p.textured ? RT_SHADE_BLOCKS_PER_CU(true) : RT_SHADE_BLOCKS_PER_CU(false))), b(BLOCK);
+	if (sky.pick > 0.0f)
+	{
+		if (p.textured)
+			hipLaunchKernelGGL((k_shade_pt_lt<true, true>), g, b, 0, (hipStream_t)s, p, sky, lt);
+		else
+			hipLaunchKernelGGL((k_shade_pt_lt<false, true>), g, b, 0, (hipStream_t)s, p, sky, lt);
+	}
+	else if (p.textured)
+		hipLaunchKernelGGL((k_shade_pt_lt<true, false>), g, b, 0, (hipStream_t)s, p, sky, lt);
+	else
+		hipLaunchKernelGGL((k_shade_pt_lt<false, false>), g, b, 0, (hipStream_t)s, p, sky, lt);
+}
+
+__global__ void __launch_bounds__(BLOCK) k_kat_lt(const Params p, const SkyView sky, const LightTreeView lt, int function, const float *in, float *out, uint32_t n)
+{
+	__shared__ float s_pot[POT_SLOTS * BLOCK];
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < n)
+		kat_item<true>(p, sky, lt, function, in, out, i, s_pot + threadIdx.x);
+}
+void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s)
+{
+	if (!n)
+		return;
+	if (function == KAT_LT_SAMPLE || function == KAT_LT_PICK_PROB)
+		hipLaunchKernelGGL(k_kat_lt, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, lt, function, in, out, n);
+	else
+		hipLaunchKernelGGL(k_kat, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, function, in, out, n);
 }
 
 // ================================================================================================================

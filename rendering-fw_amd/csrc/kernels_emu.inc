@@ -324,17 +324,48 @@ void launch_shade_pt(const Params &p, const SkyView &sky, uint32_t max_items, st
 		ClkProbe clk0;
 		clk0.last = 0, clk0.acc = nullptr;
 		if (sky.pick > 0.0f)
-			p.textured ? shade_pt_item<true, true>(p, sky, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, true>(p, sky, i, true, h4, insts[i], ctx, &clk0);
+			p.textured ? shade_pt_item<true, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0);
 		else
-			p.textured ? shade_pt_item<true, false>(p, sky, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, false>(p, sky, i, true, h4, insts[i], ctx, &clk0);
+			p.textured ? shade_pt_item<true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0);
 #else
 		// (sky sampling: what k_shade_pt_sky runs)
 		if (sky.pick > 0.0f)
-			p.textured ? shade_pt_item<true, true>(p, sky, i, true, h4, insts[i], ctx) : shade_pt_item<false, true>(p, sky, i, true, h4, insts[i], ctx);
+			p.textured ? shade_pt_item<true, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx) : shade_pt_item<false, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx);
 		else
-			p.textured ? shade_pt_item<true, false>(p, sky, i, true, h4, insts[i], ctx) : shade_pt_item<false, false>(p, sky, i, true, h4, insts[i], ctx);
+			p.textured ? shade_pt_item<true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx) : shade_pt_item<false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx);
 #endif
 	}
+	p.wv.counters->ext[p.depth + 1] += ctx.q_ext.rays, p.wv.counters->shadow[p.depth] += ctx.q_shadow.rays;
+}
+void launch_shade_pt_lt(const Params &p, const SkyView &sky, const LightTreeView &lt, uint32_t max_items, stream_t s)
+{
+	EMU_DEFER(s, launch_shade_pt_lt(p, sky, lt, max_items, s));
+	Ctx ctx;
+	const uint32_t n = p.wv.counters->ext_n[p.depth];
+	const f4 *const hits = p.depth == 0 ? p.wv.hit0 : p.wv.hit;
+	const int *const insts = p.depth == 0 ? p.wv.hit0_inst : p.wv.hit_inst;
+#if defined(RT_DIAG_SHADE_CLOCK)
+	ClkProbe clk0;
+	clk0.last = 0, clk0.acc = nullptr;
+#define RT_EMU_CLK , &clk0
+#else
+#define RT_EMU_CLK
+#endif
+	for (uint32_t i = 0; i < n; i++)
+	{
+		// (the entries launch_shade_pt passes over)
+		if (p.depth == 0 && !slot_to_pixel(p.fr, i).valid)
+			continue;
+		const f4 h4 = hits[i];
+		if ((int)fbits(h4.w) < -1)
+			continue;
+		// (what k_shade_pt_lt<TEX, SKY> runs)
+		if (sky.pick > 0.0f)
+			p.textured ? shade_pt_item<true, true, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<false, true, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
+		else
+			p.textured ? shade_pt_item<true, false, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<false, false, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
+	}
+#undef RT_EMU_CLK
 	p.wv.counters->ext[p.depth + 1] += ctx.q_ext.rays, p.wv.counters->shadow[p.depth] += ctx.q_shadow.rays;
 }
 void launch_connect(const Params &p, bool count, uint32_t max_items, stream_t s)
@@ -421,12 +452,12 @@ void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion 
 		for (uint32_t i = 0; i < d.W * d.H; i++)
 			dn_pass_item(d, 1u << k, k + 1u == d.iterations, d.img[k & 1u], d.var[k & 1u], d.img[(k + 1u) & 1u], d.var[(k + 1u) & 1u], i);
 }
-void launch_kat(const Params &p, const SkyView &sky, int function, const float *in, float *out, uint32_t n, stream_t s)
+void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
-	EMU_DEFER(s, launch_kat(p, sky, function, in, out, n, s));
+	EMU_DEFER(s, launch_kat(p, sky, lt, function, in, out, n, s));
 	float pot[POT_SLOTS];
 	for (uint32_t i = 0; i < n; i++)
-		kat_item(p, sky, function, in, out, i, pot);
+		kat_item<true>(p, sky, lt, function, in, out, i, pot);
 }
 void launch_skin_vertices(f4 *verts, f4 *vnormals, const f4 *base_verts, const f4 *base_normals, const uint32_t *joints4,
 						  const f4 *weights4, const float *mats, uint32_t joint_count, uint32_t vertex_count, stream_t s)

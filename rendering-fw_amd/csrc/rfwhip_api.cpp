@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "rt_types.h"
 #include "sky_sampling.h"
+#include "light_tree.h"
 
 #include <algorithm>
 #include <chrono>
@@ -359,6 +360,11 @@ struct rfwhip_context
 	DevBuf d_sky_alias;			 // allocated only while sky_sampling is on
 	rt::SkyView sky_view{};		 // pick == 0: the default kernels run
 	bool sky_stale = false;		 // a sky setting changed since: the next render (or update) refreshes the view
+	// light sampling (light_tree.h): 0 reference, 1 linear, 2 tree; the tree of the lights of the last rfwhip_set_lights
+	int light_sampling = 0;
+	DevBuf d_lt_nodes, d_lt_paths; // allocated only while light_sampling is tree
+	rt::LightTreeView lt_view{};   // nodes == nullptr: linear (or no light with a position)
+	bool lt_stale = false;		   // the setting changed since: the next render (or update) builds the tree
 	uint32_t tlas_root_entry = 0, instance_count = 0;
 	rt::SceneView sv;
 
@@ -483,6 +489,8 @@ static uint32_t local_rows_of(const rfwhip_context *c)
 	return ((strips + c->world - 1) / c->world) * rt::STRIP_ROWS;
 }
 
+static int update_light_tree(rfwhip_context *c, const rt::AreaLight *h_area = nullptr, const rt::PointLight *h_point = nullptr,
+							 const rt::SpotLight *h_spot = nullptr);
 static int sync_all(rfwhip_context *c);
 
 // =================================================================================================================
@@ -558,7 +566,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_sh_dir[0], &c->d_sh_dir[1], &c->d_sh_rad[0], &c->d_sh_rad[1], &c->d_rad[0], &c->d_rad[1],
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
-					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias};
+					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths};
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->guides_valid = false;
@@ -1085,6 +1093,10 @@ extern "C" int rfwhip_set_lights(rfwhip_context *c, rfwhip_light_count n, const 
 	RF_TRY(dm::sync(c->stream));
 	c->lc = n;
 	c->scene_dirty = true;
+	c->lt_stale = true;
+	if (c->light_sampling == 2) // (static_asserts below: the ABI's light records are the kernels')
+		RF_TRY(update_light_tree(c, reinterpret_cast<const rt::AreaLight *>(area), reinterpret_cast<const rt::PointLight *>(point),
+								 reinterpret_cast<const rt::SpotLight *>(spot)));
 	return RFWHIP_OK;
 }
 
@@ -1411,6 +1423,78 @@ static int update_sky_sampling(rfwhip_context *c)
 	return RFWHIP_OK;
 }
 
+// light_sampling=tree: the tree over the lights of the last rfwhip_set_lights.  rfwhip_set_lights hands the host arrays it was
+// given (h_*); rfwhip_update, a render, rfwhip_kat and rfwhip_get_light_tree after the setting changed read the lights back from
+// the device, where rfwhip_set_lights has put them (no host copy is kept).  Every rank of a group builds the same tree from the
+// same lights.  lt_stale is cleared only when the view is complete: after a failure the next render tries again (and fails
+// again) instead of running the linear branch under the name of the tree.
+static int update_light_tree(rfwhip_context *c, const rt::AreaLight *h_area, const rt::PointLight *h_point, const rt::SpotLight *h_spot)
+{
+	c->lt_stale = true;
+	c->lt_view = rt::LightTreeView{};
+	if (c->light_sampling != 2)
+	{
+		if (c->d_lt_nodes.p || c->d_lt_paths.p)
+			RF_TRY(sync_all(c)); // (a frame in flight may still read them)
+		c->d_lt_nodes.free_(), c->d_lt_paths.free_();
+		c->lt_stale = false;
+		return RFWHIP_OK;
+	}
+	const uint32_t na = c->lc.areaLightCount, np = c->lc.pointLightCount, ns = c->lc.spotLightCount, nd = c->lc.directionalLightCount;
+	if ((uint64_t)na + np + ns + nd >= (1ull << 30))
+		return set_error(RFWHIP_ERR_UNSUPPORTED, "light_sampling=tree: too many lights");
+	RF_TRY(sync_all(c));
+	std::vector<rt::AreaLight> area;
+	std::vector<rt::PointLight> point;
+	std::vector<rt::SpotLight> spot;
+	if (na && !h_area)
+	{
+		area.resize(na);
+		RF_TRY(dm::d2h(area.data(), c->d_area.p, na * sizeof(rt::AreaLight), c->stream));
+		h_area = area.data();
+	}
+	if (np && !h_point)
+	{
+		point.resize(np);
+		RF_TRY(dm::d2h(point.data(), c->d_point.p, np * sizeof(rt::PointLight), c->stream));
+		h_point = point.data();
+	}
+	if (ns && !h_spot)
+	{
+		spot.resize(ns);
+		RF_TRY(dm::d2h(spot.data(), c->d_spot.p, ns * sizeof(rt::SpotLight), c->stream));
+		h_spot = spot.data();
+	}
+	std::vector<rt::LightTreeNode> nodes;
+	std::vector<rt::LightTreePath> paths;
+	lighttree::build(h_area, na, h_point, np, h_spot, ns, nd, nodes, paths);
+	rt::LightTreeView view{};
+	view.n_spatial = na + np + ns;
+	view.node_count = (uint32_t)nodes.size();
+	if (!nodes.empty())
+	{
+		// (a sibling pair is one 128-byte line: the table starts on one)
+		RF_TRY(c->d_lt_nodes.ensure(nodes.size() * sizeof(rt::LightTreeNode) + 128));
+		rt::LightTreeNode *base = reinterpret_cast<rt::LightTreeNode *>(((uintptr_t)c->d_lt_nodes.p + 127u) & ~(uintptr_t)127u);
+		RF_TRY(dm::h2d(base, nodes.data(), nodes.size() * sizeof(rt::LightTreeNode), c->stream));
+		view.nodes = base;
+	}
+	else
+		c->d_lt_nodes.free_();
+	if (!paths.empty())
+	{
+		RF_TRY(c->d_lt_paths.ensure(paths.size() * sizeof(rt::LightTreePath)));
+		RF_TRY(dm::h2d(c->d_lt_paths.p, paths.data(), paths.size() * sizeof(rt::LightTreePath), c->stream));
+		view.paths = c->d_lt_paths.as<rt::LightTreePath>();
+	}
+	else
+		c->d_lt_paths.free_();
+	RF_TRY(dm::sync(c->stream));
+	c->lt_view = view;
+	c->lt_stale = false;
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_update(rfwhip_context *c)
 {
 	CTX_ENTER(c);
@@ -1725,6 +1809,8 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 	sv.n_area = c->lc.areaLightCount, sv.n_point = c->lc.pointLightCount, sv.n_spot = c->lc.spotLightCount;
 	sv.n_dir = c->lc.directionalLightCount;
 	RF_TRY(update_sky_sampling(c));
+	if (c->lt_stale)
+		RF_TRY(update_light_tree(c));
 	c->scene_dirty = false;
 	c->scene_version++; // (the denoiser's guides are recomputed)
 	// which instances this update changed (transform, mesh, or the mesh's vertices): the temporal stage does not reproject them
@@ -2027,6 +2113,8 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_render: scene changed since the last rfwhip_update()");
 	if (c->sky_stale)
 		RF_TRY(update_sky_sampling(c));
+	if (c->lt_stale)
+		RF_TRY(update_light_tree(c));
 	if (c->sampler == 1 && !c->have_blue_noise)
 		return set_error(RFWHIP_ERR_STATE, "sampler=bluenoise needs rfwhip_set_blue_noise() first");
 	if (c->max_depth + 2 > rt::MAX_DEPTH_SLOTS)
@@ -2265,7 +2353,10 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 				if (side && d >= 2 && d < c->max_depth) // connect(d - 2) read the buffers shade(d) is about to write
 					RF_TRY(dm::stream_wait_event(s, c->ev_conn[i][d - 2]));
 				StageTimer ts(c, KF_SHADE, -1, s);
-				rtk::launch_shade_pt(p, c->sky_view, n_shade, s);
+				if (c->light_sampling) // (linear | tree: k_shade_pt_lt; the view's nodes are null in linear)
+					rtk::launch_shade_pt_lt(p, c->sky_view, c->lt_view, n_shade, s);
+				else
+					rtk::launch_shade_pt(p, c->sky_view, n_shade, s);
 				ts.stop();
 				// The connection wave of depth d runs beside extend / shade of depth d + 1 on its own stream (it adds into
 				// rad_nee, they into rad).  The connections of the last shade call are never traced
@@ -3118,6 +3209,26 @@ static const Setting k_settings[] = {
 	{"packet", nullptr, GET { return put(out, cap, "%d", (c->packet_ok && (c->refill & 8)) ? 1 : 0); }, false},
 	// triangles in the world tree of the last rfwhip_update (0: none)
 	{"world_tree", nullptr, GET { return put(out, cap, "%zu", c->wtree.valid ? c->wtree.tris : (size_t)0); }, false},
+	// how a next-event vertex picks its light and weights it: reference = the reference's estimator (the
+	// default kernels), linear = its potentials with consistent weights, tree = the light tree with the same weights
+	{"light_sampling", SET {
+		 static const char *const names[] = {"reference", "linear", "tree"};
+		 int mode = -1;
+		 for (int k = 0; k < 3; k++)
+			 if (!strcmp(value, names[k]))
+				 mode = k;
+		 if (mode < 0)
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be \"reference\", \"linear\" or \"tree\"", key);
+		 c->light_sampling = mode;
+		 c->lt_stale = true; // (the next render builds or drops the tree, on the lights of the last rfwhip_set_lights)
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%s", c->light_sampling == 2 ? "tree" : c->light_sampling == 1 ? "linear" : "reference"); }, false},
+	// read-only: nodes of the light tree the next render would use (0: none, or light_sampling is not tree)
+	{"light_tree", nullptr, GET {
+		 if (c->lt_stale)
+			 RF_TRY(update_light_tree(c));
+		 return put(out, cap, "%u", c->lt_view.node_count); },
+	 false},
 	// read-only: p > 0, the pt shade waves run k_shade_pt_sky
 	{"sky", nullptr, GET {
 		 if (c->sky_stale && !c->scene_dirty)
@@ -3678,6 +3789,10 @@ extern "C" int rfwhip_trace_rays_form(rfwhip_context *c, int form, uint32_t grid
 	return trace_form(c, "rfwhip_trace_rays_form", form, grid_items, bins, e, 1e-5f, 1e34f, t, prim, inst, u, v, a, visible, launch_counters);
 }
 
+static_assert(sizeof(rfwhip_area_light) == sizeof(rt::AreaLight) && sizeof(rfwhip_point_light) == sizeof(rt::PointLight) &&
+				  sizeof(rfwhip_spot_light) == sizeof(rt::SpotLight),
+			  "rfwhip_set_lights hands its arrays to the light tree's builder as the kernels' records");
+static_assert(RFWHIP_KAT_LT_SAMPLE == rtk::KAT_LT_SAMPLE && RFWHIP_KAT_LT_PICK_PROB == rtk::KAT_LT_PICK_PROB, "kernels.h restates the light-tree functions");
 static_assert(RFWHIP_KAT_IN == 24 && RFWHIP_KAT_OUT == 8, "kat_item's record layout (kernels.hip)");
 static_assert(RFWHIP_STRIP_ROWS == (int)rt::STRIP_ROWS, "rfwhip.h: rfwhip_row_owner() restates rt::strip_owner()");
 extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float *in, float *out)
@@ -3685,7 +3800,7 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 	CTX_ENTER(c);
 	if (n && (!in || !out))
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: null records");
-	if (function < 0 || function > RFWHIP_KAT_SURFACE_LAYERS)
+	if (function < 0 || function > RFWHIP_KAT_LT_PICK_PROB)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: unknown function %d", function);
 	if ((function == RFWHIP_KAT_POINT_ON_LIGHT || function == RFWHIP_KAT_LIGHT_PICK_PROB) && c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the light functions use the lights of the last rfwhip_update()");
@@ -3693,6 +3808,21 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 		RF_TRY(update_sky_sampling(c));
 	if ((function == RFWHIP_KAT_SKY_SAMPLE || function == RFWHIP_KAT_SKY_PDF) && (c->scene_dirty || !c->sky_view.table))
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the sky functions use the table of the last rfwhip_update() with sky_sampling=1 and a sky with light");
+	if (function == RFWHIP_KAT_LT_SAMPLE || function == RFWHIP_KAT_LT_PICK_PROB)
+	{
+		if (c->scene_dirty || c->light_sampling != 2)
+			return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the light-tree functions use the tree of the last rfwhip_update() with light_sampling=tree");
+		if (c->lt_stale)
+			RF_TRY(update_light_tree(c));
+		// (the kernel indexes the path table with the light a record names)
+		for (size_t i = 0; i < n && function == RFWHIP_KAT_LT_PICK_PROB; i++)
+		{
+			uint32_t light;
+			memcpy(&light, in + i * RFWHIP_KAT_IN + 8, sizeof(light));
+			if (light >= total_light_count(c))
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: record %zu names light %u of %u", i, light, total_light_count(c));
+		}
+	}
 	if (function == RFWHIP_KAT_BLUE_NOISE && !c->have_blue_noise)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: no blue-noise table (rfwhip_set_blue_noise)");
 	if ((function == RFWHIP_KAT_TEX_FETCH || function == RFWHIP_KAT_SURFACE_LAYERS) && c->scene_dirty)
@@ -3732,7 +3862,7 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 		rtk::Params p;
 		fill_params(c, nullptr, p);
 		p.cam.blue_noise = c->have_blue_noise ? c->d_blue_noise.as<uint32_t>() : nullptr;
-		rtk::launch_kat(p, c->sky_view, function, d_in.as<float>(), d_out.as<float>(), (uint32_t)n, c->stream);
+		rtk::launch_kat(p, c->sky_view, c->lt_view, function, d_in.as<float>(), d_out.as<float>(), (uint32_t)n, c->stream);
 		rc = dm::last_launch_error();
 	}
 	if (!rc)
@@ -3800,6 +3930,33 @@ extern "C" int rfwhip_get_bvh(rfwhip_context *c, size_t mesh_index, rfwhip_bvh_n
 	if (prim_indices && prim_cap)
 		memcpy(prim_indices, m.bvh.order.data(), std::min(prim_cap, m.bvh.order.size()) * 4);
 	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_get_light_tree(rfwhip_context *c, rfwhip_light_tree_node *nodes, size_t node_cap, rfwhip_light_tree_path *paths,
+									 size_t light_cap)
+{
+	static_assert(sizeof(rfwhip_light_tree_node) == sizeof(rt::LightTreeNode) && sizeof(rfwhip_light_tree_path) == sizeof(rt::LightTreePath),
+				  "rfwhip_abi.h restates the light tree's records");
+	if (!c)
+		return -set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null context");
+	if (c->cleaned)
+		return -set_error(RFWHIP_ERR_STATE, "context already cleaned up");
+	if (dm::use(c->device))
+		return -RFWHIP_ERR_HIP;
+	if (c->lt_stale && update_light_tree(c))
+		return -RFWHIP_ERR_STATE;
+	if (c->light_sampling != 2)
+		return 0;
+	if (sync_all(c))
+		return -RFWHIP_ERR_STATE;
+	// no host copy is kept: fetched on demand (a test hook)
+	if (nodes && node_cap && c->lt_view.nodes &&
+		dm::d2h(nodes, c->lt_view.nodes, std::min<size_t>(node_cap, c->lt_view.node_count) * sizeof(rt::LightTreeNode), c->stream))
+		return -RFWHIP_ERR_STATE;
+	if (paths && light_cap && c->lt_view.paths &&
+		dm::d2h(paths, c->lt_view.paths, std::min<size_t>(light_cap, total_light_count(c)) * sizeof(rt::LightTreePath), c->stream))
+		return -RFWHIP_ERR_STATE;
+	return (int)c->lt_view.node_count;
 }
 
 extern "C" int rfwhip_get_bvh4(rfwhip_context *c, size_t mesh_index, void *nodes4c, void *nodes4f, uint32_t *src4, size_t node_cap,

@@ -1683,6 +1683,287 @@ RT_FN f3 random_point_on_light(const SceneView &sc, float r0, float r1, f3 I, f3
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// light tree (setting light_sampling = linear | tree; the tree: light_tree.h; formulas: include/rfwhip.h)
+// ---------------------------------------------------------------------------------------------------------------
+// A bounding cosine, c + LT_COS_SLACK cut off at 0: it reaches 0 only LT_COS_SLACK radians past pi / 2.  The cosines below come out
+// of products of rounded sines and cosines, and a light whose potential is positive must never lose a node of its path to the last
+// bit of one of them (the bound has to be conservative, or the estimator is biased).  Continuous, so that the float64 model of the
+// tests and this code agree to rounding everywhere.
+constexpr float LT_COS_SLACK = 1e-5f;
+// d <= r (the point is inside the node's bounding sphere): E / max(r^2, LT_R2_FLOOR).  The floor keeps the importance of a lone
+// point light finite at its own position (r = 0); it is far below the square of any extent a scene has.
+constexpr float LT_R2_FLOOR = 1e-12f;
+RT_FN float lt_cos_bound(float c) { return fmaxf(0.0f, c + LT_COS_SLACK); }
+// cos(max(0, a - b)) for a in [0, pi], b in [0, pi / 2] from their sines and cosines
+RT_FN float lt_cos_sub(float cos_a, float cos_b, float sin_b)
+{
+	if (cos_a >= cos_b)
+		return 1.0f;
+	const float sin_a = m_sqrtf(fmaxf(0.0f, 1.0f - cos_a * cos_a));
+	return lt_cos_bound(cos_a * cos_b + sin_a * sin_b);
+}
+// The importance of a node for the point I with shading normal N: with c, r the centre and radius of the box's bounding sphere,
+// v = I - c, d = |v|, theta_u = asin(r / d), theta = angle(axis, v), theta_i = angle(N, -v):
+//     E cos(max(0, theta - theta_o - theta_u)) cos(max(0, theta_i - theta_u)) / d^2,     E / max(r^2, floor) for d <= r.
+RT_FN float lt_importance(const LightTreeNode &n, f3 I, f3 N)
+{
+	const f3 lo = ld3(n.lo), hi = ld3(n.hi);
+	const f3 c = (lo + hi) * 0.5f, h = (hi - lo) * 0.5f;
+	const float r2 = dot(h, h);
+	const f3 v = I - c;
+	const float d2 = dot(v, v);
+	if (!(d2 > r2))
+		return n.energy * m_rcp(fmaxf(r2, LT_R2_FLOOR));
+	const float inv_d = m_rcp(m_sqrtf(d2));
+	const float sin_u = fminf(1.0f, m_sqrtf(r2) * inv_d);
+	const float cos_u = m_sqrtf(fmaxf(0.0f, 1.0f - sin_u * sin_u));
+	const f3 w = v * inv_d;
+	// the light's side: theta against theta_s = theta_o + theta_u (up to 3 pi / 2)
+	float t_o = 1.0f;
+	if (n.cos_o > -1.0f)
+	{
+		const float cos_o = n.cos_o, sin_o = m_sqrtf(fmaxf(0.0f, 1.0f - cos_o * cos_o));
+		const float cos_s = cos_o * cos_u - sin_o * sin_u, sin_s = sin_o * cos_u + cos_o * sin_u;
+		const float cos_t = clampf(dot(ld3(n.axis), w), -1.0f, 1.0f);
+		if (sin_s >= 0.0f && cos_t < cos_s) // (theta_s < pi and theta > theta_s)
+		{
+			const float sin_t = m_sqrtf(fmaxf(0.0f, 1.0f - cos_t * cos_t));
+			t_o = lt_cos_bound(cos_t * cos_s + sin_t * sin_s);
+		}
+	}
+	// the receiver's side
+	const float t_i = lt_cos_sub(clampf(-dot(N, w), -1.0f, 1.0f), cos_u, sin_u);
+	return ((n.energy * t_o) * t_i) * m_rcp(d2);
+}
+// The top of the selection: the tree's root by its importance, then the directional lights by pot_dir, in that order.
+// Returns the sum; w_root = the root's share of it.
+RT_FN float lt_top(const SceneView &sc, const LightTreeView &lt, f3 I, f3 N, float &w_root)
+{
+	w_root = 0.0f;
+	if (lt.n_spatial)
+	{
+		const LightTreeNode root = lt.nodes[0];
+		w_root = lt_importance(root, I, N);
+	}
+	float sd = 0.0f;
+	for (uint32_t i = 0; i < sc.n_dir; i++)
+		sd += pot_dir(sc, i, N);
+	return w_root + sd;
+}
+// One level: the importances of the children of a node (`child`: its left child) -> the probabilities of going left and right
+// (0, 0: nowhere to go); L, R: what the descent needs of the two children (child, light, count)
+struct LtChild
+{
+	uint32_t child, light, count;
+};
+RT_FN void lt_level(const LightTreeView &lt, uint32_t child, f3 I, f3 N, float &pl, float &pr, LtChild &cl, LtChild &cr)
+{
+	const LightTreeNode L = lt.nodes[child], R = lt.nodes[child + 1u];
+	const float wl = lt_importance(L, I, N), wr = lt_importance(R, I, N);
+	const float s = wl + wr;
+	pl = 0.0f, pr = 0.0f;
+	if (s > 0.0f)
+		pl = m_div(wl, s), pr = m_div(wr, s);
+	cl.child = L.child, cl.light = L.light, cl.count = L.count;
+	cr.child = R.child, cr.light = R.light, cr.count = R.count;
+}
+// Draws a light: r1 chooses among [tree, directional 0 .. k - 1] and is rescaled into the interval of what it chose at every level
+// (left child first).  Returns false for "no light" (nothing has a positive importance).  q = the probability of `light`,
+// rank = its position in the order r1 walks through (leaves left to right, then the directional lights).
+RT_FN bool lt_sample(const SceneView &sc, const LightTreeView &lt, float r1, f3 I, f3 N, uint32_t &light, float &q, uint32_t &rank)
+{
+	light = 0u, q = 0.0f, rank = 0u;
+	float w_root;
+	const float sum = lt_top(sc, lt, I, N, w_root);
+	if (!(sum > 0.0f))
+		return false;
+	const float x = r1 * sum;
+	const float sd = sum - w_root;
+	if (!(w_root > 0.0f && (x < w_root || !(sd > 0.0f))))
+	{
+		// a directional light: the first whose running sum reaches x (the last with a positive potential, should rounding leave none)
+		const float x2 = x - w_root;
+		float total = 0.0f, mine = 0.0f;
+		uint32_t k = 0u;
+		for (uint32_t i = 0; i < sc.n_dir; i++)
+		{
+			const float p = pot_dir(sc, i, N);
+			if (p > 0.0f)
+			{
+				k = i, mine = p, total += p;
+				if (total >= x2)
+					break;
+			}
+		}
+		if (!(mine > 0.0f))
+			return false;
+		light = lt.n_spatial + k, rank = light;
+		q = m_div(mine, sum);
+		return true;
+	}
+	q = m_div(w_root, sum);
+	float u = fminf(m_div(x, w_root), 0.99999994f);
+	LtChild cur;
+	{
+		const LightTreeNode root = lt.nodes[0];
+		cur.child = root.child, cur.light = root.light, cur.count = root.count;
+	}
+	for (uint32_t level = 0; level <= 32u; level++)
+	{
+		if (cur.child == 0u)
+		{
+			light = cur.light;
+			return true;
+		}
+		float pl, pr;
+		LtChild cl, cr;
+		lt_level(lt, cur.child, I, N, pl, pr, cl, cr);
+		if (!(pl + pr > 0.0f))
+			break;
+		if (u < pl)
+		{
+			q = q * pl;
+			u = fminf(m_div(u, pl), 0.99999994f);
+			cur = cl;
+		}
+		else
+		{
+			q = q * pr;
+			u = fminf(fmaxf(m_div(u - pl, pr), 0.0f), 0.99999994f);
+			rank += cl.count;
+			cur = cr;
+		}
+	}
+	q = 0.0f;
+	return false;
+}
+// The probability with which lt_sample draws `light` at (I, N): the same operations in the same order along the light's stored path.
+RT_FN float lt_pick_prob(const SceneView &sc, const LightTreeView &lt, uint32_t light, f3 I, f3 N)
+{
+	float w_root;
+	const float sum = lt_top(sc, lt, I, N, w_root);
+	if (!(sum > 0.0f))
+		return 0.0f;
+	if (light >= lt.n_spatial)
+	{
+		const uint32_t k = light - lt.n_spatial;
+		return k < sc.n_dir ? m_div(fmaxf(pot_dir(sc, k, N), 0.0f), sum) : 0.0f;
+	}
+	if (!(w_root > 0.0f))
+		return 0.0f;
+	float q = m_div(w_root, sum);
+	const LightTreePath path = lt.paths[light];
+	uint32_t child = lt.nodes[0].child;
+	for (uint32_t level = 0; level < path.depth && level < 32u; level++)
+	{
+		float pl, pr;
+		LtChild cl, cr;
+		lt_level(lt, child, I, N, pl, pr, cl, cr);
+		const bool right = (path.bits >> level) & 1u;
+		q = q * (right ? pr : pl);
+		child = right ? cr.child : cl.child;
+	}
+	return q;
+}
+// The point r0's barycentrics (`bary`) give on `light`, its radiance, and the density the consistent weights of light_sampling =
+// linear | tree divide by: an area light's solid-angle density dist^2 / (area LNdotL) — without the reference's 1 / |radiance| —
+// and a delta light's lightPdf exactly as random_point_on_light gives it (delta = true: no BSDF ray finds such a light).
+RT_FN f3 lt_point_on_light(const SceneView &sc, uint32_t li, f3 bary, f3 I, f3 N, float &lightPdf, f3 &lightColor, bool &delta)
+{
+	delta = li >= sc.n_area;
+	if (li < sc.n_area)
+	{
+		const AreaLight &l = sc.area[li];
+		lightColor = ld3(l.radiance);
+		const f3 LN = ld3(l.normal);
+		const f3 P = (ld3(l.vertex0) * bary.x + ld3(l.vertex1) * bary.y) + ld3(l.vertex2) * bary.z;
+		f3 L = I - P;
+		const float sqDist = dot(L, L);
+		L = normalize(L);
+		const float LNdotL = dot(L, LN);
+		lightPdf = (LNdotL > 0 && dot(L, N) < 0) ? m_div(sqDist, l.area * LNdotL) : 0;
+		return P;
+	}
+	li -= sc.n_area;
+	if (li < sc.n_point)
+	{
+		const PointLight &l = sc.point[li];
+		const f3 pos = ld3(l.position);
+		lightColor = ld3(l.radiance);
+		const f3 L = I - pos;
+		lightPdf = dot(L, N) < 0 ? m_div(dot(L, L), l.energy) : 0;
+		return pos;
+	}
+	li -= sc.n_point;
+	if (li < sc.n_spot)
+	{
+		const SpotLight &l = sc.spot[li];
+		const f3 P = ld3(l.position);
+		f3 L = I - P;
+		const float sqDist = dot(L, L);
+		L = normalize(L);
+		const float d = m_div(fmaxf(0.0f, dot(L, ld3(l.direction)) - l.cosOuter), l.cosInner - l.cosOuter);
+		const float LNdotL = fminf(1.0f, d);
+		lightPdf = (LNdotL > 0 && dot(L, N) < 0) ? m_div(sqDist, LNdotL * l.energy) : 0;
+		lightColor = ld3(l.radiance);
+		return P;
+	}
+	li -= sc.n_spot;
+	const DirectionalLight &l = sc.dir[li];
+	const f3 L = ld3(l.direction);
+	lightColor = ld3(l.radiance);
+	lightPdf = dot(L, N) < 0 ? m_rcp(l.energy) : 0;
+	return I - L * 1000.0f;
+}
+// The probability with which random_point_on_light draws area light `idx` together with the point of barycentrics `bary` on it:
+// its rule weighs every light at the point the SAME barycentrics give on it (the barycentrics are drawn first, then the light).
+// light_pick_prob (lights.h:83-116) weighs every light in the direction of the one hit point instead — close, but not the rule
+// that picks, and the two ways of finding an emitter must be weighted by the same rule or their weights do not add up to one.
+RT_FN float lt_linear_pick_prob(const SceneView &sc, uint32_t idx, f3 O, f3 N, f3 bary)
+{
+	float sum = 0, mine = 0;
+	for (uint32_t i = 0; i < sc.n_area; i++)
+	{
+		const float p = pot_area(sc, i, O, N, mk3(0, 0, 0), bary);
+		if (i == idx)
+			mine = p;
+		sum += p;
+	}
+	for (uint32_t i = 0; i < sc.n_point; i++)
+		sum += pot_point(sc, i, O, N);
+	for (uint32_t i = 0; i < sc.n_spot; i++)
+		sum += pot_spot(sc, i, O, N);
+	for (uint32_t i = 0; i < sc.n_dir; i++)
+		sum += pot_dir(sc, i, N);
+	if (sum <= 0)
+		return 0;
+	return m_div(mine, sum);
+}
+// Next-event sampling of light_sampling = linear (lt.nodes null: random_point_on_light's choice and pickProb, bit for bit) and
+// tree.  lightPdf = 0: no light.
+RT_FN f3 lt_random_point_on_light(const SceneView &sc, const LightTreeView &lt, float r0, float r1, f3 I, f3 N, float &pickProb,
+								  float &lightPdf, f3 &lightColor, uint32_t &light, bool &delta, float *pot_cache RT_CLK_PARAM)
+{
+	f3 P = mk3(1, 1, 1);
+	delta = false;
+	bool found;
+	if (lt.nodes == nullptr) // (wave-uniform: a kernel argument)
+	{
+		P = random_point_on_light(sc, r0, r1, I, N, pickProb, lightPdf, lightColor, light, pot_cache RT_CLK_ARG);
+		found = lightPdf > 0;
+	}
+	else
+	{
+		uint32_t rank;
+		found = lt_sample(sc, lt, r1, I, N, light, pickProb, rank);
+	}
+	lightPdf = 0;
+	if (found)
+		P = lt_point_on_light(sc, light, random_barycentrics(r0), I, N, lightPdf, lightColor, delta);
+	return P;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // sky sampling (setting sky_sampling; the table: sky_sampling.h; formulas: include/rfwhip.h)
 // ---------------------------------------------------------------------------------------------------------------
 // a texel's weight: its luminance, 0 for a negative or NaN one (the host's table and this must agree on which texels are black)
@@ -1856,8 +2137,12 @@ RT_FN void pt_textures(const SceneView &sc, const CamView &cam, f3 D, float t, c
 // finding the sky — that sample and a BSDF-sampled miss after a non-specular vertex — are weighted against each other (balance
 // heuristic); the lights' selection probability and the emitter hit's weight take the factor 1 - p.  Every line of it sits under
 // SKY: the default kernels (SKY = false) are the code they were.
-template <bool TEX, bool SKY, class Sink>
-RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const CamView &cam, const FrameView &fr, uint32_t max_depth, bool active,
+// LT = true (setting light_sampling = linear | tree): the light of a next-event vertex is drawn by lt_random_point_on_light — through
+// the light tree, or by today's potentials when lt.nodes is null — and the weights are consistent: an area light's next-event term
+// divides by shadowPdf + q p_omega with its solid-angle density p_omega, a delta light's by q lightPdf alone, and an emitter a BSDF
+// ray finds takes its q from the rule that picks.  Every line of it sits under LT.
+template <bool TEX, bool SKY, bool LT, class Sink>
+RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const LightTreeView &lt, const CamView &cam, const FrameView &fr, uint32_t max_depth, bool active,
 					const PathIn &in, const Hit &h, ShadeOut &out, float *pot_cache, Sink &sink RT_CLK_PARAM)
 {
 	out.radiance = mk3(0, 0, 0);
@@ -1947,7 +2232,7 @@ RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const CamView &cam,
 					const int ltri = sf.ltri;
 					// the reference reads the material id as light index (device_structs.h:37,40); lightTriIdx is meant
 					float pickProb =
-						(ltri >= 0 && (uint32_t)ltri < sc.n_area) ? light_pick_prob(sc, ltri, in.O, lastN, I) : 0.0f;
+						(ltri >= 0 && (uint32_t)ltri < sc.n_area) ? (LT ? (lt.nodes != nullptr ? lt_pick_prob(sc, lt, (uint32_t)ltri, in.O, lastN) : lt_linear_pick_prob(sc, (uint32_t)ltri, in.O, lastN, mk3(sf.bw0, sf.bw1, sf.bw2))) : light_pick_prob(sc, ltri, in.O, lastN, I)) : 0.0f;
 					if (SKY)
 						pickProb = pickProb * (1.0f - sky.pick);
 					if ((in.bsdfPdf + lightPdf * pickProb) <= 0)
@@ -1972,6 +2257,12 @@ RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const CamView &cam,
 			else
 				flags &= ~1u;
 			seed = wang_hash(pixel * 16789u + sampleIdx * 1791u + in.depth * 720898027u);
+			// (LT: a stream of the vertex's own.  The reference's seed of depth 0 is the primary ray's (pt_primary_ray): its light
+			// selection number IS the pixel jitter's second coordinate, so which light a vertex picks depends on where in the pixel it
+			// lies, and the expectation over a pixel then depends on the picking rule — by several per cent of a tile at low
+			// resolutions.  The consistent weights promise an expectation that does not: DESIGN.md section 12.)
+			if (LT)
+				seed = wang_hash(seed + 0x632BE5ABu);
 			flip = (dot(D, N) > 0) ? -1.0f : 1.0f;
 			N = N * flip;
 			iN = iN * flip;
@@ -1998,6 +2289,7 @@ RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const CamView &cam,
 				// sky: q1 < p picks the sky, with (q0, q1 / p); a light is picked with (q0, (q1 - p) / (1 - p)) and probability 1 - p
 				const bool sky_nee = SKY && (q1 < sky.pick || sky.pick >= 1.0f);
 				float skyPdf = 0.0f;
+				bool delta = false; // (LT: a point, spot or directional light was drawn)
 				if (sky_nee)
 				{
 					const float coin = random_float(seed), a = random_float(seed), b = random_float(seed);
@@ -2012,7 +2304,10 @@ RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const CamView &cam,
 				{
 					if (SKY)
 						q1 = (q1 - sky.pick) * sky.inv_rest;
-					L = random_point_on_light(sc, q0, q1, I, iN, pickProb, lightPdf, lightColor, light, pot_cache RT_CLK_ARG) - I;
+					if (LT)
+						L = lt_random_point_on_light(sc, lt, q0, q1, I, iN, pickProb, lightPdf, lightColor, light, delta, pot_cache RT_CLK_ARG) - I;
+					else
+						L = random_point_on_light(sc, q0, q1, I, iN, pickProb, lightPdf, lightColor, light, pot_cache RT_CLK_ARG) - I;
 					if (SKY)
 						pickProb = pickProb * (1.0f - sky.pick);
 					RT_TICK(12);
@@ -2030,6 +2325,8 @@ RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const CamView &cam,
 						// the same integral as the miss branch's
 						f3 contribution = sky_nee ? ((T * bs) * lightColor) * m_div(NdotL, (shadowPdf + sky.pick * skyPdf) * survival_probability(T))
 												  : ((T * bs) * lightColor) * m_div(NdotL, shadowPdf + lightPdf * pickProb);
+						if (LT && delta)
+							contribution = ((T * bs) * lightColor) * m_div(NdotL, lightPdf * pickProb);
 						contribution = clamp_intensity(contribution, cam.clamp_value);
 						if (!any_nan(contribution))
 						{

@@ -360,6 +360,34 @@ struct SkyView
 	FastDiv div_w;		 // texel index -> row
 };
 
+// Light tree (setting light_sampling=tree; the host build: light_tree.h; formulas: include/rfwhip.h): a binary
+// tree over the area, point and spot lights in pot_any()'s index order.  Node 0 is the root, node 1 is unused, and the two children
+// of a node sit side by side from an even index on: one 128-byte line holds a sibling pair.
+struct alignas(64) LightTreeNode
+{
+	float lo[3], energy; // box of the lights below; sum of their energies (negative / NaN: 0)
+	float hi[3], cos_o;	 // cosine of the half angle of the normals' cone; -1: every direction (a point or spot light below)
+	float axis[3];		 // the cone's axis
+	uint32_t child;		 // left child, the right one is child + 1; 0: a leaf
+	uint32_t light;		 // a leaf's light
+	uint32_t count;		 // lights below
+	uint32_t pad[2];
+};
+static_assert(sizeof(LightTreeNode) == 64, "light-tree node");
+// A light's way down from the root: bit i set = right at level i; `depth` levels.  (Directional lights are not in the tree: 0, 0.)
+struct LightTreePath
+{
+	uint32_t bits, depth;
+};
+static_assert(sizeof(LightTreePath) == 8, "light-tree path");
+// What k_shade_pt_lt needs beyond the scene.  nodes == nullptr: light_sampling=linear (today's potentials, the consistent weights).
+struct LightTreeView
+{
+	const LightTreeNode *nodes;
+	const LightTreePath *paths;
+	uint32_t node_count, n_spatial; // n_spatial = n_area + n_point + n_spot: the lights in the tree
+};
+
 // Which image rows this rank owns, and how path slots map to pixels.
 struct FrameView
 {

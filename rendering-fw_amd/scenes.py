@@ -600,6 +600,85 @@ def terrain(n=708, extent=100.0, height=6.0, seed=0x5EED, width=1920, height_px=
     return s
 
 
+def add_lamp(s, n, center=(0.0, 6.0, 0.0), radius=1.0, color=(12.0, 10.4, 8.0)):
+    """An emissive sphere of exactly n triangles as real geometry (bands of latitude, cut off after n triangles), with the n
+    area lights rfw::system derives from it: Scene.update_area_lights for this one mesh, vectorised — a lamp of tens of
+    thousands of triangles takes milliseconds.  For the light-tree tests and tools/light_tree_time.py."""
+    n = int(n)
+    cols = max(3, int(math.ceil(math.sqrt(n / 2.0))))
+    rows = max(1, int(math.ceil(n / (2.0 * cols))))
+    # latitudes strictly inside (0, pi): no degenerate triangles at the poles
+    th = np.linspace(0.08 * np.pi, 0.92 * np.pi, rows + 1)
+    ph = np.linspace(0.0, 2.0 * np.pi, cols, endpoint=False)
+    d = np.stack([np.sin(th)[:, None] * np.cos(ph)[None, :], np.repeat(np.cos(th)[:, None], cols, 1),
+                  np.sin(th)[:, None] * np.sin(ph)[None, :]], -1)
+    verts = (np.asarray(center, np.float64) + radius * d).reshape(-1, 3).astype(np.float32)
+    r, c = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    a, b = (r * cols + c).ravel(), (r * cols + (c + 1) % cols).ravel()
+    idx = np.empty((2 * rows * cols, 3), np.uint32)
+    idx[0::2] = np.stack([a, b, a + cols], 1)          # outward-facing winding
+    idx[1::2] = np.stack([b, b + cols, a + cols], 1)
+    idx = idx[:n]
+    em = s.add_material(color=color, roughness=1.0)
+    mesh = s.add_mesh(verts, idx, material=em)
+    inst = s.add_instance(mesh)
+    tris = s.meshes[mesh]["triangles"]
+    base = len(s.area_lights)
+    lights = np.zeros(n, dtype=abi.AREA_LIGHT_DTYPE)
+    v0, v1, v2 = tris["vertex0"][:, :3], tris["vertex1"][:, :3], tris["vertex2"][:, :3]
+    lights["vertex0"], lights["vertex1"], lights["vertex2"] = v0, v1, v2
+    lights["position"] = (v0 + v1 + v2) * np.float32(1.0 / 3.0)
+    col = np.asarray(color, np.float32)
+    lights["energy"] = np.float32(np.linalg.norm(col))
+    lights["radiance"] = col
+    lights["normal"] = np.stack([tris["Nx"], tris["Ny"], tris["Nz"]], 1)
+    lights["triIdx"], lights["instIdx"] = np.arange(n), inst
+    lights["area"] = tris["area"]
+    tris["lightTriIdx"] = base + np.arange(n)
+    s.area_lights = np.concatenate([s.area_lights, lights])
+    return mesh
+
+
+def lamp_scene(n=300, width=480, height=270, extras=True, ground=24):
+    """A bumpy ground under an open sky-less dome with a lamp of n emissive triangles (add_lamp) above it; extras: two point
+    lights, a spot and a directional light beside the lamp — every kind of light the light tree and its flat list handle."""
+    s = Scene()
+    s.name = "lamp_%d" % n
+    g = np.arange(ground + 1)
+    ix, iz = np.meshgrid(g, g, indexing="xy")
+    ext = 20.0
+    x, z = (ix / ground - 0.5) * ext, (iz / ground - 0.5) * ext
+    y = 0.6 * (_hash01(ix // 3, iz // 3, 0x1A3F) - 0.5) + 0.15 * (_hash01(ix, iz, 0x77) - 0.5)
+    verts = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
+    i00 = (iz[:-1, :-1] * (ground + 1) + ix[:-1, :-1]).ravel()
+    i10, i01, i11 = i00 + 1, i00 + (ground + 1), i00 + (ground + 2)
+    idx = np.empty((2 * ground * ground, 3), np.uint32)
+    idx[0::2] = np.stack([i00, i01, i10], 1)
+    idx[1::2] = np.stack([i10, i01, i11], 1)
+    p0, p1, p2 = verts[idx[:, 0]], verts[idx[:, 1]], verts[idx[:, 2]]
+    vn = _accumulate_vertex_normals(len(verts), idx, np.cross(p1 - p0, p2 - p0))
+    matte = s.add_material(color=(0.6, 0.55, 0.5), roughness=0.9)
+    gloss = s.add_material(color=(0.8, 0.8, 0.85), roughness=0.3, metallic=0.5)
+    cell = np.arange(2 * ground * ground) // 2
+    mats = np.where(((cell % ground) // 4 + (cell // ground) // 4) % 3 == 0, gloss, matte).astype(np.uint32)
+    s.add_instance(s.add_mesh(verts, idx, normals=vn, material=mats))
+    bv, bi = _box((-0.5, 0.0, -0.5), (0.5, 1.0, 0.5))
+    box = s.add_mesh(bv, bi, material=matte)
+    s.add_instance(box, _translate(-3.0, 0.2, 1.0) @ _rot_y(25) @ np.diag([2.0, 3.0, 2.0, 1.0]))
+    s.add_instance(box, _translate(3.5, 0.2, -1.5) @ _rot_y(-20) @ np.diag([2.5, 1.5, 2.5, 1.0]))
+    add_lamp(s, n, center=(0.5, 5.0, 0.5), radius=1.2)
+    if extras:
+        s.add_point_light((-6.0, 4.0, -4.0), (30.0, 26.0, 20.0))
+        s.add_point_light((6.0, 3.0, 5.0), (12.0, 18.0, 26.0))
+        s.add_spot_light((0.0, 7.0, -7.0), 20.0, (60.0, 60.0, 50.0), 35.0, (0.0, -1.0, 0.8))
+        s.add_directional_light((0.4, -1.0, 0.3), (0.8, 0.8, 0.9))
+    cam = Camera(aperture=0.0, FOV=50.0, focalDistance=5.0)
+    cam.look_at((0.5, 6.5, -15.0), (0.0, 2.0, 0.0))
+    cam.resize(width, height)
+    s.camera = cam
+    return s
+
+
 def _checker_texture(size, c0, c1, cells=8, seed=1):
     yy, xx = np.mgrid[0:size, 0:size]
     m = (((xx * cells) // size + (yy * cells) // size) % 2).astype(np.float32)[..., None]
