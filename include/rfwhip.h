@@ -137,6 +137,41 @@ RFWHIP_API int rfwhip_read_local_framebuffer_stream(rfwhip_context *ctx, void *r
 RFWHIP_API int rfwhip_deinterleave_stream(rfwhip_context *ctx, const void *gathered_device, void *rgba_device,
 										  void *hip_stream);
 
+/* ---- display stage (no GL needed: the reference does these steps in its GL shaders) -------------------------------------
+ * The presented linear float4 image -> something a host can show or save: the reference's ACES tone map with the camera's
+ * brightness and contrast (rfw::system::render_frame(camera, status, toneMap), assets/shaders/tone-map.frag, system.cpp:682-711),
+ * the FXAA of its window blit (assets/shaders/draw-tex-fxaa.vert:15-22, .frag:17-57), an optional sRGB encoding, and 8-bit
+ * quantisation, in ONE kernel on the device (csrc/display.h has the formulas).  The stage always runs on the
+ * FULL image — after the gather and after the denoiser, on the root — never on a rank's strips (FXAA needs a pixel's neighbours).
+ * Every entry point above still returns linear float4; with the display settings at their defaults and none of the calls below
+ * made, nothing changes.
+ *   Settings (not listed by rfwhip_get_settings):
+ *     display_tonemap = "aces" (default) | "none" (clamp to [0, 1] only)
+ *     display_fxaa    = "0" | "1" (default)
+ *     display_srgb    = "0" (default: the reference's bytes) | "1" (the sRGB OETF on the colour channels)
+ *   Per colour channel x of a pixel: v = min(max(x - 0.5 contrast + 0.5 + brightness, 0), 65504); a NaN channel becomes 0; the upper
+ *   clamp (our one deviation from the reference, for non-finite input only) keeps +inf finite.  alpha = clamp(in.w, 0, 1), untouched
+ *   by FXAA and the encoding.  Brightness and contrast: the camera of the last rfwhip_render; before the first render the
+ *   reference's defaults (0.05, 1; Camera.cpp:8-9) applied to the empty image.
+ *   Formats: RGBA8 = 4 bytes per pixel, R in the lowest byte, each (int)rintf(c * 255); RGBA32F = the same values as 4 floats. */
+enum rfwhip_display_format
+{
+	RFWHIP_DISPLAY_RGBA8 = 0,
+	RFWHIP_DISPLAY_RGBA32F = 1
+};
+/* World-1 contexts: present -> denoise when on -> display, into host or device memory of width * height * (4 | 16) bytes.  The host
+ * variant copies only the format's bytes. */
+RFWHIP_API int rfwhip_read_display(rfwhip_context *ctx, int format, void *out_host);
+RFWHIP_API int rfwhip_read_display_device(rfwhip_context *ctx, int format, void *out_device);
+/* Stream-ordered: the stage on a full float4 image in device memory, enqueued on the caller's hipStream_t; nothing waits on the host.
+ * A rfwhip_comm_* host calls it on the root behind rfwhip_comm_gather (ordered by the caller: rfwhip_comm_wait or an event).  The input
+ * is read-only and in place is not allowed: rgba_device == out_device is RFWHIP_ERR_INVALID_ARGUMENT. */
+RFWHIP_API int rfwhip_display_stream(rfwhip_context *ctx, const void *rgba_device, void *out_device, int format, void *hip_stream);
+/* Known-answer hook, the counterpart of rfwhip_denoise_image: the stage on a host image of the context's target size with the
+ * context's display settings and the given brightness and contrast. */
+RFWHIP_API int rfwhip_display_image(rfwhip_context *ctx, const float *rgba_in, float brightness, float contrast, int format,
+									void *out_host);
+
 /* Where a context runs and what it renders into (for hosts that move its strips themselves). */
 RFWHIP_API int rfwhip_get_placement(rfwhip_context *ctx, int *device_ordinal, int *rank, int *world);
 RFWHIP_API int rfwhip_get_target_size(rfwhip_context *ctx, uint32_t *width, uint32_t *height);
@@ -186,6 +221,14 @@ RFWHIP_API int rfwhip_group_framebuffer_device(rfwhip_group *group, void **rgba_
 #define RFWHIP_PRESENT_SLOTS 4
 RFWHIP_API int rfwhip_group_present_async(rfwhip_group *group, int slot);
 RFWHIP_API int rfwhip_group_present_wait(rfwhip_group *group, int slot, const float **rgba_host);
+/* The display stage for a group (see rfwhip_read_display): read_display = gather + display on the root + wait + copy of the format's
+ * bytes.  present_display_async / _wait are present_async / _wait with the display stage behind the gather: the same slots, streams
+ * and events, and the copy carries the display image (a quarter of the float image's bytes for RGBA8).  A slot remembers what was
+ * last presented into it: rfwhip_group_present_wait on a slot that holds a display image, and rfwhip_group_present_display_wait on
+ * one that holds a float image, return RFWHIP_ERR_STATE. */
+RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
+RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
+RFWHIP_API int rfwhip_group_present_display_wait(rfwhip_group *group, int slot, const void **out_host, int *format);
 
 /* rfwhip_comm_*: one process per device (e.g. under torch.distributed.run).  Rank 0 calls rfwhip_comm_unique_id and
  * hands the RFWHIP_COMM_ID_BYTES bytes to the other ranks by any means (a file, MPI, a torch broadcast); then EVERY rank
@@ -419,6 +462,7 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   light_sampling = "reference" (default: the reference's estimator, the default kernels) | "linear" (its potentials, consistent
  *                  weights) | "tree" (the light tree, O(log lights) per next-event vertex, the same weights): rfwhip_get_light_tree
  *                  below has the formulas.  The parity integrator ignores it.
+ *   display_tonemap / display_fxaa / display_srgb = the display stage, see rfwhip_read_display above.
  * Returns the number of keys; fills up to cap pointers with static strings. */
 RFWHIP_API int rfwhip_set_setting(rfwhip_context *ctx, const char *key, const char *value);
 RFWHIP_API int rfwhip_get_setting(rfwhip_context *ctx, const char *key, char *value, size_t cap);
@@ -444,7 +488,8 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
 
 /* Accumulated hipEvent time (ms) and launch count per kernel family since the last reset; requires
  * stage_timing=1.  which: 0 generate, 1 extend, 2 shade, 3 connect, 4 finalize, 5 refit, 6 denoise (a guide pass is two launches,
- * guide rays + depth gradient; a filter is 1 + denoise_iterations launches: demodulation / variance, then the a-trous passes). */
+ * guide rays + depth gradient; a filter is 1 + denoise_iterations launches: demodulation / variance, then the a-trous passes),
+ * 7 display (one launch per displayed image). */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

@@ -87,6 +87,10 @@ class CoreBinding:
                                   "get_light_tree": (i32, [vp, vp, sz, vp, sz]),
                                   "read_denoise_guides": (i32, [vp, vp, vp]),
                                   "denoise_image": (i32, [vp, vp, vp]),
+                                  "display_image": (i32, [vp, vp, fp, fp, i32, vp]),
+                                  "read_display": (i32, [vp, i32, vp]),
+                                  "read_display_device": (i32, [vp, i32, vp]),
+                                  "display_stream": (i32, [vp, vp, vp, i32, vp]),
                                   "read_denoise_history": (i32, [vp, vp, vp, vp, vp, vp]),
                                   "read_denoise_motion": (i32, [vp, vp, vp, vp]),
                                   "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32]),
@@ -363,6 +367,41 @@ class CoreBinding:
         self._check(self._fn("denoise_image")(self._ctx, src.ctypes.data, out.ctypes.data))
         return out
 
+    # ---- display stage (include/rfwhip.h, rfwhip_read_display) ----------------------------------------------------
+    DISPLAY_FORMATS = {"rgba8": 0, "rgba32f": 1}
+
+    @classmethod
+    def display_format(cls, format):
+        """(code, numpy dtype) of a display format: "rgba8" | "rgba32f", or the C ABI's number (an unknown number goes to
+        the library, which refuses it)."""
+        code = cls.DISPLAY_FORMATS[format] if format in cls.DISPLAY_FORMATS else int(format)
+        return code, (np.uint8 if code == 0 else np.float32)
+
+    def display(self, format="rgba8"):
+        """The presented image after the display stage — tone map, FXAA, encoding, with the display_* settings and the
+        last render's camera: H x W x 4 uint8 ("rgba8") or float32 ("rgba32f")."""
+        code, dt = self.display_format(format)
+        out = np.empty((self.height, self.width, 4), dtype=dt)
+        self._check(self._fn("read_display")(self._ctx, code, out.ctypes.data))
+        return out
+
+    def read_display_device(self, device_ptr, format="rgba8"):
+        self._check(self._fn("read_display_device")(self._ctx, self.display_format(format)[0], C.c_void_p(device_ptr)))
+
+    def display_stream(self, rgba_device_ptr, out_device_ptr, format="rgba8", stream=0):
+        """Stream-ordered display stage on a full float4 image in device memory (rfwhip_display_stream)."""
+        self._check(self._fn("display_stream")(self._ctx, C.c_void_p(rgba_device_ptr or None), C.c_void_p(out_device_ptr or None),
+                                               self.display_format(format)[0], C.c_void_p(stream or None)))
+
+    def display_image(self, rgba, brightness=0.05, contrast=1.0, format="rgba8"):
+        """The display stage on a given H x W x 4 float32 image with the context's display_* settings."""
+        src = np.ascontiguousarray(rgba, dtype=np.float32).reshape(self.height, self.width, 4)
+        code, dt = self.display_format(format)
+        out = np.empty((self.height, self.width, 4), dtype=dt)
+        self._check(self._fn("display_image")(self._ctx, src.ctypes.data, float(brightness), float(contrast), code,
+                                              out.ctypes.data))
+        return out
+
     def read_denoise_history(self):
         """The temporal stage of the last presented frame (include/rfwhip.h, "denoise_temporal"; world-1 contexts):
         {"pre": H x W x 4 (I~, lum), "var": H x W, "history": H x W x 4 (colour history, lum), "moments": H x W x 2,
@@ -385,10 +424,11 @@ class CoreBinding:
     # ---- measurement hooks -------------------------------------------------------------------------------------------
     KERNELS = ("generate", "extend", "shade", "connect", "finalize", "refit")
     DENOISE = 6  # kernel family of the denoiser (guide pass + filter), outside KERNELS: the render's stages
+    DISPLAY = 7  # ... and of the display stage (one launch per displayed image)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -489,6 +529,11 @@ class RenderGroup:
                                 ("last_error", C.c_char_p, [])]:
             f = self._fn(name)
             f.restype, f.argtypes = res, args
+        for name, res, args in [("group_read_display", i32, [vp, i32, vp]), ("group_present_display_async", i32, [vp, i32, i32]),
+                                ("group_present_display_wait", i32, [vp, i32, C.POINTER(vp), C.POINTER(i32)])]:
+            if hasattr(lib, prefix + name):
+                f = self._fn(name)
+                f.restype, f.argtypes = res, args
         devs = (i32 * len(devices))(*[int(d) for d in devices])
         self._g = vp()
         self._check(self._fn("group_create")(devs, len(devices), self.TRANSPORTS[transport], C.byref(self._g)))
@@ -554,6 +599,26 @@ class RenderGroup:
         self._check(self._fn("group_present_wait")(self._g, int(slot), C.byref(ptr)))
         buf = (C.c_float * (self.width * self.height * 4)).from_address(ptr.value)
         return np.frombuffer(buf, dtype=np.float32).reshape(self.height, self.width, 4)
+
+    def display(self, format="rgba8"):
+        """gather + the display stage on the root + wait: H x W x 4 uint8 ("rgba8") or float32 ("rgba32f")."""
+        code, dt = CoreBinding.display_format(format)
+        out = np.empty((self.height, self.width, 4), dtype=dt)
+        self._check(self._fn("group_read_display")(self._g, code, out.ctypes.data))
+        return out
+
+    def present_display_async(self, slot, format="rgba8"):
+        """present_async with the display stage behind the gather: the copy carries the display image."""
+        self._check(self._fn("group_present_display_async")(self._g, int(slot), CoreBinding.display_format(format)[0]))
+
+    def present_display_wait(self, slot):
+        """Block until slot's display image has landed; a numpy view of the pinned buffer (uint8 or float32 by its format)."""
+        ptr, fmt = C.c_void_p(), C.c_int()
+        self._check(self._fn("group_present_display_wait")(self._g, int(slot), C.byref(ptr), C.byref(fmt)))
+        n = self.width * self.height * 4
+        if fmt.value == 0:
+            return np.frombuffer((C.c_uint8 * n).from_address(ptr.value), dtype=np.uint8).reshape(self.height, self.width, 4)
+        return np.frombuffer((C.c_float * n).from_address(ptr.value), dtype=np.float32).reshape(self.height, self.width, 4)
 
     def framebuffer_device(self):
         """(device pointer, device ordinal) of the root-side image of the last completed gather."""

@@ -15,8 +15,8 @@ class Camera:
     direction: tuple = (0.0, 0.0, 1.0)
     focalDistance: float = 5.0
     aperture: float = 0.0001  # camera.h:31 (the parity configs set 0)
-    brightness: float = 0.0
-    contrast: float = 0.0
+    brightness: float = 0.05  # Camera.cpp:8-9: what the display stage's tone map takes (include/rfwhip.h, rfwhip_read_display)
+    contrast: float = 1.0
     FOV: float = 40.0
     aspectRatio: float = 1.0
     clampValue: float = 10.0

@@ -55,6 +55,7 @@ class RenderComm:
             f = getattr(self._lib, name)
             f.restype, f.argtypes = res, args
         self._c = vp()
+        self._ctx = ctx
         self._id = C.create_string_buffer(bytes(id_bytes), 128) if id_bytes is not None else None
         self._check(self._lib.rfwhip_comm_create(ctx._ctx, self._id, C.byref(self._c)))
 
@@ -68,6 +69,12 @@ class RenderComm:
 
     def wait(self):
         self._check(self._lib.rfwhip_comm_wait(self._c))
+
+    def display(self, full_rgba_device_ptr, out_device_ptr, format="rgba8", stream=0):
+        """Root only: the display stage (rfwhip_display_stream) on the gathered full image, enqueued on the caller's
+        hipStream_t (an int, e.g. torch.cuda.current_stream().cuda_stream; 0: the null stream) — order it behind the gather
+        (wait(), or an event).  out: width * height * 4 bytes ("rgba8") or * 16 ("rgba32f") of device memory."""
+        self._ctx.display_stream(full_rgba_device_ptr, out_device_ptr, format, stream)
 
     def destroy(self):
         if self._c:

@@ -83,6 +83,17 @@ struct DnMotion
 	float *dump;			  // rfwhip_read_denoise_motion: 8 floats per pixel (state, X_P, n'_p, 0), or null
 };
 
+// The display stage (display.h): the full W x H float4 image `in` -> one pixel per pixel in `out` (in != out)
+struct DisplayView
+{
+	uint32_t W, H;
+	const rt::f4 *in;
+	void *out;					// W x H uint32 (format 0, RFWHIP_DISPLAY_RGBA8) or W x H float4 (format 1, RFWHIP_DISPLAY_RGBA32F)
+	float brightness, contrast; // the camera's (rfwhip_camera)
+	uint32_t tonemap;			// 0 aces, 1 none
+	uint32_t fxaa, srgb, format;
+};
+
 // capacity of the LDS top-of-tree cache the kernels were built with
 uint32_t max_lds_nodes();
 
@@ -125,6 +136,8 @@ void launch_denoise_guides(const Params &p, const DnView &d, rt::f4 *surf, strea
 void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion *m, stream_t s);
 // demodulation + the temporal stage, into d.img[0] / d.var[0] (rfwhip_read_denoise_history): 2 launches
 void launch_denoise_temporal(const DnView &d, const DnTemporal &t, const DnMotion *m, stream_t s);
+// the display stage: one launch of k_display (fxaa: the LDS-tiled kernel; else its halo-free pointwise variant)
+void launch_display(const DisplayView &v, stream_t s);
 // a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
 rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,

@@ -941,6 +941,8 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 
 // the denoiser of the presented image: guide pass + a-trous filter (work items shared with the emulation)
 #include "denoise.h"
+// the display stage: tone map + FXAA + encoding of the presented image (the work item shared with the emulation)
+#include "display.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }
 
 // Which launches of the pt primary wave take the packet form (the device's launchers and the emulation's driver): a single-sample
@@ -2471,6 +2473,62 @@ void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, in
 		hipLaunchKernelGGL(k_kat_lt, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, lt, function, in, out, n);
 	else
 		hipLaunchKernelGGL(k_kat, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, function, in, out, n);
+}
+
+// ---- display stage (display.h).  k_display<true>: a workgroup owns DP_TILE_X x DP_TILE_Y pixels; it tone-maps the tile and a halo of
+// DP_HALO texels ONCE per texel into three LDS colour planes (coalesced float4 row reads; each texel of the image is read from HBM by
+// its own tile and by the neighbours whose halo it is in, never once per tap), then wave w runs the items of rows 4 w .. 4 w + 3, lane =
+// column: every tap of a wave instruction whose lanes agree on dir reads 64 consecutive floats of one plane row (no bank conflict),
+// and every store is one contiguous 256-byte (RGBA8) / 1 KiB (RGBA32F) run per wave.  k_display<false>: pointwise, no LDS. ----
+static_assert(BLOCK == 4 * DP_TILE_X && DP_TILE_Y % 4 == 0, "display workgroup = 4 waves, each a 64-pixel row segment at a time");
+static_assert(3 * DP_LDS_H * DP_PITCH * sizeof(float) <= 64 * 1024, "display tile in LDS");
+template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const DisplayView v)
+{
+	if constexpr (!FXAA)
+	{
+		const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+		if (i >= (size_t)v.W * v.H)
+			return;
+		const f4 c = v.in[i];
+		const f3 t = dp_tone(v, c);
+		dp_item<false>(v, [&](int, int) -> f3 { return t; }, (int)(i % v.W), (int)(i / v.W), c.w);
+	}
+	else
+	{
+		__shared__ float s_rgb[3][DP_LDS_H * DP_PITCH];
+		const int W = (int)v.W, H = (int)v.H;
+		const int x0 = (int)blockIdx.x * DP_TILE_X - DP_HALO, y0 = (int)blockIdx.y * DP_TILE_Y - DP_HALO;
+		for (int k = (int)threadIdx.x; k < DP_LDS_W * DP_LDS_H; k += BLOCK)
+		{
+			const int ly = k / DP_LDS_W, lx = k - ly * DP_LDS_W, gx = x0 + lx, gy = y0 + ly;
+			if (gx >= 0 && gx < W && gy >= 0 && gy < H) // (texels outside the image are never fetched: the taps clamp to the edge first)
+			{
+				const f3 t = dp_tone(v, v.in[(size_t)gy * v.W + (size_t)gx]);
+				const int o = ly * DP_PITCH + lx;
+				s_rgb[0][o] = t.x, s_rgb[1][o] = t.y, s_rgb[2][o] = t.z;
+			}
+		}
+		__syncthreads();
+		// (xi, yi) is inside the image and within DP_HALO of a pixel of this tile: inside the LDS tile
+		const auto fetch = [&](int xi, int yi) -> f3 {
+			const int o = (yi - y0) * DP_PITCH + (xi - x0);
+			return mk3(s_rgb[0][o], s_rgb[1][o], s_rgb[2][o]);
+		};
+		const int x = (int)blockIdx.x * DP_TILE_X + (int)(threadIdx.x & 63u);
+		const int yw = (int)blockIdx.y * DP_TILE_Y + (int)(threadIdx.x >> 6) * (DP_TILE_Y / 4);
+		if (x < W)
+			for (int r = 0; r < DP_TILE_Y / 4; r++)
+				if (yw + r < H)
+					dp_item<true>(v, fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
+	}
+}
+void launch_display(const DisplayView &v, stream_t s)
+{
+	if (v.fxaa)
+		hipLaunchKernelGGL(k_display<true>, dim3((v.W + DP_TILE_X - 1) / DP_TILE_X, (v.H + DP_TILE_Y - 1) / DP_TILE_Y), dim3(BLOCK), 0,
+						   (hipStream_t)s, v);
+	else
+		hipLaunchKernelGGL(k_display<false>, dim3((uint32_t)(((size_t)v.W * v.H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)s, v);
 }
 
 // ================================================================================================================

@@ -452,6 +452,21 @@ void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion 
 		for (uint32_t i = 0; i < d.W * d.H; i++)
 			dn_pass_item(d, 1u << k, k + 1u == d.iterations, d.img[k & 1u], d.var[k & 1u], d.img[(k + 1u) & 1u], d.var[(k + 1u) & 1u], i);
 }
+void launch_display(const DisplayView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_display(v, s));
+	// the direct fetch: the texel is tone-mapped where it is read
+	const auto fetch = [&](int xi, int yi) -> f3 { return dp_tone(v, v.in[(size_t)yi * v.W + (size_t)xi]); };
+	for (uint32_t y = 0; y < v.H; y++)
+		for (uint32_t x = 0; x < v.W; x++)
+		{
+			const float a = v.in[(size_t)y * v.W + x].w;
+			if (v.fxaa)
+				dp_item<true>(v, fetch, (int)x, (int)y, a);
+			else
+				dp_item<false>(v, fetch, (int)x, (int)y, a);
+		}
+}
 void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
 	EMU_DEFER(s, launch_kat(p, sky, lt, function, in, out, n, s));

@@ -13,6 +13,13 @@
 // returns with frame k - n + 1 on the host (rfwhip_group_present_async / _wait): the devices never idle between frames; with 1
 // it returns with frame k finished, like the reference's backends.
 //
+// Display stage: RFWHIP_DISPLAY=aces|none (unset by default: nothing changes) — render_frame presents the 8-bit display image of
+// include/rfwhip.h (rfwhip_read_display: the reference's tone map with the camera's brightness / contrast, FXAA; "none": no tone
+// curve) instead of the float image: rfwhip_group_present_display_async / _wait with frames in flight, a quarter of the bytes over
+// PCIe, and the GL upload is GL_RGBA / GL_UNSIGNED_BYTE.  Leave it unset under rfw::system with toneMap = true: the system
+// tone-maps again on top of whatever the backend delivers (system.cpp:682-711).  Headless hosts read the bytes with
+// hiprtReadDisplay.
+//
 // Headless by default (RenderTarget::BUFFER, context.h:27-34): the GPU box has no OpenGL.  With
 // -DRFWHIP_PLUGIN_WITH_GL (needs GLEW, i.e. the reference's own build environment) render_frame also uploads the
 // float4 image into the GL texture handed to init(), the same way EmbreeRT presents (EmbreeRT/src/Context.cpp:289-297).
@@ -33,7 +40,9 @@
 #endif
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -73,6 +82,14 @@ class Context final : public rfw::RenderContext
 			m_Cores.push_back(rfwhip_group_context(m_Group, i));
 		if (const char *f = std::getenv("RFWHIP_FRAMES_IN_FLIGHT"))
 			m_InFlight = std::max(1, std::min(RFWHIP_PRESENT_SLOTS, std::atoi(f)));
+		if (const char *d = std::getenv("RFWHIP_DISPLAY"))
+		{
+			const std::string mode = d;
+			if (mode != "aces" && mode != "none")
+				throw std::runtime_error("HipRT: RFWHIP_DISPLAY must be \"aces\" or \"none\"");
+			m_Display = true;
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_tonemap", mode.c_str()));
+		}
 		const char *integ = std::getenv("RFWHIP_INTEGRATOR");
 		HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "integrator", integ ? integ : "pt"));
 		if (m_InFlight >= RFWHIP_PRESENT_SLOTS) // four frames in flight need four sets of wave buffers (the default ring is three)
@@ -135,8 +152,9 @@ class Context final : public rfw::RenderContext
 		m_Width = width, m_Height = height;
 		HIPRT_CHECK(rfwhip_group_init(m_Group, width, height));
 		// a resize frees the pinned host images of the frames in flight: the window of frames starts over
-		m_Frame = 0, m_Latest = nullptr;
+		m_Frame = 0, m_Latest = nullptr, m_LatestDisplay = nullptr;
 		m_Host.assign(size_t(width) * height * 4, 0.0f);
+		m_HostDisplay.assign(m_Display ? size_t(width) * height * 4 : 0, 0);
 	}
 
 	void cleanup() override
@@ -157,24 +175,40 @@ class Context final : public rfw::RenderContext
 		std::memcpy(&cam, &camera, sizeof(cam)); // position .. pixelCount are the first 60 bytes (camera.h:27-37)
 		HIPRT_CHECK(rfwhip_group_render(m_Group, &cam, status == rfw::Reset ? RFWHIP_RESET : RFWHIP_CONVERGE));
 		const float *image = nullptr;
+		const void *display = nullptr;
 		if (m_InFlight >= 2)
 		{
 			// frame k and its way to the host are enqueued; what is handed out is frame k - (n - 1) (the first n - 1 calls wait
 			// for frame 0, their own oldest)
-			const int n = m_InFlight;
-			HIPRT_CHECK(rfwhip_group_present_async(m_Group, (int)(m_Frame % (unsigned)n)));
+			const int n = m_InFlight, slot = (int)(m_Frame % (unsigned)n);
 			const unsigned long long oldest = m_Frame >= (unsigned)(n - 1) ? m_Frame - (unsigned)(n - 1) : 0;
-			HIPRT_CHECK(rfwhip_group_present_wait(m_Group, (int)(oldest % (unsigned)n), &image));
-			m_Latest = image;
+			if (m_Display)
+			{
+				HIPRT_CHECK(rfwhip_group_present_display_async(m_Group, slot, RFWHIP_DISPLAY_RGBA8));
+				HIPRT_CHECK(rfwhip_group_present_display_wait(m_Group, (int)(oldest % (unsigned)n), &display, nullptr));
+			}
+			else
+			{
+				HIPRT_CHECK(rfwhip_group_present_async(m_Group, slot));
+				HIPRT_CHECK(rfwhip_group_present_wait(m_Group, (int)(oldest % (unsigned)n), &image));
+			}
 		}
 		else
-		{
 			HIPRT_CHECK(rfwhip_group_wait(m_Group)); // the reference's render_frame returns with the frame finished
-			m_Latest = nullptr;
-		}
+		m_Latest = image, m_LatestDisplay = static_cast<const uint8_t *>(display);
 		m_Frame++;
 #ifdef RFWHIP_PLUGIN_WITH_GL
-		if (m_Target)
+		if (m_Target && m_Display)
+		{
+			if (!display)
+			{
+				HIPRT_CHECK(rfwhip_group_read_display(m_Group, RFWHIP_DISPLAY_RGBA8, m_HostDisplay.data()));
+				display = m_HostDisplay.data();
+			}
+			glBindTexture(GL_TEXTURE_2D, m_Target);
+			glTexSubImage2D(GL_TEXTURE_2D, 0, 0, 0, m_Width, m_Height, GL_RGBA, GL_UNSIGNED_BYTE, display);
+		}
+		else if (m_Target)
 		{
 			if (!image)
 			{
@@ -196,6 +230,18 @@ class Context final : public rfw::RenderContext
 			return RFWHIP_OK;
 		}
 		return rfwhip_group_read_framebuffer(m_Group, rgba);
+	}
+
+	// ... and the display image (RGBA8) of that frame: with RFWHIP_DISPLAY and frames in flight the bytes render_frame received,
+	// else the display stage of the newest frame, read now
+	int read_display(uint8_t *rgba8)
+	{
+		if (m_LatestDisplay)
+		{
+			std::memcpy(rgba8, m_LatestDisplay, size_t(m_Width) * m_Height * 4);
+			return RFWHIP_OK;
+		}
+		return rfwhip_group_read_display(m_Group, RFWHIP_DISPLAY_RGBA8, rgba8);
 	}
 
 	void set_materials(const std::vector<rfw::DeviceMaterial> &materials,
@@ -328,6 +374,9 @@ class Context final : public rfw::RenderContext
 	unsigned long long m_Frame = 0;
 	unsigned m_ProbeY = 0; // row of the probe pixel: decides which rank's record get_probe_results reads
 	const float *m_Latest = nullptr;
+	bool m_Display = false; // RFWHIP_DISPLAY: render_frame presents the display image
+	const uint8_t *m_LatestDisplay = nullptr;
+	std::vector<uint8_t> m_HostDisplay;
 	GLuint m_Target = 0;
 	uint m_Width = 0, m_Height = 0;
 	std::vector<float> m_Host;
@@ -349,4 +398,9 @@ HIPRT_EXPORT void destroyRenderContext(rfw::RenderContext *ptr)
 HIPRT_EXPORT int hiprtReadFramebuffer(rfw::RenderContext *ptr, float *rgba)
 {
 	return static_cast<Context *>(ptr)->read(rgba);
+}
+// ... and the presentable image: width * height * 4 bytes, R first (the display stage, include/rfwhip.h rfwhip_read_display)
+HIPRT_EXPORT int hiprtReadDisplay(rfw::RenderContext *ptr, uint8_t *rgba8)
+{
+	return static_cast<Context *>(ptr)->read_display(rgba8);
 }

@@ -206,7 +206,8 @@ enum KernelFamily
 	KF_FINALIZE = 4,
 	KF_REFIT = 5,
 	KF_DENOISE = 6, // the denoiser of the presented image: guide pass + filter (denoise.h)
-	KF_COUNT = 7
+	KF_DISPLAY = 7, // the display stage: tone map + FXAA + encoding (display.h), one launch per displayed image
+	KF_COUNT = 8
 };
 
 struct TimedSpan
@@ -362,6 +363,9 @@ struct rfwhip_context
 	bool sky_stale = false;		 // a sky setting changed since: the next render (or update) refreshes the view
 	// light sampling (light_tree.h): 0 reference, 1 linear, 2 tree; the tree of the lights of the last rfwhip_set_lights
 	int light_sampling = 0;
+	// the display stage (display.h): tone map 0 aces | 1 none, FXAA, sRGB encoding; d_display: where the host reads land
+	int display_tonemap = 0, display_fxaa = 1, display_srgb = 0;
+	DevBuf d_display;
 	DevBuf d_lt_nodes, d_lt_paths; // allocated only while light_sampling is tree
 	rt::LightTreeView lt_view{};   // nodes == nullptr: linear (or no light with a position)
 	bool lt_stale = false;		   // the setting changed since: the next render (or update) builds the tree
@@ -391,8 +395,8 @@ struct rfwhip_context
 	std::vector<TimedSpan> spans;
 	std::vector<dm::event_t> event_pool;
 	size_t events_used = 0;
-	float kernel_ms[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0};
-	uint32_t kernel_launches[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+	float kernel_ms[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
+	uint32_t kernel_launches[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
 	rfwhip_render_stats stats;
 	std::chrono::steady_clock::time_point render_t0;
 	bool render_pending = false;
@@ -566,7 +570,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_sh_dir[0], &c->d_sh_dir[1], &c->d_sh_rad[0], &c->d_sh_rad[1], &c->d_rad[0], &c->d_rad[1],
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
-					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths};
+					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display};
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->guides_valid = false;
@@ -2911,6 +2915,102 @@ extern "C" int rfwhip_read_framebuffer(rfwhip_context *c, float *rgba_host)
 	return dm::d2h(rgba_host, c->d_present.p, bytes, c->stream);
 }
 
+// ---- display stage (settings "display_*"; work item: display.h) -----------------------------------------------------------------
+static size_t display_pixel_bytes(int format) { return format == RFWHIP_DISPLAY_RGBA8 ? 4u : sizeof(f4); }
+static int display_check_format(const char *who, int format)
+{
+	if (format != RFWHIP_DISPLAY_RGBA8 && format != RFWHIP_DISPLAY_RGBA32F)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: unknown display format %d", who, format);
+	return RFWHIP_OK;
+}
+// one launch on `stream`: the full W x H float4 image `in` -> `out` in `format`, with the context's display settings
+static int display_enqueue(rfwhip_context *c, const f4 *in, void *out, float brightness, float contrast, int format, void *stream)
+{
+	rtk::DisplayView v;
+	v.W = c->W, v.H = c->H, v.in = in, v.out = out;
+	v.brightness = brightness, v.contrast = contrast;
+	v.tonemap = (uint32_t)c->display_tonemap, v.fxaa = (uint32_t)c->display_fxaa, v.srgb = (uint32_t)c->display_srgb;
+	v.format = (uint32_t)format;
+	StageTimer t(c, KF_DISPLAY, -1, stream);
+	rtk::launch_display(v, stream);
+	t.stop(1);
+	return dm::last_launch_error();
+}
+// brightness and contrast of the presented image: the camera of the last render; before the first one the reference's defaults
+// (Camera.cpp:8-9)
+static void display_camera(const rfwhip_context *c, float &brightness, float &contrast)
+{
+	brightness = c->have_last_cam ? c->last_cam.brightness : 0.05f;
+	contrast = c->have_last_cam ? c->last_cam.contrast : 1.0f;
+}
+
+extern "C" int rfwhip_display_stream(rfwhip_context *c, const void *rgba_device, void *out_device, int format, void *hip_stream)
+{
+	CTX_ENTER(c);
+	if (!rgba_device || !out_device)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null image");
+	if (rgba_device == out_device)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_display_stream: in place is not allowed (FXAA reads the neighbours of a pixel)");
+	RF_TRY(display_check_format("rfwhip_display_stream", format));
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	float b, k;
+	display_camera(c, b, k);
+	return display_enqueue(c, (const f4 *)rgba_device, out_device, b, k, format, hip_stream);
+}
+
+extern "C" int rfwhip_read_display_device(rfwhip_context *c, int format, void *out_device)
+{
+	CTX_ENTER(c);
+	if (!out_device)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null destination");
+	RF_TRY(display_check_format("rfwhip_read_display*", format));
+	if (c->world != 1)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_display*: this rank owns 1/%d of the image; the display stage runs on the "
+											"gathered image (rfwhip_group_read_display, rfwhip_display_stream)", c->world);
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	// present -> denoise when on -> display
+	const size_t bytes = (size_t)c->W * c->H * sizeof(f4);
+	RF_TRY(c->d_present.ensure(bytes));
+	RF_TRY(dm::zero(c->d_present.p, bytes, c->stream));
+	RF_TRY(rfwhip_read_framebuffer_device(c, c->d_present.p));
+	float b, k;
+	display_camera(c, b, k);
+	RF_TRY(display_enqueue(c, c->d_present.as<f4>(), out_device, b, k, format, c->stream));
+	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_read_display(rfwhip_context *c, int format, void *out_host)
+{
+	CTX_ENTER(c);
+	if (!out_host)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null destination");
+	RF_TRY(display_check_format("rfwhip_read_display*", format));
+	const size_t bytes = (size_t)c->W * c->H * display_pixel_bytes(format);
+	RF_TRY(c->d_display.ensure(bytes));
+	RF_TRY(rfwhip_read_display_device(c, format, c->d_display.p));
+	return dm::d2h(out_host, c->d_display.p, bytes, c->stream); // (only the format's bytes travel)
+}
+
+extern "C" int rfwhip_display_image(rfwhip_context *c, const float *rgba_in, float brightness, float contrast, int format, void *out_host)
+{
+	CTX_ENTER(c);
+	if (!rgba_in || !out_host)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null image");
+	RF_TRY(display_check_format("rfwhip_display_image", format));
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	RF_TRY(sync_all(c));
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
+	RF_TRY(c->d_display.ensure(px * display_pixel_bytes(format)));
+	RF_TRY(dm::h2d(c->d_present.p, rgba_in, px * sizeof(f4), c->stream));
+	RF_TRY(display_enqueue(c, c->d_present.as<f4>(), c->d_display.p, brightness, contrast, format, c->stream));
+	RF_TRY(dm::d2h(out_host, c->d_display.p, px * display_pixel_bytes(format), c->stream));
+	return dm::sync(c->stream);
+}
+
 extern "C" int rfwhip_read_local_framebuffer_device(rfwhip_context *c, void *rgba_device)
 {
 	CTX_ENTER(c);
@@ -3223,6 +3323,20 @@ static const Setting k_settings[] = {
 		 c->lt_stale = true; // (the next render builds or drops the tree, on the lights of the last rfwhip_set_lights)
 		 return RFWHIP_OK; },
 	 GET { return put(out, cap, "%s", c->light_sampling == 2 ? "tree" : c->light_sampling == 1 ? "linear" : "reference"); }, false},
+	// the display stage (display.h): what rfwhip_read_display* / rfwhip_display_* apply to the presented image
+	{"display_tonemap", ENUM2(display_tonemap, "aces", "none"), false},
+	{"display_fxaa", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 c->display_fxaa = on;
+		 return RFWHIP_OK; },
+	 GET_INT(display_fxaa), false},
+	{"display_srgb", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 c->display_srgb = on;
+		 return RFWHIP_OK; },
+	 GET_INT(display_srgb), false},
 	// read-only: nodes of the light tree the next render would use (0: none, or light_sampling is not tree)
 	{"light_tree", nullptr, GET {
 		 if (c->lt_stale)

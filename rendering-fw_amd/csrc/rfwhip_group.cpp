@@ -142,6 +142,11 @@ struct rfwhip_group
 	void *copy_stream = nullptr; // the device-to-host copies run beside the gather chain, not inside it
 	dm::event_t host_ready[SLOTS], slot_done[SLOTS];
 	bool host_events = false, host_pending[SLOTS] = {};
+	// display stage (rfwhip_group_read_display / _present_display_*): the root's display image of a read, of each slot, and what a
+	// slot was last presented with: SLOT_NONE, SLOT_FLOAT, or SLOT_DISPLAY + the format
+	static constexpr int SLOT_NONE = -2, SLOT_FLOAT = -1, SLOT_DISPLAY = 0;
+	void *disp = nullptr, *slot_disp[SLOTS] = {};
+	int slot_kind[SLOTS] = {SLOT_NONE, SLOT_NONE, SLOT_NONE, SLOT_NONE};
 	size_t chunk_bytes() const { return (size_t)local_rows * W * PIXEL_BYTES; }
 };
 struct rfwhip_comm
@@ -162,14 +167,15 @@ void release_buffers(rfwhip_group *g)
 	if (g->root_local >= 0)
 	{
 		(void)dm::use(g->ep[g->root_local].device);
-		dm::release(g->staging), dm::release(g->full);
+		dm::release(g->staging), dm::release(g->full), dm::release(g->disp);
 	}
-	g->staging = g->full = nullptr;
+	g->staging = g->full = g->disp = nullptr;
 	g->staging_read_valid = false;
 	for (int k = 0; k < rfwhip_group::SLOTS; k++)
 	{
 		dm::host_free(g->host_img[k]), g->host_img[k] = nullptr, g->host_pending[k] = false;
 		dm::release(g->slot_img[k]), g->slot_img[k] = nullptr;
+		dm::release(g->slot_disp[k]), g->slot_disp[k] = nullptr, g->slot_kind[k] = rfwhip_group::SLOT_NONE;
 	}
 }
 
@@ -581,10 +587,15 @@ extern "C" int rfwhip_group_read_framebuffer(rfwhip_group *g, float *rgba_host)
 // Pipelined presentation: frame k's image travels to the host while the next frames render.  present_async enqueues gather +
 // device-to-host copy into pinned host image `slot` (0 .. RFWHIP_PRESENT_SLOTS - 1) and returns; present_wait blocks until
 // that copy has landed.  With n slots a host keeps n frames in flight: render(k), present_async(k % n), present_wait((k + 1) % n).
-extern "C" int rfwhip_group_present_async(rfwhip_group *g, int slot)
+static_assert(rfwhip_group::SLOTS == 4, "slot_kind's initialiser");
+static size_t display_bytes(int format) { return format == RFWHIP_DISPLAY_RGBA8 ? 4u : PIXEL_BYTES; }
+
+// kind: SLOT_FLOAT, or SLOT_DISPLAY + format: the display stage runs behind the gather (and the root's denoiser) on the root's
+// gather stream, and the copy carries its output
+static int present_async(rfwhip_group *g, int slot, int kind, const char *who)
 {
 	if (!g || slot < 0 || slot >= rfwhip_group::SLOTS)
-		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_async: bad arguments");
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
 	if (g->root_local < 0 || !g->full)
 		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "no render target");
 	Endpoint &root = g->ep[(size_t)g->root_local];
@@ -601,37 +612,98 @@ extern "C" int rfwhip_group_present_async(rfwhip_group *g, int slot)
 		g->host_events = true;
 	}
 	if (!g->host_img[slot])
-		GR_TRY(dm::host_alloc(&g->host_img[slot], bytes));
+		GR_TRY(dm::host_alloc(&g->host_img[slot], bytes)); // (sized for the float image: either kind fits)
 	if (!g->slot_img[slot])
 		GR_TRY(dm::alloc(&g->slot_img[slot], bytes));
-	// the slot's device image is rewritten only after its previous copy to the host has read it
+	const bool display = kind != rfwhip_group::SLOT_FLOAT;
+	if (display && !g->slot_disp[slot])
+		GR_TRY(dm::alloc(&g->slot_disp[slot], bytes));
+	// the slot's device images are rewritten only after the slot's previous copy to the host has read them
 	if (g->host_pending[slot])
 		GR_TRY(dm::stream_wait_event(root.stream, g->host_ready[slot]));
 	GR_TRY(gather(g, g->slot_img[slot]));
+	if (display && rfwhip_display_stream(root.ctx, g->slot_img[slot], g->slot_disp[slot], kind, root.stream))
+		return RFWHIP_ERR_STATE; // (the context's message stands)
 	GR_TRY(dm::use(root.device));
 	GR_TRY(dm::event_record(g->slot_done[slot], root.stream));
 	// ... and the copy rides its own stream: the next frame's present / transfer / de-interleave do not queue behind 33 MB of PCIe
+	// (a display image: 8 MB as RGBA8)
 	GR_TRY(dm::stream_wait_event(g->copy_stream, g->slot_done[slot]));
-	GR_TRY(dm::d2h_async(g->host_img[slot], g->slot_img[slot], bytes, g->copy_stream));
+	if (display)
+		GR_TRY(dm::d2h_async(g->host_img[slot], g->slot_disp[slot], (size_t)g->W * g->H * display_bytes(kind), g->copy_stream));
+	else
+		GR_TRY(dm::d2h_async(g->host_img[slot], g->slot_img[slot], bytes, g->copy_stream));
 	GR_TRY(dm::event_record(g->host_ready[slot], g->copy_stream));
-	g->host_pending[slot] = true;
+	g->host_pending[slot] = true, g->slot_kind[slot] = kind;
 	return RFWHIP_OK;
 }
 
-extern "C" int rfwhip_group_present_wait(rfwhip_group *g, int slot, const float **rgba_host)
+static int present_wait(rfwhip_group *g, int slot, bool display, const char *who)
 {
-	if (!g || slot < 0 || slot >= rfwhip_group::SLOTS || !rgba_host)
-		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_wait: bad arguments");
-	if (!g->host_img[slot])
-		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "rfwhip_group_present_wait: nothing was presented into slot %d", slot);
+	if (g->slot_kind[slot] == rfwhip_group::SLOT_NONE || !g->host_img[slot])
+		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "%s: nothing was presented into slot %d", who, slot);
+	if ((g->slot_kind[slot] != rfwhip_group::SLOT_FLOAT) != display)
+		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "%s: slot %d holds a %s image (presented with rfwhip_group_present_%sasync)", who,
+										 slot, display ? "float" : "display", display ? "" : "display_");
 	if (g->host_pending[slot])
 	{
 		GR_TRY(dm::use(g->ep[(size_t)g->root_local].device));
 		GR_TRY(dm::event_sync(g->host_ready[slot]));
 		g->host_pending[slot] = false;
 	}
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_group_present_async(rfwhip_group *g, int slot)
+{
+	return present_async(g, slot, rfwhip_group::SLOT_FLOAT, "rfwhip_group_present_async");
+}
+
+extern "C" int rfwhip_group_present_wait(rfwhip_group *g, int slot, const float **rgba_host)
+{
+	if (!g || slot < 0 || slot >= rfwhip_group::SLOTS || !rgba_host)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_wait: bad arguments");
+	GR_TRY(present_wait(g, slot, false, "rfwhip_group_present_wait"));
 	*rgba_host = (const float *)g->host_img[slot];
 	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_group_present_display_async(rfwhip_group *g, int slot, int format)
+{
+	if (format != RFWHIP_DISPLAY_RGBA8 && format != RFWHIP_DISPLAY_RGBA32F)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_display_async: unknown display format %d", format);
+	return present_async(g, slot, format, "rfwhip_group_present_display_async");
+}
+
+extern "C" int rfwhip_group_present_display_wait(rfwhip_group *g, int slot, const void **out_host, int *format)
+{
+	if (!g || slot < 0 || slot >= rfwhip_group::SLOTS || !out_host)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_display_wait: bad arguments");
+	GR_TRY(present_wait(g, slot, true, "rfwhip_group_present_display_wait"));
+	*out_host = g->host_img[slot];
+	if (format)
+		*format = g->slot_kind[slot];
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_group_read_display(rfwhip_group *g, int format, void *out_host)
+{
+	if (!g || !out_host)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null argument");
+	if (format != RFWHIP_DISPLAY_RGBA8 && format != RFWHIP_DISPLAY_RGBA32F)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_read_display: unknown display format %d", format);
+	if (g->root_local < 0 || !g->full)
+		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "no render target");
+	Endpoint &root = g->ep[(size_t)g->root_local];
+	GR_TRY(dm::use(root.device));
+	if (!g->disp)
+		GR_TRY(dm::alloc(&g->disp, (size_t)g->W * g->H * PIXEL_BYTES));
+	GR_TRY(gather(g, nullptr));
+	if (rfwhip_display_stream(root.ctx, g->full, g->disp, format, root.stream))
+		return RFWHIP_ERR_STATE; // (the context's message stands)
+	GR_TRY(wait_all(g));
+	GR_TRY(dm::use(root.device));
+	return dm::d2h(out_host, g->disp, (size_t)g->W * g->H * display_bytes(format), root.stream);
 }
 
 extern "C" int rfwhip_group_framebuffer_device(rfwhip_group *g, void **rgba_device, int *device_ordinal)
