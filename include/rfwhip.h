@@ -172,6 +172,63 @@ RFWHIP_API int rfwhip_display_stream(rfwhip_context *ctx, const void *rgba_devic
 RFWHIP_API int rfwhip_display_image(rfwhip_context *ctx, const float *rgba_in, float brightness, float contrast, int format,
 									void *out_host);
 
+/* ---- noise estimate: when has a progressive render converged? ---------------------------------------------------------------
+ * With noise_estimate = 1 the resolve of every rfwhip_render (its variant k_resolve_noise) keeps two floats per pixel beside the
+ * accumulator — sumY, the sum of the luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel's samples (a sample's value is what
+ * the resolve adds to the accumulator for it), and M2 = sum (Y - mean)^2, updated per call in the shifted, mergeable form
+ * (csrc/noise.h has the formulas).  The framebuffer is bit-identical with the setting on and off; the moments
+ * are cleared wherever the accumulator is (RFWHIP_RESET, rfwhip_init) and begin with the first RESET or rfwhip_init after the
+ * setting came on.  With it off nothing is allocated and no other kernel runs.
+ *   Settings (not listed by rfwhip_get_settings):
+ *     noise_estimate  = "0" (default) | "1"
+ *     noise_floor     = a finite number > 0 (default 0.01): added to the mean, so that a black pixel has a finite error
+ *     noise_threshold = a finite number > 0 (default 0.05): a pixel has converged when its error is at most this
+ *   Per pixel, n >= 2 samples (n is the context's sample count since the last RESET, one number for all pixels):
+ *     mean = sumY / n,  var = M2 / (n - 1),  e = sqrt(var / n) / (mean + noise_floor)
+ *   the standard error of the mean relative to the mean; e = FLT_MAX where a moment is not finite (a NaN or infinite sample): such a
+ *   pixel never converges.
+ *   Tiles: 32 x 8 pixels, aligned to the ownership strips, so a tile belongs to one rank; a partial tile counts its real pixels. */
+typedef struct rfwhip_noise_stats
+{
+	uint64_t samples;	/* n */
+	uint64_t pixels;	/* pixels judged (a rank: the pixels of its strips) */
+	uint64_t converged; /* ... of which e <= threshold */
+	double mean_error;	/* sum of e / pixels */
+	float max_error;
+	float threshold;	/* noise_threshold as it was applied */
+} rfwhip_noise_stats;
+typedef struct rfwhip_noise_tile
+{
+	float sum_e; /* over the tile's pixels, at most FLT_MAX */
+	float max_e;
+	uint32_t pixels;
+	uint32_t converged;
+} rfwhip_noise_tile;
+/* Two kernels on the context's stream behind the last render — per-pixel error and per-tile records, then ONE workgroup that folds
+ * the tile records in index order (no float atomics: the same state gives the same bytes) — and a wait for the 32 bytes of the
+ * result; the map stays on the device.  RFWHIP_ERR_STATE when noise_estimate is off (or came on after the accumulation began) or
+ * n < 2.  A rank of a strip split answers for its own strips: rfwhip_group_get_noise adds the ranks' answers; a rfwhip_comm_* host
+ * (one process per device) adds its ranks' records itself — pixels, converged and mean_error * pixels are sums, max_error a maximum. */
+RFWHIP_API int rfwhip_get_noise(rfwhip_context *ctx, rfwhip_noise_stats *stats);
+/* World-1 contexts: e of every pixel, width * height floats, row 0 first. */
+RFWHIP_API int rfwhip_read_noise_map(rfwhip_context *ctx, float *e);
+/* The tile records of this rank, row-major: tiles_x = ceil(width / 32), tiles_y = this rank's padded rows / 8 (world 1:
+ * ceil(height / 8)).  cap = records the array holds; too few: RFWHIP_ERR_INVALID_ARGUMENT. */
+RFWHIP_API int rfwhip_read_noise_tiles(rfwhip_context *ctx, rfwhip_noise_tile *records, size_t cap, uint32_t *tiles_x, uint32_t *tiles_y);
+/* Test hook, world-1 contexts: the two moments of every pixel, width * height floats each. */
+RFWHIP_API int rfwhip_read_noise_moments(rfwhip_context *ctx, float *sumY, float *m2);
+/* Known-answer hooks, the counterparts of rfwhip_display_image: the product's kernels on the caller's data, whatever the context
+ * renders and whether or not noise_estimate is on.
+ * rfwhip_noise_merge: one call's update of `pixels` pixels that hold n_a samples with the moments sumY_a / m2_a, on S given sample
+ * values per pixel (samples_rgb: pixels x S x 3 floats, a pixel's samples in order).
+ * rfwhip_noise_image: the metric on given moments of a width x height image of its own size, with n samples per pixel and the
+ * context's noise_floor / noise_threshold; e_map (width * height floats) and tiles (ceil(width / 32) * ceil(height / 8) records)
+ * may be null. */
+RFWHIP_API int rfwhip_noise_merge(rfwhip_context *ctx, size_t pixels, uint32_t n_a, const float *sumY_a, const float *m2_a, uint32_t S,
+								  const float *samples_rgb, float *sumY_out, float *m2_out);
+RFWHIP_API int rfwhip_noise_image(rfwhip_context *ctx, uint32_t width, uint32_t height, uint32_t n, const float *sumY, const float *m2,
+								  rfwhip_noise_stats *stats, float *e_map, rfwhip_noise_tile *tiles);
+
 /* Where a context runs and what it renders into (for hosts that move its strips themselves). */
 RFWHIP_API int rfwhip_get_placement(rfwhip_context *ctx, int *device_ordinal, int *rank, int *world);
 RFWHIP_API int rfwhip_get_target_size(rfwhip_context *ctx, uint32_t *width, uint32_t *height);
@@ -226,6 +283,9 @@ RFWHIP_API int rfwhip_group_present_wait(rfwhip_group *group, int slot, const fl
  * and events, and the copy carries the display image (a quarter of the float image's bytes for RGBA8).  A slot remembers what was
  * last presented into it: rfwhip_group_present_wait on a slot that holds a display image, and rfwhip_group_present_display_wait on
  * one that holds a float image, return RFWHIP_ERR_STATE. */
+/* The noise estimate of the whole image (see rfwhip_get_noise): every rank reduces its own strips on its device, the root adds the
+ * ranks' records in rank order on the host — counts exactly, the sum of errors in double, the maximum of the maxima. */
+RFWHIP_API int rfwhip_group_get_noise(rfwhip_group *group, rfwhip_noise_stats *stats);
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
 RFWHIP_API int rfwhip_group_present_display_wait(rfwhip_group *group, int slot, const void **out_host, int *format);
@@ -463,6 +523,7 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                  weights) | "tree" (the light tree, O(log lights) per next-event vertex, the same weights): rfwhip_get_light_tree
  *                  below has the formulas.  The parity integrator ignores it.
  *   display_tonemap / display_fxaa / display_srgb = the display stage, see rfwhip_read_display above.
+ *   noise_estimate / noise_floor / noise_threshold = the noise estimate, see rfwhip_get_noise above.
  * Returns the number of keys; fills up to cap pointers with static strings. */
 RFWHIP_API int rfwhip_set_setting(rfwhip_context *ctx, const char *key, const char *value);
 RFWHIP_API int rfwhip_get_setting(rfwhip_context *ctx, const char *key, char *value, size_t cap);
@@ -489,7 +550,8 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
 /* Accumulated hipEvent time (ms) and launch count per kernel family since the last reset; requires
  * stage_timing=1.  which: 0 generate, 1 extend, 2 shade, 3 connect, 4 finalize, 5 refit, 6 denoise (a guide pass is two launches,
  * guide rays + depth gradient; a filter is 1 + denoise_iterations launches: demodulation / variance, then the a-trous passes),
- * 7 display (one launch per displayed image). */
+ * 7 display (one launch per displayed image), 8 noise (the metric: two launches per query; the moments are part of the resolve,
+ * family 4). */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

@@ -91,6 +91,12 @@ class CoreBinding:
                                   "read_display": (i32, [vp, i32, vp]),
                                   "read_display_device": (i32, [vp, i32, vp]),
                                   "display_stream": (i32, [vp, vp, vp, i32, vp]),
+                                  "get_noise": (i32, [vp, C.POINTER(abi.NoiseStats)]),
+                                  "read_noise_map": (i32, [vp, vp]),
+                                  "read_noise_tiles": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
+                                  "read_noise_moments": (i32, [vp, vp, vp]),
+                                  "noise_merge": (i32, [vp, sz, u32, vp, vp, u32, vp, vp, vp]),
+                                  "noise_image": (i32, [vp, u32, u32, u32, vp, vp, C.POINTER(abi.NoiseStats), vp, vp]),
                                   "read_denoise_history": (i32, [vp, vp, vp, vp, vp, vp]),
                                   "read_denoise_motion": (i32, [vp, vp, vp, vp]),
                                   "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32]),
@@ -402,6 +408,77 @@ class CoreBinding:
                                               out.ctypes.data))
         return out
 
+    # ---- noise estimate (include/rfwhip.h, rfwhip_get_noise; setting noise_estimate = 1) ---------------------------
+    def get_noise(self):
+        """The noise of the accumulated image as a dict: samples, pixels, converged, mean_error, max_error, threshold.
+        Two small kernels and a wait for 32 bytes; raises while noise_estimate is off or fewer than 2 samples are in."""
+        st = abi.NoiseStats()
+        self._check(self._fn("get_noise")(self._ctx, C.byref(st)))
+        return st.as_dict()
+
+    def read_noise_map(self):
+        """H x W float32: every pixel's relative standard error of the mean."""
+        out = np.empty((self.height, self.width), np.float32)
+        self._check(self._fn("read_noise_map")(self._ctx, out.ctypes.data))
+        return out
+
+    def read_noise_tiles(self):
+        """This rank's tile records (abi.NOISE_TILE_DTYPE), tiles_y x tiles_x."""
+        cap = -(-self.width // abi.NOISE_TILE_X) * (int(self._fn("local_rows")(self._ctx)) // abi.NOISE_TILE_Y)
+        rec = np.zeros(max(cap, 1), abi.NOISE_TILE_DTYPE)
+        tx, ty = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("read_noise_tiles")(self._ctx, rec.ctypes.data, cap, C.byref(tx), C.byref(ty)))
+        return rec[:tx.value * ty.value].reshape(ty.value, tx.value)
+
+    def read_noise_moments(self):
+        """(sumY, M2), H x W float32 each (test hook)."""
+        a, b = np.empty((self.height, self.width), np.float32), np.empty((self.height, self.width), np.float32)
+        self._check(self._fn("read_noise_moments")(self._ctx, a.ctypes.data, b.ctypes.data))
+        return a, b
+
+    def noise_merge(self, n_a, sumY_a, m2_a, samples_rgb):
+        """Known-answer hook: one call's update of P pixels on samples_rgb (P x S x 3) -> (sumY, M2)."""
+        c = np.ascontiguousarray(samples_rgb, dtype=np.float32)
+        a, b = _f32(sumY_a).ravel(), _f32(m2_a).ravel()
+        assert c.ndim == 3 and c.shape[2] == 3 and len(a) == len(b) == c.shape[0]
+        oa, ob = np.empty_like(a), np.empty_like(b)
+        self._check(self._fn("noise_merge")(self._ctx, c.shape[0], int(n_a), a.ctypes.data, b.ctypes.data, c.shape[1], c.ctypes.data,
+                                            oa.ctypes.data, ob.ctypes.data))
+        return oa, ob
+
+    def noise_image(self, n, sumY, m2):
+        """Known-answer hook: the metric on given H x W moments -> (stats dict, error map H x W, tile records)."""
+        a, b = _f32(sumY), _f32(m2)
+        assert a.ndim == 2 and a.shape == b.shape
+        h, w = a.shape
+        st, e = abi.NoiseStats(), np.empty((h, w), np.float32)
+        tiles = np.zeros((-(-h // abi.NOISE_TILE_Y), -(-w // abi.NOISE_TILE_X)), abi.NOISE_TILE_DTYPE)
+        self._check(self._fn("noise_image")(self._ctx, w, h, int(n), a.ctypes.data, b.ctypes.data, C.byref(st), e.ctypes.data,
+                                            tiles.ctypes.data))
+        return st.as_dict(), e, tiles
+
+    def render_until(self, camera, threshold=None, max_samples=4096, check_every=1):
+        """Render until every pixel's noise is at most `threshold` (None: the noise_threshold setting as it stands) or
+        max_samples samples per pixel are in: a RESET call, then CONVERGE calls of the `spp` setting's samples each; the
+        stats are asked for every check_every calls — a query waits for the device, so a larger check_every lets the calls
+        in between overlap and stops up to check_every - 1 calls late.  Returns the last stats (a dict, see get_noise)."""
+        self.set_setting("noise_estimate", 1)
+        if threshold is not None:
+            self.set_setting("noise_threshold", repr(float(threshold)))
+        spp, cap, calls = int(self.get_setting("spp")), max(2, int(max_samples)), 0
+        while True:
+            for _ in range(max(1, int(check_every))):
+                if calls * spp < cap:
+                    self.render_async(camera, abi.CONVERGE if calls else abi.RESET)
+                    calls += 1
+            if calls * spp < 2:  # (the estimate needs two samples)
+                continue
+            st = self.get_noise()
+            if st["converged"] == st["pixels"] or calls * spp >= cap:
+                break
+        self.wait()
+        return st
+
     def read_denoise_history(self):
         """The temporal stage of the last presented frame (include/rfwhip.h, "denoise_temporal"; world-1 contexts):
         {"pre": H x W x 4 (I~, lum), "var": H x W, "history": H x W x 4 (colour history, lum), "moments": H x W x 2,
@@ -425,10 +502,11 @@ class CoreBinding:
     KERNELS = ("generate", "extend", "shade", "connect", "finalize", "refit")
     DENOISE = 6  # kernel family of the denoiser (guide pass + filter), outside KERNELS: the render's stages
     DISPLAY = 7  # ... and of the display stage (one launch per displayed image)
+    NOISE = 8  # ... and of the noise metric (two launches per get_noise)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -530,7 +608,8 @@ class RenderGroup:
             f = self._fn(name)
             f.restype, f.argtypes = res, args
         for name, res, args in [("group_read_display", i32, [vp, i32, vp]), ("group_present_display_async", i32, [vp, i32, i32]),
-                                ("group_present_display_wait", i32, [vp, i32, C.POINTER(vp), C.POINTER(i32)])]:
+                                ("group_present_display_wait", i32, [vp, i32, C.POINTER(vp), C.POINTER(i32)]),
+                                ("group_get_noise", i32, [vp, C.POINTER(abi.NoiseStats)])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -606,6 +685,12 @@ class RenderGroup:
         out = np.empty((self.height, self.width, 4), dtype=dt)
         self._check(self._fn("group_read_display")(self._g, code, out.ctypes.data))
         return out
+
+    def get_noise(self):
+        """The noise of the whole image: every rank reduces its strips, the root adds the records (CoreBinding.get_noise)."""
+        st = abi.NoiseStats()
+        self._check(self._fn("group_get_noise")(self._g, C.byref(st)))
+        return st.as_dict()
 
     def present_display_async(self, slot, format="rgba8"):
         """present_async with the display stage behind the gather: the copy carries the display image."""

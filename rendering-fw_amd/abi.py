@@ -162,6 +162,20 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class NoiseStats(C.Structure):
+    """rfwhip_noise_stats (include/rfwhip.h, rfwhip_get_noise)."""
+    _fields_ = [("samples", C.c_uint64), ("pixels", C.c_uint64), ("converged", C.c_uint64), ("mean_error", C.c_double),
+                ("max_error", C.c_float), ("threshold", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# rfwhip_noise_tile: one record per 32 x 8 noise tile
+NOISE_TILE_DTYPE = np.dtype([("sum_e", np.float32), ("max_e", np.float32), ("pixels", np.uint32), ("converged", np.uint32)])
+NOISE_TILE_X, NOISE_TILE_Y = 32, 8
+
+assert C.sizeof(NoiseStats) == 40 and NOISE_TILE_DTYPE.itemsize == 16
 assert C.sizeof(Mesh) == 56
 assert C.sizeof(Texture) == 32
 assert C.sizeof(CameraPOD) == 60

@@ -94,6 +94,33 @@ struct DisplayView
 	uint32_t fxaa, srgb, format;
 };
 
+// The noise estimate (noise.h).  One record per NZ_TILE_X x NZ_TILE_Y noise tile (= rfwhip_noise_tile) and the one record k_noise_final leaves
+constexpr uint32_t NZ_TILE_X = 32, NZ_TILE_Y = 8;
+struct NoiseTile
+{
+	float sum_e, max_e;
+	uint32_t pixels, converged;
+};
+struct NoiseTotal // 32 bytes: all the host reads back
+{
+	double sum_e;
+	unsigned long long pixels, converged;
+	float max_e;
+	uint32_t tiles;
+};
+// the metric's view of a rank's pixels, in the local layout of the accumulator (local_rows x W, row yl = a row of one of the
+// rank's strips): moments in, error map / tile records / total out
+struct NoiseView
+{
+	uint32_t W, H, local_rows, rank, world;
+	uint32_t n;			  // samples per pixel (>= 2)
+	const float *moments; // 2 per local pixel: sumY, M2
+	float *e_map;		  // local_rows x W; 0 where there is no pixel (rows >= H of the last strip)
+	NoiseTile *tiles;	  // ceil(W / 32) x local_rows / 8, row-major
+	NoiseTotal *total;
+	float floor_, threshold;
+};
+
 // capacity of the LDS top-of-tree cache the kernels were built with
 uint32_t max_lds_nodes();
 
@@ -121,6 +148,14 @@ void launch_shadow_packets(const Params &p, bool count, uint32_t max_items, stre
 // the extension rays of pe.depth and the shadow rays of pa.depth (= pe.depth - 1) in one launch (both with persistent lanes)
 void launch_trace_fused(const Params &pe, const Params &pa, bool count, uint32_t max_items, stream_t s);
 void launch_resolve(const Params &p, stream_t s);
+// noise_estimate = 1: k_resolve_noise, the resolve that also folds the call's samples into the two moments per local pixel
+// (noise.h; n_a = samples per pixel before this call).  The moments are arguments of their own: Params stays what it was
+void launch_resolve_noise(const Params &p, float *moments, uint32_t n_a, stream_t s);
+// the step update alone on given samples (rfwhip_noise_merge): samples_rgb = pixels x S x 3 floats, moments = 2 per pixel, in place
+void launch_noise_merge(const float *samples_rgb, float *moments, uint32_t pixels, uint32_t n_a, uint32_t S, stream_t s);
+// the metric: k_noise_tiles (error map + one record per tile) and k_noise_final (one workgroup, the tiles in index order)
+void launch_noise_metric(const NoiseView &v, stream_t s);
+uint32_t noise_tiles_x(uint32_t W);
 // rfwhip_kat: `function` (RFWHIP_KAT_*) on n records of 24 floats -> n records of 8 floats (device pointers)
 // (KAT_LT_*: the functions of k_kat_lt, RFWHIP_KAT_LT_* of rfwhip_abi.h; every other function runs in k_kat)
 constexpr int KAT_LT_SAMPLE = 17, KAT_LT_PICK_PROB = 18;

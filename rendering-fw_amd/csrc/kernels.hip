@@ -697,10 +697,14 @@ RT_FN void init_counters_item(WaveCounters *c, uint32_t primary_count, uint32_t 
 		c->probe_valid = 0u, c->stack_overflow = 0u;
 }
 
+// the noise estimate: the moments the resolve can keep beside acc, and the metric on them (work items shared with the emulation)
+#include "noise.h"
+
 // One pixel: its samples in sample order whatever the slot layout (rt_core.h: sample groups) — the image is independent of
 // it.  The g samples of a group are consecutive 16-byte records; they are fetched eight at a time (one 128-byte line per
 // lane and batch, the loads issued back to back) so that a line is consumed while it is in flight, not re-fetched.
-RT_FN void resolve_item(const Params &p, uint32_t li)
+// sink(rv, qv, nee): every sample once more, in the order it was added (noise.h; k_resolve's sink does nothing)
+template <typename Sink> RT_FN void resolve_item_t(const Params &p, uint32_t li, Sink &sink)
 {
 	const uint32_t x = li % p.fr.W, yl = li / p.fr.W;
 	if (local_to_global_row(p.fr, yl) >= p.fr.H)
@@ -726,6 +730,7 @@ RT_FN void resolve_item(const Params &p, uint32_t li)
 				a.x += rv[k].x, a.y += rv[k].y, a.z += rv[k].z, a.w += fabsf(rv[k].w);
 				if (q && !(rv[k].w < 0.0f))
 					a.x += qv[k].x, a.y += qv[k].y, a.z += qv[k].z;
+				sink(rv[k], qv[k], q && !(rv[k].w < 0.0f));
 			}
 		}
 		for (; i < g; i++)
@@ -736,10 +741,26 @@ RT_FN void resolve_item(const Params &p, uint32_t li)
 			{
 				const f4 qv = q[i];
 				a.x += qv.x, a.y += qv.y, a.z += qv.z;
+				sink(rv, qv, true);
 			}
+			else
+				sink(rv, rv, false);
 		}
 	}
 	p.wv.acc[li] = a;
+}
+RT_FN void resolve_item(const Params &p, uint32_t li)
+{
+	ResolveNoSink none;
+	resolve_item_t(p, li, none);
+}
+// ... and the moments of the noise estimate beside it: what happens to acc is resolve_item's, addition for addition
+RT_FN void resolve_noise_item(const Params &p, float *moments, uint32_t n_a, uint32_t li)
+{
+	NzSink sink;
+	sink.st.begin(n_a, moments[2u * li]);
+	resolve_item_t(p, li, sink);
+	nz_merge(n_a, sink.st, moments[2u * li], moments[2u * li + 1u]);
 }
 
 RT_FN void present_item(const Params &p, f4 *out, float scale, int full, uint32_t li)
@@ -1931,6 +1952,13 @@ __global__ void __launch_bounds__(BLOCK) k_resolve(const Params p)
 		resolve_item(p, i);
 }
 
+__global__ void __launch_bounds__(BLOCK) k_resolve_noise(const Params p, float *moments, uint32_t n_a)
+{
+	const uint32_t n = p.fr.W * p.fr.local_rows;
+	for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
+		resolve_noise_item(p, moments, n_a, i);
+}
+
 __global__ void __launch_bounds__(BLOCK) k_present(const Params p, f4 *out, float scale, int full)
 {
 	const uint32_t n = p.fr.W * p.fr.local_rows;
@@ -2529,6 +2557,70 @@ void launch_display(const DisplayView &v, stream_t s)
 						   (hipStream_t)s, v);
 	else
 		hipLaunchKernelGGL(k_display<false>, dim3((uint32_t)(((size_t)v.W * v.H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)s, v);
+}
+
+// ---- noise estimate (noise.h).  k_noise_tiles: a workgroup is one 32 x 8 tile, thread t its pixel (t & 31, t >> 5): a wave reads
+// and writes two 128-byte row segments of consecutive pixels.  The four sums of a tile go through a fixed xor butterfly inside each
+// wave64 and through LDS across the four waves; thread 0 adds the waves' results in wave order. ----
+static_assert(BLOCK == NZ_TILE_X * NZ_TILE_Y, "noise workgroup = one tile");
+__global__ void k_noise_merge(const float *samples_rgb, float *moments, uint32_t pixels, uint32_t n_a, uint32_t S)
+{
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < pixels)
+		nz_merge_item(samples_rgb, moments, n_a, S, i);
+}
+__global__ void __launch_bounds__(BLOCK) k_noise_tiles(const NoiseView v)
+{
+	__shared__ float s_sum[BLOCK / 64], s_max[BLOCK / 64];
+	__shared__ uint32_t s_pix[BLOCK / 64], s_conv[BLOCK / 64];
+	const uint32_t x = blockIdx.x * NZ_TILE_X + (threadIdx.x & (NZ_TILE_X - 1u)), yl = blockIdx.y * NZ_TILE_Y + threadIdx.x / NZ_TILE_X;
+	float e;
+	const bool real = nz_pixel_item(v, x, yl, e);
+	float sum = e, mx = e;
+	for (int m = 32; m >= 1; m >>= 1)
+		sum += __shfl_xor(sum, m, 64), mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+	const uint32_t pix = (uint32_t)__popcll(__ballot(real)), conv = (uint32_t)__popcll(__ballot(real && e <= v.threshold));
+	const uint32_t wave = threadIdx.x >> 6;
+	if ((threadIdx.x & 63u) == 0u)
+		s_sum[wave] = sum, s_max[wave] = mx, s_pix[wave] = pix, s_conv[wave] = conv;
+	__syncthreads();
+	if (threadIdx.x == 0u)
+	{
+		NoiseTile t = {0.0f, 0.0f, 0u, 0u};
+		for (uint32_t w = 0; w < BLOCK / 64; w++)
+			t.sum_e += s_sum[w], t.max_e = fmaxf(t.max_e, s_max[w]), t.pixels += s_pix[w], t.converged += s_conv[w];
+		t.sum_e = fminf(t.sum_e, FLT_MAX);
+		v.tiles[blockIdx.y * gridDim.x + blockIdx.x] = t;
+	}
+}
+__global__ void __launch_bounds__(BLOCK) k_noise_final(const NoiseView v, uint32_t count)
+{
+	__shared__ NoiseTotal s_part[BLOCK];
+	nz_fold(v.tiles, count, threadIdx.x, BLOCK, s_part[threadIdx.x]);
+	__syncthreads();
+	if (threadIdx.x == 0u)
+	{
+		NoiseTotal o = s_part[0];
+		for (uint32_t t = 1; t < BLOCK; t++)
+			nz_fold_add(o, s_part[t]);
+		*v.total = o;
+	}
+}
+uint32_t noise_tiles_x(uint32_t W) { return (W + NZ_TILE_X - 1u) / NZ_TILE_X; }
+void launch_resolve_noise(const Params &p, float *moments, uint32_t n_a, stream_t s)
+{
+	hipLaunchKernelGGL(k_resolve_noise, dim3(persistent_grid(p.fr.W * p.fr.local_rows, RT_GRID_BLOCKS_PER_CU, 8u)), dim3(BLOCK), 0, (hipStream_t)s, p,
+					   moments, n_a);
+}
+void launch_noise_merge(const float *samples_rgb, float *moments, uint32_t pixels, uint32_t n_a, uint32_t S, stream_t s)
+{
+	hipLaunchKernelGGL(k_noise_merge, dim3((pixels + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, samples_rgb, moments, pixels, n_a, S);
+}
+void launch_noise_metric(const NoiseView &v, stream_t s)
+{
+	const uint32_t tx = noise_tiles_x(v.W), ty = v.local_rows / NZ_TILE_Y;
+	hipLaunchKernelGGL(k_noise_tiles, dim3(tx, ty), dim3(BLOCK), 0, (hipStream_t)s, v);
+	hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, v, tx * ty);
 }
 
 // ================================================================================================================

@@ -399,6 +399,38 @@ void launch_resolve(const Params &p, stream_t s)
 	for (uint32_t i = 0; i < p.fr.W * p.fr.local_rows; i++)
 		resolve_item(p, i);
 }
+void launch_resolve_noise(const Params &p, float *moments, uint32_t n_a, stream_t s)
+{
+	EMU_DEFER(s, launch_resolve_noise(p, moments, n_a, s));
+	for (uint32_t i = 0; i < p.fr.W * p.fr.local_rows; i++)
+		resolve_noise_item(p, moments, n_a, i);
+}
+uint32_t noise_tiles_x(uint32_t W) { return (W + NZ_TILE_X - 1u) / NZ_TILE_X; }
+void launch_noise_merge(const float *samples_rgb, float *moments, uint32_t pixels, uint32_t n_a, uint32_t S, stream_t s)
+{
+	EMU_DEFER(s, launch_noise_merge(samples_rgb, moments, pixels, n_a, S, s));
+	for (uint32_t i = 0; i < pixels; i++)
+		nz_merge_item(samples_rgb, moments, n_a, S, i);
+}
+void launch_noise_metric(const NoiseView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_noise_metric(v, s));
+	// a tile's pixels in row-major order, the tiles in index order
+	const uint32_t tx = noise_tiles_x(v.W), ty = v.local_rows / NZ_TILE_Y;
+	for (uint32_t k = 0; k < tx * ty; k++)
+	{
+		NoiseTile t = {0.0f, 0.0f, 0u, 0u};
+		for (uint32_t j = 0; j < NZ_TILE_X * NZ_TILE_Y; j++)
+		{
+			float e;
+			if (nz_pixel_item(v, (k % tx) * NZ_TILE_X + j % NZ_TILE_X, (k / tx) * NZ_TILE_Y + j / NZ_TILE_X, e))
+				t.sum_e += e, t.max_e = fmaxf(t.max_e, e), t.pixels++, t.converged += e <= v.threshold;
+		}
+		t.sum_e = fminf(t.sum_e, FLT_MAX);
+		v.tiles[k] = t;
+	}
+	nz_fold(v.tiles, tx * ty, 0u, 1u, *v.total);
+}
 void launch_present(const Params &p, f4 *out, float scale, int full, stream_t s)
 {
 	EMU_DEFER(s, launch_present(p, out, scale, full, s));

@@ -20,6 +20,10 @@
 // tone-maps again on top of whatever the backend delivers (system.cpp:682-711).  Headless hosts read the bytes with
 // hiprtReadDisplay.
 //
+// Noise estimate: RFWHIP_NOISE=1 (unset by default: nothing changes) turns the setting noise_estimate on (include/rfwhip.h,
+// rfwhip_get_noise); a host asks hiprtGetNoise when to stop converging.  It answers for the accumulator — with frames in flight,
+// for the newest frame enqueued, not the one render_frame handed out.
+//
 // Headless by default (RenderTarget::BUFFER, context.h:27-34): the GPU box has no OpenGL.  With
 // -DRFWHIP_PLUGIN_WITH_GL (needs GLEW, i.e. the reference's own build environment) render_frame also uploads the
 // float4 image into the GL texture handed to init(), the same way EmbreeRT presents (EmbreeRT/src/Context.cpp:289-297).
@@ -89,6 +93,12 @@ class Context final : public rfw::RenderContext
 				throw std::runtime_error("HipRT: RFWHIP_DISPLAY must be \"aces\" or \"none\"");
 			m_Display = true;
 			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_tonemap", mode.c_str()));
+		}
+		if (const char *nz = std::getenv("RFWHIP_NOISE"))
+		{
+			if (std::string(nz) != "0" && std::string(nz) != "1")
+				throw std::runtime_error("HipRT: RFWHIP_NOISE must be \"0\" or \"1\"");
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "noise_estimate", nz));
 		}
 		const char *integ = std::getenv("RFWHIP_INTEGRATOR");
 		HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "integrator", integ ? integ : "pt"));
@@ -243,6 +253,9 @@ class Context final : public rfw::RenderContext
 		}
 		return rfwhip_group_read_display(m_Group, RFWHIP_DISPLAY_RGBA8, rgba8);
 	}
+
+	// the noise of the accumulated image (RFWHIP_NOISE=1; else RFWHIP_ERR_STATE)
+	int get_noise(rfwhip_noise_stats *stats) { return rfwhip_group_get_noise(m_Group, stats); }
 
 	void set_materials(const std::vector<rfw::DeviceMaterial> &materials,
 					   const std::vector<rfw::MaterialTexIds> &texDescriptors) override
@@ -403,4 +416,10 @@ HIPRT_EXPORT int hiprtReadFramebuffer(rfw::RenderContext *ptr, float *rgba)
 HIPRT_EXPORT int hiprtReadDisplay(rfw::RenderContext *ptr, uint8_t *rgba8)
 {
 	return static_cast<Context *>(ptr)->read_display(rgba8);
+}
+// ... and how noisy the accumulated image still is (the noise estimate, include/rfwhip.h rfwhip_get_noise): 0, or an rfwhip_status
+// (rfwhip_last_error has the text) — without RFWHIP_NOISE=1, or before the second sample
+HIPRT_EXPORT int hiprtGetNoise(rfw::RenderContext *ptr, rfwhip_noise_stats *stats)
+{
+	return static_cast<Context *>(ptr)->get_noise(stats);
 }

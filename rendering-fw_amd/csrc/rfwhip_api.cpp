@@ -207,7 +207,8 @@ enum KernelFamily
 	KF_REFIT = 5,
 	KF_DENOISE = 6, // the denoiser of the presented image: guide pass + filter (denoise.h)
 	KF_DISPLAY = 7, // the display stage: tone map + FXAA + encoding (display.h), one launch per displayed image
-	KF_COUNT = 8
+	KF_NOISE = 8,	// the noise metric: k_noise_tiles + k_noise_final (noise.h), two launches per query
+	KF_COUNT = 9
 };
 
 struct TimedSpan
@@ -366,6 +367,12 @@ struct rfwhip_context
 	// the display stage (display.h): tone map 0 aces | 1 none, FXAA, sRGB encoding; d_display: where the host reads land
 	int display_tonemap = 0, display_fxaa = 1, display_srgb = 0;
 	DevBuf d_display;
+	// the noise estimate (noise.h): d_noise = two moments per local pixel, allocated while noise_estimate is on.  noise_live: the
+	// moments cover every sample of the accumulator (the setting was on at the last RESET / rfwhip_init and ever since)
+	int noise_estimate = 0;
+	float noise_floor = 0.01f, noise_threshold = 0.05f;
+	bool noise_live = false;
+	DevBuf d_noise, d_noise_map, d_noise_tiles, d_noise_total, d_noise_in;
 	DevBuf d_lt_nodes, d_lt_paths; // allocated only while light_sampling is tree
 	rt::LightTreeView lt_view{};   // nodes == nullptr: linear (or no light with a position)
 	bool lt_stale = false;		   // the setting changed since: the next render (or update) builds the tree
@@ -395,8 +402,8 @@ struct rfwhip_context
 	std::vector<TimedSpan> spans;
 	std::vector<dm::event_t> event_pool;
 	size_t events_used = 0;
-	float kernel_ms[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
-	uint32_t kernel_launches[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
+	float kernel_ms[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+	uint32_t kernel_launches[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 	rfwhip_render_stats stats;
 	std::chrono::steady_clock::time_point render_t0;
 	bool render_pending = false;
@@ -570,9 +577,11 @@ static void free_all(rfwhip_context *c)
 					  &c->d_sh_dir[0], &c->d_sh_dir[1], &c->d_sh_rad[0], &c->d_sh_rad[1], &c->d_rad[0], &c->d_rad[1],
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
-					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display};
+					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
+					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in};
 	for (DevBuf *b : bufs)
 		b->free_();
+	c->noise_live = false;
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->dn_inst_ver_stale = true;
@@ -633,6 +642,18 @@ extern "C" void rfwhip_destroy(rfwhip_context *c)
 }
 
 static int dn_ensure(rfwhip_context *c);
+// the moments of the noise estimate start over with the accumulator (RESET, rfwhip_init); off: no buffer
+static int noise_clear(rfwhip_context *c, uint32_t local_rows, uint32_t width, void *stream)
+{
+	c->noise_live = c->noise_estimate != 0;
+	if (!c->noise_live)
+		return RFWHIP_OK;
+	const size_t bytes = (size_t)local_rows * width * 2u * sizeof(float);
+	if (bytes > c->d_noise.cap)
+		RF_TRY(sync_all(c));
+	RF_TRY(c->d_noise.ensure(bytes));
+	return dm::zero(c->d_noise.p, bytes, stream);
+}
 
 #define CTX_ENTER(c)                                                                      \
 	if (!(c))                                                                             \
@@ -659,6 +680,7 @@ extern "C" int rfwhip_init(rfwhip_context *c, uint32_t width, uint32_t height)
 	RF_TRY(c->d_acc.ensure((size_t)lr * width * sizeof(f4)));
 	RF_TRY(dm::zero(c->d_acc.p, (size_t)lr * width * sizeof(f4), c->stream));
 	c->samples_done = 0;
+	RF_TRY(noise_clear(c, lr, width, c->stream));
 	c->fr.W = width, c->fr.H = height, c->fr.local_rows = lr;
 	c->fr.inv_w = 1.0f / (float)width, c->fr.inv_h = 1.0f / (float)height;
 	c->fr.tiles_x = (width + rt::TILE - 1) / rt::TILE;
@@ -2215,6 +2237,7 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	{
 		RF_TRY(dm::zero(c->d_acc.p, (size_t)c->fr.local_rows * c->W * sizeof(f4), s0));
 		c->samples_done = 0;
+		RF_TRY(noise_clear(c, c->fr.local_rows, c->W, s0));
 		// decorrelated reset frames for the denoiser's temporal stage: the sample indices go on where the last frame's ended
 		// (mod 256: the blue-noise sampler's table)
 		c->sample_origin = c->dn_temporal ? (uint32_t)(c->samples_total % 256u) : 0u;
@@ -2434,7 +2457,10 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	}
 	{
 		StageTimer tf(c, KF_FINALIZE, -1);
-		rtk::launch_resolve(base, s0);
+		if (c->noise_live)
+			rtk::launch_resolve_noise(base, c->d_noise.as<float>(), c->samples_done, s0);
+		else
+			rtk::launch_resolve(base, s0);
 		tf.stop();
 	}
 	RF_TRY(dm::event_record(c->ev_resolve[par], s0));
@@ -3011,6 +3037,160 @@ extern "C" int rfwhip_display_image(rfwhip_context *c, const float *rgba_in, flo
 	return dm::sync(c->stream);
 }
 
+// ---- noise estimate (settings "noise_*"; work items: noise.h) -----------------------------------------------------------------------
+// the metric on `moments` (local layout of `rows` x W) for n samples per pixel: two launches on the context's stream and the 32-byte
+// record back on the host; the error map and the tile records stay in d_noise_map / d_noise_tiles
+static int noise_metric(rfwhip_context *c, const float *moments, uint32_t W, uint32_t H, uint32_t rows, uint32_t rank, uint32_t world,
+						uint32_t n, rtk::NoiseTotal *total)
+{
+	const uint32_t tiles = rtk::noise_tiles_x(W) * (rows / rtk::NZ_TILE_Y);
+	RF_TRY(c->d_noise_map.ensure((size_t)rows * W * sizeof(float)));
+	RF_TRY(c->d_noise_tiles.ensure((size_t)tiles * sizeof(rtk::NoiseTile)));
+	RF_TRY(c->d_noise_total.ensure(sizeof(rtk::NoiseTotal)));
+	rtk::NoiseView v;
+	v.W = W, v.H = H, v.local_rows = rows, v.rank = rank, v.world = world, v.n = n;
+	v.moments = moments, v.e_map = c->d_noise_map.as<float>(), v.tiles = c->d_noise_tiles.as<rtk::NoiseTile>();
+	v.total = c->d_noise_total.as<rtk::NoiseTotal>();
+	v.floor_ = c->noise_floor, v.threshold = c->noise_threshold;
+	{
+		StageTimer t(c, KF_NOISE, -1);
+		rtk::launch_noise_metric(v, c->stream);
+		t.stop(2);
+	}
+	RF_TRY(dm::last_launch_error());
+	RF_TRY(dm::d2h(total, c->d_noise_total.p, sizeof(*total), c->stream));
+	return dm::sync(c->stream);
+}
+static void noise_fill_stats(const rfwhip_context *c, const rtk::NoiseTotal &t, uint64_t samples, rfwhip_noise_stats *st)
+{
+	st->samples = samples, st->pixels = t.pixels, st->converged = t.converged;
+	st->mean_error = t.pixels ? t.sum_e / (double)t.pixels : 0.0;
+	st->max_error = t.max_e, st->threshold = c->noise_threshold;
+}
+// the metric on the context's own moments
+static int noise_own(rfwhip_context *c, const char *who, rtk::NoiseTotal *total)
+{
+	if (!c->noise_estimate)
+		return set_error(RFWHIP_ERR_STATE, "%s: noise_estimate is off", who);
+	if (!c->noise_live)
+		return set_error(RFWHIP_ERR_STATE, "%s: noise_estimate came on after the accumulation began; render with RFWHIP_RESET first", who);
+	if (c->samples_done < 2u)
+		return set_error(RFWHIP_ERR_STATE, "%s: %u samples per pixel, the estimate needs 2", who, c->samples_done);
+	// (the last render's resolve is on the context's stream: the metric runs behind it)
+	return noise_metric(c, c->d_noise.as<float>(), c->W, c->H, c->fr.local_rows, (uint32_t)c->rank, (uint32_t)c->world, c->samples_done, total);
+}
+
+extern "C" int rfwhip_get_noise(rfwhip_context *c, rfwhip_noise_stats *stats)
+{
+	CTX_ENTER(c);
+	if (!stats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null stats");
+	rtk::NoiseTotal t;
+	RF_TRY(noise_own(c, "rfwhip_get_noise", &t));
+	noise_fill_stats(c, t, c->samples_done, stats);
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_noise_map(rfwhip_context *c, float *e)
+{
+	CTX_ENTER(c);
+	if (!e)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null map");
+	if (c->world != 1)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_noise_map: this rank owns 1/%d of the image", c->world);
+	rtk::NoiseTotal t;
+	RF_TRY(noise_own(c, "rfwhip_read_noise_map", &t));
+	RF_TRY(dm::d2h(e, c->d_noise_map.p, (size_t)c->W * c->H * sizeof(float), c->stream)); // (world 1: local row = image row)
+	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_read_noise_tiles(rfwhip_context *c, rfwhip_noise_tile *records, size_t cap, uint32_t *tiles_x, uint32_t *tiles_y)
+{
+	CTX_ENTER(c);
+	if (!records || !tiles_x || !tiles_y)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null destination");
+	const uint32_t tx = rtk::noise_tiles_x(c->W), ty = c->fr.local_rows / rtk::NZ_TILE_Y;
+	if (c->noise_estimate && c->W && cap < (size_t)tx * ty)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_noise_tiles: room for %zu records, the context has %u x %u tiles", cap, tx, ty);
+	rtk::NoiseTotal t;
+	RF_TRY(noise_own(c, "rfwhip_read_noise_tiles", &t));
+	*tiles_x = tx, *tiles_y = ty;
+	RF_TRY(dm::d2h(records, c->d_noise_tiles.p, (size_t)tx * ty * sizeof(rtk::NoiseTile), c->stream));
+	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_read_noise_moments(rfwhip_context *c, float *sumY, float *m2)
+{
+	CTX_ENTER(c);
+	if (!sumY || !m2)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null destination");
+	if (c->world != 1)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_noise_moments: this rank owns 1/%d of the image", c->world);
+	if (!c->noise_estimate || !c->noise_live)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_noise_moments: %s", !c->noise_estimate ? "noise_estimate is off" : "noise_estimate came on after the accumulation began; render with RFWHIP_RESET first");
+	const size_t px = (size_t)c->W * c->H;
+	std::vector<float> both(px * 2u);
+	RF_TRY(dm::d2h(both.data(), c->d_noise.p, px * 2u * sizeof(float), c->stream));
+	RF_TRY(dm::sync(c->stream));
+	for (size_t i = 0; i < px; i++)
+		sumY[i] = both[2u * i], m2[i] = both[2u * i + 1u];
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_noise_merge(rfwhip_context *c, size_t pixels, uint32_t n_a, const float *sumY_a, const float *m2_a, uint32_t S,
+								  const float *samples_rgb, float *sumY_out, float *m2_out)
+{
+	CTX_ENTER(c);
+	if (!sumY_a || !m2_a || !samples_rgb || !sumY_out || !m2_out)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null array");
+	if (!pixels || !S || pixels > (1u << 24) || S > 4096u)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_noise_merge: 1 .. 2^24 pixels and 1 .. 4096 samples, got %zu and %u", pixels, S);
+	RF_TRY(sync_all(c));
+	const size_t sb = pixels * S * 3u * sizeof(float), mb = pixels * 2u * sizeof(float);
+	RF_TRY(c->d_noise_in.ensure(sb + mb));
+	std::vector<float> both(pixels * 2u);
+	for (size_t i = 0; i < pixels; i++)
+		both[2u * i] = sumY_a[i], both[2u * i + 1u] = m2_a[i];
+	float *d_samples = c->d_noise_in.as<float>(), *d_mom = d_samples + pixels * S * 3u;
+	RF_TRY(dm::h2d(d_samples, samples_rgb, sb, c->stream));
+	RF_TRY(dm::h2d(d_mom, both.data(), mb, c->stream));
+	rtk::launch_noise_merge(d_samples, d_mom, (uint32_t)pixels, n_a, S, c->stream);
+	RF_TRY(dm::last_launch_error());
+	RF_TRY(dm::d2h(both.data(), d_mom, mb, c->stream));
+	RF_TRY(dm::sync(c->stream));
+	for (size_t i = 0; i < pixels; i++)
+		sumY_out[i] = both[2u * i], m2_out[i] = both[2u * i + 1u];
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_noise_image(rfwhip_context *c, uint32_t W, uint32_t H, uint32_t n, const float *sumY, const float *m2,
+								  rfwhip_noise_stats *stats, float *e_map, rfwhip_noise_tile *tiles)
+{
+	CTX_ENTER(c);
+	if (!sumY || !m2 || !stats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null array");
+	if (!W || !H || W > 65536u || H > 65536u || (size_t)W * H > (1u << 26))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_noise_image: bad size %ux%u", W, H);
+	if (n < 2u)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_noise_image: %u samples per pixel, the estimate needs 2", n);
+	RF_TRY(sync_all(c));
+	const uint32_t rows = (H + rt::STRIP_ROWS - 1) / rt::STRIP_ROWS * rt::STRIP_ROWS; // (a world-1 context's local rows)
+	const size_t px = (size_t)W * H, lpx = (size_t)W * rows;
+	std::vector<float> both(lpx * 2u, 0.0f);
+	for (size_t i = 0; i < px; i++)
+		both[2u * i] = sumY[i], both[2u * i + 1u] = m2[i];
+	RF_TRY(c->d_noise_in.ensure(lpx * 2u * sizeof(float)));
+	RF_TRY(dm::h2d(c->d_noise_in.p, both.data(), lpx * 2u * sizeof(float), c->stream));
+	rtk::NoiseTotal t;
+	RF_TRY(noise_metric(c, c->d_noise_in.as<float>(), W, H, rows, 0u, 1u, n, &t));
+	noise_fill_stats(c, t, n, stats);
+	if (e_map)
+		RF_TRY(dm::d2h(e_map, c->d_noise_map.p, px * sizeof(float), c->stream));
+	if (tiles)
+		RF_TRY(dm::d2h(tiles, c->d_noise_tiles.p, (size_t)t.tiles * sizeof(rtk::NoiseTile), c->stream));
+	return dm::sync(c->stream);
+}
+
 extern "C" int rfwhip_read_local_framebuffer_device(rfwhip_context *c, void *rgba_device)
 {
 	CTX_ENTER(c);
@@ -3337,6 +3517,23 @@ static const Setting k_settings[] = {
 		 c->display_srgb = on;
 		 return RFWHIP_OK; },
 	 GET_INT(display_srgb), false},
+	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
+	{"noise_estimate", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 if (!on && c->noise_estimate)
+		 {
+			 RF_TRY(sync_all(c)); // (a resolve in flight may still write the moments)
+			 c->d_noise.free_(), c->d_noise_map.free_(), c->d_noise_tiles.free_(), c->d_noise_total.free_();
+			 c->noise_live = false;
+		 }
+		 c->noise_estimate = on; // (on: the moments begin with the next RESET or rfwhip_init)
+		 return RFWHIP_OK; },
+	 GET_INT(noise_estimate), false},
+	{"noise_floor", SET { return set_float(c->noise_floor, key, value, [](float f) { return f > 0.0f && f < 1e30f; }, "be a finite number > 0", false); },
+	 GET { return put(out, cap, "%g", c->noise_floor); }, false},
+	{"noise_threshold", SET { return set_float(c->noise_threshold, key, value, [](float f) { return f > 0.0f && f < 1e30f; }, "be a finite number > 0", false); },
+	 GET { return put(out, cap, "%g", c->noise_threshold); }, false},
 	// read-only: nodes of the light tree the next render would use (0: none, or light_sampling is not tree)
 	{"light_tree", nullptr, GET {
 		 if (c->lt_stale)
@@ -3909,6 +4106,8 @@ static_assert(sizeof(rfwhip_area_light) == sizeof(rt::AreaLight) && sizeof(rfwhi
 static_assert(RFWHIP_KAT_LT_SAMPLE == rtk::KAT_LT_SAMPLE && RFWHIP_KAT_LT_PICK_PROB == rtk::KAT_LT_PICK_PROB, "kernels.h restates the light-tree functions");
 static_assert(RFWHIP_KAT_IN == 24 && RFWHIP_KAT_OUT == 8, "kat_item's record layout (kernels.hip)");
 static_assert(RFWHIP_STRIP_ROWS == (int)rt::STRIP_ROWS, "rfwhip.h: rfwhip_row_owner() restates rt::strip_owner()");
+static_assert(sizeof(rfwhip_noise_tile) == sizeof(rtk::NoiseTile) && sizeof(rtk::NoiseTotal) == 32 && sizeof(rfwhip_noise_stats) == 40,
+			  "rfwhip.h: the noise records are the kernels' (kernels.h)");
 extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float *in, float *out)
 {
 	CTX_ENTER(c);

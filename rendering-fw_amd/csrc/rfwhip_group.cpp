@@ -706,6 +706,29 @@ extern "C" int rfwhip_group_read_display(rfwhip_group *g, int format, void *out_
 	return dm::d2h(out_host, g->disp, (size_t)g->W * g->H * display_bytes(format), root.stream);
 }
 
+extern "C" int rfwhip_group_get_noise(rfwhip_group *g, rfwhip_noise_stats *stats)
+{
+	if (!g || !stats)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null argument");
+	// every rank's two kernels and its 32-byte record; the ranks' records in rank order (g->ep is in rank order)
+	rfwhip_noise_stats sum = {0, 0, 0, 0.0, 0.0f, 0.0f};
+	double sum_e = 0.0;
+	for (auto &e : g->ep)
+	{
+		rfwhip_noise_stats st;
+		const int rc = rfwhip_get_noise(e.ctx, &st);
+		if (rc)
+			return rc;
+		sum.samples = st.samples, sum.threshold = st.threshold;
+		sum.pixels += st.pixels, sum.converged += st.converged;
+		sum_e += st.mean_error * (double)st.pixels;
+		sum.max_error = st.max_error > sum.max_error ? st.max_error : sum.max_error;
+	}
+	sum.mean_error = sum.pixels ? sum_e / (double)sum.pixels : 0.0;
+	*stats = sum;
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_group_framebuffer_device(rfwhip_group *g, void **rgba_device, int *device_ordinal)
 {
 	if (!g || !rgba_device)
