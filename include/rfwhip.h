@@ -190,7 +190,7 @@ RFWHIP_API int rfwhip_display_image(rfwhip_context *ctx, const float *rgba_in, f
  *   Tiles: 32 x 8 pixels, aligned to the ownership strips, so a tile belongs to one rank; a partial tile counts its real pixels. */
 typedef struct rfwhip_noise_stats
 {
-	uint64_t samples;	/* n */
+	uint64_t samples;	/* n: the context's sample count since the RESET (with adaptive_sampling too, where a tile's own count is n_tile) */
 	uint64_t pixels;	/* pixels judged (a rank: the pixels of its strips) */
 	uint64_t converged; /* ... of which e <= threshold */
 	double mean_error;	/* sum of e / pixels */
@@ -228,6 +228,53 @@ RFWHIP_API int rfwhip_noise_merge(rfwhip_context *ctx, size_t pixels, uint32_t n
 								  const float *samples_rgb, float *sumY_out, float *m2_out);
 RFWHIP_API int rfwhip_noise_image(rfwhip_context *ctx, uint32_t width, uint32_t height, uint32_t n, const float *sumY, const float *m2,
 								  rfwhip_noise_stats *stats, float *e_map, rfwhip_noise_tile *tiles);
+
+/* ---- adaptive sampling: samples only where the noise estimate asks for them ---------------------------------------------------
+ * With adaptive_sampling = 1 (beside noise_estimate = 1, pt integrator) every 32 x 8 noise tile of a rank carries a sample count n_tile
+ * and an active flag; RFWHIP_RESET and rfwhip_init set n_tile = 0 and active = 1.  A render call of S = spp samples traces primary
+ * paths only for the pixels of active tiles and adds S to their n_tile; the sample indices are what they are without the setting
+ * (a retired pixel does not draw the indices of the calls it sits out), so an active pixel's accumulator, moments and error are, bit
+ * for bit, those of the same calls with the setting off.  Calls since the RESET are numbered 1, 2, ..; after call k with
+ * k % adaptive_every == 0 a DECISION is taken on the device: an active tile retires when n_tile >= adaptive_min_samples and every
+ * real pixel of it has e <= noise_threshold (its record has converged == pixels).  A RETIRED TILE STAYS RETIRED until the next RESET
+ * or rfwhip_init, whatever noise_threshold, noise_floor or adaptive_min_samples do later: its accumulator, moments and error are
+ * frozen.  The mask a call uses is a function of the state after the call before it and of nothing else — no scheduling setting
+ * (ring, streams, overlap, sub_batch_paths, fuse, refill, group_flags, sample_group) and no pipelining of rfwhip_render calls changes
+ * a bit of any image.  Stopping a tile by an estimate made of the very samples it is judged by biases its mean slightly (DESIGN.md
+ * section 15); adaptive_min_samples is the guard.
+ *   Settings (not listed by rfwhip_get_settings):
+ *     adaptive_sampling    = "0" (default) | "1"; like the moments it takes effect — on AND off — with the next RESET or
+ *                            rfwhip_init.  "1" without noise_estimate = 1 is RFWHIP_ERR_STATE, and so is noise_estimate = 0 while
+ *                            this is on or while the accumulation in progress is an adaptive one
+ *     adaptive_min_samples = integer >= 2 (default 16); read at every decision: a new value holds from the next decision on
+ *     adaptive_every       = integer in [1, 64] (default 4): render calls between two decisions; read after every call (a
+ *                            decision follows call k when k % adaptive_every == 0 with the value as it stands then)
+ *   rfwhip_render with integrator = parity returns RFWHIP_ERR_STATE while the setting is on.
+ *   Every presented image (rfwhip_read_framebuffer*, the local / stream forms, the group's and a comm host's gathers, and with them
+ *   the denoiser and the display stage) scales a pixel by 1 / n_tile, the float32 quotient 1.0f / (float)n_tile (0 for 0).
+ *   rfwhip_get_noise and the noise reads use n_tile per tile; rfwhip_noise_stats::samples stays the context's count since the RESET.
+ *   rfwhip_read_primary_hits reports prim -2 ("not sampled in the last call") and t 1e34 for the pixels of retired tiles;
+ *   rfwhip_get_probe_results keeps its last valid answer when the probe pixel was not sampled.
+ *   The queries below return RFWHIP_ERR_STATE unless the accumulation in progress is an adaptive one (the setting was on at the last
+ *   RESET / rfwhip_init). */
+typedef struct rfwhip_adaptive_stats
+{
+	uint64_t tiles;			  /* tiles of this rank with at least one real pixel */
+	uint64_t active_tiles;
+	uint64_t pixels;		  /* real pixels of those tiles */
+	uint64_t active_pixels;
+	uint64_t samples_taken;	  /* sum over tiles of n_tile x real pixels */
+	uint64_t samples_uniform; /* samples since the RESET x pixels: what the same calls take without the setting */
+} rfwhip_adaptive_stats;
+/* Waits for the calls enqueued so far and reads the tiles' 5 bytes each. */
+RFWHIP_API int rfwhip_get_adaptive(rfwhip_context *ctx, rfwhip_adaptive_stats *stats);
+/* n_tile and the active flag of every tile of this rank, row-major, tiles_x x tiles_y as rfwhip_read_noise_tiles (the tiles of the
+ * padded rows below the image included).  cap = tiles the arrays hold; too few: RFWHIP_ERR_INVALID_ARGUMENT. */
+RFWHIP_API int rfwhip_read_adaptive_tiles(rfwhip_context *ctx, uint32_t *n, uint8_t *active, size_t cap, uint32_t *tiles_x, uint32_t *tiles_y);
+/* Known-answer hook: forces the mask.  active = one byte per tile in the order of rfwhip_read_adaptive_tiles, count = their number;
+ * a 0 retires the tile now, a non-zero byte leaves it as it is — flags only clear, a retired tile stays retired.  Waits for the
+ * calls enqueued so far. */
+RFWHIP_API int rfwhip_adaptive_set_tiles(rfwhip_context *ctx, const uint8_t *active, size_t count);
 
 /* Where a context runs and what it renders into (for hosts that move its strips themselves). */
 RFWHIP_API int rfwhip_get_placement(rfwhip_context *ctx, int *device_ordinal, int *rank, int *world);
@@ -286,6 +333,9 @@ RFWHIP_API int rfwhip_group_present_wait(rfwhip_group *group, int slot, const fl
 /* The noise estimate of the whole image (see rfwhip_get_noise): every rank reduces its own strips on its device, the root adds the
  * ranks' records in rank order on the host — counts exactly, the sum of errors in double, the maximum of the maxima. */
 RFWHIP_API int rfwhip_group_get_noise(rfwhip_group *group, rfwhip_noise_stats *stats);
+/* Adaptive sampling of the whole image (see rfwhip_get_adaptive): tiles and their decisions are per rank; the ranks' records are
+ * added in rank order. */
+RFWHIP_API int rfwhip_group_get_adaptive(rfwhip_group *group, rfwhip_adaptive_stats *stats);
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
 RFWHIP_API int rfwhip_group_present_display_wait(rfwhip_group *group, int slot, const void **out_host, int *format);
@@ -524,6 +574,7 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                  below has the formulas.  The parity integrator ignores it.
  *   display_tonemap / display_fxaa / display_srgb = the display stage, see rfwhip_read_display above.
  *   noise_estimate / noise_floor / noise_threshold = the noise estimate, see rfwhip_get_noise above.
+ *   adaptive_sampling / adaptive_min_samples / adaptive_every = adaptive sampling, see rfwhip_get_adaptive above.
  * Returns the number of keys; fills up to cap pointers with static strings. */
 RFWHIP_API int rfwhip_set_setting(rfwhip_context *ctx, const char *key, const char *value);
 RFWHIP_API int rfwhip_get_setting(rfwhip_context *ctx, const char *key, char *value, size_t cap);

@@ -97,6 +97,9 @@ class CoreBinding:
                                   "read_noise_moments": (i32, [vp, vp, vp]),
                                   "noise_merge": (i32, [vp, sz, u32, vp, vp, u32, vp, vp, vp]),
                                   "noise_image": (i32, [vp, u32, u32, u32, vp, vp, C.POINTER(abi.NoiseStats), vp, vp]),
+                                  "get_adaptive": (i32, [vp, C.POINTER(abi.AdaptiveStats)]),
+                                  "read_adaptive_tiles": (i32, [vp, vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
+                                  "adaptive_set_tiles": (i32, [vp, vp, sz]),
                                   "read_denoise_history": (i32, [vp, vp, vp, vp, vp, vp]),
                                   "read_denoise_motion": (i32, [vp, vp, vp, vp]),
                                   "get_counters": (i32, [vp, C.POINTER(abi.Counters), i32]),
@@ -479,6 +482,27 @@ class CoreBinding:
         self.wait()
         return st
 
+    # ---- adaptive sampling (include/rfwhip.h, rfwhip_get_adaptive; setting adaptive_sampling = 1) ------------------
+    def get_adaptive(self):
+        """Adaptive sampling so far as a dict: tiles, active_tiles, pixels, active_pixels, samples_taken, samples_uniform."""
+        st = abi.AdaptiveStats()
+        self._check(self._fn("get_adaptive")(self._ctx, C.byref(st)))
+        return st.as_dict()
+
+    def read_adaptive_tiles(self):
+        """(n_tile uint32, active bool), tiles_y x tiles_x each: this rank's tiles in the order of read_noise_tiles."""
+        cap = -(-self.width // abi.NOISE_TILE_X) * (int(self._fn("local_rows")(self._ctx)) // abi.NOISE_TILE_Y)
+        n, a = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint8)
+        tx, ty = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("read_adaptive_tiles")(self._ctx, n.ctypes.data, a.ctypes.data, cap, C.byref(tx), C.byref(ty)))
+        k = tx.value * ty.value
+        return n[:k].reshape(ty.value, tx.value), a[:k].reshape(ty.value, tx.value).astype(bool)
+
+    def adaptive_set_tiles(self, active):
+        """Known-answer hook: retire the tiles whose flag is false (flags only clear; tiles in the order of read_adaptive_tiles)."""
+        a = np.ascontiguousarray(np.asarray(active).ravel() != 0, dtype=np.uint8)
+        self._check(self._fn("adaptive_set_tiles")(self._ctx, a.ctypes.data, len(a)))
+
     def read_denoise_history(self):
         """The temporal stage of the last presented frame (include/rfwhip.h, "denoise_temporal"; world-1 contexts):
         {"pre": H x W x 4 (I~, lum), "var": H x W, "history": H x W x 4 (colour history, lum), "moments": H x W x 2,
@@ -609,7 +633,8 @@ class RenderGroup:
             f.restype, f.argtypes = res, args
         for name, res, args in [("group_read_display", i32, [vp, i32, vp]), ("group_present_display_async", i32, [vp, i32, i32]),
                                 ("group_present_display_wait", i32, [vp, i32, C.POINTER(vp), C.POINTER(i32)]),
-                                ("group_get_noise", i32, [vp, C.POINTER(abi.NoiseStats)])]:
+                                ("group_get_noise", i32, [vp, C.POINTER(abi.NoiseStats)]),
+                                ("group_get_adaptive", i32, [vp, C.POINTER(abi.AdaptiveStats)])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -690,6 +715,12 @@ class RenderGroup:
         """The noise of the whole image: every rank reduces its strips, the root adds the records (CoreBinding.get_noise)."""
         st = abi.NoiseStats()
         self._check(self._fn("group_get_noise")(self._g, C.byref(st)))
+        return st.as_dict()
+
+    def get_adaptive(self):
+        """Adaptive sampling of the whole image: the ranks' records added up (CoreBinding.get_adaptive)."""
+        st = abi.AdaptiveStats()
+        self._check(self._fn("group_get_adaptive")(self._g, C.byref(st)))
         return st.as_dict()
 
     def present_display_async(self, slot, format="rgba8"):

@@ -171,10 +171,19 @@ class NoiseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AdaptiveStats(C.Structure):
+    """rfwhip_adaptive_stats (include/rfwhip.h, rfwhip_get_adaptive)."""
+    _fields_ = [(n, C.c_uint64) for n in ("tiles", "active_tiles", "pixels", "active_pixels", "samples_taken", "samples_uniform")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 # rfwhip_noise_tile: one record per 32 x 8 noise tile
 NOISE_TILE_DTYPE = np.dtype([("sum_e", np.float32), ("max_e", np.float32), ("pixels", np.uint32), ("converged", np.uint32)])
 NOISE_TILE_X, NOISE_TILE_Y = 32, 8
 
+assert C.sizeof(AdaptiveStats) == 48
 assert C.sizeof(NoiseStats) == 40 and NOISE_TILE_DTYPE.itemsize == 16
 assert C.sizeof(Mesh) == 56
 assert C.sizeof(Texture) == 32

@@ -120,6 +120,17 @@ struct NoiseView
 	NoiseTotal *total;
 	float floor_, threshold;
 };
+// adaptive sampling (adaptive.h): the per-tile state of a rank beside the tile records of the metric
+struct AdaptiveView
+{
+	uint32_t ntx, count;   // noise tiles per row, and in all (= ntx * local_rows / 8)
+	uint32_t tiles_x;	   // slot tiles per row (FrameView::tiles_x): the mask's row length
+	uint32_t min_samples;  // adaptive_min_samples
+	uint32_t *n_tile;	   // samples the tile's pixels hold
+	unsigned char *active; // 1 until the tile retires
+	unsigned char *mask;   // one byte per slot tile, tiles_x x local_rows / 8 (padded to whole words): 1 = trace
+	const NoiseTile *tiles;
+};
 
 // capacity of the LDS top-of-tree cache the kernels were built with
 uint32_t max_lds_nodes();
@@ -156,6 +167,19 @@ void launch_noise_merge(const float *samples_rgb, float *moments, uint32_t pixel
 // the metric: k_noise_tiles (error map + one record per tile) and k_noise_final (one workgroup, the tiles in index order)
 void launch_noise_metric(const NoiseView &v, stream_t s);
 uint32_t noise_tiles_x(uint32_t W);
+// adaptive_sampling = 1 (adaptive.h).  The pt primary wave with the mask as an argument of its own (k_primary_packet_masked /
+// k_extend_masked: Params, and every other kernel's code, stay what they were), ...
+void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s);
+// ... k_resolve_adaptive (launch_resolve_noise for the pixels of active tiles, n_a per tile), k_present_adaptive (scale per tile), ...
+void launch_resolve_adaptive(const Params &p, float *moments, const AdaptiveView &a, stream_t s);
+void launch_present_adaptive(const Params &p, rt::f4 *out, const AdaptiveView &a, int full, stream_t s);
+// ... the metric with n per tile (final: k_noise_final behind it, as launch_noise_metric; else the tile records alone), ...
+void launch_noise_metric_adaptive(const NoiseView &v, const uint32_t *n_tile, bool final, stream_t s);
+// ... and k_adaptive_step: n_tile += add on active tiles; decide: retire by the tile records
+void launch_adaptive_step(const AdaptiveView &a, uint32_t add, bool decide, stream_t s);
+void launch_adaptive_reset(const AdaptiveView &a, stream_t s); // n_tile = 0, every tile active
+// k_adaptive_connections: behind the shade launch of `depth`, the connections of that depth are traced whatever the other tiles do
+void launch_adaptive_connections(rt::WaveCounters *c, uint32_t depth, stream_t s);
 // rfwhip_kat: `function` (RFWHIP_KAT_*) on n records of 24 floats -> n records of 8 floats (device pointers)
 // (KAT_LT_*: the functions of k_kat_lt, RFWHIP_KAT_LT_* of rfwhip_abi.h; every other function runs in k_kat)
 constexpr int KAT_LT_SAMPLE = 17, KAT_LT_PICK_PROB = 18;

@@ -778,6 +778,9 @@ RT_FN void present_item(const Params &p, f4 *out, float scale, int full, uint32_
 		out[li] = y < p.fr.H ? v : mk4(0, 0, 0, 0);
 }
 
+// adaptive sampling: the masked primary wave, the resolve and the present per tile, the decision (work items shared with the emulation)
+#include "adaptive.h"
+
 RT_FN void deinterleave_item(const f4 *gathered, f4 *out, uint32_t W, uint32_t H, uint32_t local_rows, uint32_t world,
 							 uint32_t gi)
 {
@@ -1076,6 +1079,23 @@ __global__ void __launch_bounds__(BLOCK, RT_PRIMARY_WAVES) k_extend(const Params
 		const uint32_t i = c * BLOCK + threadIdx.x;
 		if (c < w.nchunks)
 			extend_item<GEN, COUNT>(p, i, i < count, ctx);
+	}
+	clock_out(p.wv.counters, p.depth);
+}
+
+// k_extend<GEN_PT> with the mask of adaptive sampling (adaptive.h)
+template <bool COUNT>
+__global__ void __launch_bounds__(BLOCK, RT_PRIMARY_WAVES) k_extend_masked(const Params p, const uint32_t count, const unsigned char *mask)
+{
+	clock_in(p.wv.counters, p.depth);
+	RT_STACK_DECL_CLOSEST
+	ChunkQueue w(p, count);
+	uint32_t c;
+	while (w.next(c))
+	{
+		const uint32_t i = c * BLOCK + threadIdx.x;
+		if (c < w.nchunks)
+			extend_masked_item<COUNT>(p, mask, i, i < count, ctx);
 	}
 	clock_out(p.wv.counters, p.depth);
 }
@@ -1709,70 +1729,17 @@ __device__ __forceinline__ const Params &fresh_params()
 template <bool COUNT>
 __global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet(const Params p, const uint32_t count)
 {
-	clock_in(p.wv.counters, 0);
-	uint32_t *const head = &p.wv.counters->work[p.queue][0];
-	const uint32_t lane = __lane_id();
-	uint32_t run = count / (gridDim.x * (blockDim.x / 64u) * 4u);
-	run = run > (uint32_t)RT_PACKET_CHUNK ? (uint32_t)RT_PACKET_CHUNK : (run < 64u ? 64u : (run & ~63u));
-	TStat st;
-	st.inner = 0, st.tris = 0, st.lds = 0;
-	uint32_t nrays = 0;
-	for (;;)
-	{
-		uint32_t g = 0;
-		if (lane == 0)
-			g = atomicAdd(head, run);
-		g = (uint32_t)__builtin_amdgcn_readfirstlane((int)g);
-		if (g >= count)
-			break;
-		const uint32_t end = g + run < count ? g + run : count;
-		for (uint32_t base = g; base < end; base += 64u)
-		{
-			const uint32_t idx = base + lane;
-			bool active = idx < end;
-			f3 O = mk3(0, 0, 0), D = mk3(0, 0, 1);
-			{
-				const Params &q = fresh_params();
-				if (active)
-				{
-					const PixelRef pr = slot_to_pixel(q.fr, idx);
-					active = pr.valid;
-					if (active)
-					{
-						pt_primary_ray(q.cam, q.fr, pr.x, pr.y, q.fr.sample_base + pr.sample, O, D);
-						// VESTIGE: nothing reads this record (the shade kernel regenerates the primary ray); the store stays because dropping it
-						// changes this kernel's code object — a performance change with its own measurement (DESIGN_LOG.md, round 7)
-						if (q.cam.aperture != 0.0f)
-							q.wv.org[0][idx] = mk4(O.x, O.y, O.z, ubits((idx << 1) | 1u));
-					}
-				}
-			}
-			Hit h;
-			h.t = 1e34f, h.u = 0.0f, h.v = 0.0f, h.prim = -1, h.inst = -1;
-			trace_packet<COUNT>(fresh_params().sc, active, O, D, 1e-5f, h, st);
-			if (active)
-			{
-				primary_finish_item(fresh_params(), idx, D, h); // (hit record, or the sky term of a miss)
-				nrays++;
-			}
-			// a group without a hit is finished here (27 % of the terrain's): the shade kernel's scan passes it by
-			{
-				unsigned char *const done = fresh_params().wv.hit0_done;
-				const bool none = __ballot(active && h.prim >= 0) == 0ull;
-				if (done && lane == 0u)
-					done[base >> 6] = none ? 1 : 0;
-			}
-		}
-	}
-	if (COUNT)
-	{
-		WaveCounters *const wc = p.wv.counters;
-		Ctx ctx;
-		ctx.add64(&wc->inner_extend, st.inner);
-		ctx.add64(&wc->tris_extend, st.tris);
-		ctx.add64(&wc->rays_extend, nrays);
-	}
-	clock_out(p.wv.counters, 0);
+	constexpr bool MASKED = false;
+	const unsigned char *const mask = nullptr;
+#include "primary_packet_body.h"
+}
+// adaptive sampling (adaptive.h): the mask is an argument of its own.  (Params first: fresh_params reads them from offset 0 of the
+// kernarg segment)
+template <bool COUNT>
+__global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet_masked(const Params p, const uint32_t count, const unsigned char *mask)
+{
+	constexpr bool MASKED = true;
+#include "primary_packet_body.h"
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -2621,6 +2588,104 @@ void launch_noise_metric(const NoiseView &v, stream_t s)
 	const uint32_t tx = noise_tiles_x(v.W), ty = v.local_rows / NZ_TILE_Y;
 	hipLaunchKernelGGL(k_noise_tiles, dim3(tx, ty), dim3(BLOCK), 0, (hipStream_t)s, v);
 	hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, v, tx * ty);
+}
+
+// ---- adaptive sampling (adaptive.h) ----
+__global__ void __launch_bounds__(BLOCK) k_resolve_adaptive(const Params p, float *moments, const AdaptiveView a)
+{
+	const uint32_t n = p.fr.W * p.fr.local_rows;
+	for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
+		resolve_adaptive_item(p, moments, a, i);
+}
+__global__ void __launch_bounds__(BLOCK) k_present_adaptive(const Params p, f4 *out, const AdaptiveView a, int full)
+{
+	const uint32_t n = p.fr.W * p.fr.local_rows;
+	for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
+		present_adaptive_item(p, out, a, full, i);
+}
+// k_noise_tiles with n per tile.  Its reduction is k_noise_tiles', line for line, and a change to one is a change to both.  It is a
+// copy because sharing it changes the code k_noise_tiles compiles to: with the reduction in one __forceinline__ function that both
+// kernels call, four v_add_u32 of k_noise_tiles' last fold come out with their operands exchanged (tools/dev/isa_same.py --labels:
+// 1 differs) — the same numbers, not the same code, and the kernels that exist stay instruction for instruction what they are
+__global__ void __launch_bounds__(BLOCK) k_noise_tiles_adaptive(const NoiseView v, const uint32_t *n_tile)
+{
+	__shared__ float s_sum[BLOCK / 64], s_max[BLOCK / 64];
+	__shared__ uint32_t s_pix[BLOCK / 64], s_conv[BLOCK / 64];
+	const uint32_t x = blockIdx.x * NZ_TILE_X + (threadIdx.x & (NZ_TILE_X - 1u)), yl = blockIdx.y * NZ_TILE_Y + threadIdx.x / NZ_TILE_X;
+	float e;
+	const bool real = ad_noise_pixel_item(v, n_tile, x, yl, e);
+	float sum = e, mx = e;
+	for (int m = 32; m >= 1; m >>= 1)
+		sum += __shfl_xor(sum, m, 64), mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+	const uint32_t pix = (uint32_t)__popcll(__ballot(real)), conv = (uint32_t)__popcll(__ballot(real && e <= v.threshold));
+	const uint32_t wave = threadIdx.x >> 6;
+	if ((threadIdx.x & 63u) == 0u)
+		s_sum[wave] = sum, s_max[wave] = mx, s_pix[wave] = pix, s_conv[wave] = conv;
+	__syncthreads();
+	if (threadIdx.x == 0u)
+	{
+		NoiseTile t = {0.0f, 0.0f, 0u, 0u};
+		for (uint32_t w = 0; w < BLOCK / 64; w++)
+			t.sum_e += s_sum[w], t.max_e = fmaxf(t.max_e, s_max[w]), t.pixels += s_pix[w], t.converged += s_conv[w];
+		t.sum_e = fminf(t.sum_e, FLT_MAX);
+		v.tiles[blockIdx.y * gridDim.x + blockIdx.x] = t;
+	}
+}
+__global__ void k_adaptive_step(const AdaptiveView a, uint32_t add, int decide)
+{
+	adaptive_step_item(a, add, decide != 0, blockIdx.x * BLOCK + threadIdx.x);
+}
+__global__ void k_adaptive_reset(const AdaptiveView a) { adaptive_reset_item(a, blockIdx.x * BLOCK + threadIdx.x); }
+void launch_adaptive_reset(const AdaptiveView &a, stream_t s)
+{
+	hipLaunchKernelGGL(k_adaptive_reset, dim3((a.count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, a);
+}
+__global__ void k_adaptive_connections(WaveCounters *c, uint32_t depth)
+{
+	if (blockIdx.x == 0u && threadIdx.x == 0u)
+		adaptive_connections_item(c, depth);
+}
+void launch_adaptive_connections(WaveCounters *c, uint32_t depth, stream_t s)
+{
+	hipLaunchKernelGGL(k_adaptive_connections, dim3(1), dim3(64), 0, (hipStream_t)s, c, depth);
+}
+void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s)
+{
+	const dim3 g(persistent_grid(max_items)), b(BLOCK);
+	hipStream_t st = (hipStream_t)s;
+	if (primary_packet_form(p, max_items))
+	{
+		const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
+		if (count)
+			hipLaunchKernelGGL((k_primary_packet_masked<true>), gt, bt, 0, st, p, max_items, mask);
+		else
+			hipLaunchKernelGGL((k_primary_packet_masked<false>), gt, bt, 0, st, p, max_items, mask);
+	}
+	else if (count)
+		hipLaunchKernelGGL((k_extend_masked<true>), g, b, 0, st, p, max_items, mask);
+	else
+		hipLaunchKernelGGL((k_extend_masked<false>), g, b, 0, st, p, max_items, mask);
+}
+void launch_resolve_adaptive(const Params &p, float *moments, const AdaptiveView &a, stream_t s)
+{
+	hipLaunchKernelGGL(k_resolve_adaptive, dim3(persistent_grid(p.fr.W * p.fr.local_rows, RT_GRID_BLOCKS_PER_CU, 8u)), dim3(BLOCK), 0, (hipStream_t)s, p,
+					   moments, a);
+}
+void launch_present_adaptive(const Params &p, f4 *out, const AdaptiveView &a, int full, stream_t s)
+{
+	hipLaunchKernelGGL(k_present_adaptive, dim3(persistent_grid(p.fr.W * p.fr.local_rows, RT_GRID_BLOCKS_PER_CU, 8u)), dim3(BLOCK), 0, (hipStream_t)s, p,
+					   out, a, full);
+}
+void launch_noise_metric_adaptive(const NoiseView &v, const uint32_t *n_tile, bool final, stream_t s)
+{
+	const uint32_t tx = noise_tiles_x(v.W), ty = v.local_rows / NZ_TILE_Y;
+	hipLaunchKernelGGL(k_noise_tiles_adaptive, dim3(tx, ty), dim3(BLOCK), 0, (hipStream_t)s, v, n_tile);
+	if (final)
+		hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, v, tx * ty);
+}
+void launch_adaptive_step(const AdaptiveView &a, uint32_t add, bool decide, stream_t s)
+{
+	hipLaunchKernelGGL(k_adaptive_step, dim3((a.count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, a, add, decide ? 1 : 0);
 }
 
 // ================================================================================================================

@@ -228,13 +228,22 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 		}
 	}
 }
-template <bool COUNT> void primary(const Params &p, uint32_t count)
+// mask (adaptive.h): one byte per slot tile, null = every tile is traced
+template <bool COUNT> void primary(const Params &p, uint32_t count, const unsigned char *mask = nullptr)
 {
 	TStat st;
 	st.inner = 0, st.tris = 0, st.lds = 0;
 	unsigned long long nrays = 0;
 	for (uint32_t base = 0; base < count; base += WAVE)
 	{
+		if (mask && !mask[ad_slot_tile(p.fr, base)]) // (a retired tile's group: void records, nothing traced)
+		{
+			for (uint32_t idx = base; idx < base + WAVE && idx < count; idx++)
+				p.wv.hit0[idx] = ad_void_hit();
+			if (p.wv.hit0_done)
+				p.wv.hit0_done[base >> 6] = 1;
+			continue;
+		}
 		bool active[WAVE];
 		f3 O[WAVE], D[WAVE];
 		Hit h[WAVE];
@@ -295,6 +304,18 @@ void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, str
 		else
 			count ? extend_item<GEN_PARITY, true>(p, i, true, ctx) : extend_item<GEN_PARITY, false>(p, i, true, ctx);
 	}
+}
+void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s)
+{
+	EMU_DEFER(s, launch_extend_masked(p, mask, count, max_items, s));
+	if (RT_PRIMARY_PACKET_RULE(p, max_items))
+	{
+		count ? packet_emu::primary<true>(p, max_items, mask) : packet_emu::primary<false>(p, max_items, mask);
+		return;
+	}
+	Ctx ctx(p);
+	for (uint32_t i = 0; i < max_items; i++)
+		count ? extend_masked_item<true>(p, mask, i, true, ctx) : extend_masked_item<false>(p, mask, i, true, ctx);
 }
 void launch_shade_parity(const Params &p, bool count, uint32_t max_items, stream_t s)
 {
@@ -430,6 +451,55 @@ void launch_noise_metric(const NoiseView &v, stream_t s)
 		v.tiles[k] = t;
 	}
 	nz_fold(v.tiles, tx * ty, 0u, 1u, *v.total);
+}
+void launch_resolve_adaptive(const Params &p, float *moments, const AdaptiveView &a, stream_t s)
+{
+	EMU_DEFER(s, launch_resolve_adaptive(p, moments, a, s));
+	for (uint32_t i = 0; i < p.fr.W * p.fr.local_rows; i++)
+		resolve_adaptive_item(p, moments, a, i);
+}
+void launch_present_adaptive(const Params &p, f4 *out, const AdaptiveView &a, int full, stream_t s)
+{
+	EMU_DEFER(s, launch_present_adaptive(p, out, a, full, s));
+	for (uint32_t i = 0; i < p.fr.W * p.fr.local_rows; i++)
+		present_adaptive_item(p, out, a, full, i);
+}
+void launch_noise_metric_adaptive(const NoiseView &v, const uint32_t *n_tile, bool final, stream_t s)
+{
+	EMU_DEFER(s, launch_noise_metric_adaptive(v, n_tile, final, s));
+	// (launch_noise_metric's loops with n per tile)
+	const uint32_t tx = noise_tiles_x(v.W), ty = v.local_rows / NZ_TILE_Y;
+	for (uint32_t k = 0; k < tx * ty; k++)
+	{
+		NoiseTile t = {0.0f, 0.0f, 0u, 0u};
+		for (uint32_t j = 0; j < NZ_TILE_X * NZ_TILE_Y; j++)
+		{
+			float e;
+			if (ad_noise_pixel_item(v, n_tile, (k % tx) * NZ_TILE_X + j % NZ_TILE_X, (k / tx) * NZ_TILE_Y + j / NZ_TILE_X, e))
+				t.sum_e += e, t.max_e = fmaxf(t.max_e, e), t.pixels++, t.converged += e <= v.threshold;
+		}
+		t.sum_e = fminf(t.sum_e, FLT_MAX);
+		v.tiles[k] = t;
+	}
+	if (final)
+		nz_fold(v.tiles, tx * ty, 0u, 1u, *v.total);
+}
+void launch_adaptive_connections(WaveCounters *c, uint32_t depth, stream_t s)
+{
+	EMU_DEFER(s, launch_adaptive_connections(c, depth, s));
+	adaptive_connections_item(c, depth);
+}
+void launch_adaptive_reset(const AdaptiveView &a, stream_t s)
+{
+	EMU_DEFER(s, launch_adaptive_reset(a, s));
+	for (uint32_t t = 0; t < a.count; t++)
+		adaptive_reset_item(a, t);
+}
+void launch_adaptive_step(const AdaptiveView &a, uint32_t add, bool decide, stream_t s)
+{
+	EMU_DEFER(s, launch_adaptive_step(a, add, decide, s));
+	for (uint32_t t = 0; t < a.count; t++)
+		adaptive_step_item(a, add, decide, t);
 }
 void launch_present(const Params &p, f4 *out, float scale, int full, stream_t s)
 {

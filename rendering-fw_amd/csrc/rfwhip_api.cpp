@@ -373,6 +373,19 @@ struct rfwhip_context
 	float noise_floor = 0.01f, noise_threshold = 0.05f;
 	bool noise_live = false;
 	DevBuf d_noise, d_noise_map, d_noise_tiles, d_noise_total, d_noise_in;
+	// adaptive sampling (adaptive.h): per noise tile a sample count and an active flag, per slot tile a mask byte; the buffers live and
+	// die with d_noise.  adaptive_live: the state covers the accumulation (the setting was on, beside noise_estimate, at the last RESET /
+	// rfwhip_init).  The setting takes effect, on AND off, with the next RESET or rfwhip_init: a tile's accumulator holds n_tile samples
+	// and only the adaptive present scales it right
+	int adaptive_sampling = 0, adaptive_min_samples = 16, adaptive_every = 4;
+	bool adaptive_live = false;
+	uint32_t adaptive_calls = 0; // render calls since the RESET
+	DevBuf d_ad_n, d_ad_active, d_ad_mask;
+	// the mask changed on the main stream (RESET, a decision call): ev_adaptive is recorded behind it, and a sub-batch stream that has
+	// not waited for that record yet (adaptive_seen[i] != adaptive_serial) does so before its next primary wave
+	dm::event_t ev_adaptive;
+	bool adaptive_mask_moved = false;
+	uint64_t adaptive_serial = 0, adaptive_seen[MAX_SUB] = {};
 	DevBuf d_lt_nodes, d_lt_paths; // allocated only while light_sampling is tree
 	rt::LightTreeView lt_view{};   // nodes == nullptr: linear (or no light with a position)
 	bool lt_stale = false;		   // the setting changed since: the next render (or update) builds the tree
@@ -578,10 +591,11 @@ static void free_all(rfwhip_context *c)
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
 					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
-					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in};
+					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in,
+					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask};
 	for (DevBuf *b : bufs)
 		b->free_();
-	c->noise_live = false;
+	c->noise_live = false, c->adaptive_live = false;
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->dn_inst_ver_stale = true;
@@ -596,6 +610,7 @@ static void free_all(rfwhip_context *c)
 		for (int r = 0; r < rfwhip_context::MAX_RING; r++)
 			dm::event_destroy(c->ev_resolve[r]);
 		dm::event_destroy(c->ev_present_in), dm::event_destroy(c->ev_present_out), dm::event_destroy(c->ev_dn);
+		dm::event_destroy(c->ev_adaptive);
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			dm::event_destroy(c->ev_sub_done[i]), dm::event_destroy(c->ev_conn_last[i]);
@@ -643,16 +658,61 @@ extern "C" void rfwhip_destroy(rfwhip_context *c)
 
 static int dn_ensure(rfwhip_context *c);
 // the moments of the noise estimate start over with the accumulator (RESET, rfwhip_init); off: no buffer
+// the metric's view of `moments` (local layout of `rows` x W) with n samples per pixel; the outputs are the context's buffers
+static rtk::NoiseView noise_view(rfwhip_context *c, const float *moments, uint32_t W, uint32_t H, uint32_t rows, uint32_t rank, uint32_t world, uint32_t n)
+{
+	rtk::NoiseView v;
+	v.W = W, v.H = H, v.local_rows = rows, v.rank = rank, v.world = world, v.n = n;
+	v.moments = moments, v.e_map = c->d_noise_map.as<float>(), v.tiles = c->d_noise_tiles.as<rtk::NoiseTile>();
+	v.total = c->d_noise_total.as<rtk::NoiseTotal>();
+	v.floor_ = c->noise_floor, v.threshold = c->noise_threshold;
+	return v;
+}
+static rtk::AdaptiveView adaptive_view(rfwhip_context *c, uint32_t local_rows, uint32_t width)
+{
+	rtk::AdaptiveView a;
+	a.ntx = rtk::noise_tiles_x(width), a.count = a.ntx * (local_rows / rtk::NZ_TILE_Y);
+	a.tiles_x = (width + rt::TILE - 1) / rt::TILE, a.min_samples = (uint32_t)c->adaptive_min_samples;
+	a.n_tile = c->d_ad_n.as<uint32_t>(), a.active = c->d_ad_active.as<unsigned char>(), a.mask = c->d_ad_mask.as<unsigned char>();
+	a.tiles = c->d_noise_tiles.as<rtk::NoiseTile>();
+	return a;
+}
+static rtk::AdaptiveView adaptive_view(rfwhip_context *c) { return adaptive_view(c, c->fr.local_rows, c->W); }
 static int noise_clear(rfwhip_context *c, uint32_t local_rows, uint32_t width, void *stream)
 {
+	const bool was_adaptive = c->adaptive_live;
 	c->noise_live = c->noise_estimate != 0;
+	c->adaptive_live = c->noise_live && c->adaptive_sampling != 0;
+	c->adaptive_calls = 0;
+	if (was_adaptive && !c->adaptive_live)
+	{
+		RF_TRY(sync_all(c)); // (a primary wave or a present in flight may still read them)
+		c->d_ad_n.free_(), c->d_ad_active.free_(), c->d_ad_mask.free_();
+	}
 	if (!c->noise_live)
 		return RFWHIP_OK;
 	const size_t bytes = (size_t)local_rows * width * 2u * sizeof(float);
-	if (bytes > c->d_noise.cap)
+	const uint32_t tiles = rtk::noise_tiles_x(width) * (local_rows / rtk::NZ_TILE_Y);
+	const size_t mask_bytes = ((size_t)((width + rt::TILE - 1) / rt::TILE) * (local_rows / rt::TILE) + 7u) & ~(size_t)3u; // (whole words: a scalar load per wave)
+	if (bytes > c->d_noise.cap || (c->adaptive_live && ((size_t)tiles * 4u > c->d_ad_n.cap || mask_bytes > c->d_ad_mask.cap)))
 		RF_TRY(sync_all(c));
 	RF_TRY(c->d_noise.ensure(bytes));
-	return dm::zero(c->d_noise.p, bytes, stream);
+	RF_TRY(dm::zero(c->d_noise.p, bytes, stream));
+	if (c->adaptive_live)
+	{
+		// (the decision calls run the metric: its buffers are the queries')
+		RF_TRY(c->d_noise_map.ensure((size_t)local_rows * width * sizeof(float)));
+		RF_TRY(c->d_noise_tiles.ensure((size_t)tiles * sizeof(rtk::NoiseTile)));
+		RF_TRY(c->d_noise_total.ensure(sizeof(rtk::NoiseTotal)));
+		RF_TRY(c->d_ad_n.ensure((size_t)tiles * 4u));
+		RF_TRY(c->d_ad_active.ensure(tiles));
+		RF_TRY(c->d_ad_mask.ensure(mask_bytes));
+		RF_TRY(dm::zero(c->d_ad_mask.p, mask_bytes, stream));
+		rtk::launch_adaptive_reset(adaptive_view(c, local_rows, width), stream);
+		RF_TRY(dm::last_launch_error());
+		c->adaptive_mask_moved = true;
+	}
+	return RFWHIP_OK;
 }
 
 #define CTX_ENTER(c)                                                                      \
@@ -2067,6 +2127,7 @@ static int ensure_sub_batches(rfwhip_context *c, int subs)
 		RF_TRY(dm::event_create(&c->ev_present_in));
 		RF_TRY(dm::event_create(&c->ev_present_out));
 		RF_TRY(dm::event_create(&c->ev_dn));
+		RF_TRY(dm::event_create(&c->ev_adaptive));
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			RF_TRY(dm::event_create(&c->ev_sub_done[i]));
@@ -2143,6 +2204,8 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		RF_TRY(update_light_tree(c));
 	if (c->sampler == 1 && !c->have_blue_noise)
 		return set_error(RFWHIP_ERR_STATE, "sampler=bluenoise needs rfwhip_set_blue_noise() first");
+	if (c->integrator == 0 && (c->adaptive_sampling || c->adaptive_live))
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_render: adaptive_sampling needs integrator=pt");
 	if (c->max_depth + 2 > rt::MAX_DEPTH_SLOTS)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "max_depth %d too large", c->max_depth);
 	const size_t paths = (size_t)c->fr.slots * (size_t)c->spp;
@@ -2243,6 +2306,12 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		c->sample_origin = c->dn_temporal ? (uint32_t)(c->samples_total % 256u) : 0u;
 		c->dn_reset_since = true;
 	}
+	if (c->adaptive_live && c->adaptive_mask_moved)
+	{
+		RF_TRY(dm::event_record(c->ev_adaptive, s0));
+		c->adaptive_serial++, c->adaptive_mask_moved = false;
+	}
+	const rtk::AdaptiveView ad = c->adaptive_live ? adaptive_view(c) : rtk::AdaptiveView{};
 	const uint32_t packets = (c->W / 4u) * (c->H / 2u);
 	if (c->integrator == 0 && c->jitter == 0)
 	{
@@ -2307,6 +2376,11 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 			RF_TRY(dm::stream_wait_event(s, c->ev_resolve[prev]));
 		if (c->conn_used[i]) // the previous call's connection waves still use this sub-batch's counters and shadow buffers
 			RF_TRY(dm::stream_wait_event(s, c->ev_conn_last[i]));
+		if (c->adaptive_live && c->adaptive_seen[i] != c->adaptive_serial) // the mask this call reads: the state after the previous call
+		{
+			RF_TRY(dm::stream_wait_event(s, c->ev_adaptive));
+			c->adaptive_seen[i] = c->adaptive_serial;
+		}
 		rtk::Params p = base;
 		const size_t off_rad = (size_t)c->fr.slots * s_begin; // this sub-batch's slice of the radiance buffers of the call
 		const size_t off = alternate ? (paths + pad) * par : off_rad + (size_t)k * pad; // and of every per-ray buffer (padded)
@@ -2373,6 +2447,8 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 				}
 				if (pa_pending)
 					rtk::launch_trace_fused(p, pa, count, n_ext, s); // extension rays of depth d + shadow rays of depth d - 1
+				else if (d == 0 && c->adaptive_live)
+					rtk::launch_extend_masked(p, ad.mask, count, n, s);
 				else
 					rtk::launch_extend(p, d == 0 ? rtk::GEN_PT : rtk::GEN_BUFFER, count, d == 0 ? n : n_ext, s);
 				pa_pending = false;
@@ -2385,6 +2461,11 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 				else
 					rtk::launch_shade_pt(p, c->sky_view, n_shade, s);
 				ts.stop();
+				// The one place where a path's light depends on other pixels: the connections of depth d are traced only when some path
+				// of the sub-batch went on to depth d + 1 (connection_count: the reference's host loop).  A frame always has such a
+				// path; the few active tiles of an adaptive call may not, so the call says so itself (adaptive.h)
+				if (c->adaptive_live && connect && d < c->max_depth)
+					rtk::launch_adaptive_connections(p.wv.counters, (uint32_t)d, s);
 				// The connection wave of depth d runs beside extend / shade of depth d + 1 on its own stream (it adds into
 				// rad_nee, they into rad).  The connections of the last shade call are never traced
 				// (CUDART/src/Context.cpp:109-120): the shade kernel does not emit them, and no wave is launched for them.
@@ -2457,13 +2538,31 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	}
 	{
 		StageTimer tf(c, KF_FINALIZE, -1);
-		if (c->noise_live)
+		if (c->adaptive_live)
+			rtk::launch_resolve_adaptive(base, c->d_noise.as<float>(), ad, s0);
+		else if (c->noise_live)
 			rtk::launch_resolve_noise(base, c->d_noise.as<float>(), c->samples_done, s0);
 		else
 			rtk::launch_resolve(base, s0);
 		tf.stop();
 	}
 	RF_TRY(dm::event_record(c->ev_resolve[par], s0));
+	if (c->adaptive_live)
+	{
+		// the tiles' counts go on; after every adaptive_every-th call the metric at those counts decides which tiles retire.  Only
+		// then does the mask move: the next primary waves wait for the record behind it, and on other calls for nothing
+		const bool decide = ++c->adaptive_calls % (uint32_t)c->adaptive_every == 0u;
+		rtk::launch_adaptive_step(ad, (uint32_t)c->spp, false, s0);
+		if (decide)
+		{
+			StageTimer tn(c, KF_NOISE, -1);
+			rtk::launch_noise_metric_adaptive(noise_view(c, c->d_noise.as<float>(), c->W, c->H, c->fr.local_rows, (uint32_t)c->rank, (uint32_t)c->world, 2u), ad.n_tile, false, s0);
+			tn.stop();
+			rtk::launch_adaptive_step(ad, 0u, true, s0);
+			RF_TRY(dm::event_record(c->ev_adaptive, s0));
+			c->adaptive_serial++;
+		}
+	}
 	c->resolve_recorded[par] = true;
 	c->call_slot = (par + 1u) % (uint32_t)ring;
 	RF_TRY(dm::last_launch_error());
@@ -2499,6 +2598,13 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 	uint32_t stack_overflow = wc.stack_overflow;
 	const rt::WaveCounters wc0 = wc; // (as read: the sums below fold the other sub-batches' counts into wc)
 	std::vector<rt::WaveCounters> more;
+	// (adaptive sampling: "one path went on" written by k_adaptive_connections, adaptive.h, is no ray — its queue is empty)
+	uint32_t ext_marks[rt::MAX_DEPTH_SLOTS] = {};
+	auto count_marks = [&](const rt::WaveCounters &w) {
+		for (int d = 1; d < rt::MAX_DEPTH_SLOTS; d++)
+			ext_marks[d] += c->adaptive_live && w.ext[d] == 1u && w.ext_n[d] == 0u;
+	};
+	count_marks(wc);
 	for (int d = 0; d + 1 < rt::MAX_DEPTH_SLOTS; d++)
 		if (!wc.ext[d + 1])
 			wc.shadow[d] = 0;
@@ -2507,6 +2613,7 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 		rt::WaveCounters w2;
 		RF_TRY(dm::d2h(&w2, c->d_counters_sub[i].p, sizeof(w2), c->stream));
 		more.push_back(w2);
+		count_marks(w2);
 		stack_overflow += w2.stack_overflow;
 		for (int d = 0; d < rt::MAX_DEPTH_SLOTS; d++)
 		{
@@ -2515,6 +2622,8 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 				wc.shadow[d] += w2.shadow[d];
 		}
 	}
+	for (int d = 1; d < rt::MAX_DEPTH_SLOTS; d++)
+		wc.ext[d] -= ext_marks[d];
 	// k_trace_fused: the shadow rays' share of each depth's launch, from the workgroups' tick sums since the last wait (over the
 	// counter sets of the last frame's sub-batches: the frames of a pipelined series render the same scene)
 	double shadow_share[rt::MAX_DEPTH_SLOTS];
@@ -2633,7 +2742,10 @@ static int present(rfwhip_context *c, f4 *dst_device, int full)
 	rtk::Params p;
 	fill_params(c, nullptr, p);
 	const float scale = c->samples_done ? 1.0f / (float)c->samples_done : 0.0f;
-	rtk::launch_present(p, dst_device, scale, full, c->stream);
+	if (c->adaptive_live) // (a tile's pixels hold n_tile samples)
+		rtk::launch_present_adaptive(p, dst_device, adaptive_view(c), full, c->stream);
+	else
+		rtk::launch_present(p, dst_device, scale, full, c->stream);
 	RF_TRY(dm::last_launch_error());
 	return 0;
 }
@@ -3040,21 +3152,23 @@ extern "C" int rfwhip_display_image(rfwhip_context *c, const float *rgba_in, flo
 // ---- noise estimate (settings "noise_*"; work items: noise.h) -----------------------------------------------------------------------
 // the metric on `moments` (local layout of `rows` x W) for n samples per pixel: two launches on the context's stream and the 32-byte
 // record back on the host; the error map and the tile records stay in d_noise_map / d_noise_tiles
+// n_tile != null (adaptive sampling): n per tile
 static int noise_metric(rfwhip_context *c, const float *moments, uint32_t W, uint32_t H, uint32_t rows, uint32_t rank, uint32_t world,
-						uint32_t n, rtk::NoiseTotal *total)
+						uint32_t n, rtk::NoiseTotal *total, const uint32_t *n_tile = nullptr)
 {
 	const uint32_t tiles = rtk::noise_tiles_x(W) * (rows / rtk::NZ_TILE_Y);
+	if (c->adaptive_live && (size_t)rows * W * sizeof(float) > c->d_noise_map.cap)
+		RF_TRY(sync_all(c)); // (rfwhip_noise_image on a larger image: a decision call in flight writes these buffers)
 	RF_TRY(c->d_noise_map.ensure((size_t)rows * W * sizeof(float)));
 	RF_TRY(c->d_noise_tiles.ensure((size_t)tiles * sizeof(rtk::NoiseTile)));
 	RF_TRY(c->d_noise_total.ensure(sizeof(rtk::NoiseTotal)));
-	rtk::NoiseView v;
-	v.W = W, v.H = H, v.local_rows = rows, v.rank = rank, v.world = world, v.n = n;
-	v.moments = moments, v.e_map = c->d_noise_map.as<float>(), v.tiles = c->d_noise_tiles.as<rtk::NoiseTile>();
-	v.total = c->d_noise_total.as<rtk::NoiseTotal>();
-	v.floor_ = c->noise_floor, v.threshold = c->noise_threshold;
+	const rtk::NoiseView v = noise_view(c, moments, W, H, rows, rank, world, n);
 	{
 		StageTimer t(c, KF_NOISE, -1);
-		rtk::launch_noise_metric(v, c->stream);
+		if (n_tile)
+			rtk::launch_noise_metric_adaptive(v, n_tile, true, c->stream);
+		else
+			rtk::launch_noise_metric(v, c->stream);
 		t.stop(2);
 	}
 	RF_TRY(dm::last_launch_error());
@@ -3077,7 +3191,8 @@ static int noise_own(rfwhip_context *c, const char *who, rtk::NoiseTotal *total)
 	if (c->samples_done < 2u)
 		return set_error(RFWHIP_ERR_STATE, "%s: %u samples per pixel, the estimate needs 2", who, c->samples_done);
 	// (the last render's resolve is on the context's stream: the metric runs behind it)
-	return noise_metric(c, c->d_noise.as<float>(), c->W, c->H, c->fr.local_rows, (uint32_t)c->rank, (uint32_t)c->world, c->samples_done, total);
+	return noise_metric(c, c->d_noise.as<float>(), c->W, c->H, c->fr.local_rows, (uint32_t)c->rank, (uint32_t)c->world, c->samples_done, total,
+						c->adaptive_live ? c->d_ad_n.as<uint32_t>() : nullptr);
 }
 
 extern "C" int rfwhip_get_noise(rfwhip_context *c, rfwhip_noise_stats *stats)
@@ -3191,6 +3306,107 @@ extern "C" int rfwhip_noise_image(rfwhip_context *c, uint32_t W, uint32_t H, uin
 	return dm::sync(c->stream);
 }
 
+// ---- adaptive sampling (settings "adaptive_*"; work items: adaptive.h) --------------------------------------------------------------
+static int adaptive_own(rfwhip_context *c, const char *who)
+{
+	if (!c->adaptive_live)
+		return set_error(RFWHIP_ERR_STATE, "%s: %s", who, c->adaptive_sampling ? "adaptive_sampling came on after the accumulation began; render with RFWHIP_RESET first" : "adaptive_sampling is off");
+	return RFWHIP_OK;
+}
+// the real pixels of noise tile (tx, ty) of this rank
+static uint32_t adaptive_tile_pixels(const rfwhip_context *c, uint32_t tx, uint32_t ty)
+{
+	const uint32_t w = std::min(rtk::NZ_TILE_X, c->W - tx * rtk::NZ_TILE_X);
+	uint32_t rows = 0;
+	for (uint32_t r = 0; r < rtk::NZ_TILE_Y; r++)
+	{
+		const uint32_t yl = ty * rtk::NZ_TILE_Y + r;
+		rows += rt::strip_of_local(yl / rt::STRIP_ROWS, (uint32_t)c->rank, (uint32_t)c->world) * rt::STRIP_ROWS + yl % rt::STRIP_ROWS < c->H;
+	}
+	return w * rows;
+}
+// the tiles' state as the last render call enqueued leaves it
+static int adaptive_read(rfwhip_context *c, std::vector<uint32_t> &n, std::vector<unsigned char> &active)
+{
+	const uint32_t tiles = rtk::noise_tiles_x(c->W) * (c->fr.local_rows / rtk::NZ_TILE_Y);
+	n.resize(tiles), active.resize(tiles);
+	RF_TRY(dm::d2h(n.data(), c->d_ad_n.p, (size_t)tiles * 4u, c->stream));
+	RF_TRY(dm::d2h(active.data(), c->d_ad_active.p, tiles, c->stream));
+	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_get_adaptive(rfwhip_context *c, rfwhip_adaptive_stats *stats)
+{
+	CTX_ENTER(c);
+	if (!stats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null stats");
+	RF_TRY(adaptive_own(c, "rfwhip_get_adaptive"));
+	std::vector<uint32_t> n;
+	std::vector<unsigned char> active;
+	RF_TRY(adaptive_read(c, n, active));
+	rfwhip_adaptive_stats st = {0, 0, 0, 0, 0, 0};
+	const uint32_t ntx = rtk::noise_tiles_x(c->W);
+	for (uint32_t t = 0; t < (uint32_t)n.size(); t++)
+	{
+		const uint64_t px = adaptive_tile_pixels(c, t % ntx, t / ntx);
+		if (!px)
+			continue; // (the padded rows below the image)
+		st.tiles++, st.pixels += px, st.samples_taken += px * n[t];
+		if (active[t])
+			st.active_tiles++, st.active_pixels += px;
+	}
+	st.samples_uniform = st.pixels * c->samples_done;
+	*stats = st;
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_adaptive_tiles(rfwhip_context *c, uint32_t *n, uint8_t *active, size_t cap, uint32_t *tiles_x, uint32_t *tiles_y)
+{
+	CTX_ENTER(c);
+	if (!n || !active || !tiles_x || !tiles_y)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null destination");
+	RF_TRY(adaptive_own(c, "rfwhip_read_adaptive_tiles"));
+	const uint32_t tx = rtk::noise_tiles_x(c->W), ty = c->fr.local_rows / rtk::NZ_TILE_Y;
+	if (cap < (size_t)tx * ty)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_adaptive_tiles: room for %zu tiles, the context has %u x %u", cap, tx, ty);
+	std::vector<uint32_t> hn;
+	std::vector<unsigned char> ha;
+	RF_TRY(adaptive_read(c, hn, ha));
+	memcpy(n, hn.data(), hn.size() * 4u), memcpy(active, ha.data(), ha.size());
+	*tiles_x = tx, *tiles_y = ty;
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_adaptive_set_tiles(rfwhip_context *c, const uint8_t *active, size_t count)
+{
+	CTX_ENTER(c);
+	if (!active)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null flags");
+	RF_TRY(adaptive_own(c, "rfwhip_adaptive_set_tiles"));
+	const rtk::AdaptiveView a = adaptive_view(c);
+	if (count != a.count)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_adaptive_set_tiles: %zu flags, the context has %u tiles", count, a.count);
+	RF_TRY(sync_all(c));
+	std::vector<uint32_t> n;
+	std::vector<unsigned char> cur;
+	RF_TRY(adaptive_read(c, n, cur));
+	// (flags only clear: a retired tile stays retired)
+	std::vector<unsigned char> mask((size_t)a.tiles_x * (c->fr.local_rows / rt::TILE), 1);
+	for (uint32_t t = 0; t < a.count; t++)
+	{
+		cur[t] = cur[t] && active[t];
+		const uint32_t ty = t / a.ntx, sx = (t % a.ntx) * (rtk::NZ_TILE_X / rt::TILE);
+		for (uint32_t k = 0; k < rtk::NZ_TILE_X / rt::TILE; k++)
+			if (sx + k < a.tiles_x)
+				mask[(size_t)ty * a.tiles_x + sx + k] = cur[t];
+	}
+	RF_TRY(dm::h2d(a.active, cur.data(), cur.size(), c->stream));
+	RF_TRY(dm::h2d(a.mask, mask.data(), mask.size(), c->stream));
+	RF_TRY(dm::sync(c->stream));
+	c->adaptive_mask_moved = true; // (the next call's sub-batch streams wait for the main stream once more: plain order, nothing is in flight)
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_read_local_framebuffer_device(rfwhip_context *c, void *rgba_device)
 {
 	CTX_ENTER(c);
@@ -3219,7 +3435,10 @@ extern "C" int rfwhip_read_local_framebuffer_stream(rfwhip_context *c, void *rgb
 	rtk::Params p;
 	fill_params(c, nullptr, p);
 	const float scale = c->samples_done ? 1.0f / (float)c->samples_done : 0.0f;
-	rtk::launch_present(p, (f4 *)rgba_device, scale, 0, hip_stream);
+	if (c->adaptive_live)
+		rtk::launch_present_adaptive(p, (f4 *)rgba_device, adaptive_view(c), 0, hip_stream);
+	else
+		rtk::launch_present(p, (f4 *)rgba_device, scale, 0, hip_stream);
 	RF_TRY(dm::last_launch_error());
 	RF_TRY(dm::event_record(c->ev_present_out, hip_stream));
 	c->present_pending = true;
@@ -3521,6 +3740,9 @@ static const Setting k_settings[] = {
 	{"noise_estimate", SET {
 		 bool on;
 		 RF_TRY(parse_01(key, value, &on));
+		 if (!on && (c->adaptive_sampling || c->adaptive_live))
+			 return set_error(RFWHIP_ERR_STATE, c->adaptive_sampling ? "noise_estimate: adaptive_sampling is on and needs it; turn that off first"
+																	 : "noise_estimate: the accumulation is an adaptive one; render with RFWHIP_RESET first");
 		 if (!on && c->noise_estimate)
 		 {
 			 RF_TRY(sync_all(c)); // (a resolve in flight may still write the moments)
@@ -3530,6 +3752,17 @@ static const Setting k_settings[] = {
 		 c->noise_estimate = on; // (on: the moments begin with the next RESET or rfwhip_init)
 		 return RFWHIP_OK; },
 	 GET_INT(noise_estimate), false},
+	// adaptive sampling (adaptive.h); on and off with the next RESET or rfwhip_init
+	{"adaptive_sampling", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 if (on && !c->noise_estimate)
+			 return set_error(RFWHIP_ERR_STATE, "adaptive_sampling needs noise_estimate=1");
+		 c->adaptive_sampling = on;
+		 return RFWHIP_OK; },
+	 GET_INT(adaptive_sampling), false},
+	{"adaptive_min_samples", SET { return set_int_in(c->adaptive_min_samples, key, value, 2, 1 << 30); }, GET_INT(adaptive_min_samples), false},
+	{"adaptive_every", SET { return set_int_in(c->adaptive_every, key, value, 1, 64); }, GET_INT(adaptive_every), false},
 	{"noise_floor", SET { return set_float(c->noise_floor, key, value, [](float f) { return f > 0.0f && f < 1e30f; }, "be a finite number > 0", false); },
 	 GET { return put(out, cap, "%g", c->noise_floor); }, false},
 	{"noise_threshold", SET { return set_float(c->noise_threshold, key, value, [](float f) { return f > 0.0f && f < 1e30f; }, "be a finite number > 0", false); },
@@ -4106,6 +4339,7 @@ static_assert(sizeof(rfwhip_area_light) == sizeof(rt::AreaLight) && sizeof(rfwhi
 static_assert(RFWHIP_KAT_LT_SAMPLE == rtk::KAT_LT_SAMPLE && RFWHIP_KAT_LT_PICK_PROB == rtk::KAT_LT_PICK_PROB, "kernels.h restates the light-tree functions");
 static_assert(RFWHIP_KAT_IN == 24 && RFWHIP_KAT_OUT == 8, "kat_item's record layout (kernels.hip)");
 static_assert(RFWHIP_STRIP_ROWS == (int)rt::STRIP_ROWS, "rfwhip.h: rfwhip_row_owner() restates rt::strip_owner()");
+static_assert(sizeof(rfwhip_adaptive_stats) == 48, "rfwhip.h: six uint64");
 static_assert(sizeof(rfwhip_noise_tile) == sizeof(rtk::NoiseTile) && sizeof(rtk::NoiseTotal) == 32 && sizeof(rfwhip_noise_stats) == 40,
 			  "rfwhip.h: the noise records are the kernels' (kernels.h)");
 extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float *in, float *out)

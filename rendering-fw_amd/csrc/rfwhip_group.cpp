@@ -729,6 +729,25 @@ extern "C" int rfwhip_group_get_noise(rfwhip_group *g, rfwhip_noise_stats *stats
 	return RFWHIP_OK;
 }
 
+extern "C" int rfwhip_group_get_adaptive(rfwhip_group *g, rfwhip_adaptive_stats *stats)
+{
+	if (!g || !stats)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null argument");
+	// tiles belong to one rank each: the ranks' records add up, in rank order (g->ep is in rank order)
+	rfwhip_adaptive_stats sum = {0, 0, 0, 0, 0, 0};
+	for (auto &e : g->ep)
+	{
+		rfwhip_adaptive_stats st;
+		const int rc = rfwhip_get_adaptive(e.ctx, &st);
+		if (rc)
+			return rc;
+		sum.tiles += st.tiles, sum.active_tiles += st.active_tiles, sum.pixels += st.pixels, sum.active_pixels += st.active_pixels;
+		sum.samples_taken += st.samples_taken, sum.samples_uniform += st.samples_uniform;
+	}
+	*stats = sum;
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_group_framebuffer_device(rfwhip_group *g, void **rgba_device, int *device_ordinal)
 {
 	if (!g || !rgba_device)
