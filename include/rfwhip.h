@@ -567,7 +567,9 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   rfwhip_get_setting also answers read-only keys: "textured" (the textured shade kernel variant is in use), "packet" (the
  *   pt primary wave can run in packet form), "world_tree" (triangles in the world tree of the last update; 0: none),
  *   "shadow_bins_per_run", "shadow_packets_on", "sky" (the last update left p > 0: the shade waves run the sky variant),
- *   "light_tree" (nodes of the light tree the next render would use; 0: none, or light_sampling is not "tree").
+ *   "light_tree" (nodes of the light tree the next render would use; 0: none, or light_sampling is not "tree"),
+ *   "lights_bound" (area lights the last refresh of lights_follow_geometry found bound; 0 while that setting is off),
+ *   "light_tree_refits" (refits of the light tree on the device since it was last built).
  *   Not listed by rfwhip_get_settings, but settable:
  *   light_sampling = "reference" (default: the reference's estimator, the default kernels) | "linear" (its potentials, consistent
  *                  weights) | "tree" (the light tree, O(log lights) per next-event vertex, the same weights): rfwhip_get_light_tree
@@ -575,6 +577,8 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   display_tonemap / display_fxaa / display_srgb = the display stage, see rfwhip_read_display above.
  *   noise_estimate / noise_floor / noise_threshold = the noise estimate, see rfwhip_get_noise above.
  *   adaptive_sampling / adaptive_min_samples / adaptive_every = adaptive sampling, see rfwhip_get_adaptive above.
+ *   lights_follow_geometry = "0" (default) | "1": rfwhip_update derives the area lights of emissive geometry on the device and
+ *                  refits the light tree, see rfwhip_read_area_lights below.
  * Returns the number of keys; fills up to cap pointers with static strings. */
 RFWHIP_API int rfwhip_set_setting(rfwhip_context *ctx, const char *key, const char *value);
 RFWHIP_API int rfwhip_get_setting(rfwhip_context *ctx, const char *key, char *value, size_t cap);
@@ -734,6 +738,59 @@ RFWHIP_API int rfwhip_get_bvh4(rfwhip_context *ctx, size_t mesh_index, void *nod
  * left first, and rescales r1 into the child's interval; q is the product of the probabilities. */
 RFWHIP_API int rfwhip_get_light_tree(rfwhip_context *ctx, rfwhip_light_tree_node *nodes, size_t node_cap,
 									 rfwhip_light_tree_path *paths, size_t light_cap);
+
+/* ---- moving emitters: setting lights_follow_geometry = "0" (default) | "1" --------------------------------------------------
+ * Poses, morphs, same-count rfwhip_set_mesh and rfwhip_set_instance move geometry on the device; an area light is a record the
+ * host derived from host triangles (system::update_area_lights, system.cpp:967-1032) and stays where it was.  With "1",
+ * rfwhip_update() brings the lights of the last rfwhip_set_lights up to date on the device, before anything reads them.
+ *
+ * BOUND.  An area light is bound when instIdx names an instance in use, triIdx is below the triangle count of that instance's
+ * mesh, and that triangle is a light triangle (its lightTriIdx >= 0: the back-pointer of system.cpp:1021).  Every other area
+ * light — the (-1, -1) of a free-standing light, an index out of range, a triangle that does not emit — is unbound and keeps
+ * the host's bytes, always.  Binding is evaluated anew at every refresh.  Point, spot and directional lights are never touched.
+ *
+ * REFRESH (system.cpp:1003-1024).  Runs in rfwhip_update when the setting is on, an area light exists, and since the last
+ * refresh an instance was set, a mesh was set, posed or morphed (or placed again), the lights were set, or the setting came on.
+ * Per bound light, with v_j the current object-space vertices of triangle triIdx (after pose and morph), M the instance's
+ * transform and Nm the normal matrix given to rfwhip_set_instance, all in float32:
+ *   vertex_j = M v_j                      per coordinate fma(m2, z, fma(m1, y, m0 x)) + m3
+ *   position = ((vertex0 + vertex1) + vertex2) * (1/3)
+ *   normal   = Nm N                       N: the face normal of the triangle's shading record as the device's update_triangles
+ *                                         (rfwhip_pose_mesh / rfwhip_morph_mesh) or the last rfwhip_set_mesh left it; not renormalised
+ *   area     = |(v1 - v0) x (v2 - v0)| / 2   in OBJECT space, as the reference's updateArea has it (its quirk under a scaling
+ *                                         transform, kept for parity); the same float is written to the triangle's shading
+ *                                         record, which the emitter-hit density reads: both sides of MIS see one area
+ *   radiance, energy, triIdx, instIdx and the two padding words stay bit for bit.
+ *
+ * REFIT.  With light_sampling=tree and a tree that stands (not stale), the refresh is followed by a refit over the EXISTING
+ * topology, bottom-up: lo / hi / axis / cos_o of every leaf that holds a bound area light and of every ancestor of such a leaf.
+ * A leaf: the min / max of its light's three vertices, the normalised normal, cos_o = 1 (a zero or non-finite normal: cos_o = -1).
+ * An inner node: the min / max of its two children's boxes (exact), and the union of its two children's cones (Conty Estevez
+ * and Kulla 2018, Alg. 1) in float32, widened by a derived margin (light_follow.h) so that it is conservative: every light
+ * below lies in the cone.  The host build unites a node's lights one after another in double, the refit unites the two children:
+ * two different bounds, both valid.  energy, child, light, count and the lights' paths stay bit for bit; leaves of point and
+ * spot lights and of unbound area lights, and inner nodes without a bound leaf below, are not rewritten.  No atomics, a fixed
+ * order: the same lights give the same bytes.  The topology is rebuilt where it always was — rfwhip_set_lights, or setting
+ * light_sampling — and that is the way to force a rebuild after emitters have moved far; a stale tree is built from the
+ * refreshed lights.  With the setting on, rfwhip_set_lights does not make the topology of the geometry fields it is handed (they
+ * are about to be overwritten and may be zeros): it leaves the tree stale, and the rfwhip_update that must follow builds it from
+ * what its refresh derives.  (A rfwhip_get_light_tree in between sees a tree of the host's fields; the update builds it anew.)
+ *
+ * ORDER.  Refresh and refit overwrite tables that render calls in flight read.  They are ordered as the device refit of
+ * rfwhip_pose_mesh is: rfwhip_update first waits for every stream of the ring, for a present on a caller's stream and for a
+ * denoise on a gather stream, enqueues the work on the context's stream, and synchronises that stream before it returns.  No
+ * scheduling setting (ring, streams, overlap, fuse, shadow_packets, shadow_side) changes a bit of any image.
+ * Every rank of a group refreshes and refits its own copy inside rfwhip_group_update; nothing crosses the gather.
+ *
+ * rfwhip_read_area_lights: the area lights as the next render would read them, setting on or off; waits for the context's
+ * stream; copies at most cap records; returns the count of the last rfwhip_set_lights, or a negative error code. */
+RFWHIP_API int rfwhip_read_area_lights(rfwhip_context *ctx, rfwhip_area_light *out, size_t cap);
+/* Known-answer hook (like rfwhip_noise_image): the product's refit kernels on the caller's tree and lights, whatever the context
+ * renders.  nodes: node_count nodes as rfwhip_get_light_tree returned them for the same light counts, refitted in place;
+ * area: the n_area area lights (lights 0 .. n_area - 1 of the tree); bound: n_area bytes, 1 = treat as bound (NULL: all).
+ * Nodes that are not laid out as the build lays them out are RFWHIP_ERR_INVALID_ARGUMENT. */
+RFWHIP_API int rfwhip_light_tree_refit(rfwhip_context *ctx, rfwhip_light_tree_node *nodes, size_t node_count,
+									   const rfwhip_area_light *area, size_t n_area, const uint8_t *bound);
 
 #ifdef __cplusplus
 }

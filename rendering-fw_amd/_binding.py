@@ -85,6 +85,8 @@ class CoreBinding:
                                                             vp, vp, vp]),
                                   "get_bvh4": (i32, [vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(abi.Bvh4Info)]),
                                   "get_light_tree": (i32, [vp, vp, sz, vp, sz]),
+                                  "read_area_lights": (i32, [vp, vp, sz]),
+                                  "light_tree_refit": (i32, [vp, vp, sz, vp, sz, vp]),
                                   "read_denoise_guides": (i32, [vp, vp, vp]),
                                   "denoise_image": (i32, [vp, vp, vp]),
                                   "display_image": (i32, [vp, vp, fp, fp, i32, vp]),
@@ -590,6 +592,31 @@ class CoreBinding:
         if n < 0:
             self._check(-n)
         return nodes, paths
+
+    def read_area_lights(self):
+        """The area lights as the next render would read them (AREA_LIGHT_DTYPE): with lights_follow_geometry=1 the bound ones
+        are what the last update() derived on the device, every other one holds the bytes of set_lights."""
+        f = self._fn("read_area_lights")
+        n = f(self._ctx, None, 0)
+        if n < 0:
+            self._check(-n)
+        out = np.zeros(n, abi.AREA_LIGHT_DTYPE)
+        n = f(self._ctx, out.ctypes.data if len(out) else None, len(out))
+        if n < 0:
+            self._check(-n)
+        return out
+
+    def light_tree_refit(self, nodes, area, bound=None):
+        """Known-answer hook: the refit kernels of lights_follow_geometry on a tree get_light_tree returned (for the same
+        light counts) and the given area lights (lights 0 .. len(area) - 1 of the tree); bound: per area light 1 = refit its
+        leaf (None: all).  Returns the refitted nodes."""
+        nd = np.array(nodes, dtype=abi.LIGHT_TREE_NODE_DTYPE, copy=True)
+        a = np.ascontiguousarray(area, dtype=abi.AREA_LIGHT_DTYPE)
+        b = None if bound is None else np.ascontiguousarray(bound, dtype=np.uint8).reshape(-1)
+        assert b is None or len(b) == len(a)
+        self._check(self._fn("light_tree_refit")(self._ctx, nd.ctypes.data, len(nd), a.ctypes.data if len(a) else None, len(a),
+                                                 None if b is None else b.ctypes.data))
+        return nd
 
     def get_bvh4(self, mesh_index):
         """The traversed tree of a resident mesh as it sits on the device (entries absolute): {"nodes4c": NODE4C_DTYPE,

@@ -253,4 +253,41 @@ void launch_morph_vertices(rt::f4 *verts, rt::f4 *vnormals, const rt::f4 *base_v
 void launch_skin_shade(rt::TriShade *shade, const rt::f4 *verts, const rt::f4 *vnormals, const uint32_t *indices,
 					   uint32_t tri_count, stream_t s);
 
+// Moving emitters (setting "lights_follow_geometry"; work items: light_follow.h; formulas: include/rfwhip.h).
+// One record per instance slot: the transform and normal matrix of the last rfwhip_set_instance (rows 0..2, row-major, the normal
+// matrix's rows padded to four floats) and the mesh's current object-space vertices — the arrays the temporal stage's motion
+// table points at (DnMotionInst::cur / indices), with the same rule for "the vertices of triangle k".  tri_count == 0: not in use.
+struct alignas(16) LightInst
+{
+	float m[12], nrm[12];
+	const rt::f4 *verts;
+	const uint32_t *indices; // three per triangle, or null: triangle k has the vertices 3 k .. 3 k + 2
+	uint32_t tri_count, shade_base;
+	uint32_t pad[2];
+};
+struct LightFollowView
+{
+	rt::AreaLight *area; // the lights of the last rfwhip_set_lights: bound ones are rewritten in place
+	const LightInst *inst;
+	rt::TriShade *tri_shade; // scene-wide: a bound triangle's area (ex.x) is written beside its light's
+	unsigned char *bound;	 // per area light: 1 bound, 0 unbound
+	uint32_t *bound_count;	 // zeroed by the caller in front of the launch; the bound lights are added to it
+	uint32_t n_area, n_inst;
+};
+// k_light_refresh: one area light per lane
+void launch_light_refresh(const LightFollowView &v, stream_t s);
+// The light tree's levels (light_tree.h lays the nodes out breadth first): level l is nodes [first[l], first[l] + count[l])
+constexpr uint32_t LT_MAX_LEVELS = 32;
+struct LightTreeLevels
+{
+	uint32_t first[LT_MAX_LEVELS], count[LT_MAX_LEVELS];
+	uint32_t levels;
+};
+// Bottom-up refit of lo / hi / axis / cos_o over the existing topology: a leaf of a bound area light from its light, an inner node
+// with such a leaf below from its two children; every other node keeps its bytes.  touched: one byte per node (scratch).  Levels
+// wider than a workgroup get a launch each, deepest first; the levels above them run in ONE workgroup with a barrier between
+// levels (k_lt_refit_top)
+void launch_light_tree_refit(rt::LightTreeNode *nodes, const LightTreeLevels &lv, const rt::AreaLight *area, uint32_t n_area,
+							 const unsigned char *bound, unsigned char *touched, stream_t s);
+
 } // namespace rtk

@@ -967,6 +967,8 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 #include "denoise.h"
 // the display stage: tone map + FXAA + encoding of the presented image (the work item shared with the emulation)
 #include "display.h"
+// moving emitters: the area lights of emissive geometry and the light tree's refit (work items shared with the emulation)
+#include "light_follow.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }
 
 // Which launches of the pt primary wave take the packet form (the device's launchers and the emulation's driver): a single-sample
@@ -2686,6 +2688,57 @@ void launch_noise_metric_adaptive(const NoiseView &v, const uint32_t *n_tile, bo
 void launch_adaptive_step(const AdaptiveView &a, uint32_t add, bool decide, stream_t s)
 {
 	hipLaunchKernelGGL(k_adaptive_step, dim3((a.count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, a, add, decide ? 1 : 0);
+}
+
+// ---- moving emitters (light_follow.h).  k_light_refresh: one area light per lane; the bound lights of a wave are counted with one
+// ballot and one integer atomic per wave (an integer sum: the same lights give the same count).  The refit runs level by level from
+// the deepest up.  A level wider than a workgroup is a launch of its own (k_lt_refit_level: stream order is the barrier); the levels
+// above — each at most BLOCK nodes — run in ONE workgroup with a __syncthreads between them (k_lt_refit_top): a tree of n lights
+// has ceil(log2 n) + 1 levels of which all but log2(n / BLOCK) are that narrow, so 65 536 lights take 9 launches instead of 17 and
+// a tree of up to BLOCK lights takes one.  A node is written by the one lane that owns it and read, a level later, by its parent's. ----
+__global__ void __launch_bounds__(BLOCK) k_light_refresh(const LightFollowView v)
+{
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	const bool bound = i < v.n_area && lf_refresh_item(v, i);
+	const unsigned long long mask = __ballot(bound);
+	if ((threadIdx.x & 63u) == 0u && mask)
+		atomicAdd(v.bound_count, (uint32_t)__popcll(mask));
+}
+void launch_light_refresh(const LightFollowView &v, stream_t s)
+{
+	if (v.n_area)
+		hipLaunchKernelGGL(k_light_refresh, dim3((v.n_area + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, v);
+}
+__global__ void __launch_bounds__(BLOCK) k_lt_refit_level(LightTreeNode *nodes, uint32_t first, uint32_t count, const AreaLight *area,
+														  uint32_t n_area, const unsigned char *bound, unsigned char *touched)
+{
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < count)
+		lf_refit_item(nodes, area, n_area, bound, touched, first + i);
+}
+__global__ void __launch_bounds__(BLOCK) k_lt_refit_top(LightTreeNode *nodes, const LightTreeLevels lv, uint32_t top, const AreaLight *area,
+														uint32_t n_area, const unsigned char *bound, unsigned char *touched)
+{
+	// levels top - 1 .. 0, each at most BLOCK nodes wide (the launcher's choice of `top`)
+	for (uint32_t l = top; l-- > 0u;)
+	{
+		if (threadIdx.x < lv.count[l])
+			lf_refit_item(nodes, area, n_area, bound, touched, lv.first[l] + threadIdx.x);
+		__syncthreads(); // (workgroup-wide: the level's global writes are visible to the lanes of the next)
+	}
+}
+void launch_light_tree_refit(LightTreeNode *nodes, const LightTreeLevels &lv, const AreaLight *area, uint32_t n_area,
+							 const unsigned char *bound, unsigned char *touched, stream_t s)
+{
+	// top: the levels 0 .. top - 1 are all at most BLOCK wide (a last level narrower than the one above it still gets its own launch)
+	uint32_t top = 0;
+	while (top < lv.levels && lv.count[top] <= (uint32_t)BLOCK)
+		top++;
+	for (uint32_t l = lv.levels; l-- > top;)
+		hipLaunchKernelGGL(k_lt_refit_level, dim3((lv.count[l] + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, nodes, lv.first[l],
+						   lv.count[l], area, n_area, bound, touched);
+	if (top)
+		hipLaunchKernelGGL(k_lt_refit_top, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nodes, lv, top, area, n_area, bound, touched);
 }
 
 // ================================================================================================================

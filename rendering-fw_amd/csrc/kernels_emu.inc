@@ -650,3 +650,17 @@ void launch_refit(Node *all_nodes, uint32_t node_base, const int *parents, uint3
 	}
 }
 
+void launch_light_refresh(const LightFollowView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_light_refresh(v, s));
+	for (uint32_t i = 0; i < v.n_area; i++)
+		*v.bound_count += lf_refresh_item(v, i) ? 1u : 0u;
+}
+void launch_light_tree_refit(LightTreeNode *nodes, const LightTreeLevels &lv, const AreaLight *area, uint32_t n_area,
+							 const unsigned char *bound, unsigned char *touched, stream_t s)
+{
+	EMU_DEFER(s, launch_light_tree_refit(nodes, lv, area, n_area, bound, touched, s));
+	for (uint32_t l = lv.levels; l-- > 0u;)
+		for (uint32_t i = 0; i < lv.count[l]; i++)
+			lf_refit_item(nodes, area, n_area, bound, touched, lv.first[l] + i);
+}

@@ -194,6 +194,45 @@ inline void build(const rt::AreaLight *area, uint32_t n_area, const rt::PointLig
 		next += 2u;
 	}
 }
+
+// The level ranges of a tree in build()'s layout, for the refit on the device (light_follow.h): level l is the nodes
+// [first[l], first[l] + count[l]), level 0 the root, level 1 starts at node 2, every further level directly behind the one above.
+// Checked on the way, because the refit indexes by what the nodes say: a child pair is even, inside the table and behind its
+// parent's level, a leaf's light is one of the n_spatial lights, the table has build()'s size.  false: not such a tree.
+inline bool levels(const rt::LightTreeNode *nodes, size_t node_count, uint32_t n_spatial, uint32_t *first, uint32_t *count, uint32_t max_levels,
+				   uint32_t &n_levels)
+{
+	n_levels = 0;
+	if (!node_count)
+		return n_spatial == 0;
+	if (node_count != (n_spatial == 1 ? (size_t)1 : 2 * (size_t)n_spatial) || !max_levels)
+		return false;
+	first[0] = 0u, count[0] = 1u, n_levels = 1;
+	for (;;)
+	{
+		const uint32_t l = n_levels - 1u, end = l ? first[l] + count[l] : 2u;
+		uint32_t lo = 0xFFFFFFFFu, hi = 0u, inner = 0u;
+		for (uint32_t i = first[l]; i < first[l] + count[l]; i++)
+		{
+			const rt::LightTreeNode &nd = nodes[i];
+			if (!nd.child)
+			{
+				if (nd.light >= n_spatial)
+					return false;
+				continue;
+			}
+			if ((nd.child & 1u) || nd.child < end || (size_t)nd.child + 1u >= node_count)
+				return false;
+			lo = std::min(lo, nd.child), hi = std::max(hi, nd.child + 2u), inner++;
+		}
+		if (!inner)
+			break;
+		if (lo != end || hi - lo != 2u * inner || n_levels == max_levels)
+			return false;
+		first[n_levels] = lo, count[n_levels] = hi - lo, n_levels++;
+	}
+	return node_count == 1 || (size_t)first[n_levels - 1u] + count[n_levels - 1u] == node_count;
+}
 } // namespace lighttree
 #if !defined(__clang__)
 #pragma GCC pop_options

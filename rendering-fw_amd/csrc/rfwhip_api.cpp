@@ -389,6 +389,14 @@ struct rfwhip_context
 	DevBuf d_lt_nodes, d_lt_paths; // allocated only while light_sampling is tree
 	rt::LightTreeView lt_view{};   // nodes == nullptr: linear (or no light with a position)
 	bool lt_stale = false;		   // the setting changed since: the next render (or update) builds the tree
+	// moving emitters (light_follow.h): the setting, "something a bound light depends on changed since the last refresh", what the
+	// last refresh found, the level ranges of the tree as built and the refits it has had since
+	int lights_follow = 0;
+	bool lf_dirty = false;
+	bool lt_rebuild_after_refresh = false; // rfwhip_set_lights under the setting: the next refresh is followed by a build, not a refit
+	uint32_t lights_bound = 0, lt_refits = 0;
+	rtk::LightTreeLevels lt_levels{};
+	DevBuf d_lf_inst, d_lf_bound, d_lf_count, d_lt_touched;
 	uint32_t tlas_root_entry = 0, instance_count = 0;
 	rt::SceneView sv;
 
@@ -592,7 +600,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
 					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
 					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in,
-					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask};
+					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask, &c->d_lf_inst, &c->d_lf_bound, &c->d_lf_count, &c->d_lt_touched};
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->noise_live = false, c->adaptive_live = false;
@@ -970,7 +978,7 @@ static int refit_deformed(rfwhip_context *c, MeshRec &m, RefitTimer &timer)
 		m.bounds_min[a] = root.bmin[a] - 2e-5f, m.bounds_max[a] = root.bmax[a] + 2e-5f;
 	timer.add(5);
 	m.posed = true, m.edits++;
-	c->scene_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
+	c->scene_dirty = true, c->lf_dirty = true; // instance boxes change: the TLAS is rebuilt in update()
 	return RFWHIP_OK;
 }
 
@@ -993,6 +1001,7 @@ extern "C" int rfwhip_set_mesh(rfwhip_context *c, size_t index, const rfwhip_mes
 	const bool same_topology = m.used && m.resident && !m.dirty && m.vertexCount == mesh->vertexCount &&
 							   m.triCount == mesh->triangleCount && m.indexed == (mesh->indices != nullptr);
 	RF_TRY(sync_all(c));
+	c->lf_dirty = true;
 	if (same_topology)
 		RF_TRY(dn_snapshot_mesh(c, m));
 	else
@@ -1155,7 +1164,7 @@ extern "C" int rfwhip_set_instance(rfwhip_context *c, size_t index, size_t mesh_
 	InstRec &in = c->instances[index];
 	in.used = true, in.mesh = mesh_index;
 	memcpy(in.transform, transform16, 64), memcpy(in.normal, normal_matrix9, 36);
-	c->scene_dirty = true;
+	c->scene_dirty = true, c->lf_dirty = true;
 	return RFWHIP_OK;
 }
 
@@ -1178,9 +1187,12 @@ extern "C" int rfwhip_set_lights(rfwhip_context *c, rfwhip_light_count n, const 
 	RF_TRY(dm::h2d(c->d_dir.p, directional, n.directionalLightCount * sizeof(rfwhip_directional_light), c->stream));
 	RF_TRY(dm::sync(c->stream));
 	c->lc = n;
-	c->scene_dirty = true;
+	c->scene_dirty = true, c->lf_dirty = true;
 	c->lt_stale = true;
-	if (c->light_sampling == 2) // (static_asserts below: the ABI's light records are the kernels')
+	// lights_follow_geometry=1: the host's geometry fields are about to be overwritten (and may be zeros), so the topology is not
+	// made of them: the tree stays stale and rfwhip_update builds it from the lights its refresh derives
+	c->lt_rebuild_after_refresh = c->lights_follow != 0;
+	if (c->light_sampling == 2 && !c->lights_follow) // (static_asserts below: the ABI's light records are the kernels')
 		RF_TRY(update_light_tree(c, reinterpret_cast<const rt::AreaLight *>(area), reinterpret_cast<const rt::PointLight *>(point),
 								 reinterpret_cast<const rt::SpotLight *>(spot)));
 	return RFWHIP_OK;
@@ -1518,6 +1530,7 @@ static int update_light_tree(rfwhip_context *c, const rt::AreaLight *h_area, con
 {
 	c->lt_stale = true;
 	c->lt_view = rt::LightTreeView{};
+	c->lt_levels.levels = 0, c->lt_refits = 0;
 	if (c->light_sampling != 2)
 	{
 		if (c->d_lt_nodes.p || c->d_lt_paths.p)
@@ -1576,8 +1589,93 @@ static int update_light_tree(rfwhip_context *c, const rt::AreaLight *h_area, con
 	else
 		c->d_lt_paths.free_();
 	RF_TRY(dm::sync(c->stream));
+	// the level ranges of the new topology, for the refits that follow it (light_follow.h).  No new way for a build to fail: a tree
+	// whose levels cannot be read (build() lays out none such) has no ranges, and refresh_lights rebuilds it instead of refitting
+	if (!lighttree::levels(nodes.data(), nodes.size(), view.n_spatial, c->lt_levels.first, c->lt_levels.count, rtk::LT_MAX_LEVELS, c->lt_levels.levels))
+		c->lt_levels.levels = 0;
+	c->lt_refits = 0;
 	c->lt_view = view;
 	c->lt_stale = false;
+	return RFWHIP_OK;
+}
+
+// lights_follow_geometry=1: the bound area lights from the current triangles and transforms, and — where a tree stands — its refit
+// (light_follow.h).  Called by rfwhip_update behind its sync_all and behind everything it writes of meshes and instances, in front
+// of everything that reads the lights: the rule of rfwhip_pose_mesh's device refit — every stream of the ring drained first, the
+// work enqueued on the context's stream, the stream synchronised before the call returns.
+static int refresh_lights_enqueue(rfwhip_context *c, std::vector<rtk::LightInst> &tab, uint32_t &bound)
+{
+	const uint32_t na = c->lc.areaLightCount;
+	for (size_t i = 0; i < c->instances.size(); i++)
+	{
+		const InstRec &in = c->instances[i];
+		if (!in.used || in.mesh >= c->meshes.size() || !c->meshes[in.mesh].used || !c->meshes[in.mesh].resident)
+			continue;
+		const MeshRec &m = c->meshes[in.mesh];
+		rtk::LightInst &e = tab[i];
+		for (int r = 0; r < 3; r++)
+		{
+			for (int col = 0; col < 4; col++)
+				e.m[4 * r + col] = in.transform[4 * col + r];
+			for (int col = 0; col < 3; col++)
+				e.nrm[4 * r + col] = in.normal[3 * col + r];
+		}
+		e.verts = m.d_verts.as<f4>(), e.indices = m.indexed ? m.d_indices.as<uint32_t>() : nullptr;
+		e.tri_count = (uint32_t)m.triCount, e.shade_base = m.shade_base;
+	}
+	RF_TRY(c->d_lf_inst.ensure(tab.size() * sizeof(rtk::LightInst)));
+	RF_TRY(c->d_lf_bound.ensure(na));
+	RF_TRY(c->d_lf_count.ensure(sizeof(uint32_t)));
+	RF_TRY(dm::h2d(c->d_lf_inst.p, tab.data(), tab.size() * sizeof(rtk::LightInst), c->stream));
+	RF_TRY(dm::zero(c->d_lf_count.p, sizeof(uint32_t), c->stream));
+	rtk::LightFollowView v{};
+	v.area = c->d_area.as<rt::AreaLight>(), v.inst = c->d_lf_inst.as<rtk::LightInst>(), v.tri_shade = c->d_tri_shade.as<rt::TriShade>();
+	v.bound = c->d_lf_bound.as<unsigned char>(), v.bound_count = c->d_lf_count.as<uint32_t>();
+	v.n_area = na, v.n_inst = (uint32_t)c->instances.size();
+	rtk::launch_light_refresh(v, c->stream);
+	RF_TRY(dm::last_launch_error());
+	// (a stale tree is built from the refreshed lights by update_light_tree, which follows in rfwhip_update)
+	if (c->light_sampling == 2 && !c->lt_stale && c->lt_view.nodes)
+	{
+		if (!c->lt_levels.levels)
+			c->lt_stale = true; // (no level ranges: built again instead)
+		else
+		{
+			RF_TRY(c->d_lt_touched.ensure(c->lt_view.node_count));
+			rtk::launch_light_tree_refit(const_cast<rt::LightTreeNode *>(c->lt_view.nodes), c->lt_levels, c->d_area.as<rt::AreaLight>(), na,
+										 c->d_lf_bound.as<unsigned char>(), c->d_lt_touched.as<unsigned char>(), c->stream);
+			RF_TRY(dm::last_launch_error());
+			c->lt_refits++;
+		}
+	}
+	return dm::d2h(&bound, c->d_lf_count.p, sizeof(bound), c->stream);
+}
+static int refresh_lights(rfwhip_context *c)
+{
+	if (!c->lights_follow)
+	{
+		c->lights_bound = 0, c->lt_rebuild_after_refresh = false;
+		return RFWHIP_OK;
+	}
+	// the lights of a rfwhip_set_lights under the setting: whatever tree was made of the host's geometry fields since (a
+	// rfwhip_get_light_tree in between) is built again from what this refresh derives
+	if (c->lt_rebuild_after_refresh)
+		c->lt_stale = true, c->lt_rebuild_after_refresh = false;
+	if (!c->lf_dirty)
+		return RFWHIP_OK;
+	c->lights_bound = 0;
+	if (c->lc.areaLightCount)
+	{
+		std::vector<rtk::LightInst> tab(std::max<size_t>(1, c->instances.size()));
+		memset(tab.data(), 0, tab.size() * sizeof(rtk::LightInst));
+		uint32_t bound = 0;
+		const int rc = refresh_lights_enqueue(c, tab, bound);
+		const int rs = dm::sync(c->stream); // (on every path: nothing enqueued may outlive `tab`)
+		RF_TRY(rc);
+		RF_TRY(rs);
+		c->lights_bound = bound;
+	}
+	c->lf_dirty = false; // (only now: after a failure the next rfwhip_update tries again)
 	return RFWHIP_OK;
 }
 
@@ -1612,6 +1710,7 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 		relayout = true; // the TLAS lives behind the BLAS nodes in the same array: grow it together
 	if (relayout)
 	{
+		c->lf_dirty = true; // (the shading records are uploaded again: a bound triangle's area is the host's once more)
 		size_t nodes = 0, tris = 0, nodes4 = 0;
 		for (auto &m : c->meshes)
 			if (m.used)
@@ -1894,6 +1993,7 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 	sv.spot = c->d_spot.as<rt::SpotLight>(), sv.dir = c->d_dir.as<rt::DirectionalLight>();
 	sv.n_area = c->lc.areaLightCount, sv.n_point = c->lc.pointLightCount, sv.n_spot = c->lc.spotLightCount;
 	sv.n_dir = c->lc.directionalLightCount;
+	RF_TRY(refresh_lights(c));
 	RF_TRY(update_sky_sampling(c));
 	if (c->lt_stale)
 		RF_TRY(update_light_tree(c));
@@ -3767,6 +3867,18 @@ static const Setting k_settings[] = {
 	 GET { return put(out, cap, "%g", c->noise_floor); }, false},
 	{"noise_threshold", SET { return set_float(c->noise_threshold, key, value, [](float f) { return f > 0.0f && f < 1e30f; }, "be a finite number > 0", false); },
 	 GET { return put(out, cap, "%g", c->noise_threshold); }, false},
+	// moving emitters (light_follow.h): rfwhip_update derives the bound area lights on the device and refits the tree
+	{"lights_follow_geometry", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 if (on && !c->lights_follow)
+			 c->lf_dirty = true; // (turned on: the next rfwhip_update refreshes)
+		 c->lights_follow = on;
+		 return RFWHIP_OK; },
+	 GET_INT(lights_follow), false},
+	// read-only: bound area lights at the last refresh (0 while the setting is off); refits of the light tree since it was built
+	{"lights_bound", nullptr, GET { return put(out, cap, "%u", c->lights_follow ? c->lights_bound : 0u); }, false},
+	{"light_tree_refits", nullptr, GET { return put(out, cap, "%u", c->lt_refits); }, false},
 	// read-only: nodes of the light tree the next render would use (0: none, or light_sampling is not tree)
 	{"light_tree", nullptr, GET {
 		 if (c->lt_stale)
@@ -4550,6 +4662,63 @@ extern "C" int rfwhip_get_bvh4(rfwhip_context *c, size_t mesh_index, void *nodes
 		}
 	}
 	return RFWHIP_OK;
+}
+
+// ---- moving emitters (setting "lights_follow_geometry"; work items: light_follow.h) ---------------------------------------------
+extern "C" int rfwhip_read_area_lights(rfwhip_context *c, rfwhip_area_light *out, size_t cap)
+{
+	CTX_ENTER(c);
+	const size_t n = std::min<size_t>(cap, c->lc.areaLightCount);
+	if (n && !out)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_area_lights: null array");
+	if (n)
+		RF_TRY(dm::d2h(out, c->d_area.p, n * sizeof(rfwhip_area_light), c->stream));
+	RF_TRY(dm::sync(c->stream));
+	return (int)c->lc.areaLightCount;
+}
+
+extern "C" int rfwhip_light_tree_refit(rfwhip_context *c, rfwhip_light_tree_node *nodes, size_t node_count, const rfwhip_area_light *area,
+									   size_t n_area, const uint8_t *bound)
+{
+	CTX_ENTER(c);
+	if (!nodes || !node_count || (n_area && !area))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_light_tree_refit: null array");
+	if (node_count >= (1ull << 31) || (node_count != 1 && (node_count & 1)))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_light_tree_refit: %zu nodes is not the size of a light tree", node_count);
+	const uint32_t n_spatial = node_count == 1 ? 1u : (uint32_t)(node_count / 2);
+	if (n_area > n_spatial)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_light_tree_refit: %zu area lights, but the tree holds %u lights", n_area, n_spatial);
+	rtk::LightTreeLevels lv{};
+	if (!lighttree::levels(reinterpret_cast<const rt::LightTreeNode *>(nodes), node_count, n_spatial, lv.first, lv.count, rtk::LT_MAX_LEVELS, lv.levels))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_light_tree_refit: the nodes are not a tree as rfwhip_get_light_tree returns it");
+	RF_TRY(sync_all(c));
+	const std::vector<uint8_t> all(bound ? 0 : n_area, 1);
+	DevBuf d_nodes, d_area, d_bound, d_touched;
+	int rc = d_nodes.ensure(node_count * sizeof(rt::LightTreeNode));
+	if (!rc)
+		rc = d_area.ensure(std::max<size_t>(1, n_area) * sizeof(rt::AreaLight));
+	if (!rc)
+		rc = d_bound.ensure(std::max<size_t>(1, n_area));
+	if (!rc)
+		rc = d_touched.ensure(node_count);
+	if (!rc)
+		rc = dm::h2d(d_nodes.p, nodes, node_count * sizeof(rt::LightTreeNode), c->stream);
+	if (!rc && n_area)
+		rc = dm::h2d(d_area.p, area, n_area * sizeof(rt::AreaLight), c->stream);
+	if (!rc && n_area)
+		rc = dm::h2d(d_bound.p, bound ? bound : all.data(), n_area, c->stream);
+	if (!rc)
+	{
+		rtk::launch_light_tree_refit(d_nodes.as<rt::LightTreeNode>(), lv, d_area.as<rt::AreaLight>(), (uint32_t)n_area,
+									 d_bound.as<unsigned char>(), d_touched.as<unsigned char>(), c->stream);
+		rc = dm::last_launch_error();
+	}
+	if (!rc)
+		rc = dm::d2h(nodes, d_nodes.p, node_count * sizeof(rt::LightTreeNode), c->stream);
+	const int rs = dm::sync(c->stream); // (on every path: nothing enqueued may outlive the buffers)
+	rc = rc ? rc : rs;
+	d_nodes.free_(), d_area.free_(), d_bound.free_(), d_touched.free_();
+	return rc;
 }
 
 #if defined(RFWHIP_HOST_EMULATION) && defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
