@@ -172,6 +172,59 @@ RFWHIP_API int rfwhip_display_stream(rfwhip_context *ctx, const void *rgba_devic
 RFWHIP_API int rfwhip_display_image(rfwhip_context *ctx, const float *rgba_in, float brightness, float contrast, int format,
 									void *out_host);
 
+/* ---- exposure meter: the display stage measures the image it shows ------------------------------------------------------------
+ * A luminance histogram of the image in front of the display kernel, a robust average of it, and a multiplicative exposure with
+ * temporal adaptation: two small kernels on the device, stream-ordered, nothing read back (csrc/metering.h has the formulas;
+ * DESIGN.md section 17).  Off by default: with display_exposure = "manual" and display_exposure_ev = 0 every entry point above
+ * launches the kernels and returns the bits it did without the meter.
+ *   Settings (not listed by rfwhip_get_settings):
+ *     display_exposure        = "manual" (default) | "auto"
+ *     display_exposure_ev     = stops, finite, in [-32, 32] (default 0); manual: E = 2^ev; auto: a compensation added to the target
+ *     display_exposure_key    = the target key, a finite number > 0 (default 0.18)
+ *     display_exposure_low / _high = the percentile window, 0 <= low < high <= 1 (defaults 0.1 / 0.9); a set that breaks the order is
+ *                               refused and leaves both values unchanged
+ *     display_exposure_speed  = the fraction of the way to the target per STEP, in (0, 1] (default 1 = immediate).  Per step, not
+ *                               per second: the same calls give the same images
+ *     display_exposure_min_ev / _max_ev = the clamp of the target, finite, in [-64, 64], min <= max (defaults -16 / 16)
+ *   Per pixel: c = max(rgb, 0) (a NaN channel is 0), Y = 0.2126 r + 0.7152 g + 0.0722 b; valid iff 0 < Y < +inf, every other pixel
+ *   counts as `excluded`.  bin = clamp((bits(Y) >> 20) - 888, 0, 255): 256 bins, 8 per octave over [2^-16, 2^16), linear inside an
+ *   octave; bin b stands for lambda_b = (b >> 3) - 16 + log2(1 + ((b & 7) + 0.5) / 8) in log2 units.
+ *   A STEP: N = valid pixels; the histogram's mass between low N and high N (a bin cut by an end counts with the part inside) gives
+ *   lambda = the mean of lambda_b over it, in double.  No mass (no valid pixel): no step, the state stays.  Else, in float32:
+ *     l_target = clamp(log2(key) - lambda + ev, min_ev, max_ev);  l = first step ? l_target : l + speed (l_target - l);  E = 2^l
+ *   and the display's tone step sees x E per colour channel in place of x (alpha untouched).
+ *   WHEN a step is taken (auto): rfwhip_read_display / _device meter the presented image behind the denoiser, in front of the display
+ *   kernel, on the context's stream — ONE step per rfwhip_render call: a second read of the same frame returns the same bytes and
+ *   leaves `steps` alone; a change of a display_exposure* setting meters the frame again.  rfwhip_display_stream and
+ *   rfwhip_display_image show a caller's image: every call is one step on that image, on the given stream.
+ *   rfwhip_group_read_display and rfwhip_group_present_display_async go through rfwhip_display_stream on the root: a group read or
+ *   present is one step, nothing is read back to the host on that path, and frames in flight stay in flight.  RFWHIP_RESET does not
+ *   reset the exposure (a camera move must not flash), neither does rfwhip_init; rfwhip_meter_reset does. */
+#define RFWHIP_METER_BINS 256
+typedef struct rfwhip_meter_stats /* 32 bytes: the record as it lies on the device */
+{
+	float exposure;		  /* E = 2^log2_exposure: 1 before any step; manual mode with ev != 0 writes 2^ev here when it displays */
+	float log2_exposure;  /* l, after adaptation */
+	float log2_target;	  /* l_target of the last step */
+	float log2_luminance; /* lambda of the last step */
+	uint32_t valid;		  /* pixels in the histogram of the last metered image */
+	uint32_t excluded;	  /* ... and left out of it */
+	uint32_t steps;		  /* steps taken since rfwhip_meter_reset (or the context's creation) */
+	uint32_t reserved;
+} rfwhip_meter_stats;
+/* The record / the summed histogram of the last step (excluded may be null), after everything enqueued on the context's streams and
+ * after a step enqueued on a caller's stream.  RFWHIP_ERR_STATE before rfwhip_init. */
+RFWHIP_API int rfwhip_get_meter(rfwhip_context *ctx, rfwhip_meter_stats *stats);
+RFWHIP_API int rfwhip_read_meter_histogram(rfwhip_context *ctx, uint32_t bins[RFWHIP_METER_BINS], uint32_t *excluded);
+/* E = 1, steps = 0: the next step is a first step. */
+RFWHIP_API int rfwhip_meter_reset(rfwhip_context *ctx);
+/* Known-answer hooks, the counterparts of rfwhip_display_image, under the current settings.
+ * rfwhip_meter_image: one step on a host image of the context's target size; bins (RFWHIP_METER_BINS words) may be null.
+ * rfwhip_meter_histogram: the reduce alone (k_meter_reduce) on a caller's histogram, whose counts add up to at most 2^32 - 1. */
+RFWHIP_API int rfwhip_meter_image(rfwhip_context *ctx, const float *rgba_in, rfwhip_meter_stats *stats, uint32_t *bins);
+RFWHIP_API int rfwhip_meter_histogram(rfwhip_context *ctx, const uint32_t bins[RFWHIP_METER_BINS], uint32_t excluded,
+									  rfwhip_meter_stats *stats);
+
 /* ---- noise estimate: when has a progressive render converged? ---------------------------------------------------------------
  * With noise_estimate = 1 the resolve of every rfwhip_render (its variant k_resolve_noise) keeps two floats per pixel beside the
  * accumulator — sumY, the sum of the luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel's samples (a sample's value is what
@@ -336,6 +389,9 @@ RFWHIP_API int rfwhip_group_get_noise(rfwhip_group *group, rfwhip_noise_stats *s
 /* Adaptive sampling of the whole image (see rfwhip_get_adaptive): tiles and their decisions are per rank; the ranks' records are
  * added in rank order. */
 RFWHIP_API int rfwhip_group_get_adaptive(rfwhip_group *group, rfwhip_adaptive_stats *stats);
+/* The exposure meter of a group (see rfwhip_get_meter): the root's record — the root shows the gathered image, so its meter is the
+ * group's.  Waits for the steps of the reads and presents enqueued so far. */
+RFWHIP_API int rfwhip_group_get_meter(rfwhip_group *group, rfwhip_meter_stats *stats);
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
 RFWHIP_API int rfwhip_group_present_display_wait(rfwhip_group *group, int slot, const void **out_host, int *format);
@@ -575,6 +631,8 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                  weights) | "tree" (the light tree, O(log lights) per next-event vertex, the same weights): rfwhip_get_light_tree
  *                  below has the formulas.  The parity integrator ignores it.
  *   display_tonemap / display_fxaa / display_srgb = the display stage, see rfwhip_read_display above.
+ *   display_exposure / display_exposure_ev / _key / _low / _high / _speed / _min_ev / _max_ev = the exposure meter, see
+ *                  rfwhip_get_meter above.
  *   noise_estimate / noise_floor / noise_threshold = the noise estimate, see rfwhip_get_noise above.
  *   adaptive_sampling / adaptive_min_samples / adaptive_every = adaptive sampling, see rfwhip_get_adaptive above.
  *   lights_follow_geometry = "0" (default) | "1": rfwhip_update derives the area lights of emissive geometry on the device and
@@ -606,7 +664,8 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * stage_timing=1.  which: 0 generate, 1 extend, 2 shade, 3 connect, 4 finalize, 5 refit, 6 denoise (a guide pass is two launches,
  * guide rays + depth gradient; a filter is 1 + denoise_iterations launches: demodulation / variance, then the a-trous passes),
  * 7 display (one launch per displayed image), 8 noise (the metric: two launches per query; the moments are part of the resolve,
- * family 4). */
+ * family 4), 9 the exposure meter's histogram pass k_meter_hist and 10 its reduce k_meter_reduce (one launch each per step; the
+ * exposed display kernels count as family 7). */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

@@ -300,7 +300,9 @@ enum rfwhip_kat_function
 	RFWHIP_KAT_SURFACE_LAYERS = 16,   /* [0] = instance, [1] = triangle (ints), [2..3] = barycentrics u, v (weights of vertex 1, 2), [4..6] = D, [7] = t, [8] = the camera's spread angle -> [0..2] = colour after the texture layers, [3..5] = shading normal after the normal maps, [6] = flags (int): bit 0 alpha pass-through, bit 1 the material is textured */
 	/* the light tree of light_sampling=tree (rt_core.h: lt_sample / lt_pick_prob); RFWHIP_ERR_STATE in any other mode */
 	RFWHIP_KAT_LT_SAMPLE = 17,		   /* [0..2] = I, [3..5] = N, [6] = r0, [7] = r1 -> [0..2] = P, [3] = q, [4] = lightPdf (area: dist^2 / (area LNdotL)), [5] = the light (int, -1: none), [6] = its rank in the order r1 walks through (int) */
-	RFWHIP_KAT_LT_PICK_PROB = 18 	   /* [0..2] = I, [3..5] = N, [8] = light (int) -> q, bit for bit what LT_SAMPLE gives when it draws that light */
+	RFWHIP_KAT_LT_PICK_PROB = 18, 	   /* [0..2] = I, [3..5] = N, [8] = light (int) -> q, bit for bit what LT_SAMPLE gives when it draws that light */
+	/* the exposure meter's bin of a luminance (csrc/metering.h: mt_bin; rfwhip.h, rfwhip_get_meter, has the formula) */
+	RFWHIP_KAT_METER_BIN = 19		   /* [0..7] = eight Y values -> eight bins (ints, 0..255); -1 where Y is not valid (not 0 < Y < +inf) */
 };
 
 #ifdef __cplusplus

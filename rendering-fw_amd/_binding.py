@@ -93,6 +93,11 @@ class CoreBinding:
                                   "read_display": (i32, [vp, i32, vp]),
                                   "read_display_device": (i32, [vp, i32, vp]),
                                   "display_stream": (i32, [vp, vp, vp, i32, vp]),
+                                  "get_meter": (i32, [vp, C.POINTER(abi.MeterStats)]),
+                                  "read_meter_histogram": (i32, [vp, vp, C.POINTER(u32)]),
+                                  "meter_reset": (i32, [vp]),
+                                  "meter_image": (i32, [vp, vp, C.POINTER(abi.MeterStats), vp]),
+                                  "meter_histogram": (i32, [vp, vp, u32, C.POINTER(abi.MeterStats)]),
                                   "get_noise": (i32, [vp, C.POINTER(abi.NoiseStats)]),
                                   "read_noise_map": (i32, [vp, vp]),
                                   "read_noise_tiles": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
@@ -413,6 +418,41 @@ class CoreBinding:
                                               out.ctypes.data))
         return out
 
+    # ---- exposure meter (include/rfwhip.h, rfwhip_get_meter; setting display_exposure = auto) -----------------------
+    def meter(self):
+        """The exposure meter's record as a dict: exposure (E), log2_exposure, log2_target, log2_luminance, valid, excluded,
+        steps."""
+        st = abi.MeterStats()
+        self._check(self._fn("get_meter")(self._ctx, C.byref(st)))
+        return st.as_dict()
+
+    def meter_histogram(self):
+        """(bins: 256 uint32, excluded) of the last metered image."""
+        bins, ex = np.zeros(abi.METER_BINS, np.uint32), C.c_uint32()
+        self._check(self._fn("read_meter_histogram")(self._ctx, bins.ctypes.data, C.byref(ex)))
+        return bins, int(ex.value)
+
+    def meter_image(self, rgba):
+        """Known-answer hook: one step of the meter on an H x W x 4 float32 image under the current display_exposure*
+        settings -> (record dict, bins)."""
+        src = np.ascontiguousarray(rgba, dtype=np.float32).reshape(self.height, self.width, 4)
+        st, bins = abi.MeterStats(), np.zeros(abi.METER_BINS, np.uint32)
+        self._check(self._fn("meter_image")(self._ctx, src.ctypes.data, C.byref(st), bins.ctypes.data))
+        return st.as_dict(), bins
+
+    def meter_from_histogram(self, bins, excluded=0):
+        """Known-answer hook: the meter's reduce alone on a histogram of 256 counts -> record dict."""
+        b = np.ascontiguousarray(bins, dtype=np.uint32).reshape(-1)
+        if len(b) != abi.METER_BINS:
+            raise ValueError("a meter histogram has %d bins, got %d" % (abi.METER_BINS, len(b)))
+        st = abi.MeterStats()
+        self._check(self._fn("meter_histogram")(self._ctx, b.ctypes.data, int(excluded), C.byref(st)))
+        return st.as_dict()
+
+    def meter_reset(self):
+        """E = 1, steps = 0: the next step is a first step."""
+        self._check(self._fn("meter_reset")(self._ctx))
+
     # ---- noise estimate (include/rfwhip.h, rfwhip_get_noise; setting noise_estimate = 1) ---------------------------
     def get_noise(self):
         """The noise of the accumulated image as a dict: samples, pixels, converged, mean_error, max_error, threshold.
@@ -529,10 +569,11 @@ class CoreBinding:
     DENOISE = 6  # kernel family of the denoiser (guide pass + filter), outside KERNELS: the render's stages
     DISPLAY = 7  # ... and of the display stage (one launch per displayed image)
     NOISE = 8  # ... and of the noise metric (two launches per get_noise)
+    METER_HIST, METER_REDUCE = 9, 10  # ... and of the exposure meter's two kernels (one launch each per step)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -552,7 +593,7 @@ class CoreBinding:
     # known-answer hook: RFWHIP_KAT_* (include/rfwhip_abi.h)
     KAT = {"bsdf_eval": 0, "bsdf_pdf": 1, "bsdf_sample": 2, "tangent_space": 3, "pack_normal": 4,
            "random_barycentrics": 5, "point_on_light": 6, "light_pick_prob": 7, "blue_noise": 8, "hash": 9, "half_to_float": 10, "fastdiv": 11, "tex_wrap": 12,
-           "sky_sample": 13, "sky_pdf": 14, "tex_fetch": 15, "surface_layers": 16, "lt_sample": 17, "lt_pick_prob": 18}
+           "sky_sample": 13, "sky_pdf": 14, "tex_fetch": 15, "surface_layers": 16, "lt_sample": 17, "lt_pick_prob": 18, "meter_bin": 19}
 
     def kat(self, function, records):
         """One of the path tracer's functions on n records (n x 24 float32, integers as bit patterns) -> n x 8 float32."""
@@ -661,7 +702,8 @@ class RenderGroup:
         for name, res, args in [("group_read_display", i32, [vp, i32, vp]), ("group_present_display_async", i32, [vp, i32, i32]),
                                 ("group_present_display_wait", i32, [vp, i32, C.POINTER(vp), C.POINTER(i32)]),
                                 ("group_get_noise", i32, [vp, C.POINTER(abi.NoiseStats)]),
-                                ("group_get_adaptive", i32, [vp, C.POINTER(abi.AdaptiveStats)])]:
+                                ("group_get_adaptive", i32, [vp, C.POINTER(abi.AdaptiveStats)]),
+                                ("group_get_meter", i32, [vp, C.POINTER(abi.MeterStats)])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -748,6 +790,12 @@ class RenderGroup:
         """Adaptive sampling of the whole image: the ranks' records added up (CoreBinding.get_adaptive)."""
         st = abi.AdaptiveStats()
         self._check(self._fn("group_get_adaptive")(self._g, C.byref(st)))
+        return st.as_dict()
+
+    def meter(self):
+        """The exposure meter of the group: the root's record (CoreBinding.meter)."""
+        st = abi.MeterStats()
+        self._check(self._fn("group_get_meter")(self._g, C.byref(st)))
         return st.as_dict()
 
     def present_display_async(self, slot, format="rgba8"):

@@ -171,6 +171,18 @@ class NoiseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MeterStats(C.Structure):
+    """rfwhip_meter_stats (include/rfwhip.h, rfwhip_get_meter): the exposure meter's 32-byte record."""
+    _fields_ = [("exposure", C.c_float), ("log2_exposure", C.c_float), ("log2_target", C.c_float), ("log2_luminance", C.c_float),
+                ("valid", C.c_uint32), ("excluded", C.c_uint32), ("steps", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+METER_BINS = 256
+
+
 class AdaptiveStats(C.Structure):
     """rfwhip_adaptive_stats (include/rfwhip.h, rfwhip_get_adaptive)."""
     _fields_ = [(n, C.c_uint64) for n in ("tiles", "active_tiles", "pixels", "active_pixels", "samples_taken", "samples_uniform")]

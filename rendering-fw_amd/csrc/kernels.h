@@ -94,6 +94,36 @@ struct DisplayView
 	uint32_t fxaa, srgb, format;
 };
 
+// The exposure meter (metering.h).  A histogram is MT_BINS bins; a record of one is MT_RECORD words: the bins, then `excluded`,
+// padded to whole 16-byte rows (the reduce reads four bins per lane)
+constexpr uint32_t MT_BINS = 256u, MT_RECORD = MT_BINS + 4u;
+// The 32-byte record k_meter_reduce leaves on the device (= rfwhip_meter_stats) ...
+struct MeterRecord
+{
+	float E, l, l_target, lambda; // the exposure 2^l, l after adaptation, its clamped target, the window's mean log2 luminance
+	uint32_t valid, excluded;	  // pixels counted into the histogram / left out of it (the last metered image)
+	uint32_t steps, reserved;	  // steps taken since the last reset
+};
+// ... what a step is taken with (the display_exposure_* settings; log2_key: log2 of the key, computed in double) ...
+struct MeterParams
+{
+	double low, high;
+	float log2_key, ev, ev_min, ev_max, speed;
+	uint32_t pad;
+};
+// ... the histogram pass's view: `pixels` float4 pixels in, one partial record of MT_RECORD words per MT_RANGE pixels out ...
+struct MeterView
+{
+	const rt::f4 *in;
+	uint32_t pixels;
+	uint32_t *partial;
+};
+// ... and the exposed display's: E of the record, a scalar load (DisplayView stays what it was)
+struct ExposureView
+{
+	const MeterRecord *rec;
+};
+
 // The noise estimate (noise.h).  One record per NZ_TILE_X x NZ_TILE_Y noise tile (= rfwhip_noise_tile) and the one record k_noise_final leaves
 constexpr uint32_t NZ_TILE_X = 32, NZ_TILE_Y = 8;
 struct NoiseTile
@@ -197,6 +227,15 @@ void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion 
 void launch_denoise_temporal(const DnView &d, const DnTemporal &t, const DnMotion *m, stream_t s);
 // the display stage: one launch of k_display (fxaa: the LDS-tiled kernel; else its halo-free pointwise variant)
 void launch_display(const DisplayView &v, stream_t s);
+// ... and its exposed twin k_display_exposed: every colour channel times e.rec->E in front of the tone step (metering.h)
+void launch_display_exposed(const DisplayView &v, const ExposureView &e, stream_t s);
+// the exposure meter (metering.h).  k_meter_hist: meter_records(v.pixels) partial records; k_meter_reduce: one workgroup sums `records`
+// of them into hist (MT_RECORD words: the bins, then excluded) and takes a step on rec (rfwhip_meter_histogram
+// poses a caller's histogram as one record)
+uint32_t meter_records(uint32_t pixels);
+void launch_meter_hist(const MeterView &v, stream_t s);
+void launch_meter_reduce(const uint32_t *partial, uint32_t records, uint32_t *hist, const MeterParams &m, MeterRecord *rec, stream_t s);
+constexpr int KAT_METER_BIN = 19; // (RFWHIP_KAT_METER_BIN: k_kat_meter, metering.h)
 // a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
 rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,

@@ -967,6 +967,8 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 #include "denoise.h"
 // the display stage: tone map + FXAA + encoding of the presented image (the work item shared with the emulation)
 #include "display.h"
+// the exposure meter: luminance histogram, robust average, adapted exposure (work items shared with the emulation)
+#include "metering.h"
 // moving emitters: the area lights of emissive geometry and the light tree's refit (work items shared with the emulation)
 #include "light_follow.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }
@@ -2462,11 +2464,20 @@ __global__ void __launch_bounds__(BLOCK) k_kat_lt(const Params p, const SkyView 
 	if (i < n)
 		kat_item<true>(p, sky, lt, function, in, out, i, s_pot + threadIdx.x);
 }
+// RFWHIP_KAT_METER_BIN (metering.h): a kernel of its own, k_kat keeps its code
+__global__ void __launch_bounds__(BLOCK) k_kat_meter(const float *in, float *out, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < n)
+		mt_kat_item(in, out, i);
+}
 void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
 	if (!n)
 		return;
-	if (function == KAT_LT_SAMPLE || function == KAT_LT_PICK_PROB)
+	if (function == KAT_METER_BIN)
+		hipLaunchKernelGGL(k_kat_meter, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, in, out, n);
+	else if (function == KAT_LT_SAMPLE || function == KAT_LT_PICK_PROB)
 		hipLaunchKernelGGL(k_kat_lt, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, lt, function, in, out, n);
 	else
 		hipLaunchKernelGGL(k_kat, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, function, in, out, n);
@@ -2519,6 +2530,50 @@ template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const Di
 					dp_item<true>(v, fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
 	}
 }
+// k_display_exposed (metering.h): k_display with every colour channel of a texel times E in front of dp_tone.  A kernel of its own,
+// its body restated: k_display keeps its code to the instruction
+RT_FN f4 dp_exposed(const f4 &c, float E) { return mk4(c.x * E, c.y * E, c.z * E, c.w); }
+template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display_exposed(const DisplayView v, const ExposureView e)
+{
+	const float E = e.rec->E; // (a uniform address: one scalar load)
+	if constexpr (!FXAA)
+	{
+		const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+		if (i >= (size_t)v.W * v.H)
+			return;
+		const f4 c = v.in[i];
+		const f3 t = dp_tone(v, dp_exposed(c, E));
+		dp_item<false>(v, [&](int, int) -> f3 { return t; }, (int)(i % v.W), (int)(i / v.W), c.w);
+	}
+	else
+	{
+		__shared__ float s_rgb[3][DP_LDS_H * DP_PITCH];
+		const int W = (int)v.W, H = (int)v.H;
+		const int x0 = (int)blockIdx.x * DP_TILE_X - DP_HALO, y0 = (int)blockIdx.y * DP_TILE_Y - DP_HALO;
+		for (int k = (int)threadIdx.x; k < DP_LDS_W * DP_LDS_H; k += BLOCK)
+		{
+			const int ly = k / DP_LDS_W, lx = k - ly * DP_LDS_W, gx = x0 + lx, gy = y0 + ly;
+			if (gx >= 0 && gx < W && gy >= 0 && gy < H) // (texels outside the image are never fetched: the taps clamp to the edge first)
+			{
+				const f3 t = dp_tone(v, dp_exposed(v.in[(size_t)gy * v.W + (size_t)gx], E));
+				const int o = ly * DP_PITCH + lx;
+				s_rgb[0][o] = t.x, s_rgb[1][o] = t.y, s_rgb[2][o] = t.z;
+			}
+		}
+		__syncthreads();
+		// (xi, yi) is inside the image and within DP_HALO of a pixel of this tile: inside the LDS tile
+		const auto fetch = [&](int xi, int yi) -> f3 {
+			const int o = (yi - y0) * DP_PITCH + (xi - x0);
+			return mk3(s_rgb[0][o], s_rgb[1][o], s_rgb[2][o]);
+		};
+		const int x = (int)blockIdx.x * DP_TILE_X + (int)(threadIdx.x & 63u);
+		const int yw = (int)blockIdx.y * DP_TILE_Y + (int)(threadIdx.x >> 6) * (DP_TILE_Y / 4);
+		if (x < W)
+			for (int r = 0; r < DP_TILE_Y / 4; r++)
+				if (yw + r < H)
+					dp_item<true>(v, fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
+	}
+}
 void launch_display(const DisplayView &v, stream_t s)
 {
 	if (v.fxaa)
@@ -2526,6 +2581,158 @@ void launch_display(const DisplayView &v, stream_t s)
 						   (hipStream_t)s, v);
 	else
 		hipLaunchKernelGGL(k_display<false>, dim3((uint32_t)(((size_t)v.W * v.H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)s, v);
+}
+void launch_display_exposed(const DisplayView &v, const ExposureView &e, stream_t s)
+{
+	if (v.fxaa)
+		hipLaunchKernelGGL(k_display_exposed<true>, dim3((v.W + DP_TILE_X - 1) / DP_TILE_X, (v.H + DP_TILE_Y - 1) / DP_TILE_Y), dim3(BLOCK), 0,
+						   (hipStream_t)s, v, e);
+	else
+		hipLaunchKernelGGL(k_display_exposed<false>, dim3((uint32_t)(((size_t)v.W * v.H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)s, v, e);
+}
+
+// ---- exposure meter (metering.h).  k_meter_hist: workgroup g owns the pixels [g MT_RANGE, (g + 1) MT_RANGE): MT_RANGE / BLOCK rounds of
+// one float4 per thread (a wave reads 1 KiB of consecutive pixels per round).  Every wave counts into an LDS histogram of its own —
+// a quarter of the lanes that can meet on a word — and a wave whose lanes all name ONE bin (a flat image, a saturated or a dark
+// region) adds its population count with a single atomic instead of 64 serialised ones.  Integer atomics in LDS only; the four
+// copies are added in wave order and leave as one partial record with plain stores. ----
+__global__ void __launch_bounds__(BLOCK) k_meter_hist(const MeterView v)
+{
+	__shared__ uint32_t s_hist[BLOCK / 64][MT_BINS];
+	__shared__ uint32_t s_excl[BLOCK / 64];
+	const uint32_t wave = threadIdx.x >> 6;
+	for (uint32_t k = threadIdx.x; k < (BLOCK / 64) * MT_BINS; k += BLOCK)
+		(&s_hist[0][0])[k] = 0u;
+	__syncthreads();
+	const uint32_t base = blockIdx.x * MT_RANGE; // (pixels < 2^32: no overflow below the last range's end, which is clamped by `i < v.pixels`)
+	uint32_t excl = 0u;						   // wave-uniform
+#pragma unroll
+	for (uint32_t r = 0; r < MT_RANGE / BLOCK; r++)
+	{
+		const uint32_t i = base + r * BLOCK + threadIdx.x;
+		const bool real = i >= base && i < v.pixels; // (i >= base: the sum wrapped, past the image)
+		float Y = 0.0f;
+		if (real)
+			Y = mt_luma(v.in[i]);
+		const bool valid = real && mt_valid(Y);
+		const uint32_t bin = mt_bin(Y);
+		excl += (uint32_t)__popcll(__ballot(real && !valid));
+		const unsigned long long m = __ballot(valid);
+		if (m != 0ull)
+		{
+			const uint32_t lead = (uint32_t)__shfl((int)bin, __ffsll((long long)m) - 1, 64); // the first valid lane's bin
+			if (__ballot(valid && bin != lead) == 0ull)
+			{
+				if ((threadIdx.x & 63u) == 0u)
+					atomicAdd(&s_hist[wave][lead], (uint32_t)__popcll(m));
+			}
+			else if (valid)
+				atomicAdd(&s_hist[wave][bin], 1u);
+		}
+	}
+	if ((threadIdx.x & 63u) == 0u)
+		s_excl[wave] = excl;
+	__syncthreads();
+	uint32_t *rec = v.partial + (size_t)blockIdx.x * MT_RECORD;
+	static_assert(BLOCK == (int)MT_BINS, "thread t stores bin t");
+	uint32_t n = 0u;
+	for (uint32_t w = 0; w < BLOCK / 64; w++)
+		n += s_hist[w][threadIdx.x];
+	rec[threadIdx.x] = n;
+	if (threadIdx.x == 0u)
+	{
+		uint32_t e = 0u;
+		for (uint32_t w = 0; w < BLOCK / 64; w++)
+			e += s_excl[w];
+		rec[MT_BINS] = e;
+	}
+}
+// one workgroup of MT_FOLD x 64 threads.  Lane `col` of wave q adds the bins 4 col .. 4 col + 3 (one 16-byte load: a wave reads a
+// record's 1 KiB of bins at once) of the records q, q + MT_FOLD, .. in two independent chains; thread b adds the MT_FOLD partial
+// sums of bin b (integers: any order gives the same words); the excluded words go through a butterfly per wave.  Then metering.h's
+// fixed shape with bin b on thread b: an integer prefix sum through LDS, the weight and the term of the bin, the two sums over
+// the tree x_b += x_{b+s}, and thread 0 takes the step (mt_step)
+constexpr uint32_t MT_FOLD = 16u, MT_REDUCE_THREADS = MT_FOLD * 64u;
+static_assert(MT_BINS == 4u * 64u, "a wave's lanes cover a record's bins with one uint4 each");
+__global__ void __launch_bounds__(MT_REDUCE_THREADS) k_meter_reduce(const uint32_t *partial, uint32_t records, uint32_t *hist, const MeterParams m,
+																  MeterRecord *rec)
+{
+	__shared__ uint32_t s_part[MT_FOLD][MT_BINS];
+	__shared__ uint32_t s_scan[2][MT_BINS];
+	__shared__ uint32_t s_excl[MT_FOLD];
+	__shared__ double s_num[MT_BINS], s_den[MT_BINS];
+	const uint32_t t = threadIdx.x, col = t & 63u, q = t >> 6;
+	uint4 a = make_uint4(0u, 0u, 0u, 0u), c = a;
+	uint32_t r = q;
+#pragma unroll 4
+	for (; r + MT_FOLD < records; r += 2u * MT_FOLD)
+	{
+		const uint4 x = *(const uint4 *)(partial + (size_t)r * MT_RECORD + 4u * col);
+		const uint4 y = *(const uint4 *)(partial + (size_t)(r + MT_FOLD) * MT_RECORD + 4u * col);
+		a.x += x.x, a.y += x.y, a.z += x.z, a.w += x.w;
+		c.x += y.x, c.y += y.y, c.z += y.z, c.w += y.w;
+	}
+	if (r < records)
+	{
+		const uint4 x = *(const uint4 *)(partial + (size_t)r * MT_RECORD + 4u * col);
+		a.x += x.x, a.y += x.y, a.z += x.z, a.w += x.w;
+	}
+	s_part[q][4u * col] = a.x + c.x, s_part[q][4u * col + 1u] = a.y + c.y, s_part[q][4u * col + 2u] = a.z + c.z, s_part[q][4u * col + 3u] = a.w + c.w;
+	uint32_t e = 0u;
+	for (uint32_t k = t; k < records; k += MT_REDUCE_THREADS)
+		e += partial[(size_t)k * MT_RECORD + MT_BINS];
+	for (int k = 32; k >= 1; k >>= 1)
+		e += (uint32_t)__shfl_xor((int)e, k, 64);
+	if (col == 0u)
+		s_excl[q] = e;
+	__syncthreads();
+	uint32_t h = 0u;
+	if (t < MT_BINS)
+	{
+		for (uint32_t k = 0; k < MT_FOLD; k++)
+			h += s_part[k][t];
+		hist[t] = h, s_scan[0][t] = h;
+	}
+	__syncthreads();
+	uint32_t cur = 0u; // inclusive prefix sums, ping-pong: log2(MT_BINS) = 8 rounds end in s_scan[0]
+	for (uint32_t d = 1u; d < MT_BINS; d <<= 1)
+	{
+		if (t < MT_BINS)
+			s_scan[cur ^ 1u][t] = s_scan[cur][t] + (t >= d ? s_scan[cur][t - d] : 0u);
+		__syncthreads();
+		cur ^= 1u;
+	}
+	if (t < MT_BINS)
+	{
+		const uint32_t C1 = s_scan[cur][t], N = s_scan[cur][MT_BINS - 1u];
+		const double w = mt_weight(C1 - h, C1, N, m);
+		s_den[t] = w, s_num[t] = mt_term(w, t);
+	}
+	__syncthreads();
+	for (uint32_t s = MT_BINS / 2u; s >= 1u; s >>= 1)
+	{
+		if (t < s)
+			s_num[t] += s_num[t + s], s_den[t] += s_den[t + s];
+		__syncthreads();
+	}
+	if (t == 0u)
+	{
+		uint32_t excl = 0u;
+		for (uint32_t k = 0; k < MT_FOLD; k++)
+			excl += s_excl[k];
+		hist[MT_BINS] = excl;
+		mt_step(s_scan[cur][MT_BINS - 1u], excl, s_num[0], s_den[0], m, rec);
+	}
+}
+uint32_t meter_records(uint32_t pixels) { return (uint32_t)(((size_t)pixels + MT_RANGE - 1u) / MT_RANGE); }
+void launch_meter_hist(const MeterView &v, stream_t s)
+{
+	if (v.pixels)
+		hipLaunchKernelGGL(k_meter_hist, dim3(meter_records(v.pixels)), dim3(BLOCK), 0, (hipStream_t)s, v);
+}
+void launch_meter_reduce(const uint32_t *partial, uint32_t records, uint32_t *hist, const MeterParams &m, MeterRecord *rec, stream_t s)
+{
+	hipLaunchKernelGGL(k_meter_reduce, dim3(1), dim3(MT_REDUCE_THREADS), 0, (hipStream_t)s, partial, records, hist, m, rec);
 }
 
 // ---- noise estimate (noise.h).  k_noise_tiles: a workgroup is one 32 x 8 tile, thread t its pixel (t & 31, t >> 5): a wave reads

@@ -569,12 +569,62 @@ void launch_display(const DisplayView &v, stream_t s)
 				dp_item<false>(v, fetch, (int)x, (int)y, a);
 		}
 }
+void launch_display_exposed(const DisplayView &v, const ExposureView &e, stream_t s)
+{
+	EMU_DEFER(s, launch_display_exposed(v, e, s));
+	const float E = e.rec->E;
+	const auto fetch = [&](int xi, int yi) -> f3 {
+		const f4 c = v.in[(size_t)yi * v.W + (size_t)xi];
+		return dp_tone(v, mk4(c.x * E, c.y * E, c.z * E, c.w));
+	};
+	for (uint32_t y = 0; y < v.H; y++)
+		for (uint32_t x = 0; x < v.W; x++)
+		{
+			const float a = v.in[(size_t)y * v.W + x].w;
+			if (v.fxaa)
+				dp_item<true>(v, fetch, (int)x, (int)y, a);
+			else
+				dp_item<false>(v, fetch, (int)x, (int)y, a);
+		}
+}
+// the exposure meter (metering.h): the same partial records, range by range, and the same fold
+uint32_t meter_records(uint32_t pixels) { return (uint32_t)(((size_t)pixels + MT_RANGE - 1u) / MT_RANGE); }
+void launch_meter_hist(const MeterView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_meter_hist(v, s));
+	for (uint32_t g = 0; g < meter_records(v.pixels); g++)
+	{
+		uint32_t *rec = v.partial + (size_t)g * MT_RECORD;
+		for (uint32_t b = 0; b < MT_RECORD; b++)
+			rec[b] = 0u;
+		for (size_t i = (size_t)g * MT_RANGE; i < (size_t)(g + 1u) * MT_RANGE && i < v.pixels; i++)
+		{
+			const float Y = mt_luma(v.in[i]);
+			rec[mt_valid(Y) ? mt_bin(Y) : MT_BINS]++;
+		}
+	}
+}
+void launch_meter_reduce(const uint32_t *partial, uint32_t records, uint32_t *hist, const MeterParams &m, MeterRecord *rec, stream_t s)
+{
+	EMU_DEFER(s, launch_meter_reduce(partial, records, hist, m, rec, s));
+	for (uint32_t b = 0; b < MT_RECORD; b++)
+	{
+		uint32_t n = 0u;
+		for (uint32_t r = 0; r < records; r++)
+			n += partial[(size_t)r * MT_RECORD + b];
+		hist[b] = n;
+	}
+	mt_finish(hist, hist[MT_BINS], m, rec);
+}
 void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
 	EMU_DEFER(s, launch_kat(p, sky, lt, function, in, out, n, s));
 	float pot[POT_SLOTS];
 	for (uint32_t i = 0; i < n; i++)
-		kat_item<true>(p, sky, lt, function, in, out, i, pot);
+		if (function == KAT_METER_BIN)
+			mt_kat_item(in, out, i);
+		else
+			kat_item<true>(p, sky, lt, function, in, out, i, pot);
 }
 void launch_skin_vertices(f4 *verts, f4 *vnormals, const f4 *base_verts, const f4 *base_normals, const uint32_t *joints4,
 						  const f4 *weights4, const float *mats, uint32_t joint_count, uint32_t vertex_count, stream_t s)

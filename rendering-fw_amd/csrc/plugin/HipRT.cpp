@@ -20,6 +20,12 @@
 // tone-maps again on top of whatever the backend delivers (system.cpp:682-711).  Headless hosts read the bytes with
 // hiprtReadDisplay.
 //
+// Exposure: RFWHIP_EXPOSURE=auto|manual beside RFWHIP_DISPLAY (unset by default: nothing changes) sets display_exposure — with
+// auto every presented display image is metered on the device behind the gather and shown with the adapted exposure (include/rfwhip.h,
+// rfwhip_get_meter: one step per present, nothing read back, frames in flight stay in flight); RFWHIP_EXPOSURE_SPEED (optional) is
+// display_exposure_speed.  A host reads the meter's record with hiprtGetExposure: with frames in flight it is the newest
+// frame's, not the one render_frame handed out.
+//
 // Noise estimate: RFWHIP_NOISE=1 (unset by default: nothing changes) turns the setting noise_estimate on (include/rfwhip.h,
 // rfwhip_get_noise); a host asks hiprtGetNoise when to stop converging.  It answers for the accumulator — with frames in flight,
 // for the newest frame enqueued, not the one render_frame handed out.
@@ -94,6 +100,15 @@ class Context final : public rfw::RenderContext
 			m_Display = true;
 			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_tonemap", mode.c_str()));
 		}
+		if (const char *x = std::getenv("RFWHIP_EXPOSURE"))
+		{
+			const std::string mode = x;
+			if (mode != "auto" && mode != "manual")
+				throw std::runtime_error("HipRT: RFWHIP_EXPOSURE must be \"auto\" or \"manual\"");
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_exposure", mode.c_str()));
+		}
+		if (const char *sp = std::getenv("RFWHIP_EXPOSURE_SPEED"))
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_exposure_speed", sp));
 		if (const char *nz = std::getenv("RFWHIP_NOISE"))
 		{
 			if (std::string(nz) != "0" && std::string(nz) != "1")
@@ -256,6 +271,8 @@ class Context final : public rfw::RenderContext
 
 	// the noise of the accumulated image (RFWHIP_NOISE=1; else RFWHIP_ERR_STATE)
 	int get_noise(rfwhip_noise_stats *stats) { return rfwhip_group_get_noise(m_Group, stats); }
+	// the exposure meter's record (RFWHIP_EXPOSURE=auto; else exposure 1 and no steps)
+	int get_exposure(rfwhip_meter_stats *stats) { return rfwhip_group_get_meter(m_Group, stats); }
 
 	void set_materials(const std::vector<rfw::DeviceMaterial> &materials,
 					   const std::vector<rfw::MaterialTexIds> &texDescriptors) override
@@ -422,4 +439,10 @@ HIPRT_EXPORT int hiprtReadDisplay(rfw::RenderContext *ptr, uint8_t *rgba8)
 HIPRT_EXPORT int hiprtGetNoise(rfw::RenderContext *ptr, rfwhip_noise_stats *stats)
 {
 	return static_cast<Context *>(ptr)->get_noise(stats);
+}
+// ... and how the display image is exposed (the exposure meter, include/rfwhip.h rfwhip_get_meter): the record of the newest frame
+// presented — exposure, its log2, the target, the metered luminance, valid / excluded pixels and the steps taken
+HIPRT_EXPORT int hiprtGetExposure(rfw::RenderContext *ptr, rfwhip_meter_stats *stats)
+{
+	return static_cast<Context *>(ptr)->get_exposure(stats);
 }

@@ -208,7 +208,9 @@ enum KernelFamily
 	KF_DENOISE = 6, // the denoiser of the presented image: guide pass + filter (denoise.h)
 	KF_DISPLAY = 7, // the display stage: tone map + FXAA + encoding (display.h), one launch per displayed image
 	KF_NOISE = 8,	// the noise metric: k_noise_tiles + k_noise_final (noise.h), two launches per query
-	KF_COUNT = 9
+	KF_METER_HIST = 9,	 // the exposure meter's histogram pass k_meter_hist (metering.h), one launch per step
+	KF_METER_REDUCE = 10, // ... and its one-workgroup reduce k_meter_reduce, one launch per step
+	KF_COUNT = 11
 };
 
 struct TimedSpan
@@ -367,6 +369,18 @@ struct rfwhip_context
 	// the display stage (display.h): tone map 0 aces | 1 none, FXAA, sRGB encoding; d_display: where the host reads land
 	int display_tonemap = 0, display_fxaa = 1, display_srgb = 0;
 	DevBuf d_display;
+	// the exposure meter (metering.h): the display_exposure* settings; d_meter_rec = the 32-byte record (allocated, with steps = 0 and
+	// E = 1, by the first call that needs it), d_meter_hist = the summed histogram, d_meter_part = the partial records of one pass
+	int exposure_auto = 0; // display_exposure: 0 manual, 1 auto
+	float exposure_ev = 0.0f, exposure_key = 0.18f, exposure_low = 0.1f, exposure_high = 0.9f, exposure_speed = 1.0f;
+	float exposure_min_ev = -16.0f, exposure_max_ev = 16.0f;
+	DevBuf d_meter_rec, d_meter_hist, d_meter_part;
+	bool meter_have = false;			   // rfwhip_read_display* has metered frame meter_serial under the settings as they stand
+	unsigned long long meter_serial = 0;
+	bool meter_manual_stale = true;		   // manual mode: the record's E is not (yet) exp2(display_exposure_ev)
+	float meter_manual_E = 1.0f;		   // ... the value the next exposed display uploads (kept here: the copy's source)
+	dm::event_t ev_meter;				   // behind the last step enqueued on a caller's stream (rfwhip_display_stream)
+	bool ev_meter_ready = false, meter_pending = false;
 	// the noise estimate (noise.h): d_noise = two moments per local pixel, allocated while noise_estimate is on.  noise_live: the
 	// moments cover every sample of the accumulator (the setting was on at the last RESET / rfwhip_init and ever since)
 	int noise_estimate = 0;
@@ -423,8 +437,8 @@ struct rfwhip_context
 	std::vector<TimedSpan> spans;
 	std::vector<dm::event_t> event_pool;
 	size_t events_used = 0;
-	float kernel_ms[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-	uint32_t kernel_launches[KF_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+	float kernel_ms[KF_COUNT] = {};
+	uint32_t kernel_launches[KF_COUNT] = {};
 	rfwhip_render_stats stats;
 	std::chrono::steady_clock::time_point render_t0;
 	bool render_pending = false;
@@ -599,11 +613,15 @@ static void free_all(rfwhip_context *c)
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
 					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
+					  &c->d_meter_rec, &c->d_meter_hist, &c->d_meter_part,
 					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in,
 					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask, &c->d_lf_inst, &c->d_lf_bound, &c->d_lf_count, &c->d_lt_touched};
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->noise_live = false, c->adaptive_live = false;
+	c->meter_have = false, c->meter_manual_stale = true, c->meter_pending = false;
+	if (c->ev_meter_ready)
+		dm::event_destroy(c->ev_meter), c->ev_meter_ready = false;
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->dn_inst_ver_stale = true;
@@ -2214,6 +2232,11 @@ static int sync_all(rfwhip_context *c)
 		RF_TRY(dm::event_sync(c->ev_dn));
 		c->dn_pending = false;
 	}
+	if (c->meter_pending) // (a meter step on a caller's stream writes the record and the histogram)
+	{
+		RF_TRY(dm::event_sync(c->ev_meter));
+		c->meter_pending = false;
+	}
 	return 0;
 }
 
@@ -3161,16 +3184,119 @@ static int display_check_format(const char *who, int format)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: unknown display format %d", who, format);
 	return RFWHIP_OK;
 }
-// one launch on `stream`: the full W x H float4 image `in` -> `out` in `format`, with the context's display settings
-static int display_enqueue(rfwhip_context *c, const f4 *in, void *out, float brightness, float contrast, int format, void *stream)
+// ---- exposure meter (settings "display_exposure*"; work items: metering.h) ------------------------------------------------------
+static_assert(sizeof(rfwhip_meter_stats) == sizeof(rtk::MeterRecord) && sizeof(rtk::MeterRecord) == 32, "rfwhip.h: the meter's record is the kernels' (kernels.h)");
+static_assert(RFWHIP_METER_BINS == (int)rtk::MT_BINS, "rfwhip.h restates the histogram's size");
+static const rtk::MeterRecord k_meter_fresh = {1.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u, 0u}; // before any step: E = 1, steps = 0
+// the record and the summed histogram (a fresh record the first time) and room for the partial records of `pixels` pixels
+static int meter_ensure(rfwhip_context *c, size_t pixels)
+{
+	if (!c->d_meter_rec.p)
+	{
+		RF_TRY(c->d_meter_rec.ensure(sizeof(rtk::MeterRecord)));
+		RF_TRY(c->d_meter_hist.ensure(rtk::MT_RECORD * sizeof(uint32_t)));
+		RF_TRY(dm::h2d(c->d_meter_rec.p, &k_meter_fresh, sizeof(k_meter_fresh), c->stream));
+		RF_TRY(dm::zero(c->d_meter_hist.p, rtk::MT_RECORD * sizeof(uint32_t), c->stream));
+		RF_TRY(dm::sync(c->stream));
+		c->meter_manual_stale = true;
+	}
+	const size_t need = (size_t)std::max(1u, rtk::meter_records((uint32_t)pixels)) * rtk::MT_RECORD * sizeof(uint32_t);
+	if (need > c->d_meter_part.cap)
+	{
+		RF_TRY(sync_all(c)); // (a step in flight writes the records this reallocates)
+		RF_TRY(c->d_meter_part.ensure(need));
+	}
+	return 0;
+}
+static rtk::MeterParams meter_params(const rfwhip_context *c)
+{
+	rtk::MeterParams m;
+	m.low = (double)c->exposure_low, m.high = (double)c->exposure_high;
+	m.log2_key = (float)log2((double)c->exposure_key);
+	m.ev = c->exposure_ev, m.ev_min = c->exposure_min_ev, m.ev_max = c->exposure_max_ev, m.speed = c->exposure_speed, m.pad = 0u;
+	return m;
+}
+// behind work on the record enqueued on `stream`: a caller's stream is remembered by an event (rfwhip_get_meter, sync_all)
+static int meter_mark(rfwhip_context *c, void *stream)
+{
+	if (stream == c->stream)
+		return 0;
+	if (!c->ev_meter_ready)
+	{
+		RF_TRY(dm::event_create(&c->ev_meter, false));
+		c->ev_meter_ready = true;
+	}
+	RF_TRY(dm::event_record(c->ev_meter, stream));
+	c->meter_pending = true;
+	return 0;
+}
+// the reduce on `records` partial records in d_meter_part, enqueued on `stream`
+static int meter_reduce(rfwhip_context *c, uint32_t records, void *stream)
+{
+	StageTimer t(c, KF_METER_REDUCE, -1, stream);
+	rtk::launch_meter_reduce(c->d_meter_part.as<uint32_t>(), records, c->d_meter_hist.as<uint32_t>(), meter_params(c),
+							 c->d_meter_rec.as<rtk::MeterRecord>(), stream);
+	t.stop(1);
+	RF_TRY(dm::last_launch_error());
+	c->meter_manual_stale = true; // (a step writes E)
+	c->meter_have = false;		  // (... and the record is this image's: rfwhip_read_display* claims it for its frame)
+	return meter_mark(c, stream);
+}
+// ONE STEP on the full W x H image `img`, enqueued on `stream`: two launches, nothing comes back to the host
+static int meter_step(rfwhip_context *c, const f4 *img, void *stream)
+{
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(meter_ensure(c, px));
+	rtk::MeterView v;
+	v.in = img, v.pixels = (uint32_t)px, v.partial = c->d_meter_part.as<uint32_t>();
+	{
+		StageTimer t(c, KF_METER_HIST, -1, stream);
+		rtk::launch_meter_hist(v, stream);
+		t.stop(1);
+	}
+	RF_TRY(dm::last_launch_error());
+	return meter_reduce(c, rtk::meter_records(v.pixels), stream);
+}
+
+// one launch on `stream`: the full W x H float4 image `in` -> `out` in `format`, with the context's display settings.
+// display_exposure = auto: the exposed kernel with the record's E — `step`: behind one step of the meter on `in`;
+// manual with display_exposure_ev != 0: the exposed kernel with E = exp2(ev), written into the record when it is not there yet;
+// manual, ev = 0: k_display, as without the meter
+static int display_enqueue(rfwhip_context *c, const f4 *in, void *out, float brightness, float contrast, int format, void *stream, bool step)
 {
 	rtk::DisplayView v;
 	v.W = c->W, v.H = c->H, v.in = in, v.out = out;
 	v.brightness = brightness, v.contrast = contrast;
 	v.tonemap = (uint32_t)c->display_tonemap, v.fxaa = (uint32_t)c->display_fxaa, v.srgb = (uint32_t)c->display_srgb;
 	v.format = (uint32_t)format;
+	const bool exposed = c->exposure_auto || c->exposure_ev != 0.0f;
+	if (c->exposure_auto)
+	{
+		if (step)
+			RF_TRY(meter_step(c, in, stream));
+		else
+			RF_TRY(meter_ensure(c, 0));
+	}
+	else if (exposed)
+	{
+		RF_TRY(meter_ensure(c, 0));
+		if (c->meter_manual_stale)
+		{
+			c->meter_manual_E = exp2f(c->exposure_ev);
+			RF_TRY(dm::h2d(c->d_meter_rec.p, &c->meter_manual_E, sizeof(float), stream)); // (E is the record's first word)
+			RF_TRY(meter_mark(c, stream));
+			c->meter_manual_stale = false;
+		}
+	}
 	StageTimer t(c, KF_DISPLAY, -1, stream);
-	rtk::launch_display(v, stream);
+	if (exposed)
+	{
+		rtk::ExposureView e;
+		e.rec = c->d_meter_rec.as<rtk::MeterRecord>();
+		rtk::launch_display_exposed(v, e, stream);
+	}
+	else
+		rtk::launch_display(v, stream);
 	t.stop(1);
 	return dm::last_launch_error();
 }
@@ -3194,7 +3320,7 @@ extern "C" int rfwhip_display_stream(rfwhip_context *c, const void *rgba_device,
 		return set_error(RFWHIP_ERR_STATE, "no render target");
 	float b, k;
 	display_camera(c, b, k);
-	return display_enqueue(c, (const f4 *)rgba_device, out_device, b, k, format, hip_stream);
+	return display_enqueue(c, (const f4 *)rgba_device, out_device, b, k, format, hip_stream, true); // (auto: every call is a step)
 }
 
 extern "C" int rfwhip_read_display_device(rfwhip_context *c, int format, void *out_device)
@@ -3215,7 +3341,11 @@ extern "C" int rfwhip_read_display_device(rfwhip_context *c, int format, void *o
 	RF_TRY(rfwhip_read_framebuffer_device(c, c->d_present.p));
 	float b, k;
 	display_camera(c, b, k);
-	RF_TRY(display_enqueue(c, c->d_present.as<f4>(), out_device, b, k, format, c->stream));
+	// auto exposure: one step per render call — a further read of the same frame under the same settings shows it with the same E
+	const bool step = c->exposure_auto && (!c->meter_have || c->meter_serial != c->frame_serial);
+	RF_TRY(display_enqueue(c, c->d_present.as<f4>(), out_device, b, k, format, c->stream, step));
+	if (step)
+		c->meter_have = true, c->meter_serial = c->frame_serial;
 	return dm::sync(c->stream);
 }
 
@@ -3244,9 +3374,97 @@ extern "C" int rfwhip_display_image(rfwhip_context *c, const float *rgba_in, flo
 	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
 	RF_TRY(c->d_display.ensure(px * display_pixel_bytes(format)));
 	RF_TRY(dm::h2d(c->d_present.p, rgba_in, px * sizeof(f4), c->stream));
-	RF_TRY(display_enqueue(c, c->d_present.as<f4>(), c->d_display.p, brightness, contrast, format, c->stream));
+	RF_TRY(display_enqueue(c, c->d_present.as<f4>(), c->d_display.p, brightness, contrast, format, c->stream, true));
 	RF_TRY(dm::d2h(out_host, c->d_display.p, px * display_pixel_bytes(format), c->stream));
 	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_get_meter(rfwhip_context *c, rfwhip_meter_stats *stats)
+{
+	CTX_ENTER(c);
+	if (!stats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_get_meter: null stats");
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	RF_TRY(sync_all(c));
+	RF_TRY(meter_ensure(c, 0));
+	return dm::d2h(stats, c->d_meter_rec.p, sizeof(*stats), c->stream);
+}
+
+extern "C" int rfwhip_read_meter_histogram(rfwhip_context *c, uint32_t *bins, uint32_t *excluded)
+{
+	CTX_ENTER(c);
+	if (!bins)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_meter_histogram: null bins");
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	RF_TRY(sync_all(c));
+	RF_TRY(meter_ensure(c, 0));
+	uint32_t h[rtk::MT_RECORD];
+	RF_TRY(dm::d2h(h, c->d_meter_hist.p, sizeof(h), c->stream));
+	memcpy(bins, h, rtk::MT_BINS * sizeof(uint32_t));
+	if (excluded)
+		*excluded = h[rtk::MT_BINS];
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_meter_reset(rfwhip_context *c)
+{
+	CTX_ENTER(c);
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	RF_TRY(sync_all(c));
+	RF_TRY(meter_ensure(c, 0));
+	RF_TRY(dm::h2d(c->d_meter_rec.p, &k_meter_fresh, sizeof(k_meter_fresh), c->stream));
+	RF_TRY(dm::zero(c->d_meter_hist.p, rtk::MT_RECORD * sizeof(uint32_t), c->stream));
+	c->meter_have = false, c->meter_manual_stale = true;
+	return dm::sync(c->stream);
+}
+
+// the record and, where asked for, the histogram, after the step(s) enqueued on the context's stream
+static int meter_answer(rfwhip_context *c, rfwhip_meter_stats *stats, uint32_t *bins)
+{
+	RF_TRY(dm::d2h(stats, c->d_meter_rec.p, sizeof(*stats), c->stream));
+	if (bins)
+		RF_TRY(dm::d2h(bins, c->d_meter_hist.p, rtk::MT_BINS * sizeof(uint32_t), c->stream));
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_meter_image(rfwhip_context *c, const float *rgba_in, rfwhip_meter_stats *stats, uint32_t *bins)
+{
+	CTX_ENTER(c);
+	if (!rgba_in || !stats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_meter_image: null image or stats");
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	RF_TRY(sync_all(c));
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
+	RF_TRY(dm::h2d(c->d_present.p, rgba_in, px * sizeof(f4), c->stream));
+	RF_TRY(meter_step(c, c->d_present.as<f4>(), c->stream));
+	return meter_answer(c, stats, bins);
+}
+
+extern "C" int rfwhip_meter_histogram(rfwhip_context *c, const uint32_t *bins, uint32_t excluded, rfwhip_meter_stats *stats)
+{
+	CTX_ENTER(c);
+	if (!bins || !stats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_meter_histogram: null bins or stats");
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	unsigned long long total = 0;
+	for (uint32_t b = 0; b < rtk::MT_BINS; b++)
+		total += bins[b];
+	if (total > 0xFFFFFFFFull)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_meter_histogram: the counts add up to %llu, more than 2^32 - 1", total);
+	RF_TRY(sync_all(c));
+	RF_TRY(meter_ensure(c, 0));
+	uint32_t h[rtk::MT_RECORD] = {};
+	memcpy(h, bins, rtk::MT_BINS * sizeof(uint32_t));
+	h[rtk::MT_BINS] = excluded;
+	RF_TRY(dm::h2d(c->d_meter_part.p, h, sizeof(h), c->stream)); // (posed as the one partial record of a pass)
+	RF_TRY(meter_reduce(c, 1u, c->stream));
+	return meter_answer(c, stats, nullptr);
 }
 
 // ---- noise estimate (settings "noise_*"; work items: noise.h) -----------------------------------------------------------------------
@@ -3688,6 +3906,25 @@ static int set_denoise_stage(rfwhip_context *c, int &stage, const char *key, con
 	stage = on;
 	return RFWHIP_OK;
 }
+// display_exposure*: the record's E (manual mode) and the frame rfwhip_read_display* metered are those of the old settings
+static int exposure_changed(rfwhip_context *c)
+{
+	c->meter_have = false, c->meter_manual_stale = true;
+	return RFWHIP_OK;
+}
+// one end of an ordered pair (display_exposure_low < _high in [0, 1]; _min_ev <= _max_ev in [-64, 64]): a value that breaks the
+// range or the order is refused and both ends keep their values
+static int set_exposure_pair(rfwhip_context *c, float &lo, float &hi, bool set_lo, const char *key, const char *value, const char *must)
+{
+	const bool window = &lo == &c->exposure_low;
+	float f = 0.0f;
+	RF_TRY(set_float(f, key, value, [](float x) { return x >= -64.0f && x <= 64.0f; }, must, false));
+	const float nlo = set_lo ? f : lo, nhi = set_lo ? hi : f;
+	if (window ? !(f >= 0.0f && f <= 1.0f && nlo < nhi) : !(nlo <= nhi))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must %s", key, must);
+	lo = nlo, hi = nhi;
+	return exposure_changed(c);
+}
 static int put(char *out, size_t cap, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 static int put(char *out, size_t cap, const char *fmt, ...)
 {
@@ -3836,6 +4073,32 @@ static const Setting k_settings[] = {
 		 c->display_srgb = on;
 		 return RFWHIP_OK; },
 	 GET_INT(display_srgb), false},
+	// the exposure meter (metering.h): how rfwhip_read_display* / rfwhip_display_* expose the image they show.
+	// A change of any of them makes the next read of the same frame meter it again
+	{"display_exposure", SET {
+		 RF_TRY(set_enum2(c->exposure_auto, key, value, "manual", "auto"));
+		 return exposure_changed(c); },
+	 GET { return put(out, cap, "%s", c->exposure_auto ? "auto" : "manual"); }, false},
+	{"display_exposure_ev", SET {
+		 RF_TRY(set_float(c->exposure_ev, key, value, [](float f) { return f >= -32.0f && f <= 32.0f; }, "be a finite number in [-32, 32]", false));
+		 return exposure_changed(c); },
+	 GET { return put(out, cap, "%g", c->exposure_ev); }, false},
+	{"display_exposure_key", SET {
+		 RF_TRY(set_float(c->exposure_key, key, value, [](float f) { return f > 0.0f && f < 1e30f; }, "be a finite number > 0", false));
+		 return exposure_changed(c); },
+	 GET { return put(out, cap, "%g", c->exposure_key); }, false},
+	{"display_exposure_low", SET { return set_exposure_pair(c, c->exposure_low, c->exposure_high, true, key, value, "be in [0, 1] and below display_exposure_high"); },
+	 GET { return put(out, cap, "%g", c->exposure_low); }, false},
+	{"display_exposure_high", SET { return set_exposure_pair(c, c->exposure_low, c->exposure_high, false, key, value, "be in [0, 1] and above display_exposure_low"); },
+	 GET { return put(out, cap, "%g", c->exposure_high); }, false},
+	{"display_exposure_speed", SET {
+		 RF_TRY(set_float(c->exposure_speed, key, value, [](float f) { return f > 0.0f && f <= 1.0f; }, "be in (0, 1]", false));
+		 return exposure_changed(c); },
+	 GET { return put(out, cap, "%g", c->exposure_speed); }, false},
+	{"display_exposure_min_ev", SET { return set_exposure_pair(c, c->exposure_min_ev, c->exposure_max_ev, true, key, value, "be a finite number in [-64, 64], at most display_exposure_max_ev"); },
+	 GET { return put(out, cap, "%g", c->exposure_min_ev); }, false},
+	{"display_exposure_max_ev", SET { return set_exposure_pair(c, c->exposure_min_ev, c->exposure_max_ev, false, key, value, "be a finite number in [-64, 64], at least display_exposure_min_ev"); },
+	 GET { return put(out, cap, "%g", c->exposure_max_ev); }, false},
 	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
 	{"noise_estimate", SET {
 		 bool on;
@@ -3990,6 +4253,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)
@@ -4449,6 +4713,7 @@ static_assert(sizeof(rfwhip_area_light) == sizeof(rt::AreaLight) && sizeof(rfwhi
 				  sizeof(rfwhip_spot_light) == sizeof(rt::SpotLight),
 			  "rfwhip_set_lights hands its arrays to the light tree's builder as the kernels' records");
 static_assert(RFWHIP_KAT_LT_SAMPLE == rtk::KAT_LT_SAMPLE && RFWHIP_KAT_LT_PICK_PROB == rtk::KAT_LT_PICK_PROB, "kernels.h restates the light-tree functions");
+static_assert(RFWHIP_KAT_METER_BIN == rtk::KAT_METER_BIN, "kernels.h restates the meter's function");
 static_assert(RFWHIP_KAT_IN == 24 && RFWHIP_KAT_OUT == 8, "kat_item's record layout (kernels.hip)");
 static_assert(RFWHIP_STRIP_ROWS == (int)rt::STRIP_ROWS, "rfwhip.h: rfwhip_row_owner() restates rt::strip_owner()");
 static_assert(sizeof(rfwhip_adaptive_stats) == 48, "rfwhip.h: six uint64");
@@ -4459,7 +4724,7 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 	CTX_ENTER(c);
 	if (n && (!in || !out))
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: null records");
-	if (function < 0 || function > RFWHIP_KAT_LT_PICK_PROB)
+	if (function < 0 || function > RFWHIP_KAT_METER_BIN)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: unknown function %d", function);
 	if ((function == RFWHIP_KAT_POINT_ON_LIGHT || function == RFWHIP_KAT_LIGHT_PICK_PROB) && c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the light functions use the lights of the last rfwhip_update()");

@@ -729,6 +729,16 @@ extern "C" int rfwhip_group_get_noise(rfwhip_group *g, rfwhip_noise_stats *stats
 	return RFWHIP_OK;
 }
 
+extern "C" int rfwhip_group_get_meter(rfwhip_group *g, rfwhip_meter_stats *stats)
+{
+	if (!g || !stats)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null argument");
+	if (g->root_local < 0)
+		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "rfwhip_group_get_meter: the root is not in this group");
+	// the root's context waits for the steps enqueued on the gather stream (its record of them is an event)
+	return rfwhip_get_meter(g->ep[(size_t)g->root_local].ctx, stats);
+}
+
 extern "C" int rfwhip_group_get_adaptive(rfwhip_group *g, rfwhip_adaptive_stats *stats)
 {
 	if (!g || !stats)
