@@ -665,7 +665,11 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * guide rays + depth gradient; a filter is 1 + denoise_iterations launches: demodulation / variance, then the a-trous passes),
  * 7 display (one launch per displayed image), 8 noise (the metric: two launches per query; the moments are part of the resolve,
  * family 4), 9 the exposure meter's histogram pass k_meter_hist and 10 its reduce k_meter_reduce (one launch each per step; the
- * exposed display kernels count as family 7). */
+ * exposed display kernels count as family 7), 11 the primary wave's ordering pass k_order4f: a pt render call whose primary wave
+ * runs in packet form and is large enough (or RFWHIP_PRIMARY_ORDER=1 in the environment when the context was created; =0: never)
+ * reads a second float node table whose nodes hold their children near to far as seen from the camera, rewritten in front of the
+ * call when the camera position or a tree has changed since — `launches` counts those passes, one per rewrite, with or without
+ * stage_timing; the image does not depend on it. */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

@@ -570,10 +570,11 @@ class CoreBinding:
     DISPLAY = 7  # ... and of the display stage (one launch per displayed image)
     NOISE = 8  # ... and of the noise metric (two launches per get_noise)
     METER_HIST, METER_REDUCE = 9, 10  # ... and of the exposure meter's two kernels (one launch each per step)
+    PRIMARY_ORDER = 11  # ... and of the primary wave's ordering pass (one count per rewrite of the camera-ordered node table)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 

@@ -173,8 +173,11 @@ void launch_init_counters(rt::WaveCounters *c, uint32_t primary_count, stream_t 
 void launch_set_ext_count(rt::WaveCounters *c, uint32_t depth, uint32_t count, stream_t s);
 void launch_rng_states(uint32_t *states, const uint32_t base_state[4], const uint32_t *jump_table,
 					   uint32_t packets_per_sample, uint32_t spp, stream_t s);
-void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s);
+// ordered (GEN_PT in packet form only): the camera-ordered copy of SceneView::nodes4f (launch_order4f) — the primary wave reads it
+// in place of nodes4f and takes every node's children as they come; null: the primary wave sorts them itself
+void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s, const rt::Node4f *ordered = nullptr);
 bool primary_packet_form(const Params &p, uint32_t max_items); // the pt primary wave of such a launch fills WaveView::hit0_done
+bool primary_packet_walk(const Params &p, uint32_t max_items); // ... and walks the tree once per wave (the emulation's does too)
 void launch_shade_parity(const Params &p, bool count, uint32_t max_items, stream_t s);
 uint32_t queue_pad(uint32_t max_items); // extra slots per queue and launch for the void entries of unfinished blocks
 // sky.pick > 0 (setting sky_sampling): the sky variant k_shade_pt_sky, which takes the table as an argument of its own (Params, and
@@ -199,7 +202,7 @@ void launch_noise_metric(const NoiseView &v, stream_t s);
 uint32_t noise_tiles_x(uint32_t W);
 // adaptive_sampling = 1 (adaptive.h).  The pt primary wave with the mask as an argument of its own (k_primary_packet_masked /
 // k_extend_masked: Params, and every other kernel's code, stay what they were), ...
-void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s);
+void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s, const rt::Node4f *ordered = nullptr);
 // ... k_resolve_adaptive (launch_resolve_noise for the pixels of active tiles, n_a per tile), k_present_adaptive (scale per tile), ...
 void launch_resolve_adaptive(const Params &p, float *moments, const AdaptiveView &a, stream_t s);
 void launch_present_adaptive(const Params &p, rt::f4 *out, const AdaptiveView &a, int full, stream_t s);
@@ -260,6 +263,9 @@ void launch_refresh4(rt::Node4c *nodes4, const uint32_t *src4, uint32_t count4, 
 constexpr uint32_t PACKET_STACK = 61;
 // every compressed node once more with float planes (rt::Node4f), for the packet traversal's scalar fetches
 void launch_expand4(const rt::Node4c *nodes4, rt::Node4f *out, uint32_t count4, stream_t s);
+// the primary wave's ordering pass (primary_order.h): nodes first .. first + count - 1 of `in` into the same nodes of `out`, their
+// children near to far as seen from `origin` (ordered = false: copied as they are)
+void launch_order4f(const rt::Node4f *in, rt::Node4f *out, uint32_t first, uint32_t count, const float origin[3], bool ordered, stream_t s);
 // BVH construction on the device (lbvh.hip), end to end in mesh-local arrays (node_base = tri_base = n4_base = 0):
 //   nodes / parents / flags   2 n entries   BVH2 in the reference's layout, device entries, one triangle per leaf
 //   nodes4 / src4             <= n / 4 n    the compressed 4-wide nodes the rays fetch, breadth-first, + their BVH2 sources

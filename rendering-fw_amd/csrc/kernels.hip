@@ -35,6 +35,10 @@
 
 #include <string.h>
 #include <algorithm>
+#if defined(RT_DEV_PACKET_COST) // (development: the emulation prints what the primary wave walks, kernels_emu.inc)
+#include <stdio.h>
+#include <stdlib.h>
+#endif
 
 using namespace rt;
 
@@ -935,6 +939,9 @@ RT_FN void expand4_item(const Node4c *nodes4, Node4f *out, uint32_t i)
 	out[i] = f;
 }
 
+// the primary wave's ordering pass: a node's children near to far as seen from the camera (the work item shared with the emulation)
+#include "primary_order.h"
+
 // refit, pass 1: rewrite the leaf-ordered triangle vertices from the new mesh vertices
 RT_FN void refit_tris_item(f4 *tri_verts, const f4 *verts, const uint32_t *indices, uint32_t slot)
 {
@@ -1534,7 +1541,10 @@ __device__ __forceinline__ uint32_t packet_key(float tk_lane, unsigned long long
 
 // ANY (round 6: the shadow rays of the primary vertices, sorted by light): occlusion query — hit.t holds the ray's length on entry, a
 // lane that finds a triangle inside (t_min, length) has hit.prim >= 0 and leaves the packet; the wave stops when none is left.
-template <bool COUNT, bool ANY = false>
+// ORDERED (closest hit only): sc.nodes4f is the camera-ordered table (primary_order.h) — every node's children stand near to far
+// as seen from where the wave's rays leave, and are taken as they come, like ANY's: no keys, no comparators, ref_lane unused.
+// The leaf phase is the closest-hit one, so every lane still finds ITS nearest hit whatever the order.
+template <bool COUNT, bool ANY = false, bool ORDERED = false>
 __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool active, const f3 O, const f3 D, const float t_min, Hit &hit, TStat &st)
 {
 	unsigned long long act = __ballot(active);
@@ -1544,6 +1554,8 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 	hit.t = active ? hit.t : -3.0e38f;
 	if (act == 0ull)
 		return;
+	static_assert(!(ANY && ORDERED), "the ordered table is the primary wave's");
+	constexpr bool ASIS = ANY || ORDERED; // the children are taken as they come
 	int ref_lane = __ffsll((long long)act) - 1;
 	PacketSpace sp;
 	const char *const nodes = (const char *)sc.nodes4f; // (the table stays below 4 GiB: 32-bit byte offsets)
@@ -1618,7 +1630,7 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 			// (ANY: an occlusion ray that reaches its light walks every node along it whatever the order, and most do — the children
 			// are taken as they come: no entry distances fetched from the reference lane, no comparators)
 			uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-			if (!ANY)
+			if (!ASIS)
 				k0 = packet_key(tk[0], m[0], ref_lane), k1 = packet_key(tk[1], m[1], ref_lane), k2 = packet_key(tk[2], m[2], ref_lane), k3 = packet_key(tk[3], m[3], ref_lane);
 			uint32_t e0 = ent[0], e1 = ent[1], e2 = ent[2], e3 = ent[3];
 #define RT_PSWAP(KA, EA, KB, EB)                          \
@@ -1628,7 +1640,7 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 		KB = sw ? KA : KB, EB = sw ? EA : EB;             \
 		KA = kl, EA = el;                                 \
 	}
-			if (!ANY)
+			if (!ASIS)
 			{
 				RT_PSWAP(k0, e0, k1, e1)
 				RT_PSWAP(k2, e2, k3, e3)
@@ -1638,11 +1650,11 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 			// (three of the five comparators: the nearest entered child first, the others in no particular order — all five measure
 			// the same, 5.18 against 4.93 ms per primary wave; (key, entry) as one 64-bit scalar each and s_cselect_b64: the compiler
 			// splits the selects again.)  The pop below reads what was just written
-			if (ANY)
+			if (ASIS)
 				stk.push3_masks(e3, m[3], e2, m[2], e1, m[1]);
 			else
 				stk.push3_keys(e3, k3, e2, k2, e1, k1);
-			if (ANY ? m[0] == 0ull : k0 == 0xFFFFFFFFu)
+			if (ASIS ? m[0] == 0ull : k0 == 0xFFFFFFFFu)
 				e0 = stk.pop();
 			cur = e0;
 		}
@@ -1730,10 +1742,20 @@ __device__ __forceinline__ const Params &fresh_params()
 	return *(const Params *)ka;
 }
 
+// Two instantiations of the body: k_primary_packet reads the camera-ordered table — p.sc.nodes4f is the ordered copy for this launch
+// (launch_extend, `ordered`) — and is what every large call runs; k_primary_packet_sorting sorts a node's children itself, per wave
+// and node step, for the calls that have no ordered table (small frames, RFWHIP_PRIMARY_ORDER=0).
 template <bool COUNT>
 __global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet(const Params p, const uint32_t count)
 {
-	constexpr bool MASKED = false;
+	constexpr bool MASKED = false, ORDERED = true;
+	const unsigned char *const mask = nullptr;
+#include "primary_packet_body.h"
+}
+template <bool COUNT>
+__global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet_sorting(const Params p, const uint32_t count)
+{
+	constexpr bool MASKED = false, ORDERED = false;
 	const unsigned char *const mask = nullptr;
 #include "primary_packet_body.h"
 }
@@ -1742,7 +1764,13 @@ __global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet
 template <bool COUNT>
 __global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet_masked(const Params p, const uint32_t count, const unsigned char *mask)
 {
-	constexpr bool MASKED = true;
+	constexpr bool MASKED = true, ORDERED = true;
+#include "primary_packet_body.h"
+}
+template <bool COUNT>
+__global__ void __launch_bounds__(TRACE_BLOCK, RT_PACKET_WAVES) k_primary_packet_masked_sorting(const Params p, const uint32_t count, const unsigned char *mask)
+{
+	constexpr bool MASKED = true, ORDERED = false;
 #include "primary_packet_body.h"
 }
 
@@ -2052,6 +2080,20 @@ void launch_expand4(const Node4c *nodes4, Node4f *out, uint32_t count4, stream_t
 		hipLaunchKernelGGL(k_expand4, dim3((count4 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, nodes4, out, count4);
 }
 
+// the ordering pass of the primary wave (primary_order.h): one streaming pass, a thread per node of the range
+__global__ void __launch_bounds__(BLOCK) k_order4f(const Node4f *in, Node4f *out, uint32_t first, uint32_t count, float cx, float cy, float cz, bool ordered)
+{
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < count)
+		order4f_item(in, out, cx, cy, cz, ordered, first + i);
+}
+void launch_order4f(const Node4f *in, Node4f *out, uint32_t first, uint32_t count, const float origin[3], bool ordered, stream_t s)
+{
+	if (count)
+		hipLaunchKernelGGL(k_order4f, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, in, out, first, count, origin[0], origin[1],
+						   origin[2], ordered);
+}
+
 // Grid of the persistent kernels: more workgroups than fit on the chip at once (4-7 per CU).  The queue-driven kernels
 // do not care much (late workgroups find their queue empty), the shade kernel walks its chunks with a static stride
 // and balances better the finer that stride is.  Swept on MI355X: 8 / 16 / 32 / 64 / 128 per CU -> 1820 / 1835 /
@@ -2127,7 +2169,9 @@ bool primary_packet_form(const Params &p, uint32_t max_items)
 	return RT_PRIMARY_PACKET_RULE(p, max_items);
 }
 
-void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s)
+bool primary_packet_walk(const Params &p, uint32_t max_items) { return RT_PRIMARY_PACKET_RULE(p, max_items); }
+
+void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s, const Node4f *ordered)
 {
 	const dim3 g(persistent_grid(max_items)), b(BLOCK);
 	hipStream_t st = (hipStream_t)s;
@@ -2162,10 +2206,19 @@ void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, str
 		// tile of different pixels reaches 64 different ones and every lane tests them all.  Small launches of single samples (1-spp
 		// frames: 0.37 against 0.57 ms) keep the one-ray-per-lane kernel with its tile-row-to-XCD dealing.
 		const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
-		if (count)
-			hipLaunchKernelGGL((k_primary_packet<true>), gt, bt, 0, st, p, max_items);
+		if (ordered)
+		{
+			Params po = p;
+			po.sc.nodes4f = ordered;
+			if (count)
+				hipLaunchKernelGGL((k_primary_packet<true>), gt, bt, 0, st, po, max_items);
+			else
+				hipLaunchKernelGGL((k_primary_packet<false>), gt, bt, 0, st, po, max_items);
+		}
+		else if (count)
+			hipLaunchKernelGGL((k_primary_packet_sorting<true>), gt, bt, 0, st, p, max_items);
 		else
-			hipLaunchKernelGGL((k_primary_packet<false>), gt, bt, 0, st, p, max_items);
+			hipLaunchKernelGGL((k_primary_packet_sorting<false>), gt, bt, 0, st, p, max_items);
 	}
 	else if (gen == GEN_PT)
 	{
@@ -2858,17 +2911,26 @@ void launch_adaptive_connections(WaveCounters *c, uint32_t depth, stream_t s)
 {
 	hipLaunchKernelGGL(k_adaptive_connections, dim3(1), dim3(64), 0, (hipStream_t)s, c, depth);
 }
-void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s)
+void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s, const Node4f *ordered)
 {
 	const dim3 g(persistent_grid(max_items)), b(BLOCK);
 	hipStream_t st = (hipStream_t)s;
 	if (primary_packet_form(p, max_items))
 	{
 		const dim3 gt(trace_grid(g)), bt(TRACE_BLOCK);
-		if (count)
-			hipLaunchKernelGGL((k_primary_packet_masked<true>), gt, bt, 0, st, p, max_items, mask);
+		if (ordered)
+		{
+			Params po = p;
+			po.sc.nodes4f = ordered;
+			if (count)
+				hipLaunchKernelGGL((k_primary_packet_masked<true>), gt, bt, 0, st, po, max_items, mask);
+			else
+				hipLaunchKernelGGL((k_primary_packet_masked<false>), gt, bt, 0, st, po, max_items, mask);
+		}
+		else if (count)
+			hipLaunchKernelGGL((k_primary_packet_masked_sorting<true>), gt, bt, 0, st, p, max_items, mask);
 		else
-			hipLaunchKernelGGL((k_primary_packet_masked<false>), gt, bt, 0, st, p, max_items, mask);
+			hipLaunchKernelGGL((k_primary_packet_masked_sorting<false>), gt, bt, 0, st, p, max_items, mask);
 	}
 	else if (count)
 		hipLaunchKernelGGL((k_extend_masked<true>), g, b, 0, st, p, max_items, mask);

@@ -80,7 +80,14 @@ struct Stack
 		sp += na + nb + nc;
 	}
 };
-template <bool COUNT> void trace(const SceneView &sc, const bool *active, const f3 *O, const f3 *D, float t_min, Hit *hit, TStat &st)
+#if defined(RT_DEV_PACKET_COST)
+// development (tools/dev/packet_cost.py): what the WAVE walks — node steps and leaf triangle tests per launch of the primary wave,
+// whatever the per-ray counters say; RT_DEV_ORDER_PLANB=1 in the environment: the ordered walk with one comparator (DESIGN_LOG.md)
+static unsigned long long g_cost_nodes = 0, g_cost_tris = 0;
+#endif
+// ORDERED: the node table holds every node's children near to far as seen from the camera (primary_order.h) — they are taken as
+// they come (device: trace_packet<COUNT, false, true>, k_primary_packet; ORDERED = false: k_primary_packet_sorting)
+template <bool COUNT, bool ORDERED = false> void trace(const SceneView &sc, const bool *active, const f3 *O, const f3 *D, float t_min, Hit *hit, TStat &st)
 {
 	unsigned long long act = 0;
 	for (int l = 0; l < WAVE; l++)
@@ -161,9 +168,16 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 					else if (!(e & ENTRY_TLAS))
 						st.tris += n * (((e >> 27) & 7u) + 1u);
 				}
+#if defined(RT_DEV_PACKET_COST)
+			g_cost_nodes++;
+			static const bool planb = getenv("RT_DEV_ORDER_PLANB") && atoi(getenv("RT_DEV_ORDER_PLANB")) != 0;
+#else
+			constexpr bool planb = false;
+#endif
+			// (ORDERED: no keys — an entered child's is 0, the children stay as the table has them)
 			uint32_t kk[4], ee[4];
 			for (int k = 0; k < 4; k++)
-				kk[k] = m[k] ? fbits(tk_ref[k]) : 0xFFFFFFFFu, ee[k] = nd.entry[k];
+				kk[k] = m[k] ? (ORDERED && !(planb && k < 2) ? 0u : fbits(tk_ref[k])) : 0xFFFFFFFFu, ee[k] = nd.entry[k];
 			auto pswap = [&](int a, int b) {
 				if (kk[b] < kk[a])
 				{
@@ -171,7 +185,10 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 					kk[a] = kk[b], ee[a] = ee[b], kk[b] = tk_, ee[b] = te_;
 				}
 			};
-			pswap(0, 1), pswap(2, 3), pswap(0, 2);
+			if (!ORDERED)
+				pswap(0, 1), pswap(2, 3), pswap(0, 2);
+			else if (planb)
+				pswap(0, 1);
 			stk.push3(ee[3], kk[3] != 0xFFFFFFFFu, ee[2], kk[2] != 0xFFFFFFFFu, ee[1], kk[1] != 0xFFFFFFFFu);
 			cur = kk[0] != 0xFFFFFFFFu ? ee[0] : stk.pop();
 		}
@@ -202,6 +219,9 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 		}
 		{
 			const uint32_t first = cur & ENTRY_FIRST_MASK, count = ((cur >> 27) & 7u) + 1u;
+#if defined(RT_DEV_PACKET_COST)
+			g_cost_tris += count;
+#endif
 			float t_before[WAVE];
 			for (int l = 0; l < WAVE; l++)
 				t_before[l] = hit[l].t;
@@ -229,7 +249,7 @@ template <bool COUNT> void trace(const SceneView &sc, const bool *active, const 
 	}
 }
 // mask (adaptive.h): one byte per slot tile, null = every tile is traced
-template <bool COUNT> void primary(const Params &p, uint32_t count, const unsigned char *mask = nullptr)
+template <bool COUNT, bool ORDERED = false> void primary(const Params &p, uint32_t count, const unsigned char *mask = nullptr)
 {
 	TStat st;
 	st.inner = 0, st.tris = 0, st.lds = 0;
@@ -257,15 +277,11 @@ template <bool COUNT> void primary(const Params &p, uint32_t count, const unsign
 				const PixelRef pr = slot_to_pixel(p.fr, idx);
 				active[l] = pr.valid;
 				if (active[l])
-				{
 					pt_primary_ray(p.cam, p.fr, pr.x, pr.y, p.fr.sample_base + pr.sample, O[l], D[l]);
-					if (p.cam.aperture != 0.0f) // VESTIGE: unread, kept as k_primary_packet's twin (DESIGN_LOG.md, round 7)
-						p.wv.org[0][idx] = mk4(O[l].x, O[l].y, O[l].z, ubits((idx << 1) | 1u));
-				}
 			}
 			h[l].t = 1e34f, h[l].u = 0.0f, h[l].v = 0.0f, h[l].prim = -1, h[l].inst = -1;
 		}
-		trace<COUNT>(p.sc, active, O, D, 1e-5f, h, st);
+		trace<COUNT, ORDERED>(p.sc, active, O, D, 1e-5f, h, st);
 		for (int l = 0; l < WAVE; l++)
 			if (active[l])
 			{
@@ -273,6 +289,10 @@ template <bool COUNT> void primary(const Params &p, uint32_t count, const unsign
 				nrays++;
 			}
 	}
+#if defined(RT_DEV_PACKET_COST)
+	fprintf(stderr, "packet_cost ordered=%d node_steps=%llu leaf_tris=%llu\n", (int)ORDERED, g_cost_nodes, g_cost_tris);
+	g_cost_nodes = g_cost_tris = 0;
+#endif
 	if (COUNT)
 	{
 		WaveCounters *const wc = p.wv.counters;
@@ -282,13 +302,21 @@ template <bool COUNT> void primary(const Params &p, uint32_t count, const unsign
 } // namespace packet_emu
 
 bool primary_packet_form(const Params &, uint32_t) { return false; } // (the emulation keeps no group flags: every record is read)
+bool primary_packet_walk(const Params &p, uint32_t max_items) { return RT_PRIMARY_PACKET_RULE(p, max_items); }
 
-void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s)
+void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, stream_t s, const Node4f *ordered)
 {
-	EMU_DEFER(s, launch_extend(p, gen, count, max_items, s));
+	EMU_DEFER(s, launch_extend(p, gen, count, max_items, s, ordered));
 	if (gen == GEN_PT && RT_PRIMARY_PACKET_RULE(p, max_items)) // (the device's rule)
 	{
-		count ? packet_emu::primary<true>(p, max_items) : packet_emu::primary<false>(p, max_items);
+		if (ordered)
+		{
+			Params po = p;
+			po.sc.nodes4f = ordered;
+			count ? packet_emu::primary<true, true>(po, max_items) : packet_emu::primary<false, true>(po, max_items);
+		}
+		else
+			count ? packet_emu::primary<true>(p, max_items) : packet_emu::primary<false>(p, max_items);
 		return;
 	}
 	Ctx ctx(p);
@@ -305,12 +333,19 @@ void launch_extend(const Params &p, int gen, bool count, uint32_t max_items, str
 			count ? extend_item<GEN_PARITY, true>(p, i, true, ctx) : extend_item<GEN_PARITY, false>(p, i, true, ctx);
 	}
 }
-void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s)
+void launch_extend_masked(const Params &p, const unsigned char *mask, bool count, uint32_t max_items, stream_t s, const Node4f *ordered)
 {
-	EMU_DEFER(s, launch_extend_masked(p, mask, count, max_items, s));
+	EMU_DEFER(s, launch_extend_masked(p, mask, count, max_items, s, ordered));
 	if (RT_PRIMARY_PACKET_RULE(p, max_items))
 	{
-		count ? packet_emu::primary<true>(p, max_items, mask) : packet_emu::primary<false>(p, max_items, mask);
+		if (ordered)
+		{
+			Params po = p;
+			po.sc.nodes4f = ordered;
+			count ? packet_emu::primary<true, true>(po, max_items, mask) : packet_emu::primary<false, true>(po, max_items, mask);
+		}
+		else
+			count ? packet_emu::primary<true>(p, max_items, mask) : packet_emu::primary<false>(p, max_items, mask);
 		return;
 	}
 	Ctx ctx(p);
@@ -663,6 +698,14 @@ void launch_expand4(const Node4c *nodes4, Node4f *out, uint32_t count4, stream_t
 	EMU_DEFER(s, launch_expand4(nodes4, out, count4, s));
 	for (uint32_t i = 0; i < count4; i++)
 		expand4_item(nodes4, out, i);
+}
+void launch_order4f(const Node4f *in, Node4f *out, uint32_t first, uint32_t count, const float origin[3], bool ordered, stream_t s)
+{
+	const f3 c = mk3(origin[0], origin[1], origin[2]); // (a host array: taken at enqueue)
+	const float cc[3] = {c.x, c.y, c.z};
+	EMU_DEFER(s, launch_order4f(in, out, first, count, cc, ordered, s));
+	for (uint32_t i = 0; i < count; i++)
+		order4f_item(in, out, origin[0], origin[1], origin[2], ordered, first + i);
 }
 void launch_refit(Node *all_nodes, uint32_t node_base, const int *parents, uint32_t node_count, f4 *tri_verts,
 				  uint32_t tri_base, const f4 *verts, const uint32_t *indices, uint32_t tri_count, uint32_t *flags, stream_t s)

@@ -1,5 +1,5 @@
 // primary_packet_body.h — the body of k_primary_packet and of k_primary_packet_masked (kernels.hip), included by both like
-// shade_pt_body.h by the shade kernels: p, count, COUNT; MASKED and `mask` (adaptive.h: one byte per slot tile) — with MASKED = false
+// shade_pt_body.h by the shade kernels: p, count, COUNT, ORDERED (the node table is camera-ordered: trace_packet); MASKED and `mask` (adaptive.h: one byte per slot tile) — with MASKED = false
 // the kernel is the code it was before the masked one existed.  A group of a retired tile leaves void hit records and traces nothing.
 	clock_in(p.wv.counters, 0);
 	uint32_t *const head = &p.wv.counters->work[p.queue][0];
@@ -45,18 +45,12 @@
 					const PixelRef pr = slot_to_pixel(q.fr, idx);
 					active = pr.valid;
 					if (active)
-					{
 						pt_primary_ray(q.cam, q.fr, pr.x, pr.y, q.fr.sample_base + pr.sample, O, D);
-						// VESTIGE: nothing reads this record (the shade kernel regenerates the primary ray); the store stays because dropping it
-						// changes this kernel's code object — a performance change with its own measurement (DESIGN_LOG.md, round 7)
-						if (q.cam.aperture != 0.0f)
-							q.wv.org[0][idx] = mk4(O.x, O.y, O.z, ubits((idx << 1) | 1u));
-					}
 				}
 			}
 			Hit h;
 			h.t = 1e34f, h.u = 0.0f, h.v = 0.0f, h.prim = -1, h.inst = -1;
-			trace_packet<COUNT>(fresh_params().sc, active, O, D, 1e-5f, h, st);
+			trace_packet<COUNT, false, ORDERED>(fresh_params().sc, active, O, D, 1e-5f, h, st);
 			if (active)
 			{
 				primary_finish_item(fresh_params(), idx, D, h); // (hit record, or the sky term of a miss)

@@ -210,7 +210,17 @@ enum KernelFamily
 	KF_NOISE = 8,	// the noise metric: k_noise_tiles + k_noise_final (noise.h), two launches per query
 	KF_METER_HIST = 9,	 // the exposure meter's histogram pass k_meter_hist (metering.h), one launch per step
 	KF_METER_REDUCE = 10, // ... and its one-workgroup reduce k_meter_reduce, one launch per step
-	KF_COUNT = 11
+	KF_PRIMARY_ORDER = 11, // the primary wave's ordering pass k_order4f (primary_order.h): ONE count per pass over the table, with or
+						   // without stage_timing (the milliseconds only with it)
+	KF_COUNT = 12
+};
+
+// A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
+struct OrderRange
+{
+	uint32_t first = 0, count = 0;
+	bool object_space = false; // the camera position goes through inv first (the mesh tree of exactly one instance)
+	float inv[12];			   // rt::Instance::inv of that instance
 };
 
 struct TimedSpan
@@ -350,6 +360,18 @@ struct rfwhip_context
 	DevBuf d_nodes4f; // float form of d_nodes4 (rt::Node4f), refreshed at the end of every rfwhip_update that may need it
 	bool nodes4f_current = false; // ... which is when the packet form of the primary wave can run (packet_ok, refill bit 3)
 	size_t nodes4_live = 0;		  // 4-wide nodes in use: all mesh trees + the top-level tree
+	// the primary wave's camera-ordered copy of d_nodes4f (primary_order.h): same size, same indexing.  It holds
+	// the order for camera position ord_cam (bits) of table version ord_version; a render call whose primary wave wants it and finds it
+	// stale rewrites it on the main stream in front of its sub-batches, which wait for ev_order
+	int primary_order = -1; // RFWHIP_PRIMARY_ORDER as the context was created: 0 never, 1 wherever the packet form runs, else by call size
+	DevBuf d_nodes4f_ord;
+	std::vector<OrderRange> ord_ranges; // the trees that have ONE origin, as the last rfwhip_update laid them out (the rest is copied)
+	unsigned long long nodes4f_version = 0, ord_version = 0; // nodes4f_version: rewrites of d_nodes4f
+	bool ord_valid = false;
+	uint32_t ord_cam[3] = {0, 0, 0};
+	dm::event_t ev_order;
+	uint64_t order_serial = 0, order_seen[MAX_SUB] = {};
+	bool ord_reader[MAX_SUB] = {}; // a primary wave of this sub-batch slot has read the table since its last rewrite
 	DevBuf d_nodes, d_nodes4, d_nodes4_src, d_tri_verts, d_tri_shade, d_tri_uv, d_tlas_prims, d_instances;
 	size_t blas_nodes4 = 0, node4_capacity = 0; // d_nodes4 = [all BLAS 4-wide nodes | TLAS 4-wide nodes | spare]
 	DevBuf d_materials, d_textures, d_tex_u32, d_tex_f4, d_sky, d_area, d_point, d_spot, d_dir;
@@ -550,6 +572,8 @@ extern "C" int rfwhip_create(int device_ordinal, int rank, int world, rfwhip_con
 	RF_TRY(dm::init(device_ordinal, &cus));
 	rfwhip_context *c = new rfwhip_context();
 	c->device = device_ordinal, c->rank = rank, c->world = world, c->cus = cus;
+	if (const char *e = getenv("RFWHIP_PRIMARY_ORDER")) // (an environment variable, read once per context: not a setting)
+		c->primary_order = e[0] == '0' && !e[1] ? 0 : (e[0] == '1' && !e[1] ? 1 : -1);
 	rtk::set_device_cus(cus);
 	memset(&c->stats, 0, sizeof(c->stats));
 	memset(&c->totals, 0, sizeof(c->totals));
@@ -605,7 +629,7 @@ static void free_all(rfwhip_context *c)
 	}
 	c->d_lbvh_scratch.free_(), c->d_blue_noise.free_();
 	c->have_blue_noise = false;
-	DevBuf *bufs[] = {&c->d_nodes4, &c->d_nodes4f, &c->d_nodes4_src, &c->d_nodes, &c->d_tri_verts, &c->d_tri_shade, &c->d_tri_uv, &c->d_tlas_prims, &c->d_instances,
+	DevBuf *bufs[] = {&c->d_nodes4, &c->d_nodes4f, &c->d_nodes4f_ord, &c->d_nodes4_src, &c->d_nodes, &c->d_tri_verts, &c->d_tri_shade, &c->d_tri_uv, &c->d_tlas_prims, &c->d_instances,
 					  &c->d_materials, &c->d_textures, &c->d_tex_u32, &c->d_tex_f4, &c->d_sky, &c->d_area, &c->d_point,
 					  &c->d_spot, &c->d_dir, &c->d_org[0], &c->d_org[1], &c->d_dir2[0], &c->d_dir2[1], &c->d_thr[0],
 					  &c->d_thr[1], &c->d_hit, &c->d_hit_inst, &c->d_hit0, &c->d_hit0_inst, &c->d_hit0_done, &c->d_sh_org[0], &c->d_sh_org[1],
@@ -619,6 +643,7 @@ static void free_all(rfwhip_context *c)
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->noise_live = false, c->adaptive_live = false;
+	c->ord_valid = false;
 	c->meter_have = false, c->meter_manual_stale = true, c->meter_pending = false;
 	if (c->ev_meter_ready)
 		dm::event_destroy(c->ev_meter), c->ev_meter_ready = false;
@@ -636,7 +661,7 @@ static void free_all(rfwhip_context *c)
 		for (int r = 0; r < rfwhip_context::MAX_RING; r++)
 			dm::event_destroy(c->ev_resolve[r]);
 		dm::event_destroy(c->ev_present_in), dm::event_destroy(c->ev_present_out), dm::event_destroy(c->ev_dn);
-		dm::event_destroy(c->ev_adaptive);
+		dm::event_destroy(c->ev_adaptive), dm::event_destroy(c->ev_order);
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			dm::event_destroy(c->ev_sub_done[i]), dm::event_destroy(c->ev_conn_last[i]);
@@ -1339,6 +1364,7 @@ static int ensure_nodes4f(rfwhip_context *c)
 	RF_TRY(dm::last_launch_error());
 	c->sv.nodes4f = c->d_nodes4f.as<rt::Node4f>();
 	c->nodes4f_current = true;
+	c->nodes4f_version++; // (the ordered copy is stale: ensure_primary_order)
 	return 0;
 }
 
@@ -1988,6 +2014,38 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 	c->packet_ok = c->packet_ok && (tlas_base + tl4c.size()) * sizeof(rt::Node4f) < (1ull << 32);
 	c->nodes4_live = tlas_base + tl4c.size(), c->nodes4f_current = false;
 	RF_TRY(ensure_nodes4f(c));
+	// the trees the primary wave's ordering pass can order (primary_order.h): a mesh tree exactly one instance walks (in that
+	// instance's object space; a flat instance's is the world), the world tree and the top-level tree
+	{
+		c->ord_ranges.clear(), c->ord_valid = false;
+		std::vector<uint32_t> uses(c->meshes.size(), 0u), who(c->meshes.size(), 0u);
+		for (uint32_t i : live)
+			if (i != WORLD_ID)
+				uses[c->instances[i].mesh]++, who[c->instances[i].mesh] = i;
+		for (size_t mi = 0; mi < c->meshes.size(); mi++)
+		{
+			const MeshRec &m = c->meshes[mi];
+			if (!m.used || !m.resident || !m.n4_count || uses[mi] != 1u || (size_t)m.n4_base + m.n4_count > tlas_base)
+				continue;
+			OrderRange r;
+			r.first = m.n4_base, r.count = m.n4_count, r.object_space = true;
+			memcpy(r.inv, inst[who[mi]].inv, sizeof(r.inv));
+			c->ord_ranges.push_back(r);
+		}
+		if (world.valid && world.resident && !world.n4.empty() && (size_t)world.n4_base + world.n4.size() <= tlas_base)
+		{
+			OrderRange r;
+			r.first = world.n4_base, r.count = (uint32_t)world.n4.size();
+			c->ord_ranges.push_back(r);
+		}
+		if (!tl4c.empty())
+		{
+			OrderRange r;
+			r.first = tlas_base, r.count = (uint32_t)tl4c.size();
+			c->ord_ranges.push_back(r);
+		}
+		std::sort(c->ord_ranges.begin(), c->ord_ranges.end(), [](const OrderRange &a, const OrderRange &b) { return a.first < b.first; });
+	}
 	RF_TRY(dm::last_launch_error());
 	RF_TRY(dm::sync(c->stream));
 	c->instance_count = (uint32_t)live.size();
@@ -2251,6 +2309,7 @@ static int ensure_sub_batches(rfwhip_context *c, int subs)
 		RF_TRY(dm::event_create(&c->ev_present_out));
 		RF_TRY(dm::event_create(&c->ev_dn));
 		RF_TRY(dm::event_create(&c->ev_adaptive));
+		RF_TRY(dm::event_create(&c->ev_order));
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			RF_TRY(dm::event_create(&c->ev_sub_done[i]));
@@ -2305,6 +2364,91 @@ static uint32_t depth_items(const rfwhip_context *c, uint32_t n, int d, bool sha
 	const double want = shade ? ext : std::max(ext, prev * shadow_per_path);
 	const double items = std::min(1.0, 1.25 * want + 0.02) * (double)n;
 	return (uint32_t)std::max(1.0, items);
+}
+
+// ---- the primary wave's camera-ordered node table (primary_order.h) ----------------------------------------------------------------
+// Does a render call of `paths` path slots use it?  RFWHIP_PRIMARY_ORDER says never / always; otherwise when the pass is noise beside
+// the call's primary wave even if the camera moves with every call: the pass reads and writes the table once, 2 x table bytes, at
+// ~0.3 ps per byte of HBM traffic; a primary path costs ~32 ps of the packet kernel (4.2 ms per 133 M, DESIGN_LOG.md).  One path slot
+// per byte moved puts the pass at 1 % of the primary wave (measured: DESIGN_LOG.md, round 8).  Small interactive frames keep the
+// kernel that sorts for itself.
+static bool primary_order_wanted(const rfwhip_context *c, size_t paths)
+{
+	if (c->primary_order == 0 || c->integrator != 1 || !c->packet_ok || !c->nodes4f_current || !(c->refill & 8) || !c->nodes4_live)
+		return false;
+	if (c->primary_order == 1)
+		return true;
+	return paths >= 2 * c->nodes4_live * sizeof(rt::Node4f);
+}
+
+// The table for camera position `pos`, rewritten on the main stream when it is stale: another position (by its bits), or d_nodes4f
+// rewritten since (every rfwhip_update that changes a tree, a pose, a refit or an instance's transform ends in ensure_nodes4f).  The
+// primary waves of the calls in flight read the table on their sub-batch streams: the rewrite waits for their ev_sub_done — every
+// one of them has been waited for by its own call's epilogue on this stream already, the waits here say so where it matters.
+static int ensure_primary_order(rfwhip_context *c, const rt::f3 &pos)
+{
+	uint32_t bits[3];
+	memcpy(&bits[0], &pos.x, 4), memcpy(&bits[1], &pos.y, 4), memcpy(&bits[2], &pos.z, 4);
+	if (c->ord_valid && c->ord_version == c->nodes4f_version && !memcmp(bits, c->ord_cam, sizeof(bits)))
+		return 0;
+	const size_t bytes = c->node4_capacity * sizeof(rt::Node4f);
+	if (bytes > c->d_nodes4f_ord.cap)
+		RF_TRY(sync_all(c)); // (the buffer moves)
+	RF_TRY(c->d_nodes4f_ord.ensure(bytes));
+	for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
+		if (c->ord_reader[i])
+		{
+			RF_TRY(dm::stream_wait_event(c->stream, c->ev_sub_done[i]));
+			c->ord_reader[i] = false;
+		}
+	const rt::Node4f *in = c->d_nodes4f.as<rt::Node4f>();
+	rt::Node4f *out = c->d_nodes4f_ord.as<rt::Node4f>();
+	StageTimer t(c, KF_PRIMARY_ORDER, -1);
+	const float cam[3] = {pos.x, pos.y, pos.z};
+	uint32_t at = 0; // ranges ascend (rfwhip_update); what lies between them is copied as it is
+	bool run_ordered = false;
+	uint32_t run_first = 0, run_count = 0;
+	float run_origin[3] = {0, 0, 0};
+	auto flush = [&]() {
+		if (run_count)
+			rtk::launch_order4f(in, out, run_first, run_count, run_origin, run_ordered, c->stream);
+		run_count = 0;
+	};
+	auto add = [&](uint32_t first, uint32_t count, bool ordered, const float *origin) { // (neighbours handled alike: one launch)
+		if (!count)
+			return;
+		if (run_count && run_first + run_count == first && run_ordered == ordered && (!ordered || !memcmp(run_origin, origin, 12)))
+		{
+			run_count += count;
+			return;
+		}
+		flush();
+		run_first = first, run_count = count, run_ordered = ordered;
+		if (ordered)
+			memcpy(run_origin, origin, 12);
+	};
+	for (const OrderRange &r : c->ord_ranges)
+	{
+		if (r.first < at || (size_t)r.first + r.count > c->nodes4_live)
+			continue; // (never: the layout's ranges are disjoint)
+		add(at, r.first - at, false, nullptr);
+		float o[3] = {cam[0], cam[1], cam[2]};
+		if (r.object_space)
+			for (int k = 0; k < 3; k++)
+				o[k] = r.inv[4 * k] * cam[0] + r.inv[4 * k + 1] * cam[1] + r.inv[4 * k + 2] * cam[2] + r.inv[4 * k + 3];
+		add(r.first, r.count, true, o);
+		at = r.first + r.count;
+	}
+	add(at, (uint32_t)c->nodes4_live - at, false, nullptr);
+	flush();
+	t.stop(0);
+	c->kernel_launches[KF_PRIMARY_ORDER]++;
+	RF_TRY(dm::last_launch_error());
+	RF_TRY(dm::event_record(c->ev_order, c->stream));
+	c->order_serial++;
+	c->ord_valid = true, c->ord_version = c->nodes4f_version;
+	memcpy(c->ord_cam, bits, sizeof(bits));
+	return 0;
 }
 
 // One render call = `spp` samples per pixel.  The samples are cut into up to `streams` sub-batches that run the whole
@@ -2475,6 +2619,14 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	fill_params(c, cam, base);
 	set_sample_group(base.fr, sgroup_log2);
 	c->sgroup_last = sgroup_log2;
+	// the primary wave's camera-ordered node table, where the packet form runs and the call is large enough (primary_order_wanted):
+	// rewritten here, on the main stream, when the camera has moved or the trees have changed
+	const rt::Node4f *ordered = nullptr;
+	if (primary_order_wanted(c, paths) && rtk::primary_packet_walk(base, (uint32_t)((size_t)c->fr.slots * (size_t)(c->spp / subs))))
+	{
+		RF_TRY(ensure_primary_order(c, base.cam.pos));
+		ordered = c->d_nodes4f_ord.as<rt::Node4f>();
+	}
 	base.wv.rad = alternate ? c->d_rad[0].as<f4>() + paths * par : c->d_rad[par].as<f4>();
 	// the connections always add into their own buffer, on a side stream or not: the image is then bit-identical whichever way
 	// a call is scheduled (e.g. the ranks of a strip split against the single-rank image)
@@ -2503,6 +2655,11 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		{
 			RF_TRY(dm::stream_wait_event(s, c->ev_adaptive));
 			c->adaptive_seen[i] = c->adaptive_serial;
+		}
+		if (ordered && c->order_seen[i] != c->order_serial) // the ordered table was rewritten since this stream last read it
+		{
+			RF_TRY(dm::stream_wait_event(s, c->ev_order));
+			c->order_seen[i] = c->order_serial;
 		}
 		rtk::Params p = base;
 		const size_t off_rad = (size_t)c->fr.slots * s_begin; // this sub-batch's slice of the radiance buffers of the call
@@ -2571,9 +2728,11 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 				if (pa_pending)
 					rtk::launch_trace_fused(p, pa, count, n_ext, s); // extension rays of depth d + shadow rays of depth d - 1
 				else if (d == 0 && c->adaptive_live)
-					rtk::launch_extend_masked(p, ad.mask, count, n, s);
+					rtk::launch_extend_masked(p, ad.mask, count, n, s, ordered);
 				else
-					rtk::launch_extend(p, d == 0 ? rtk::GEN_PT : rtk::GEN_BUFFER, count, d == 0 ? n : n_ext, s);
+					rtk::launch_extend(p, d == 0 ? rtk::GEN_PT : rtk::GEN_BUFFER, count, d == 0 ? n : n_ext, s, d == 0 ? ordered : nullptr);
+				if (d == 0 && ordered)
+					c->ord_reader[i] = true;
 				pa_pending = false;
 				te.stop();
 				if (side && d >= 2 && d < c->max_depth) // connect(d - 2) read the buffers shade(d) is about to write
@@ -4253,7 +4412,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)
@@ -4985,6 +5144,18 @@ extern "C" int rfwhip_light_tree_refit(rfwhip_context *c, rfwhip_light_tree_node
 	d_nodes.free_(), d_area.free_(), d_bound.free_(), d_touched.free_();
 	return rc;
 }
+
+#if defined(RFWHIP_HOST_EMULATION)
+// ---- the emulation libraries only (tests/test_primary_order.py): not declared in rfwhip.h, not in the product ----
+// the primary wave's ordering item (primary_order.h) on n caller-supplied rt::Node4f records (host memory, `out` another array)
+extern "C" RFWHIP_API int rfwhip_emu_order4f(const void *in, void *out, uint32_t n, const float *origin, int ordered)
+{
+	if (!in || !out || !origin || in == out)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_emu_order4f: two node arrays and an origin");
+	rtk::launch_order4f((const rt::Node4f *)in, (rt::Node4f *)out, 0u, n, origin, ordered != 0, nullptr);
+	return dm::sync(nullptr); // (the deferred-stream variant: stream 0 — a context's main stream — has run it)
+}
+#endif
 
 #if defined(RFWHIP_HOST_EMULATION) && defined(RFWHIP_EMU_STREAMS) && RFWHIP_EMU_STREAMS
 // ---- the deferred-stream emulation library only (tests/test_schedule.py): not declared in rfwhip.h, not in the product ----
