@@ -225,6 +225,37 @@ RFWHIP_API int rfwhip_meter_image(rfwhip_context *ctx, const float *rgba_in, rfw
 RFWHIP_API int rfwhip_meter_histogram(rfwhip_context *ctx, const uint32_t bins[RFWHIP_METER_BINS], uint32_t excluded,
 									  rfwhip_meter_stats *stats);
 
+/* ---- bloom: an HDR glow pyramid in front of the tone map -----------------------------------------------------------------------
+ * With display_bloom = 1 every entry point of the display stage above (rfwhip_read_display*, rfwhip_display_stream,
+ * rfwhip_display_image, the group's reads and presents) runs a chain of small kernels on the image it is about to show — behind the
+ * meter's step, which sees the unbloomed image — and the display kernel reads the chain's image instead: highlights far above display
+ * white bleed into their surroundings and stay readable as bright after the tone map clips them.  csrc/bloom.h has the formulas line
+ * by line; DESIGN.md section 19.  Off by default: nothing is allocated, no bloom kernel runs, every byte is what it was.
+ *   Settings (not listed by rfwhip_get_settings):
+ *     display_bloom           = "0" (default) | "1"
+ *     display_bloom_intensity = in [0, 16] (default 0.2): the weight of the glow added to the image
+ *     display_bloom_threshold = a finite number >= 0 (default 1): in EXPOSED units, 1 = display white under any exposure
+ *     display_bloom_knee      = in [0, 1] (default 0.5): the soft knee's half width as a fraction of the threshold
+ *     display_bloom_scatter   = in [0, 1] (default 0.7): how much of the next coarser level a level takes on the way up
+ *     display_bloom_levels    = a whole number in [1, 8] (default 6): levels of the pyramid; fewer when the image reaches 1 x 1 first
+ *     display_bloom_time      (read-only, stage_timing = 1) kernel family 12 by kernel since its last reset: the milliseconds of
+ *                               k_bloom_down0, k_bloom_down, k_bloom_up and k_bloom_apply, then their launches — eight numbers
+ *   With E the exposure the display kernel applies (the meter record's, else 1), per colour channel c = min(max(x, 0), 65504) (a NaN
+ *   channel is 0), T = threshold, K = knee T:
+ *     br = E max(c.r, c.g, c.b); soft = clamp(br - T + K, 0, 2 K); g = max(soft^2 / (4 K + 1e-4), br - T) / max(br, 1e-4); p = c g
+ *   Level k is W_k x H_k, W_0 = W, W_k = (W_{k-1} + 1) >> 1.  Level 1: texel (i, j) = the source texels (2i - 1 .. 2i + 2) x
+ *   (2j - 1 .. 2j + 2), edge-clamped, weights h (x) h with h = (1, 3, 3, 1) / 8 times the tap's 1 / (1 + luminance(p)), normalised (one
+ *   firefly does not flash a blob).  Level k + 1 from level k: the same taps, plain weights.  On the way up, k = levels - 1 .. 1:
+ *   U_k = D_k + scatter (up(U_{k+1}) - D_k), up = two taps per axis with weights (1/4, 3/4) or (3/4, 1/4).  Then
+ *   out.rgb = c + intensity up(U_1), out.a = in.a bit for bit.  The chain runs on the stream of the call; a call on another stream
+ *   than the previous one waits for that chain and its display kernel first (the pyramid and the bloomed image belong to the context).
+ * Known-answer hooks.  rfwhip_bloom_image: the chain alone (whatever display_bloom says) on a host image of the target's size under the
+ * exposure E = `exposure` (finite, >= 0) and the current display_bloom_* settings -> the linear float4 image the display kernel would read.
+ * rfwhip_read_bloom_level: U_level of the last chain, level in 1 .. the levels it ran; *w, *h = its size (either may be null); `out`
+ * holds `cap` floats and needs 4 w h (null: the size alone).  RFWHIP_ERR_STATE when no chain has run since rfwhip_init. */
+RFWHIP_API int rfwhip_bloom_image(rfwhip_context *ctx, const float *rgba_in, float exposure, float *rgba_out);
+RFWHIP_API int rfwhip_read_bloom_level(rfwhip_context *ctx, int level, float *out, size_t cap, uint32_t *w, uint32_t *h);
+
 /* ---- noise estimate: when has a progressive render converged? ---------------------------------------------------------------
  * With noise_estimate = 1 the resolve of every rfwhip_render (its variant k_resolve_noise) keeps two floats per pixel beside the
  * accumulator — sumY, the sum of the luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel's samples (a sample's value is what
@@ -633,6 +664,7 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   display_tonemap / display_fxaa / display_srgb = the display stage, see rfwhip_read_display above.
  *   display_exposure / display_exposure_ev / _key / _low / _high / _speed / _min_ev / _max_ev = the exposure meter, see
  *                  rfwhip_get_meter above.
+ *   display_bloom / display_bloom_intensity / _threshold / _knee / _scatter / _levels = bloom, see rfwhip_bloom_image above.
  *   noise_estimate / noise_floor / noise_threshold = the noise estimate, see rfwhip_get_noise above.
  *   adaptive_sampling / adaptive_min_samples / adaptive_every = adaptive sampling, see rfwhip_get_adaptive above.
  *   lights_follow_geometry = "0" (default) | "1": rfwhip_update derives the area lights of emissive geometry on the device and
@@ -669,7 +701,8 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * runs in packet form and is large enough (or RFWHIP_PRIMARY_ORDER=1 in the environment when the context was created; =0: never)
  * reads a second float node table whose nodes hold their children near to far as seen from the camera, rewritten in front of the
  * call when the camera position or a tree has changed since — `launches` counts those passes, one per rewrite, with or without
- * stage_timing; the image does not depend on it. */
+ * stage_timing; the image does not depend on it.  12 bloom: one count per launch of a chain, 2 x the levels it ran (the down
+ * passes, the up passes and the apply pass). */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

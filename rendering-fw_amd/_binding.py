@@ -98,6 +98,8 @@ class CoreBinding:
                                   "meter_reset": (i32, [vp]),
                                   "meter_image": (i32, [vp, vp, C.POINTER(abi.MeterStats), vp]),
                                   "meter_histogram": (i32, [vp, vp, u32, C.POINTER(abi.MeterStats)]),
+                                  "bloom_image": (i32, [vp, vp, C.c_float, vp]),
+                                  "read_bloom_level": (i32, [vp, i32, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
                                   "get_noise": (i32, [vp, C.POINTER(abi.NoiseStats)]),
                                   "read_noise_map": (i32, [vp, vp]),
                                   "read_noise_tiles": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
@@ -453,6 +455,23 @@ class CoreBinding:
         """E = 1, steps = 0: the next step is a first step."""
         self._check(self._fn("meter_reset")(self._ctx))
 
+    # ---- bloom (include/rfwhip.h, rfwhip_bloom_image; setting display_bloom = 1) -----------------------------------
+    def bloom_image(self, rgba, exposure=1.0):
+        """Known-answer hook: the bloom chain on an H x W x 4 float32 image under the exposure E = `exposure` and the current
+        display_bloom_* settings -> the linear H x W x 4 float32 image the display kernel would read."""
+        src = np.ascontiguousarray(rgba, dtype=np.float32).reshape(self.height, self.width, 4)
+        out = np.empty_like(src)
+        self._check(self._fn("bloom_image")(self._ctx, src.ctypes.data, float(exposure), out.ctypes.data))
+        return out
+
+    def read_bloom_level(self, level):
+        """U_level of the last bloom chain as an h x w x 4 float32 array (level 1 = half the image's size)."""
+        w, h = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("read_bloom_level")(self._ctx, int(level), None, 0, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, 4), np.float32)
+        self._check(self._fn("read_bloom_level")(self._ctx, int(level), out.ctypes.data, out.size, C.byref(w), C.byref(h)))
+        return out
+
     # ---- noise estimate (include/rfwhip.h, rfwhip_get_noise; setting noise_estimate = 1) ---------------------------
     def get_noise(self):
         """The noise of the accumulated image as a dict: samples, pixels, converged, mean_error, max_error, threshold.
@@ -571,10 +590,11 @@ class CoreBinding:
     NOISE = 8  # ... and of the noise metric (two launches per get_noise)
     METER_HIST, METER_REDUCE = 9, 10  # ... and of the exposure meter's two kernels (one launch each per step)
     PRIMARY_ORDER = 11  # ... and of the primary wave's ordering pass (one count per rewrite of the camera-ordered node table)
+    BLOOM = 12  # ... and of bloom (one count per launch of a chain: 2 x the levels it ran)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 

@@ -124,6 +124,36 @@ struct ExposureView
 	const MeterRecord *rec;
 };
 
+// Bloom (bloom.h): the display_bloom_* settings as the kernels take them ...
+struct BloomParams
+{
+	float intensity, threshold, knee, scatter;
+};
+// ... a down pass: the W x H texels of `src` (the image itself for the first one) -> the Wn x Hn texels of `dst`, Wn = (W + 1) >> 1;
+// E: the exposure behind the prefilter, one float on the device (the first pass alone reads it) ...
+struct BloomDownView
+{
+	const rt::f4 *src;
+	rt::f4 *dst;
+	uint32_t W, H, Wn, Hn;
+	const float *E;
+};
+// ... an up pass: level k (W x H, D_k in, U_k out) and level k + 1 (`next`, Wn x Hn) ...
+struct BloomUpView
+{
+	rt::f4 *level;
+	const rt::f4 *next;
+	uint32_t W, H, Wn, Hn;
+};
+// ... and the apply pass: the W x H image `in`, level 1 (`next`, Wn x Hn) -> `out` (in != out)
+struct BloomApplyView
+{
+	const rt::f4 *in;
+	const rt::f4 *next;
+	rt::f4 *out;
+	uint32_t W, H, Wn, Hn;
+};
+
 // The noise estimate (noise.h).  One record per NZ_TILE_X x NZ_TILE_Y noise tile (= rfwhip_noise_tile) and the one record k_noise_final leaves
 constexpr uint32_t NZ_TILE_X = 32, NZ_TILE_Y = 8;
 struct NoiseTile
@@ -239,6 +269,13 @@ uint32_t meter_records(uint32_t pixels);
 void launch_meter_hist(const MeterView &v, stream_t s);
 void launch_meter_reduce(const uint32_t *partial, uint32_t records, uint32_t *hist, const MeterParams &m, MeterRecord *rec, stream_t s);
 constexpr int KAT_METER_BIN = 19; // (RFWHIP_KAT_METER_BIN: k_kat_meter, metering.h)
+// bloom (bloom.h), one launch each: k_bloom_down0 (the image -> level 1: sanitise, prefilter, Karis weights and the 4 x 4 filter),
+// k_bloom_down (level k -> k + 1), k_bloom_up (U_k over D_k), k_bloom_apply (the output image).  bloom_levels: the levels a chain runs
+uint32_t bloom_levels(uint32_t W, uint32_t H, uint32_t levels);
+void launch_bloom_down0(const BloomDownView &v, const BloomParams &b, stream_t s);
+void launch_bloom_down(const BloomDownView &v, stream_t s);
+void launch_bloom_up(const BloomUpView &v, const BloomParams &b, stream_t s);
+void launch_bloom_apply(const BloomApplyView &v, const BloomParams &b, stream_t s);
 // a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
 rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,

@@ -976,6 +976,8 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 #include "display.h"
 // the exposure meter: luminance histogram, robust average, adapted exposure (work items shared with the emulation)
 #include "metering.h"
+// bloom: the HDR glow pyramid in front of the tone map (work items shared with the emulation)
+#include "bloom.h"
 // moving emitters: the area lights of emissive geometry and the light tree's refit (work items shared with the emulation)
 #include "light_follow.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }
@@ -2786,6 +2788,90 @@ void launch_meter_hist(const MeterView &v, stream_t s)
 void launch_meter_reduce(const uint32_t *partial, uint32_t records, uint32_t *hist, const MeterParams &m, MeterRecord *rec, stream_t s)
 {
 	hipLaunchKernelGGL(k_meter_reduce, dim3(1), dim3(MT_REDUCE_THREADS), 0, (hipStream_t)s, partial, records, hist, m, rec);
+}
+
+// ---- bloom (bloom.h).  A down pass: a workgroup owns BL_TILE_X x BL_TILE_Y = 32 x 8 texels of the target level, thread t the texel
+// (t & 31, t >> 5).  It stages the 66 x 18 source texels under its taps — the 64 x 16 tile and a halo of one, indices clamped to
+// the edge, so every staged address lies inside the source — into LDS once, one float4 per thread and round (a wave reads whole row
+// segments of consecutive texels), as planes of floats with an odd row pitch, and runs its 16 taps from there: each source texel
+// is loaded (and, in the first pass, sanitised, prefiltered and Karis-weighted) once instead of four times. ----
+__global__ void __launch_bounds__(BLOCK) k_bloom_down0(const BloomDownView v, const BloomParams b)
+{
+	__shared__ float s_t[4][BL_LDS_H * BL_PITCH]; // k p (three colour planes) and k
+	const float E = *v.E;						  // (a uniform address: one scalar load)
+	const int x0 = (int)blockIdx.x * (2 * BL_TILE_X) - 1, y0 = (int)blockIdx.y * (2 * BL_TILE_Y) - 1;
+	for (int k = (int)threadIdx.x; k < BL_LDS_W * BL_LDS_H; k += BLOCK)
+	{
+		const int ly = k / BL_LDS_W, lx = k - ly * BL_LDS_W;
+		const int gx = dp_edge(x0 + lx, (int)v.W), gy = dp_edge(y0 + ly, (int)v.H);
+		const f4 t = bl_stage0(v.src[(size_t)gy * v.W + (size_t)gx], E, b);
+		const int o = ly * BL_PITCH + lx;
+		s_t[0][o] = t.x, s_t[1][o] = t.y, s_t[2][o] = t.z, s_t[3][o] = t.w;
+	}
+	__syncthreads();
+	const int i = (int)blockIdx.x * BL_TILE_X + (int)(threadIdx.x & 31u), j = (int)blockIdx.y * BL_TILE_Y + (int)(threadIdx.x >> 5);
+	if (i >= (int)v.Wn || j >= (int)v.Hn)
+		return;
+	// (x, y) lies within the taps of a texel of this tile: 0 <= x - x0 < BL_LDS_W, 0 <= y - y0 < BL_LDS_H
+	const auto fetch = [&](int x, int y) -> f4 {
+		const int o = (y - y0) * BL_PITCH + (x - x0);
+		return mk4(s_t[0][o], s_t[1][o], s_t[2][o], s_t[3][o]);
+	};
+	v.dst[(size_t)j * v.Wn + (size_t)i] = bl_down0_item(fetch, i, j);
+}
+__global__ void __launch_bounds__(BLOCK) k_bloom_down(const BloomDownView v)
+{
+	__shared__ float s_t[3][BL_LDS_H * BL_PITCH];
+	const int x0 = (int)blockIdx.x * (2 * BL_TILE_X) - 1, y0 = (int)blockIdx.y * (2 * BL_TILE_Y) - 1;
+	for (int k = (int)threadIdx.x; k < BL_LDS_W * BL_LDS_H; k += BLOCK)
+	{
+		const int ly = k / BL_LDS_W, lx = k - ly * BL_LDS_W;
+		const int gx = dp_edge(x0 + lx, (int)v.W), gy = dp_edge(y0 + ly, (int)v.H);
+		const f4 t = v.src[(size_t)gy * v.W + (size_t)gx];
+		const int o = ly * BL_PITCH + lx;
+		s_t[0][o] = t.x, s_t[1][o] = t.y, s_t[2][o] = t.z;
+	}
+	__syncthreads();
+	const int i = (int)blockIdx.x * BL_TILE_X + (int)(threadIdx.x & 31u), j = (int)blockIdx.y * BL_TILE_Y + (int)(threadIdx.x >> 5);
+	if (i >= (int)v.Wn || j >= (int)v.Hn)
+		return;
+	const auto fetch = [&](int x, int y) -> f4 {
+		const int o = (y - y0) * BL_PITCH + (x - x0);
+		return mk4(s_t[0][o], s_t[1][o], s_t[2][o], 0.0f);
+	};
+	v.dst[(size_t)j * v.Wn + (size_t)i] = bl_down_item(fetch, i, j);
+}
+// one lane per texel of level k: its own D_k and four texels of level k + 1
+__global__ void __launch_bounds__(BLOCK) k_bloom_up(const BloomUpView v, const float scatter)
+{
+	const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+	if (i < (size_t)v.W * v.H)
+		bl_up_item(v, scatter, i);
+}
+// one lane per pixel of the image
+__global__ void __launch_bounds__(BLOCK) k_bloom_apply(const BloomApplyView v, const float intensity)
+{
+	const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+	if (i < (size_t)v.W * v.H)
+		bl_apply_item(v, intensity, i);
+}
+uint32_t bloom_levels(uint32_t W, uint32_t H, uint32_t levels) { return bl_levels(W, H, levels); }
+static dim3 bloom_down_grid(const BloomDownView &v) { return dim3((v.Wn + BL_TILE_X - 1) / BL_TILE_X, (v.Hn + BL_TILE_Y - 1) / BL_TILE_Y); }
+void launch_bloom_down0(const BloomDownView &v, const BloomParams &b, stream_t s)
+{
+	hipLaunchKernelGGL(k_bloom_down0, bloom_down_grid(v), dim3(BLOCK), 0, (hipStream_t)s, v, b);
+}
+void launch_bloom_down(const BloomDownView &v, stream_t s)
+{
+	hipLaunchKernelGGL(k_bloom_down, bloom_down_grid(v), dim3(BLOCK), 0, (hipStream_t)s, v);
+}
+void launch_bloom_up(const BloomUpView &v, const BloomParams &b, stream_t s)
+{
+	hipLaunchKernelGGL(k_bloom_up, dim3((uint32_t)(((size_t)v.W * v.H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)s, v, b.scatter);
+}
+void launch_bloom_apply(const BloomApplyView &v, const BloomParams &b, stream_t s)
+{
+	hipLaunchKernelGGL(k_bloom_apply, dim3((uint32_t)(((size_t)v.W * v.H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)s, v, b.intensity);
 }
 
 // ---- noise estimate (noise.h).  k_noise_tiles: a workgroup is one 32 x 8 tile, thread t its pixel (t & 31, t >> 5): a wave reads

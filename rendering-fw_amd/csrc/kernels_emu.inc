@@ -651,6 +651,40 @@ void launch_meter_reduce(const uint32_t *partial, uint32_t records, uint32_t *hi
 	}
 	mt_finish(hist, hist[MT_BINS], m, rec);
 }
+// bloom (bloom.h): the same items texel by texel; a tap is fetched (and, in the first pass, staged) where the device reads LDS
+uint32_t bloom_levels(uint32_t W, uint32_t H, uint32_t levels) { return bl_levels(W, H, levels); }
+void launch_bloom_down0(const BloomDownView &v, const BloomParams &b, stream_t s)
+{
+	EMU_DEFER(s, launch_bloom_down0(v, b, s));
+	const float E = *v.E;
+	const auto fetch = [&](int x, int y) -> f4 { return bl_stage0(v.src[(size_t)dp_edge(y, (int)v.H) * v.W + (size_t)dp_edge(x, (int)v.W)], E, b); };
+	for (uint32_t j = 0; j < v.Hn; j++)
+		for (uint32_t i = 0; i < v.Wn; i++)
+			v.dst[(size_t)j * v.Wn + i] = bl_down0_item(fetch, (int)i, (int)j);
+}
+void launch_bloom_down(const BloomDownView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_bloom_down(v, s));
+	const auto fetch = [&](int x, int y) -> f4 {
+		const f4 t = v.src[(size_t)dp_edge(y, (int)v.H) * v.W + (size_t)dp_edge(x, (int)v.W)];
+		return mk4(t.x, t.y, t.z, 0.0f);
+	};
+	for (uint32_t j = 0; j < v.Hn; j++)
+		for (uint32_t i = 0; i < v.Wn; i++)
+			v.dst[(size_t)j * v.Wn + i] = bl_down_item(fetch, (int)i, (int)j);
+}
+void launch_bloom_up(const BloomUpView &v, const BloomParams &b, stream_t s)
+{
+	EMU_DEFER(s, launch_bloom_up(v, b, s));
+	for (size_t i = 0; i < (size_t)v.W * v.H; i++)
+		bl_up_item(v, b.scatter, i);
+}
+void launch_bloom_apply(const BloomApplyView &v, const BloomParams &b, stream_t s)
+{
+	EMU_DEFER(s, launch_bloom_apply(v, b, s));
+	for (size_t i = 0; i < (size_t)v.W * v.H; i++)
+		bl_apply_item(v, b.intensity, i);
+}
 void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s)
 {
 	EMU_DEFER(s, launch_kat(p, sky, lt, function, in, out, n, s));

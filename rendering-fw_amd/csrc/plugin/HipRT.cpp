@@ -26,6 +26,10 @@
 // display_exposure_speed.  A host reads the meter's record with hiprtGetExposure: with frames in flight it is the newest
 // frame's, not the one render_frame handed out.
 //
+// Bloom: RFWHIP_BLOOM=1|0 beside RFWHIP_DISPLAY (unset by default: nothing changes) sets display_bloom — with 1 every presented
+// display image gets the glow pyramid of include/rfwhip.h (rfwhip_bloom_image) in front of the tone map, on the device, behind the
+// gather and the meter's step; the other display_bloom_* settings keep their defaults.
+//
 // Noise estimate: RFWHIP_NOISE=1 (unset by default: nothing changes) turns the setting noise_estimate on (include/rfwhip.h,
 // rfwhip_get_noise); a host asks hiprtGetNoise when to stop converging.  It answers for the accumulator — with frames in flight,
 // for the newest frame enqueued, not the one render_frame handed out.
@@ -109,6 +113,12 @@ class Context final : public rfw::RenderContext
 		}
 		if (const char *sp = std::getenv("RFWHIP_EXPOSURE_SPEED"))
 			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_exposure_speed", sp));
+		if (const char *bl = std::getenv("RFWHIP_BLOOM"))
+		{
+			if (std::string(bl) != "0" && std::string(bl) != "1")
+				throw std::runtime_error("HipRT: RFWHIP_BLOOM must be \"0\" or \"1\"");
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_bloom", bl));
+		}
 		if (const char *nz = std::getenv("RFWHIP_NOISE"))
 		{
 			if (std::string(nz) != "0" && std::string(nz) != "1")

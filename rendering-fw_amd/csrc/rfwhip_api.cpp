@@ -212,7 +212,8 @@ enum KernelFamily
 	KF_METER_REDUCE = 10, // ... and its one-workgroup reduce k_meter_reduce, one launch per step
 	KF_PRIMARY_ORDER = 11, // the primary wave's ordering pass k_order4f (primary_order.h): ONE count per pass over the table, with or
 						   // without stage_timing (the milliseconds only with it)
-	KF_COUNT = 12
+	KF_BLOOM = 12, // bloom (bloom.h): the down, up and apply passes of a chain, one count per launch
+	KF_COUNT = 13
 };
 
 // A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
@@ -403,6 +404,18 @@ struct rfwhip_context
 	float meter_manual_E = 1.0f;		   // ... the value the next exposed display uploads (kept here: the copy's source)
 	dm::event_t ev_meter;				   // behind the last step enqueued on a caller's stream (rfwhip_display_stream)
 	bool ev_meter_ready = false, meter_pending = false;
+	// bloom (bloom.h): the display_bloom* settings; d_bloom_pyr = the levels 1 .. 8 of the target's pyramid, one behind the other,
+	// d_bloom_out = the image the display kernel reads, d_bloom_one = a float 1 (the E of an unexposed display) — allocated when the
+	// setting is first on with a render target.  bloom_ran: the levels of the last chain (0: none since rfwhip_init)
+	int bloom_on = 0, bloom_levels = 6;
+	float bloom_intensity = 0.2f, bloom_threshold = 1.0f, bloom_knee = 0.5f, bloom_scatter = 0.7f;
+	DevBuf d_bloom_pyr, d_bloom_out, d_bloom_one;
+	uint32_t bloom_ran = 0;
+	float bloom_kind_ms[4] = {};		   // family KF_BLOOM by kernel: k_bloom_down0, k_bloom_down, k_bloom_up, k_bloom_apply ...
+	uint32_t bloom_kind_launches[4] = {}; // ... (stage_timing = 1; the read-only setting display_bloom_time)
+	dm::event_t ev_bloom;			  // behind the last chain and the display kernel that read its image
+	void *bloom_stream = nullptr;	  // ... the stream they ran on
+	bool ev_bloom_ready = false, bloom_marked = false, bloom_pending = false;
 	// the noise estimate (noise.h): d_noise = two moments per local pixel, allocated while noise_estimate is on.  noise_live: the
 	// moments cover every sample of the accumulator (the setting was on at the last RESET / rfwhip_init and ever since)
 	int noise_estimate = 0;
@@ -637,7 +650,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
 					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
-					  &c->d_meter_rec, &c->d_meter_hist, &c->d_meter_part,
+					  &c->d_meter_rec, &c->d_meter_hist, &c->d_meter_part, &c->d_bloom_pyr, &c->d_bloom_out, &c->d_bloom_one,
 					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in,
 					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask, &c->d_lf_inst, &c->d_lf_bound, &c->d_lf_count, &c->d_lt_touched};
 	for (DevBuf *b : bufs)
@@ -647,6 +660,9 @@ static void free_all(rfwhip_context *c)
 	c->meter_have = false, c->meter_manual_stale = true, c->meter_pending = false;
 	if (c->ev_meter_ready)
 		dm::event_destroy(c->ev_meter), c->ev_meter_ready = false;
+	c->bloom_ran = 0, c->bloom_marked = false, c->bloom_pending = false, c->bloom_stream = nullptr;
+	if (c->ev_bloom_ready)
+		dm::event_destroy(c->ev_bloom), c->ev_bloom_ready = false;
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->dn_inst_ver_stale = true;
@@ -784,6 +800,7 @@ extern "C" int rfwhip_init(rfwhip_context *c, uint32_t width, uint32_t height)
 	c->d_dn_prev.free_(), c->d_dn_ids.free_(), c->d_dn_hist.free_(), c->d_dn_surf.free_();
 	c->guides_valid = false;
 	dn_clear_history(c);
+	c->d_bloom_pyr.free_(), c->d_bloom_out.free_(), c->bloom_ran = 0; // (the pyramid's layout is the target's; back with the next chain)
 	c->samples_total = 0, c->sample_origin = 0;
 	if (c->denoise && c->rank == 0)
 		RF_TRY(dn_ensure(c));
@@ -2295,6 +2312,11 @@ static int sync_all(rfwhip_context *c)
 		RF_TRY(dm::event_sync(c->ev_meter));
 		c->meter_pending = false;
 	}
+	if (c->bloom_pending) // (a bloom chain on a caller's stream writes the pyramid and the bloomed image)
+	{
+		RF_TRY(dm::event_sync(c->ev_bloom));
+		c->bloom_pending = false;
+	}
 	return 0;
 }
 
@@ -2997,6 +3019,10 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 		case KF_FINALIZE:
 			st.finalizeTime += ms;
 			break;
+		case KF_BLOOM:
+			if (sp.depth >= 0 && sp.depth < 4)
+				c->bloom_kind_ms[sp.depth] += ms, c->bloom_kind_launches[sp.depth]++;
+			break;
 		default:
 			break;
 		}
@@ -3417,6 +3443,102 @@ static int meter_step(rfwhip_context *c, const f4 *img, void *stream)
 	return meter_reduce(c, rtk::meter_records(v.pixels), stream);
 }
 
+// ---- bloom (settings "display_bloom*"; work items: bloom.h) ---------------------------------------------------------------------
+constexpr uint32_t BLOOM_MAX_LEVELS = 8u;
+// texels in front of level `level` (1-based) in d_bloom_pyr, and that level's size
+static size_t bloom_level_offset(uint32_t W, uint32_t H, uint32_t level, uint32_t *w, uint32_t *h)
+{
+	size_t off = 0;
+	for (uint32_t k = 1u;; k++)
+	{
+		W = (W + 1u) >> 1, H = (H + 1u) >> 1;
+		if (k == level)
+			break;
+		off += (size_t)W * H;
+	}
+	*w = W, *h = H;
+	return off;
+}
+// the pyramid of the target's size (all BLOOM_MAX_LEVELS levels: display_bloom_levels may change between chains), the bloomed image
+// and the two floats of d_bloom_one: [0] = 1, the E of an unexposed display; [1] = the E rfwhip_bloom_image was given
+static int bloom_ensure(rfwhip_context *c)
+{
+	if (!c->d_bloom_one.p)
+	{
+		static const float one[2] = {1.0f, 1.0f};
+		RF_TRY(c->d_bloom_one.ensure(sizeof(one)));
+		RF_TRY(dm::h2d(c->d_bloom_one.p, one, sizeof(one), c->stream));
+		RF_TRY(dm::sync(c->stream));
+	}
+	uint32_t w, h;
+	const size_t pyr = bloom_level_offset(c->W, c->H, BLOOM_MAX_LEVELS + 1u, &w, &h) * sizeof(f4), img = (size_t)c->W * c->H * sizeof(f4);
+	if (pyr > c->d_bloom_pyr.cap || img > c->d_bloom_out.cap || !c->d_bloom_pyr.p || !c->d_bloom_out.p)
+	{
+		RF_TRY(sync_all(c)); // (a chain in flight writes the buffers this reallocates)
+		RF_TRY(c->d_bloom_pyr.ensure(pyr));
+		RF_TRY(c->d_bloom_out.ensure(img));
+	}
+	return 0;
+}
+// the chain on the full W x H image `in` with the exposure *E (a device float), enqueued on `stream`: d_bloom_out is the bloomed
+// image, the levels stay in d_bloom_pyr as U_k.  A chain on another stream than the previous one waits for that one — and for the
+// display kernel that read its image — first
+static int bloom_chain(rfwhip_context *c, const f4 *in, const float *E, void *stream)
+{
+	RF_TRY(bloom_ensure(c));
+	if (c->bloom_marked && c->bloom_stream != stream)
+		RF_TRY(dm::stream_wait_event(stream, c->ev_bloom));
+	rtk::BloomParams b;
+	b.intensity = c->bloom_intensity, b.threshold = c->bloom_threshold, b.knee = c->bloom_knee, b.scatter = c->bloom_scatter;
+	const uint32_t n = rtk::bloom_levels(c->W, c->H, (uint32_t)c->bloom_levels);
+	f4 *lv[BLOOM_MAX_LEVELS + 1];
+	uint32_t w[BLOOM_MAX_LEVELS + 1], h[BLOOM_MAX_LEVELS + 1];
+	lv[0] = nullptr, w[0] = c->W, h[0] = c->H;
+	for (uint32_t k = 1u; k <= n; k++)
+		lv[k] = c->d_bloom_pyr.as<f4>() + bloom_level_offset(c->W, c->H, k, &w[k], &h[k]);
+	// (a span per launch, its `depth` the kernel: 0 down0, 1 down, 2 up, 3 apply)
+	for (uint32_t k = 0u; k < n; k++)
+	{
+		rtk::BloomDownView v;
+		v.src = k ? lv[k] : in, v.dst = lv[k + 1u], v.W = w[k], v.H = h[k], v.Wn = w[k + 1u], v.Hn = h[k + 1u], v.E = E;
+		StageTimer t(c, KF_BLOOM, k ? 1 : 0, stream);
+		if (k == 0u)
+			rtk::launch_bloom_down0(v, b, stream);
+		else
+			rtk::launch_bloom_down(v, stream);
+		t.stop(1);
+	}
+	for (uint32_t k = n - 1u; k >= 1u; k--)
+	{
+		rtk::BloomUpView v;
+		v.level = lv[k], v.next = lv[k + 1u], v.W = w[k], v.H = h[k], v.Wn = w[k + 1u], v.Hn = h[k + 1u];
+		StageTimer t(c, KF_BLOOM, 2, stream);
+		rtk::launch_bloom_up(v, b, stream);
+		t.stop(1);
+	}
+	rtk::BloomApplyView a;
+	a.in = in, a.next = lv[1], a.out = c->d_bloom_out.as<f4>(), a.W = c->W, a.H = c->H, a.Wn = w[1], a.Hn = h[1];
+	{
+		StageTimer t(c, KF_BLOOM, 3, stream);
+		rtk::launch_bloom_apply(a, b, stream);
+		t.stop(1);
+	}
+	c->bloom_ran = n;
+	return dm::last_launch_error();
+}
+// behind the last reader of d_bloom_out on `stream`
+static int bloom_mark(rfwhip_context *c, void *stream)
+{
+	if (!c->ev_bloom_ready)
+	{
+		RF_TRY(dm::event_create(&c->ev_bloom, false));
+		c->ev_bloom_ready = true;
+	}
+	RF_TRY(dm::event_record(c->ev_bloom, stream));
+	c->bloom_marked = true, c->bloom_stream = stream, c->bloom_pending = stream != c->stream;
+	return 0;
+}
+
 // one launch on `stream`: the full W x H float4 image `in` -> `out` in `format`, with the context's display settings.
 // display_exposure = auto: the exposed kernel with the record's E — `step`: behind one step of the meter on `in`;
 // manual with display_exposure_ev != 0: the exposed kernel with E = exp2(ev), written into the record when it is not there yet;
@@ -3447,17 +3569,28 @@ static int display_enqueue(rfwhip_context *c, const f4 *in, void *out, float bri
 			c->meter_manual_stale = false;
 		}
 	}
-	StageTimer t(c, KF_DISPLAY, -1, stream);
-	if (exposed)
+	// display_bloom = 1: the bloom chain on `in` under that E (the record's first word), behind the meter's step; the display kernel
+	// reads the chain's image
+	if (c->bloom_on)
 	{
-		rtk::ExposureView e;
-		e.rec = c->d_meter_rec.as<rtk::MeterRecord>();
-		rtk::launch_display_exposed(v, e, stream);
+		RF_TRY(bloom_ensure(c));
+		RF_TRY(bloom_chain(c, in, exposed ? c->d_meter_rec.as<float>() : c->d_bloom_one.as<float>(), stream));
+		v.in = c->d_bloom_out.as<f4>();
 	}
-	else
-		rtk::launch_display(v, stream);
-	t.stop(1);
-	return dm::last_launch_error();
+	{
+		StageTimer t(c, KF_DISPLAY, -1, stream);
+		if (exposed)
+		{
+			rtk::ExposureView e;
+			e.rec = c->d_meter_rec.as<rtk::MeterRecord>();
+			rtk::launch_display_exposed(v, e, stream);
+		}
+		else
+			rtk::launch_display(v, stream);
+		t.stop(1);
+	}
+	RF_TRY(dm::last_launch_error());
+	return c->bloom_on ? bloom_mark(c, stream) : 0;
 }
 // brightness and contrast of the presented image: the camera of the last render; before the first one the reference's defaults
 // (Camera.cpp:8-9)
@@ -3535,6 +3668,51 @@ extern "C" int rfwhip_display_image(rfwhip_context *c, const float *rgba_in, flo
 	RF_TRY(dm::h2d(c->d_present.p, rgba_in, px * sizeof(f4), c->stream));
 	RF_TRY(display_enqueue(c, c->d_present.as<f4>(), c->d_display.p, brightness, contrast, format, c->stream, true));
 	RF_TRY(dm::d2h(out_host, c->d_display.p, px * display_pixel_bytes(format), c->stream));
+	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_bloom_image(rfwhip_context *c, const float *rgba_in, float exposure, float *rgba_out)
+{
+	CTX_ENTER(c);
+	if (!rgba_in || !rgba_out)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_bloom_image: null image");
+	if (!(exposure >= 0.0f && exposure < INFINITY))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_bloom_image: the exposure must be a finite number >= 0");
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	RF_TRY(sync_all(c));
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
+	RF_TRY(bloom_ensure(c));
+	RF_TRY(dm::h2d(c->d_present.p, rgba_in, px * sizeof(f4), c->stream));
+	RF_TRY(dm::h2d(c->d_bloom_one.as<float>() + 1, &exposure, sizeof(float), c->stream));
+	RF_TRY(bloom_chain(c, c->d_present.as<f4>(), c->d_bloom_one.as<float>() + 1, c->stream));
+	RF_TRY(bloom_mark(c, c->stream));
+	RF_TRY(dm::d2h(rgba_out, c->d_bloom_out.p, px * sizeof(f4), c->stream));
+	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_read_bloom_level(rfwhip_context *c, int level, float *out, size_t cap, uint32_t *w, uint32_t *h)
+{
+	CTX_ENTER(c);
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	if (!c->bloom_ran)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_bloom_level: no bloom chain has run");
+	if (level < 1 || level > (int)c->bloom_ran)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_bloom_level: level %d, the last chain ran levels 1 .. %u", level, c->bloom_ran);
+	uint32_t lw, lh;
+	const size_t off = bloom_level_offset(c->W, c->H, (uint32_t)level, &lw, &lh);
+	if (w)
+		*w = lw;
+	if (h)
+		*h = lh;
+	if (!out)
+		return RFWHIP_OK; // (the size alone)
+	if (cap < (size_t)lw * lh * 4u)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_bloom_level: level %d is %u x %u float4, room for %zu floats", level, lw, lh, cap);
+	RF_TRY(sync_all(c));
+	RF_TRY(dm::d2h(out, c->d_bloom_pyr.as<f4>() + off, (size_t)lw * lh * sizeof(f4), c->stream));
 	return dm::sync(c->stream);
 }
 
@@ -4258,6 +4436,33 @@ static const Setting k_settings[] = {
 	 GET { return put(out, cap, "%g", c->exposure_min_ev); }, false},
 	{"display_exposure_max_ev", SET { return set_exposure_pair(c, c->exposure_min_ev, c->exposure_max_ev, false, key, value, "be a finite number in [-64, 64], at least display_exposure_min_ev"); },
 	 GET { return put(out, cap, "%g", c->exposure_max_ev); }, false},
+	// bloom (bloom.h): the glow pyramid rfwhip_read_display* / rfwhip_display_* add in front of the tone map
+	{"display_bloom", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 c->bloom_on = on;
+		 return on && c->W ? bloom_ensure(c) : RFWHIP_OK; },
+	 GET_INT(bloom_on), false},
+	{"display_bloom_intensity", SET { return set_float(c->bloom_intensity, key, value, [](float f) { return f >= 0.0f && f <= 16.0f; }, "be in [0, 16]", false); },
+	 GET { return put(out, cap, "%g", c->bloom_intensity); }, false},
+	{"display_bloom_threshold", SET { return set_float(c->bloom_threshold, key, value, [](float f) { return f >= 0.0f && f < 1e30f; }, "be a finite number >= 0", false); },
+	 GET { return put(out, cap, "%g", c->bloom_threshold); }, false},
+	{"display_bloom_knee", SET { return set_float(c->bloom_knee, key, value, [](float f) { return f >= 0.0f && f <= 1.0f; }, "be in [0, 1]", false); },
+	 GET { return put(out, cap, "%g", c->bloom_knee); }, false},
+	{"display_bloom_scatter", SET { return set_float(c->bloom_scatter, key, value, [](float f) { return f >= 0.0f && f <= 1.0f; }, "be in [0, 1]", false); },
+	 GET { return put(out, cap, "%g", c->bloom_scatter); }, false},
+	{"display_bloom_levels", SET {
+		 char *end = nullptr;
+		 const long n = strtol(value, &end, 10);
+		 if (!end || *end || end == value || n < 1 || n > (long)BLOOM_MAX_LEVELS)
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be a whole number in [1, 8]", key);
+		 c->bloom_levels = (int)n;
+		 return RFWHIP_OK; },
+	 GET_INT(bloom_levels), false},
+	// (read-only, stage_timing = 1) family 12 by kernel since its last reset: the milliseconds of k_bloom_down0, k_bloom_down,
+	// k_bloom_up, k_bloom_apply, then their launches
+	{"display_bloom_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %u %u %u %u", c->bloom_kind_ms[0], c->bloom_kind_ms[1], c->bloom_kind_ms[2], c->bloom_kind_ms[3],
+													  c->bloom_kind_launches[0], c->bloom_kind_launches[1], c->bloom_kind_launches[2], c->bloom_kind_launches[3]); }, false},
 	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
 	{"noise_estimate", SET {
 		 bool on;
@@ -4412,13 +4617,16 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)
 		*launches = c->kernel_launches[which];
 	if (reset)
 		c->kernel_ms[which] = 0.0f, c->kernel_launches[which] = 0;
+	if (reset && which == KF_BLOOM)
+		for (int k = 0; k < 4; k++)
+			c->bloom_kind_ms[k] = 0.0f, c->bloom_kind_launches[k] = 0;
 	return RFWHIP_OK;
 }
 
