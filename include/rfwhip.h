@@ -256,6 +256,71 @@ RFWHIP_API int rfwhip_meter_histogram(rfwhip_context *ctx, const uint32_t bins[R
 RFWHIP_API int rfwhip_bloom_image(rfwhip_context *ctx, const float *rgba_in, float exposure, float *rgba_out);
 RFWHIP_API int rfwhip_read_bloom_level(rfwhip_context *ctx, int level, float *out, size_t cap, uint32_t *w, uint32_t *h);
 
+/* ---- colour grading and dither: white balance, CDL, a 3D LUT, ordered dither ------------------------------------------------------
+ * With display_grade = 1 every entry point of the display stage above launches ONE kernel, k_display_graded, in place of the display
+ * kernel — behind the meter's step and the bloom chain, which see the ungraded image; nothing is read back.  csrc/display_grade.h has
+ * the work items; DESIGN.md section 20.  Off by default: nothing is allocated, no new kernel runs, every byte is what it was.
+ *   Settings (not listed by rfwhip_get_settings):
+ *     display_grade            = "0" (default) | "1"
+ *     display_wb_temperature   = T in kelvin in [1667, 25000] (default 6500): the light the image was lit by; below 6500 = a warmer
+ *                                light, the image moves towards blue
+ *     display_grade_slope / display_grade_offset / display_grade_power = one number for the three channels or three "r g b"
+ *                                (defaults 1 / 0 / 1); slope finite and >= 0, offset finite, power finite and > 0; read back as three
+ *     display_grade_saturation = in [0, 4] (default 1)
+ *     display_dither           = "0" (default) | "1": ordered dither of the RGBA8 output; RGBA32F ignores it
+ *     display_lut              (read-only) the size n of the LUT set with rfwhip_set_display_lut, 0 without one
+ *     display_grade_time       (read-only, stage_timing = 1) kernel family 13 since its last reset: the milliseconds of
+ *                                k_display_graded, then its launches
+ *   A value that does not parse or lies outside its range is refused and the setting keeps its value.
+ *   Per texel, with E the exposure the display kernel would apply (the meter record's; without one nothing is multiplied):
+ *     x    <- x E
+ *     LINEAR, when the white balance, a CDL channel or the saturation is not at its identity (else x goes to the tone step as it is):
+ *       c    = min(max(x, 0), 65504) per colour channel (max = fmaxf: a NaN channel is 0); alpha is untouched throughout
+ *       WB   c <- M_wb c, row i: fmaf(M_i2, c_b, fmaf(M_i1, c_g, M_i0 c_r)); M_wb is built in double and stored as float32
+ *       CDL  c_i <- powf(max(fmaf(c_i, slope_i, offset_i), 0), power_i), for every channel whose three parameters are not (1, 0, 1);
+ *            power_i = 1: the clamped value itself, without a powf
+ *       SAT  Y = fmaf(0.0722, c_b, fmaf(0.7152, c_g, 0.2126 c_r));  c_i <- fmaf(sat, c_i - Y, Y)
+ *     TONE v = the tone step of rfwhip_read_display above on the result (brightness / contrast, aces | none, clamp to [0, 1])
+ *     LUT  v <- clamp(tetra(L, v), 0, 1), when a LUT is set (entries outside [0, 1], a look's overshoot, are accepted; what the
+ *          step hands on is clamped, so FXAA, the encoding and the bytes see values in [0, 1] as without a LUT)
+ *     FXAA, ENCODE as above, on the graded values
+ *     DITHER (RGBA8, display_dither = 1): byte = clamp(rint(255 v + d(x, y) - 0.5), 0, 255) for r, g, b, ties to even, decided without a
+ *          rounding of 255 v + d; alpha as without.  d(x, y) = (B + 0.5) / 256, B = the 16 x 16 Bayer index of (x & 15, y & 15): with
+ *          q = x ^ y, bit b (0 .. 3) of q is bit 2 (3 - b) + 1 of B and bit b of y is bit 2 (3 - b); the 2 x 2 case is [[0, 2], [3, 1]].
+ *          The same pattern for the three channels, a pure function of the pixel: two reads of a frame are equal.
+ *   A step at its identity (T = 6500; slope 1, offset 0, power 1 of a channel; saturation 1; no LUT; dither 0; no E) is skipped, not
+ *   multiplied through: display_grade = 1 with everything at its default is bit for bit display_grade = 0, for every input.
+ *   WHITE BALANCE.  The white point (x_T, y_T) of T on the Planckian locus (Kim et al.'s cubic splines):
+ *     x = -0.2661239e9 / T^3 - 0.2343589e6 / T^2 + 0.8776956e3 / T + 0.179910      T <= 4000
+ *         -3.0258469e9 / T^3 + 2.1070379e6 / T^2 + 0.2226347e3 / T + 0.240390      T >  4000
+ *     y = -1.1063814 x^3 - 1.34811020 x^2 + 2.18555832 x - 0.20219683              T <= 2222
+ *         -0.9549476 x^3 - 1.37418593 x^2 + 2.09137015 x - 0.16748867              2222 < T <= 4000
+ *          3.0817580 x^3 - 5.87338670 x^2 + 3.75112997 x - 0.37001483              T >  4000
+ *     XYZ_T = (x / y, 1, (1 - x - y) / y);  rho = B XYZ;  M_wb = M_xyz->rgb B^-1 diag(rho_6500 / rho_T) B M_rgb->xyz
+ *     B = the Bradford matrix (0.8951, 0.2664, -0.1614; -0.7502, 1.7135, 0.0367; 0.0389, -0.0685, 1.0296), M_rgb->xyz = linear Rec.709 / D65
+ *     (0.4124564, 0.3575761, 0.1804375; 0.2126729, 0.7151522, 0.0721750; 0.0193339, 0.1191920, 0.9503041), M_xyz->rgb its inverse.
+ *     The reference white is the locus point of 6500 K itself: the default is exactly the identity (the step is skipped).  One
+ *     parameter: tint, a white point off the locus, is not supported.
+ *   LUT.  L = n^3 RGB float triples, 2 <= n <= 65, red fastest (the order of a .cube file), uploaded once as float4.  tetra, per colour:
+ *     p = v (n - 1) per channel; i = min((int)p, n - 2); f = p - i; the three fractions in descending order f_a >= f_b >= f_c, ties in
+ *     channel order r, g, b; V0 = L[i], V1 = the lattice point one step along axis a, V2 = one further step along b,
+ *     V3 = L[i + (1, 1, 1)]; w = (1 - f_a, f_a - f_b, f_b - f_c, f_c); out = fmaf(w3, V3, fmaf(w2, V2, fmaf(w1, V1, w0 V0))).
+ *     A lattice colour, 1.0 included, returns its entry bit for bit whenever n - 1 is a power of two.
+ * rfwhip_set_display_lut: rgb = n^3 triples; null or n = 0 removes the LUT.  A non-finite entry or n outside [2, 65]:
+ * RFWHIP_ERR_INVALID_ARGUMENT, the old LUT stays.  In a group the LUT belongs to the root's context (rfwhip_group_set_display_lut;
+ * in a process that does not hold the root the call does nothing and returns RFWHIP_OK).
+ * rfwhip_set_display_lut_cube: the same from the text of a .cube file — LUT_3D_SIZE n (required, once), optional TITLE and "#"
+ * comments, DOMAIN_MIN 0 0 0 / DOMAIN_MAX 1 1 1 the only domains accepted, then exactly n^3 lines of three numbers; a 1D LUT, any
+ * other keyword or another count is refused and the old LUT stays.
+ * rfwhip_get_display_lut: *n = the size (0: none; may be null); `rgb` holds `cap` floats and needs 3 n^3 (null: the size alone).
+ * Known-answer hook rfwhip_grade_colors: `count` RGB triples through k_kat_grade under the current settings (whatever display_grade
+ * says) — which = 0: the LINEAR block on linear colours; 1: tetra on display colours, clamped to [0, 1] first, its result NOT clamped (without a LUT:
+ * the colours themselves).  RFWHIP_ERR_STATE before rfwhip_init. */
+RFWHIP_API int rfwhip_set_display_lut(rfwhip_context *ctx, const float *rgb, uint32_t n);
+RFWHIP_API int rfwhip_set_display_lut_cube(rfwhip_context *ctx, const char *text, size_t len);
+RFWHIP_API int rfwhip_get_display_lut(rfwhip_context *ctx, float *rgb, size_t cap, uint32_t *n);
+RFWHIP_API int rfwhip_grade_colors(rfwhip_context *ctx, int which, size_t count, const float *rgb_in, float *rgb_out);
+
 /* ---- noise estimate: when has a progressive render converged? ---------------------------------------------------------------
  * With noise_estimate = 1 the resolve of every rfwhip_render (its variant k_resolve_noise) keeps two floats per pixel beside the
  * accumulator — sumY, the sum of the luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel's samples (a sample's value is what
@@ -423,6 +488,9 @@ RFWHIP_API int rfwhip_group_get_adaptive(rfwhip_group *group, rfwhip_adaptive_st
 /* The exposure meter of a group (see rfwhip_get_meter): the root's record — the root shows the gathered image, so its meter is the
  * group's.  Waits for the steps of the reads and presents enqueued so far. */
 RFWHIP_API int rfwhip_group_get_meter(rfwhip_group *group, rfwhip_meter_stats *stats);
+/* The LUT of the display stage (rfwhip_set_display_lut above), for the root's context: the display kernel runs there. */
+RFWHIP_API int rfwhip_group_set_display_lut(rfwhip_group *group, const float *rgb, uint32_t n);
+RFWHIP_API int rfwhip_group_set_display_lut_cube(rfwhip_group *group, const char *text, size_t len);
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
 RFWHIP_API int rfwhip_group_present_display_wait(rfwhip_group *group, int slot, const void **out_host, int *format);
@@ -665,6 +733,8 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   display_exposure / display_exposure_ev / _key / _low / _high / _speed / _min_ev / _max_ev = the exposure meter, see
  *                  rfwhip_get_meter above.
  *   display_bloom / display_bloom_intensity / _threshold / _knee / _scatter / _levels = bloom, see rfwhip_bloom_image above.
+ *   display_grade / display_wb_temperature / display_grade_slope / _offset / _power / _saturation / display_dither = colour grading
+ *                  and dither, see rfwhip_set_display_lut above.
  *   noise_estimate / noise_floor / noise_threshold = the noise estimate, see rfwhip_get_noise above.
  *   adaptive_sampling / adaptive_min_samples / adaptive_every = adaptive sampling, see rfwhip_get_adaptive above.
  *   lights_follow_geometry = "0" (default) | "1": rfwhip_update derives the area lights of emissive geometry on the device and
@@ -702,7 +772,8 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * reads a second float node table whose nodes hold their children near to far as seen from the camera, rewritten in front of the
  * call when the camera position or a tree has changed since — `launches` counts those passes, one per rewrite, with or without
  * stage_timing; the image does not depend on it.  12 bloom: one count per launch of a chain, 2 x the levels it ran (the down
- * passes, the up passes and the apply pass). */
+ * passes, the up passes and the apply pass).  13 grade: k_display_graded, one launch per displayed image with display_grade = 1 (in
+ * place of family 7's). */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

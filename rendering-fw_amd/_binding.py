@@ -100,6 +100,10 @@ class CoreBinding:
                                   "meter_histogram": (i32, [vp, vp, u32, C.POINTER(abi.MeterStats)]),
                                   "bloom_image": (i32, [vp, vp, C.c_float, vp]),
                                   "read_bloom_level": (i32, [vp, i32, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
+                                  "set_display_lut": (i32, [vp, vp, u32]),
+                                  "set_display_lut_cube": (i32, [vp, C.c_char_p, sz]),
+                                  "get_display_lut": (i32, [vp, vp, sz, C.POINTER(u32)]),
+                                  "grade_colors": (i32, [vp, i32, sz, vp, vp]),
                                   "get_noise": (i32, [vp, C.POINTER(abi.NoiseStats)]),
                                   "read_noise_map": (i32, [vp, vp]),
                                   "read_noise_tiles": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
@@ -472,6 +476,39 @@ class CoreBinding:
         self._check(self._fn("read_bloom_level")(self._ctx, int(level), out.ctypes.data, out.size, C.byref(w), C.byref(h)))
         return out
 
+    # ---- colour grading and dither (include/rfwhip.h, rfwhip_set_display_lut; setting display_grade = 1) ------------
+    def set_display_lut(self, lut):
+        """The display stage's 3D LUT: an n x n x n x 3 array indexed [b][g][r] (red fastest, the order of a .cube file) or any
+        array of 3 n^3 floats in that order; None removes it."""
+        a, n = _lut_array(lut)
+        self._check(self._fn("set_display_lut")(self._ctx, a.ctypes.data if n else None, n))
+
+    def set_display_lut_cube(self, text):
+        """The LUT from the text of a .cube file (str or bytes)."""
+        raw = _cube_bytes(text)
+        self._check(self._fn("set_display_lut_cube")(self._ctx, raw, len(raw)))
+
+    def load_cube(self, path):
+        self.set_display_lut_cube(_read_file(path))
+
+    def get_display_lut(self):
+        """The LUT as an n x n x n x 3 float32 array indexed [b][g][r], or None."""
+        n = C.c_uint32()
+        self._check(self._fn("get_display_lut")(self._ctx, None, 0, C.byref(n)))
+        if not n.value:
+            return None
+        out = np.empty((n.value, n.value, n.value, 3), np.float32)
+        self._check(self._fn("get_display_lut")(self._ctx, out.ctypes.data, out.size, C.byref(n)))
+        return out
+
+    def grade_colors(self, which, rgb):
+        """Known-answer hook: colours (... x 3) through k_kat_grade under the current settings — which = 0: white balance, CDL and
+        saturation on linear colours; 1: the LUT on display colours."""
+        src = np.ascontiguousarray(rgb, dtype=np.float32)
+        out = np.empty_like(src)
+        self._check(self._fn("grade_colors")(self._ctx, int(which), src.size // 3, src.ctypes.data, out.ctypes.data))
+        return out
+
     # ---- noise estimate (include/rfwhip.h, rfwhip_get_noise; setting noise_estimate = 1) ---------------------------
     def get_noise(self):
         """The noise of the accumulated image as a dict: samples, pixels, converged, mean_error, max_error, threshold.
@@ -591,10 +628,11 @@ class CoreBinding:
     METER_HIST, METER_REDUCE = 9, 10  # ... and of the exposure meter's two kernels (one launch each per step)
     PRIMARY_ORDER = 11  # ... and of the primary wave's ordering pass (one count per rewrite of the camera-ordered node table)
     BLOOM = 12  # ... and of bloom (one count per launch of a chain: 2 x the levels it ran)
+    GRADE = 13  # ... and of the graded display kernel (one launch per displayed image with display_grade = 1)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -700,6 +738,27 @@ class CoreBinding:
         return out
 
 
+# ---- what CoreBinding and RenderGroup share of the display stage's LUT (rfwhip_set_display_lut / rfwhip_group_set_display_lut) ----
+def _lut_array(lut):
+    """(the LUT as a contiguous float32 array, n); (None, 0) for None: the call that removes the LUT."""
+    if lut is None:
+        return None, 0
+    a = np.ascontiguousarray(lut, dtype=np.float32)
+    n = a.shape[0] if a.ndim == 4 else int(round((a.size / 3.0) ** (1.0 / 3.0)))
+    if a.size != 3 * n ** 3:
+        raise ValueError("a LUT holds 3 n^3 floats, got %d" % a.size)
+    return a, n
+
+
+def _cube_bytes(text):
+    return text.encode() if isinstance(text, str) else bytes(text)
+
+
+def _read_file(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
 class RenderGroup:
     """n devices driven by ONE host thread through rfwhip_group_* (include/rfwhip.h): context i renders the strips of rank i
     of world n, one gather per presented frame lands the image on the root's device.  Looks like one RenderContext to the
@@ -724,7 +783,9 @@ class RenderGroup:
                                 ("group_present_display_wait", i32, [vp, i32, C.POINTER(vp), C.POINTER(i32)]),
                                 ("group_get_noise", i32, [vp, C.POINTER(abi.NoiseStats)]),
                                 ("group_get_adaptive", i32, [vp, C.POINTER(abi.AdaptiveStats)]),
-                                ("group_get_meter", i32, [vp, C.POINTER(abi.MeterStats)])]:
+                                ("group_get_meter", i32, [vp, C.POINTER(abi.MeterStats)]),
+                                ("group_set_display_lut", i32, [vp, vp, u32]),
+                                ("group_set_display_lut_cube", i32, [vp, C.c_char_p, C.c_size_t])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -742,6 +803,18 @@ class RenderGroup:
     def _check(self, code):
         if code != 0:
             raise RuntimeError((self._fn("last_error")() or b"unknown error").decode(errors="replace"))
+
+    # the display stage's LUT belongs to the root's context (include/rfwhip.h, rfwhip_group_set_display_lut)
+    def set_display_lut(self, lut):
+        a, n = _lut_array(lut)
+        self._check(self._fn("group_set_display_lut")(self._g, a.ctypes.data if n else None, n))
+
+    def set_display_lut_cube(self, text):
+        raw = _cube_bytes(text)
+        self._check(self._fn("group_set_display_lut_cube")(self._g, raw, len(raw)))
+
+    def load_cube(self, path):
+        self.set_display_lut_cube(_read_file(path))
 
     def __getattr__(self, name):
         # scene setters and friends: the same call on every context (set_sky, set_mesh, set_lights, set_blue_noise, ...)

@@ -154,6 +154,21 @@ struct BloomApplyView
 	uint32_t W, H, Wn, Hn;
 };
 
+// Colour grading and dither (display_grade.h): what k_display_graded takes beside the DisplayView.  flags: the GR_* bits of the steps
+// that are NOT at the identity, set by the host; rec: the record whose E the kernel applies (GR_EXPOSED, else unread);
+// lut: n^3 float4, red fastest (GR_LUT, else unread); wb: M_wb row by row
+constexpr uint32_t GR_EXPOSED = 1u, GR_WB = 2u, GR_CDL_R = 4u, GR_CDL_G = 8u, GR_CDL_B = 16u, GR_SAT = 32u, GR_LUT = 64u, GR_DITHER = 128u;
+constexpr uint32_t GR_LUT_MIN = 2u, GR_LUT_MAX = 65u; // a LUT's size n: at most 65^3 x 16 bytes = 4.4 MB
+struct GradeView
+{
+	const MeterRecord *rec;
+	const rt::f4 *lut;
+	uint32_t n, flags;
+	float wb[9];
+	float slope[3], offset[3], power[3];
+	float sat;
+};
+
 // The noise estimate (noise.h).  One record per NZ_TILE_X x NZ_TILE_Y noise tile (= rfwhip_noise_tile) and the one record k_noise_final leaves
 constexpr uint32_t NZ_TILE_X = 32, NZ_TILE_Y = 8;
 struct NoiseTile
@@ -276,6 +291,10 @@ void launch_bloom_down0(const BloomDownView &v, const BloomParams &b, stream_t s
 void launch_bloom_down(const BloomDownView &v, stream_t s);
 void launch_bloom_up(const BloomUpView &v, const BloomParams &b, stream_t s);
 void launch_bloom_apply(const BloomApplyView &v, const BloomParams &b, stream_t s);
+// colour grading and dither (display_grade.h): k_display_graded in place of k_display / k_display_exposed, and the known-answer
+// kernel k_kat_grade: n records of three floats, which = 0 (white balance, CDL, saturation) | 1 (the LUT)
+void launch_display_graded(const DisplayView &v, const GradeView &g, stream_t s);
+void launch_kat_grade(const GradeView &g, int which, const float *in, float *out, uint32_t n, stream_t s);
 // a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
 rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,

@@ -978,6 +978,8 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 #include "metering.h"
 // bloom: the HDR glow pyramid in front of the tone map (work items shared with the emulation)
 #include "bloom.h"
+// colour grading and dither: white balance, CDL, 3D LUT, ordered dither (work items shared with the emulation)
+#include "display_grade.h"
 // moving emitters: the area lights of emissive geometry and the light tree's refit (work items shared with the emulation)
 #include "light_follow.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }
@@ -2586,7 +2588,9 @@ template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const Di
 	}
 }
 // k_display_exposed (metering.h): k_display with every colour channel of a texel times E in front of dp_tone.  A kernel of its own,
-// its body restated: k_display keeps its code to the instruction
+// its body restated: k_display keeps its code to the instruction.  (display_grade.h's dg_exposed / dg_texel restate this expression,
+// dp_tone(v, dp_exposed(c, E)), so that the compiler contracts x E + offset there as it does here: the defaults of display_grade = 1
+// are bit for bit this kernel's output, which tests/test_display_grade_gpu.py asserts.  Change the two together.)
 RT_FN f4 dp_exposed(const f4 &c, float E) { return mk4(c.x * E, c.y * E, c.z * E, c.w); }
 template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display_exposed(const DisplayView v, const ExposureView e)
 {
@@ -3094,6 +3098,72 @@ void launch_light_tree_refit(LightTreeNode *nodes, const LightTreeLevels &lv, co
 						   lv.count[l], area, n_area, bound, touched);
 	if (top)
 		hipLaunchKernelGGL(k_lt_refit_top, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nodes, lv, top, area, n_area, bound, touched);
+}
+
+// ---- colour grading and dither (display_grade.h).  k_display_graded: k_display_exposed with dg_texel in place of dp_tone in front of
+// the LDS tile — the tile and its halo hold graded texels — and dg_item behind it.  A kernel of its own, its body restated: k_display
+// and k_display_exposed keep their code to the instruction.  The same tiling, the same contiguous run per wave and store; the LUT's
+// four vertices of a texel are four independent 16-byte loads from a table that stays in L2. ----
+template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display_graded(const DisplayView v, const GradeView g)
+{
+	const float E = (g.flags & GR_EXPOSED) ? g.rec->E : 1.0f; // (a uniform address: one scalar load)
+	if constexpr (!FXAA)
+	{
+		const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+		if (i >= (size_t)v.W * v.H)
+			return;
+		const f4 c = v.in[i];
+		const f3 t = dg_texel(v, g, c, E);
+		dg_item<false>(v, g, [&](int, int) -> f3 { return t; }, (int)(i % v.W), (int)(i / v.W), c.w);
+	}
+	else
+	{
+		__shared__ float s_rgb[3][DP_LDS_H * DP_PITCH];
+		const int W = (int)v.W, H = (int)v.H;
+		const int x0 = (int)blockIdx.x * DP_TILE_X - DP_HALO, y0 = (int)blockIdx.y * DP_TILE_Y - DP_HALO;
+		for (int k = (int)threadIdx.x; k < DP_LDS_W * DP_LDS_H; k += BLOCK)
+		{
+			const int ly = k / DP_LDS_W, lx = k - ly * DP_LDS_W, gx = x0 + lx, gy = y0 + ly;
+			if (gx >= 0 && gx < W && gy >= 0 && gy < H) // (texels outside the image are never fetched: the taps clamp to the edge first)
+			{
+				const f3 t = dg_texel(v, g, v.in[(size_t)gy * v.W + (size_t)gx], E);
+				const int o = ly * DP_PITCH + lx;
+				s_rgb[0][o] = t.x, s_rgb[1][o] = t.y, s_rgb[2][o] = t.z;
+			}
+		}
+		__syncthreads();
+		// (xi, yi) is inside the image and within DP_HALO of a pixel of this tile: inside the LDS tile
+		const auto fetch = [&](int xi, int yi) -> f3 {
+			const int o = (yi - y0) * DP_PITCH + (xi - x0);
+			return mk3(s_rgb[0][o], s_rgb[1][o], s_rgb[2][o]);
+		};
+		const int x = (int)blockIdx.x * DP_TILE_X + (int)(threadIdx.x & 63u);
+		const int yw = (int)blockIdx.y * DP_TILE_Y + (int)(threadIdx.x >> 6) * (DP_TILE_Y / 4);
+		if (x < W)
+			for (int r = 0; r < DP_TILE_Y / 4; r++)
+				if (yw + r < H)
+					dg_item<true>(v, g, fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
+	}
+}
+// rfwhip_grade_colors: one lane per colour
+__global__ void __launch_bounds__(BLOCK) k_kat_grade(const GradeView g, int which, const float *in, float *out, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < n)
+		dg_kat_item(g, which, in, out, i);
+}
+void launch_display_graded(const DisplayView &v, const GradeView &g, stream_t s)
+{
+	if (v.fxaa)
+		hipLaunchKernelGGL(k_display_graded<true>, dim3((v.W + DP_TILE_X - 1) / DP_TILE_X, (v.H + DP_TILE_Y - 1) / DP_TILE_Y), dim3(BLOCK), 0,
+						   (hipStream_t)s, v, g);
+	else
+		hipLaunchKernelGGL(k_display_graded<false>, dim3((uint32_t)(((size_t)v.W * v.H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)s, v, g);
+}
+void launch_kat_grade(const GradeView &g, int which, const float *in, float *out, uint32_t n, stream_t s)
+{
+	if (n)
+		hipLaunchKernelGGL(k_kat_grade, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, g, which, in, out, n);
 }
 
 // ================================================================================================================

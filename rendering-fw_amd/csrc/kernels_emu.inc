@@ -622,6 +622,28 @@ void launch_display_exposed(const DisplayView &v, const ExposureView &e, stream_
 				dp_item<false>(v, fetch, (int)x, (int)y, a);
 		}
 }
+// colour grading and dither (display_grade.h): the graded texel where it is read, the same item behind it
+void launch_display_graded(const DisplayView &v, const GradeView &g, stream_t s)
+{
+	EMU_DEFER(s, launch_display_graded(v, g, s));
+	const float E = (g.flags & GR_EXPOSED) ? g.rec->E : 1.0f;
+	const auto fetch = [&](int xi, int yi) -> f3 { return dg_texel(v, g, v.in[(size_t)yi * v.W + (size_t)xi], E); };
+	for (uint32_t y = 0; y < v.H; y++)
+		for (uint32_t x = 0; x < v.W; x++)
+		{
+			const float a = v.in[(size_t)y * v.W + x].w;
+			if (v.fxaa)
+				dg_item<true>(v, g, fetch, (int)x, (int)y, a);
+			else
+				dg_item<false>(v, g, fetch, (int)x, (int)y, a);
+		}
+}
+void launch_kat_grade(const GradeView &g, int which, const float *in, float *out, uint32_t n, stream_t s)
+{
+	EMU_DEFER(s, launch_kat_grade(g, which, in, out, n, s));
+	for (uint32_t i = 0; i < n; i++)
+		dg_kat_item(g, which, in, out, i);
+}
 // the exposure meter (metering.h): the same partial records, range by range, and the same fold
 uint32_t meter_records(uint32_t pixels) { return (uint32_t)(((size_t)pixels + MT_RANGE - 1u) / MT_RANGE); }
 void launch_meter_hist(const MeterView &v, stream_t s)

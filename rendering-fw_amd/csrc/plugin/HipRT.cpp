@@ -30,6 +30,12 @@
 // display image gets the glow pyramid of include/rfwhip.h (rfwhip_bloom_image) in front of the tone map, on the device, behind the
 // gather and the meter's step; the other display_bloom_* settings keep their defaults.
 //
+// Colour grading: RFWHIP_GRADE=1|0 beside RFWHIP_DISPLAY (unset by default: nothing changes) sets display_grade — with 1 every
+// presented display image goes through the graded display kernel of include/rfwhip.h (rfwhip_set_display_lut).  Beside it:
+// RFWHIP_GRADE_TEMPERATURE (display_wb_temperature, kelvin), RFWHIP_GRADE_SATURATION (display_grade_saturation),
+// RFWHIP_GRADE_LUT=<path of a .cube file> (rfwhip_group_set_display_lut_cube) and RFWHIP_DITHER=1|0 (display_dither); a value the
+// setting refuses, or a file that cannot be read, ends the constructor with the message.
+//
 // Noise estimate: RFWHIP_NOISE=1 (unset by default: nothing changes) turns the setting noise_estimate on (include/rfwhip.h,
 // rfwhip_get_noise); a host asks hiprtGetNoise when to stop converging.  It answers for the accumulator — with frames in flight,
 // for the newest frame enqueued, not the one render_frame handed out.
@@ -55,6 +61,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -118,6 +125,34 @@ class Context final : public rfw::RenderContext
 			if (std::string(bl) != "0" && std::string(bl) != "1")
 				throw std::runtime_error("HipRT: RFWHIP_BLOOM must be \"0\" or \"1\"");
 			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_bloom", bl));
+		}
+		if (const char *gr = std::getenv("RFWHIP_GRADE"))
+		{
+			if (std::string(gr) != "0" && std::string(gr) != "1")
+				throw std::runtime_error("HipRT: RFWHIP_GRADE must be \"0\" or \"1\"");
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_grade", gr));
+		}
+		if (const char *gt = std::getenv("RFWHIP_GRADE_TEMPERATURE"))
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_wb_temperature", gt));
+		if (const char *gs = std::getenv("RFWHIP_GRADE_SATURATION"))
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_grade_saturation", gs));
+		if (const char *dt = std::getenv("RFWHIP_DITHER"))
+		{
+			if (std::string(dt) != "0" && std::string(dt) != "1")
+				throw std::runtime_error("HipRT: RFWHIP_DITHER must be \"0\" or \"1\"");
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_dither", dt));
+		}
+		if (const char *gl = std::getenv("RFWHIP_GRADE_LUT"))
+		{
+			std::string text;
+			FILE *f = std::fopen(gl, "rb");
+			if (!f)
+				throw std::runtime_error(std::string("HipRT: RFWHIP_GRADE_LUT: cannot read ") + gl);
+			char buf[65536];
+			for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;)
+				text.append(buf, n);
+			std::fclose(f);
+			HIPRT_CHECK(rfwhip_group_set_display_lut_cube(m_Group, text.data(), text.size()));
 		}
 		if (const char *nz = std::getenv("RFWHIP_NOISE"))
 		{

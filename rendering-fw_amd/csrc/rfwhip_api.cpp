@@ -17,6 +17,7 @@
 #include "light_tree.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -213,7 +214,8 @@ enum KernelFamily
 	KF_PRIMARY_ORDER = 11, // the primary wave's ordering pass k_order4f (primary_order.h): ONE count per pass over the table, with or
 						   // without stage_timing (the milliseconds only with it)
 	KF_BLOOM = 12, // bloom (bloom.h): the down, up and apply passes of a chain, one count per launch
-	KF_COUNT = 13
+	KF_GRADE = 13, // colour grading (display_grade.h): k_display_graded in place of family 7's kernel, one count per displayed image
+	KF_COUNT = 14
 };
 
 // A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
@@ -416,6 +418,16 @@ struct rfwhip_context
 	dm::event_t ev_bloom;			  // behind the last chain and the display kernel that read its image
 	void *bloom_stream = nullptr;	  // ... the stream they ran on
 	bool ev_bloom_ready = false, bloom_marked = false, bloom_pending = false;
+	// colour grading and dither (display_grade.h): the display_grade* settings; grade_wb = M_wb of the temperature, built in double;
+	// lut_host = the LUT as it was set (n^3 triples), d_grade_lut = its float4 copy, uploaded when it is set
+	int grade_on = 0, grade_dither = 0;
+	float grade_temperature = 6500.0f, grade_wb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+	float grade_slope[3] = {1, 1, 1}, grade_offset[3] = {0, 0, 0}, grade_power[3] = {1, 1, 1}, grade_sat = 1.0f;
+	std::vector<float> lut_host;
+	uint32_t lut_n = 0;
+	DevBuf d_grade_lut;
+	dm::event_t ev_grade; // behind the last graded display kernel that read the LUT on a caller's stream
+	bool ev_grade_ready = false, grade_pending = false;
 	// the noise estimate (noise.h): d_noise = two moments per local pixel, allocated while noise_estimate is on.  noise_live: the
 	// moments cover every sample of the accumulator (the setting was on at the last RESET / rfwhip_init and ever since)
 	int noise_estimate = 0;
@@ -650,7 +662,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_rad_nee[0], &c->d_rad_nee[1], &c->d_acc, &c->d_counters, &c->d_packet_rng, &c->d_jump_table,
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
 					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
-					  &c->d_meter_rec, &c->d_meter_hist, &c->d_meter_part, &c->d_bloom_pyr, &c->d_bloom_out, &c->d_bloom_one,
+					  &c->d_meter_rec, &c->d_meter_hist, &c->d_meter_part, &c->d_bloom_pyr, &c->d_bloom_out, &c->d_bloom_one, &c->d_grade_lut,
 					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in,
 					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask, &c->d_lf_inst, &c->d_lf_bound, &c->d_lf_count, &c->d_lt_touched};
 	for (DevBuf *b : bufs)
@@ -663,6 +675,9 @@ static void free_all(rfwhip_context *c)
 	c->bloom_ran = 0, c->bloom_marked = false, c->bloom_pending = false, c->bloom_stream = nullptr;
 	if (c->ev_bloom_ready)
 		dm::event_destroy(c->ev_bloom), c->ev_bloom_ready = false;
+	c->lut_host.clear(), c->lut_n = 0, c->grade_pending = false;
+	if (c->ev_grade_ready)
+		dm::event_destroy(c->ev_grade), c->ev_grade_ready = false;
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->dn_inst_ver_stale = true;
@@ -2317,6 +2332,11 @@ static int sync_all(rfwhip_context *c)
 		RF_TRY(dm::event_sync(c->ev_bloom));
 		c->bloom_pending = false;
 	}
+	if (c->grade_pending) // (a graded display kernel on a caller's stream reads the LUT)
+	{
+		RF_TRY(dm::event_sync(c->ev_grade));
+		c->grade_pending = false;
+	}
 	return 0;
 }
 
@@ -3539,6 +3559,69 @@ static int bloom_mark(rfwhip_context *c, void *stream)
 	return 0;
 }
 
+// ---- colour grading and dither (settings "display_grade*", "display_wb_temperature", "display_dither"; work items: display_grade.h) ----
+static void mat3_mul(const double a[9], const double b[9], double o[9])
+{
+	for (int i = 0; i < 3; i++)
+		for (int j = 0; j < 3; j++)
+			o[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+}
+static void mat3_inv(const double m[9], double o[9])
+{
+	const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
+	const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
+	o[0] = c0 / det, o[1] = (m[2] * m[7] - m[1] * m[8]) / det, o[2] = (m[1] * m[5] - m[2] * m[4]) / det;
+	o[3] = c1 / det, o[4] = (m[0] * m[8] - m[2] * m[6]) / det, o[5] = (m[2] * m[3] - m[0] * m[5]) / det;
+	o[6] = c2 / det, o[7] = (m[1] * m[6] - m[0] * m[7]) / det, o[8] = (m[0] * m[4] - m[1] * m[3]) / det;
+}
+// the white point of T kelvin on the Planckian locus as XYZ with Y = 1 (the cubic-spline approximation of include/rfwhip.h)
+static void grade_white(double T, double xyz[3])
+{
+	const double x = T <= 4000.0 ? -0.2661239e9 / (T * T * T) - 0.2343589e6 / (T * T) + 0.8776956e3 / T + 0.179910
+								 : -3.0258469e9 / (T * T * T) + 2.1070379e6 / (T * T) + 0.2226347e3 / T + 0.240390;
+	const double y = T <= 2222.0	? -1.1063814 * x * x * x - 1.34811020 * x * x + 2.18555832 * x - 0.20219683
+					 : T <= 4000.0 ? -0.9549476 * x * x * x - 1.37418593 * x * x + 2.09137015 * x - 0.16748867
+									: 3.0817580 * x * x * x - 5.87338670 * x * x + 3.75112997 * x - 0.37001483;
+	xyz[0] = x / y, xyz[1] = 1.0, xyz[2] = (1.0 - x - y) / y;
+}
+// M_wb = M_xyz->rgb B^-1 diag(rho_6500 / rho_T) B M_rgb->xyz, in double, stored as float32
+static void grade_wb_matrix(double T, float out[9])
+{
+	static const double B[9] = {0.8951, 0.2664, -0.1614, -0.7502, 1.7135, 0.0367, 0.0389, -0.0685, 1.0296};
+	static const double RGB2XYZ[9] = {0.4124564, 0.3575761, 0.1804375, 0.2126729, 0.7151522, 0.0721750, 0.0193339, 0.1191920, 0.9503041};
+	double wt[3], w0[3], Bi[9], X2R[9], D[9] = {}, t0[9], t1[9], M[9];
+	grade_white(T, wt), grade_white(6500.0, w0);
+	for (int i = 0; i < 3; i++)
+	{
+		const double rt_ = B[3 * i] * wt[0] + B[3 * i + 1] * wt[1] + B[3 * i + 2] * wt[2];
+		const double r0 = B[3 * i] * w0[0] + B[3 * i + 1] * w0[1] + B[3 * i + 2] * w0[2];
+		D[4 * i] = r0 / rt_;
+	}
+	mat3_inv(B, Bi), mat3_inv(RGB2XYZ, X2R);
+	mat3_mul(B, RGB2XYZ, t0), mat3_mul(D, t0, t1), mat3_mul(Bi, t1, t0), mat3_mul(X2R, t0, M);
+	for (int i = 0; i < 9; i++)
+		out[i] = (float)M[i];
+}
+// what k_display_graded takes: the flags name the steps that are not at the identity
+static rtk::GradeView grade_view(rfwhip_context *c, bool exposed)
+{
+	rtk::GradeView g;
+	memset(&g, 0, sizeof(g));
+	g.rec = exposed ? c->d_meter_rec.as<rtk::MeterRecord>() : nullptr;
+	g.lut = c->lut_n ? c->d_grade_lut.as<f4>() : nullptr, g.n = c->lut_n;
+	g.flags = (exposed ? rtk::GR_EXPOSED : 0u) | (c->grade_temperature != 6500.0f ? rtk::GR_WB : 0u) | (c->grade_sat != 1.0f ? rtk::GR_SAT : 0u) |
+			  (c->lut_n ? rtk::GR_LUT : 0u) | (c->grade_dither ? rtk::GR_DITHER : 0u);
+	for (int i = 0; i < 3; i++)
+	{
+		if (c->grade_slope[i] != 1.0f || c->grade_offset[i] != 0.0f || c->grade_power[i] != 1.0f)
+			g.flags |= rtk::GR_CDL_R << i;
+		g.slope[i] = c->grade_slope[i], g.offset[i] = c->grade_offset[i], g.power[i] = c->grade_power[i];
+	}
+	memcpy(g.wb, c->grade_wb, sizeof(g.wb));
+	g.sat = c->grade_sat;
+	return g;
+}
+
 // one launch on `stream`: the full W x H float4 image `in` -> `out` in `format`, with the context's display settings.
 // display_exposure = auto: the exposed kernel with the record's E — `step`: behind one step of the meter on `in`;
 // manual with display_exposure_ev != 0: the exposed kernel with E = exp2(ev), written into the record when it is not there yet;
@@ -3578,8 +3661,11 @@ static int display_enqueue(rfwhip_context *c, const f4 *in, void *out, float bri
 		v.in = c->d_bloom_out.as<f4>();
 	}
 	{
-		StageTimer t(c, KF_DISPLAY, -1, stream);
-		if (exposed)
+		// display_grade = 1: the graded kernel in place of either, behind the same steps
+		StageTimer t(c, c->grade_on ? KF_GRADE : KF_DISPLAY, -1, stream);
+		if (c->grade_on)
+			rtk::launch_display_graded(v, grade_view(c, exposed), stream);
+		else if (exposed)
 		{
 			rtk::ExposureView e;
 			e.rec = c->d_meter_rec.as<rtk::MeterRecord>();
@@ -3590,6 +3676,16 @@ static int display_enqueue(rfwhip_context *c, const f4 *in, void *out, float bri
 		t.stop(1);
 	}
 	RF_TRY(dm::last_launch_error());
+	if (c->grade_on && c->lut_n && stream != c->stream)
+	{
+		if (!c->ev_grade_ready)
+		{
+			RF_TRY(dm::event_create(&c->ev_grade, false));
+			c->ev_grade_ready = true;
+		}
+		RF_TRY(dm::event_record(c->ev_grade, stream));
+		c->grade_pending = true;
+	}
 	return c->bloom_on ? bloom_mark(c, stream) : 0;
 }
 // brightness and contrast of the presented image: the camera of the last render; before the first one the reference's defaults
@@ -3714,6 +3810,155 @@ extern "C" int rfwhip_read_bloom_level(rfwhip_context *c, int level, float *out,
 	RF_TRY(sync_all(c));
 	RF_TRY(dm::d2h(out, c->d_bloom_pyr.as<f4>() + off, (size_t)lw * lh * sizeof(f4), c->stream));
 	return dm::sync(c->stream);
+}
+
+extern "C" int rfwhip_set_display_lut(rfwhip_context *c, const float *rgb, uint32_t n)
+{
+	CTX_ENTER(c);
+	if (!rgb || n == 0u)
+	{
+		RF_TRY(sync_all(c)); // (a graded display kernel in flight reads the table)
+		c->lut_host.clear(), c->lut_n = 0;
+		c->d_grade_lut.free_();
+		return RFWHIP_OK;
+	}
+	if (n < rtk::GR_LUT_MIN || n > rtk::GR_LUT_MAX)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut: the size must lie in [2, 65], got %u", n);
+	const size_t count = (size_t)n * n * n;
+	for (size_t i = 0; i < count * 3u; i++)
+		if (!(rgb[i] >= -FLT_MAX && rgb[i] <= FLT_MAX))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut: entry %zu is not finite", i / 3u);
+	std::vector<float> wide(count * 4u);
+	for (size_t i = 0; i < count; i++)
+		wide[4 * i] = rgb[3 * i], wide[4 * i + 1] = rgb[3 * i + 1], wide[4 * i + 2] = rgb[3 * i + 2], wide[4 * i + 3] = 0.0f;
+	// into a buffer of its own, swapped in once the copy has landed: a failure on the way leaves the old LUT whole
+	DevBuf fresh;
+	int rc = fresh.ensure(count * sizeof(f4));
+	if (!rc)
+		rc = dm::h2d(fresh.p, wide.data(), count * sizeof(f4), c->stream);
+	if (!rc)
+		rc = dm::sync(c->stream);
+	if (!rc)
+		rc = sync_all(c); // (a graded display kernel in flight reads the old table)
+	if (rc)
+	{
+		fresh.free_();
+		return rc;
+	}
+	std::swap(c->d_grade_lut.p, fresh.p), std::swap(c->d_grade_lut.cap, fresh.cap);
+	fresh.free_();
+	c->lut_host.assign(rgb, rgb + count * 3u), c->lut_n = n;
+	return RFWHIP_OK;
+}
+
+// .cube text: "#" comments, TITLE, LUT_3D_SIZE n, DOMAIN_MIN 0 0 0 / DOMAIN_MAX 1 1 1, then n^3 lines of three numbers, red fastest
+extern "C" int rfwhip_set_display_lut_cube(rfwhip_context *c, const char *text, size_t len)
+{
+	CTX_ENTER(c);
+	if (!text)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: null text");
+	const std::string all(text, len);
+	std::vector<float> rgb;
+	uint32_t n = 0u;
+	size_t pos = 0, line_no = 0;
+	while (pos < all.size())
+	{
+		size_t end = all.find('\n', pos);
+		if (end == std::string::npos)
+			end = all.size();
+		std::string line = all.substr(pos, end - pos);
+		pos = end + 1, line_no++;
+		const size_t first = line.find_first_not_of(" \t\r");
+		if (first == std::string::npos || line[first] == '#')
+			continue;
+		const size_t last = line.find_last_not_of(" \t\r");
+		line = line.substr(first, last - first + 1);
+		const size_t sp = line.find_first_of(" \t");
+		const std::string word = line.substr(0, sp), rest = sp == std::string::npos ? "" : line.substr(sp + 1);
+		if (word == "TITLE")
+			continue;
+		if (word == "LUT_1D_SIZE" || word == "LUT_1D_INPUT_RANGE")
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: line %zu: a 1D LUT is not supported", line_no);
+		if (word == "LUT_3D_SIZE")
+		{
+			char *e = nullptr;
+			const long v = strtol(rest.c_str(), &e, 10);
+			while (e && (*e == ' ' || *e == '\t'))
+				e++;
+			if (n || !e || e == rest.c_str() || *e || v < (long)rtk::GR_LUT_MIN || v > (long)rtk::GR_LUT_MAX)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: line %zu: LUT_3D_SIZE must be given once, a whole number in [2, 65]", line_no);
+			n = (uint32_t)v;
+			continue;
+		}
+		const bool dmin = word == "DOMAIN_MIN", dmax = word == "DOMAIN_MAX";
+		float f[3];
+		char tail = 0;
+		const int got = sscanf((dmin || dmax) ? rest.c_str() : line.c_str(), "%f %f %f %c", &f[0], &f[1], &f[2], &tail);
+		if (dmin || dmax)
+		{
+			const float want = dmin ? 0.0f : 1.0f;
+			if (got != 3 || f[0] != want || f[1] != want || f[2] != want)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: line %zu: the only domain accepted is DOMAIN_MIN 0 0 0 / DOMAIN_MAX 1 1 1", line_no);
+			continue;
+		}
+		if (got != 3 || !((word[0] >= '0' && word[0] <= '9') || word[0] == '-' || word[0] == '+' || word[0] == '.'))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: line %zu: not a keyword of a 3D LUT and not three numbers", line_no);
+		if (!n)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: line %zu: an entry in front of LUT_3D_SIZE", line_no);
+		if (rgb.size() >= (size_t)n * n * n * 3u)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: more than %u^3 entries", n);
+		rgb.insert(rgb.end(), f, f + 3);
+	}
+	if (!n)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: no LUT_3D_SIZE");
+	if (rgb.size() != (size_t)n * n * n * 3u)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_set_display_lut_cube: %zu entries, LUT_3D_SIZE %u needs %zu", rgb.size() / 3u, n, (size_t)n * n * n);
+	return rfwhip_set_display_lut(c, rgb.data(), n);
+}
+
+extern "C" int rfwhip_get_display_lut(rfwhip_context *c, float *rgb, size_t cap, uint32_t *n)
+{
+	CTX_ENTER(c);
+	if (n)
+		*n = c->lut_n;
+	if (!rgb)
+		return RFWHIP_OK; // (the size alone)
+	if (cap < c->lut_host.size())
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_get_display_lut: the LUT holds %zu floats, room for %zu", c->lut_host.size(), cap);
+	if (!c->lut_host.empty())
+		memcpy(rgb, c->lut_host.data(), c->lut_host.size() * sizeof(float));
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_grade_colors(rfwhip_context *c, int which, size_t count, const float *rgb_in, float *rgb_out)
+{
+	CTX_ENTER(c);
+	if (count && (!rgb_in || !rgb_out))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_grade_colors: null colours");
+	if (which != 0 && which != 1)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_grade_colors: which must be 0 (white balance, CDL, saturation) or 1 (the LUT), got %d", which);
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	if (count == 0)
+		return RFWHIP_OK;
+	if (count >= (1ull << 30))
+		return set_error(RFWHIP_ERR_UNSUPPORTED, "rfwhip_grade_colors: too many colours");
+	RF_TRY(sync_all(c));
+	DevBuf d_in, d_out;
+	int rc = d_in.ensure(count * 3u * sizeof(float));
+	if (!rc)
+		rc = d_out.ensure(count * 3u * sizeof(float));
+	if (!rc)
+		rc = dm::h2d(d_in.p, rgb_in, count * 3u * sizeof(float), c->stream);
+	if (!rc)
+	{
+		rtk::launch_kat_grade(grade_view(c, false), which, d_in.as<float>(), d_out.as<float>(), (uint32_t)count, c->stream);
+		rc = dm::last_launch_error();
+	}
+	if (!rc)
+		rc = dm::d2h(rgb_out, d_out.p, count * 3u * sizeof(float), c->stream);
+	d_in.free_(), d_out.free_();
+	return rc;
 }
 
 extern "C" int rfwhip_get_meter(rfwhip_context *c, rfwhip_meter_stats *stats)
@@ -4221,6 +4466,32 @@ static int set_float(float &dst, const char *key, const char *value, bool (*ok)(
 	dst = f;
 	return RFWHIP_OK;
 }
+// strict: one number for the three channels, or three separated by blanks; every one must pass `ok`, else nothing changes
+static int set_float3(float dst[3], const char *key, const char *value, bool (*ok)(float), const char *must)
+{
+	float f[3];
+	int n = 0;
+	const char *p = value;
+	for (; n < 3; n++)
+	{
+		while (*p == ' ' || *p == '\t')
+			p++;
+		if (!*p)
+			break;
+		char *end = nullptr;
+		f[n] = strtof(p, &end);
+		if (!end || end == p || !ok(f[n]))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must %s", key, must);
+		p = end;
+	}
+	while (*p == ' ' || *p == '\t')
+		p++;
+	if (*p || (n != 1 && n != 3))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must %s", key, must);
+	for (int i = 0; i < 3; i++)
+		dst[i] = f[n == 1 ? 0 : i];
+	return RFWHIP_OK;
+}
 static int set_sigma(float &dst, const char *key, const char *value)
 {
 	return set_float(dst, key, value, [](float f) { return f >= 0.0f && f < 1e30f; }, "be a finite number >= 0");
@@ -4463,6 +4734,38 @@ static const Setting k_settings[] = {
 	// k_bloom_up, k_bloom_apply, then their launches
 	{"display_bloom_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %u %u %u %u", c->bloom_kind_ms[0], c->bloom_kind_ms[1], c->bloom_kind_ms[2], c->bloom_kind_ms[3],
 													  c->bloom_kind_launches[0], c->bloom_kind_launches[1], c->bloom_kind_launches[2], c->bloom_kind_launches[3]); }, false},
+	// colour grading and dither (display_grade.h): k_display_graded in place of the display kernel
+	{"display_grade", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 c->grade_on = on;
+		 return RFWHIP_OK; },
+	 GET_INT(grade_on), false},
+	{"display_wb_temperature", SET {
+		 float t = 0.0f;
+		 RF_TRY(set_float(t, key, value, [](float f) { return f >= 1667.0f && f <= 25000.0f; }, "be a temperature in kelvin in [1667, 25000]", false));
+		 c->grade_temperature = t;
+		 grade_wb_matrix((double)t, c->grade_wb);
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%g", c->grade_temperature); }, false},
+	{"display_grade_slope", SET { return set_float3(c->grade_slope, key, value, [](float f) { return f >= 0.0f && f <= FLT_MAX; }, "be one or three finite numbers >= 0"); },
+	 GET { return put(out, cap, "%g %g %g", c->grade_slope[0], c->grade_slope[1], c->grade_slope[2]); }, false},
+	{"display_grade_offset", SET { return set_float3(c->grade_offset, key, value, [](float f) { return f >= -FLT_MAX && f <= FLT_MAX; }, "be one or three finite numbers"); },
+	 GET { return put(out, cap, "%g %g %g", c->grade_offset[0], c->grade_offset[1], c->grade_offset[2]); }, false},
+	{"display_grade_power", SET { return set_float3(c->grade_power, key, value, [](float f) { return f > 0.0f && f <= FLT_MAX; }, "be one or three finite numbers > 0"); },
+	 GET { return put(out, cap, "%g %g %g", c->grade_power[0], c->grade_power[1], c->grade_power[2]); }, false},
+	{"display_grade_saturation", SET { return set_float(c->grade_sat, key, value, [](float f) { return f >= 0.0f && f <= 4.0f; }, "be in [0, 4]", false); },
+	 GET { return put(out, cap, "%g", c->grade_sat); }, false},
+	{"display_dither", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 c->grade_dither = on;
+		 return RFWHIP_OK; },
+	 GET_INT(grade_dither), false},
+	// (read-only) the size n of the LUT of rfwhip_set_display_lut, 0 without one
+	{"display_lut", nullptr, GET { return put(out, cap, "%u", c->lut_n); }, false},
+	// (read-only, stage_timing = 1) family 13 since its last reset: the milliseconds of k_display_graded, then its launches
+	{"display_grade_time", nullptr, GET { return put(out, cap, "%.6f %u", c->kernel_ms[KF_GRADE], c->kernel_launches[KF_GRADE]); }, false},
 	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
 	{"noise_estimate", SET {
 		 bool on;
@@ -4617,7 +4920,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)

@@ -739,6 +739,24 @@ extern "C" int rfwhip_group_get_meter(rfwhip_group *g, rfwhip_meter_stats *stats
 	return rfwhip_get_meter(g->ep[(size_t)g->root_local].ctx, stats);
 }
 
+// the LUT of the display stage belongs to the root's context: the display kernel runs there, on the gathered image
+extern "C" int rfwhip_group_set_display_lut(rfwhip_group *g, const float *rgb, uint32_t n)
+{
+	if (!g)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null argument");
+	if (g->root_local < 0)
+		return RFWHIP_OK; // (the root's process holds the LUT: nothing to set here)
+	return rfwhip_set_display_lut(g->ep[(size_t)g->root_local].ctx, rgb, n);
+}
+extern "C" int rfwhip_group_set_display_lut_cube(rfwhip_group *g, const char *text, size_t len)
+{
+	if (!g)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null argument");
+	if (g->root_local < 0)
+		return RFWHIP_OK;
+	return rfwhip_set_display_lut_cube(g->ep[(size_t)g->root_local].ctx, text, len);
+}
+
 extern "C" int rfwhip_group_get_adaptive(rfwhip_group *g, rfwhip_adaptive_stats *stats)
 {
 	if (!g || !stats)
