@@ -321,6 +321,67 @@ RFWHIP_API int rfwhip_set_display_lut_cube(rfwhip_context *ctx, const char *text
 RFWHIP_API int rfwhip_get_display_lut(rfwhip_context *ctx, float *rgb, size_t cap, uint32_t *n);
 RFWHIP_API int rfwhip_grade_colors(rfwhip_context *ctx, int which, size_t count, const float *rgb_in, float *rgb_out);
 
+/* ---- baseline JPEG: the presented 8-bit frame, encoded on the device (csrc/display_jpeg.h) ------------------
+ * The display stage ends at an RGBA8 image in device memory; these calls encode that image as a baseline JPEG (T.81, JFIF) on the
+ * device, so that a host copies the few hundred kilobytes a browser, an MJPEG stream or a file takes as they are instead of 4
+ * bytes per pixel.  Four kernels behind the display kernel on the same stream (kernel family 14), nothing read back by the chain;
+ * off unless one of these calls is made: nothing is allocated before, and no other kernel changes.  Unlisted settings (a value out of
+ * range or not a whole number is RFWHIP_ERR_INVALID_ARGUMENT and the setting keeps its value):
+ *     display_jpeg_quality      1 .. 100, default 90 (the IJG scale)
+ *     display_jpeg_subsampling  "444" | "420", default 420
+ *     display_jpeg_restart      Ri, the MCUs per restart interval, 1 .. 65535, default 8
+ *     display_jpeg_bytes        (read-only) the length of the last stream this library read back to the host, 0 before
+ *     display_jpeg_time         (read-only, stage_timing = 1) kernel family 14 by kernel since its last reset: the milliseconds of
+ *                               k_jpeg_blocks, k_jpeg_entropy, k_jpeg_offsets, k_jpeg_pack, then their launches
+ * THE STREAM is defined in integers; an implementation of this text agrees with the device byte for byte.
+ *   Input: W x H RGBA8, row 0 first, R in the lowest byte; alpha is ignored.  W, H <= 65535.
+ *   MCU = 8 x 8 pixels ("444") or 16 x 16 ("420"); the image is extended to whole MCUs by clamping the pixel coordinates.
+ *   Colour (JFIF, full range):  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,  Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16,
+ *     Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16;  "420": Cb and Cr are 2 x 2 box means (a + b + c + d + 2) >> 2.
+ *     Blocks of an MCU: Y ("420": top-left, top-right, bottom-left, bottom-right), Cb, Cr.
+ *   DCT: K[u][x] = round(8192 a(u) cos((2 x + 1) u pi / 16)), a(0) = sqrt(1 / 8), a(u > 0) = 1 / 2;  X = block - 128;
+ *     T = (K X + 512) >> 10 (arithmetic shift);  S = T K^T = 2^16 x T.81's FDCT; everything fits int32.
+ *   Quantisation: q = sgn(S) ((|S| + (Q << 15)) / (Q << 16)), integer division; Q = the entry of T.81 Annex K.1 (luminance for Y,
+ *     chrominance for Cb, Cr) scaled by the quality: s = 5000 / quality below 50, else 200 - 2 quality; Q = clamp((base s + 50) / 100, 1, 255).
+ *   Entropy coding: baseline Huffman with the Annex K.3 tables; DC differences per component with the predictor 0 at the start of
+ *     every restart interval; AC run / size with ZRL and EOB (no EOB when coefficient 63 is non-zero); a negative value v is coded
+ *     as v - 1 in `size` bits; a 0x00 behind every 0xFF byte of entropy data.
+ *   Restart intervals: Ri MCUs each in raster order; every interval is padded to a byte with 1-bits; interval i is followed by
+ *     FF D0 + (i mod 8), the last one by EOI.
+ *   Header (613 bytes, built by the host): SOI; APP0 "JFIF" 1.01, units 0, density 1 : 1, no thumbnail; one DQT with tables 0 and 1
+ *     in zigzag order; SOF0 (precision 8, H, W, components 1 / 2 / 3 with sampling 0x11 or 0x22 for Y and 0x11 for the others,
+ *     tables 0 / 1 / 1); one DHT (DC0, AC0, DC1, AC1); DRI; SOS (1:00 2:11 3:11, 0, 63, 0).
+ * rfwhip_display_jpeg_bound: the capacity that always suffices for the target size under the current settings: 613 + 416 per block
+ *   (a block's code is at most 1658 bits, every byte of it may be stuffed) + 2 per interval.
+ * rfwhip_read_display_jpeg (world 1): present -> denoise when on -> display (RGBA8, as rfwhip_read_display) -> encode; the host waits
+ *   for the 32-byte record, then copies exactly *bytes.  *bytes (may be null) is the stream's length also when it did not fit: a `cap`
+ *   below it is RFWHIP_ERR_INVALID_ARGUMENT with the needed size in the message, and nothing is written to out_host.
+ * rfwhip_display_jpeg_stream: the four kernels, stream-ordered on `hip_stream`, on a W x H RGBA8 image in device memory (the output
+ *   of rfwhip_display_stream) -> the stream in out_device (cap >= 613 bytes) and the record in record_device (32 bytes); when the
+ *   stream exceeds cap nothing is written behind the header and the record's overflow is 1.  The kernels share one scratch per
+ *   context: an encode enqueued on another stream first waits, on the host, for the previous one.
+ * rfwhip_get_jpeg: the record of the last stream this library read back.
+ * Hooks: rfwhip_jpeg_image encodes a host RGBA8 image of the target's size; rfwhip_read_jpeg_coefficients copies the quantised
+ *   blocks of the last encode — *blocks of them (may be null), 64 int16 each in zigzag order, in stream order (MCU by MCU); out null:
+ *   the count alone; cap_blocks too small: RFWHIP_ERR_INVALID_ARGUMENT. */
+typedef struct rfwhip_jpeg_stats /* 32 bytes: the record as it lies on the device */
+{
+	uint32_t bytes;			/* the whole stream: header, entropy data, markers, EOI */
+	uint32_t intervals;		/* restart intervals */
+	uint32_t mcus, blocks;	/* MCUs and 8 x 8 blocks coded */
+	uint32_t stuffed_bytes; /* 0x00 bytes behind an 0xFF */
+	uint32_t overflow;		/* 1: bytes > cap, nothing was written behind the header */
+	uint32_t header_bytes;	/* 613 */
+	uint32_t reserved;
+} rfwhip_jpeg_stats;
+RFWHIP_API int rfwhip_display_jpeg_bound(rfwhip_context *ctx, size_t *bytes);
+RFWHIP_API int rfwhip_read_display_jpeg(rfwhip_context *ctx, void *out_host, size_t cap, size_t *bytes);
+RFWHIP_API int rfwhip_display_jpeg_stream(rfwhip_context *ctx, const void *rgba8_device, void *out_device, size_t cap, void *record_device,
+										   void *hip_stream);
+RFWHIP_API int rfwhip_get_jpeg(rfwhip_context *ctx, rfwhip_jpeg_stats *stats);
+RFWHIP_API int rfwhip_jpeg_image(rfwhip_context *ctx, const void *rgba8_in, void *out_host, size_t cap, size_t *bytes);
+RFWHIP_API int rfwhip_read_jpeg_coefficients(rfwhip_context *ctx, int16_t *out, size_t cap_blocks, uint32_t *blocks);
+
 /* ---- noise estimate: when has a progressive render converged? ---------------------------------------------------------------
  * With noise_estimate = 1 the resolve of every rfwhip_render (its variant k_resolve_noise) keeps two floats per pixel beside the
  * accumulator — sumY, the sum of the luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel's samples (a sample's value is what
@@ -494,6 +555,15 @@ RFWHIP_API int rfwhip_group_set_display_lut_cube(rfwhip_group *group, const char
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
 RFWHIP_API int rfwhip_group_present_display_wait(rfwhip_group *group, int slot, const void **out_host, int *format);
+/* Baseline JPEG for a group (see rfwhip_read_display_jpeg): read_display_jpeg = gather + display (RGBA8) + encode on the root + wait
+ * + copy of the record, then of exactly *bytes.  present_jpeg_async / _wait use the slots of present_async: the async call enqueues
+ * gather, display, encode and the copy of the 32-byte record and of as many bytes as the last stream had plus an eighth (one byte
+ * per pixel the first time); the wait blocks for the record, then hands exactly *bytes of the slot's stream to out_host — from
+ * the pinned copy, or with a second copy when the stream is longer than the guess (cap bytes; a smaller cap: RFWHIP_ERR_INVALID_ARGUMENT with the needed size, the slot stays
+ * presented).  A slot remembers which of the three kinds was presented into it; waiting for another kind is RFWHIP_ERR_STATE. */
+RFWHIP_API int rfwhip_group_read_display_jpeg(rfwhip_group *group, void *out_host, size_t cap, size_t *bytes);
+RFWHIP_API int rfwhip_group_present_jpeg_async(rfwhip_group *group, int slot);
+RFWHIP_API int rfwhip_group_present_jpeg_wait(rfwhip_group *group, int slot, void *out_host, size_t cap, size_t *bytes);
 
 /* rfwhip_comm_*: one process per device (e.g. under torch.distributed.run).  Rank 0 calls rfwhip_comm_unique_id and
  * hands the RFWHIP_COMM_ID_BYTES bytes to the other ranks by any means (a file, MPI, a torch broadcast); then EVERY rank
@@ -773,7 +843,7 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * call when the camera position or a tree has changed since — `launches` counts those passes, one per rewrite, with or without
  * stage_timing; the image does not depend on it.  12 bloom: one count per launch of a chain, 2 x the levels it ran (the down
  * passes, the up passes and the apply pass).  13 grade: k_display_graded, one launch per displayed image with display_grade = 1 (in
- * place of family 7's). */
+ * place of family 7's).  14 jpeg: the four kernels of a JPEG encode, one count each. */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

@@ -104,6 +104,12 @@ class CoreBinding:
                                   "set_display_lut_cube": (i32, [vp, C.c_char_p, sz]),
                                   "get_display_lut": (i32, [vp, vp, sz, C.POINTER(u32)]),
                                   "grade_colors": (i32, [vp, i32, sz, vp, vp]),
+                                  "display_jpeg_bound": (i32, [vp, C.POINTER(sz)]),
+                                  "read_display_jpeg": (i32, [vp, vp, sz, C.POINTER(sz)]),
+                                  "display_jpeg_stream": (i32, [vp, vp, vp, sz, vp, vp]),
+                                  "get_jpeg": (i32, [vp, C.POINTER(abi.JpegStats)]),
+                                  "jpeg_image": (i32, [vp, vp, vp, sz, C.POINTER(sz)]),
+                                  "read_jpeg_coefficients": (i32, [vp, vp, sz, C.POINTER(u32)]),
                                   "get_noise": (i32, [vp, C.POINTER(abi.NoiseStats)]),
                                   "read_noise_map": (i32, [vp, vp]),
                                   "read_noise_tiles": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
@@ -509,6 +515,57 @@ class CoreBinding:
         self._check(self._fn("grade_colors")(self._ctx, int(which), src.size // 3, src.ctypes.data, out.ctypes.data))
         return out
 
+    # ---- baseline JPEG of the display image (include/rfwhip.h, rfwhip_read_display_jpeg; settings display_jpeg_*) -------------
+    def jpeg_bound(self):
+        """The capacity in bytes that always suffices for the target size under the current display_jpeg_* settings."""
+        n = C.c_size_t()
+        self._check(self._fn("display_jpeg_bound")(self._ctx, C.byref(n)))
+        return int(n.value)
+
+    def _jpeg_call(self, call, cap):
+        """call(buffer address, cap, byref(bytes)) -> the stream as bytes; cap None: the bound."""
+        cap = self.jpeg_bound() if cap is None else int(cap)
+        buf, n = np.empty(max(cap, 1), np.uint8), C.c_size_t()
+        self._check(call(buf.ctypes.data, cap, C.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def display_jpeg(self, cap=None):
+        """The presented image after the display stage as a baseline JPEG (bytes), encoded on the device: what display()
+        returns as RGBA8, compressed under display_jpeg_quality / _subsampling / _restart.  cap: the host buffer's size
+        (default: the bound); a stream longer than cap raises and names its length."""
+        return self._jpeg_call(lambda p, c, n: self._fn("read_display_jpeg")(self._ctx, p, c, n), cap)
+
+    def save_jpeg(self, path):
+        """display_jpeg() into a file; returns the bytes written."""
+        data = self.display_jpeg()
+        with open(path, "wb") as f:
+            f.write(data)
+        return len(data)
+
+    def display_jpeg_stream(self, rgba8_device_ptr, out_device_ptr, cap, record_device_ptr, stream=0):
+        """Stream-ordered encode of a W x H RGBA8 image in device memory (rfwhip_display_jpeg_stream)."""
+        self._check(self._fn("display_jpeg_stream")(self._ctx, C.c_void_p(rgba8_device_ptr or None), C.c_void_p(out_device_ptr or None),
+                                                    int(cap), C.c_void_p(record_device_ptr or None), C.c_void_p(stream or None)))
+
+    def jpeg_record(self):
+        """The record of the last stream read back, as a dict (abi.JpegStats)."""
+        st = abi.JpegStats()
+        self._check(self._fn("get_jpeg")(self._ctx, C.byref(st)))
+        return st.as_dict()
+
+    def jpeg_image(self, rgba8, cap=None):
+        """Known-answer hook: an H x W x 4 uint8 image through the encoder under the current settings -> bytes."""
+        src = np.ascontiguousarray(rgba8, dtype=np.uint8).reshape(self.height, self.width, 4)
+        return self._jpeg_call(lambda p, c, n: self._fn("jpeg_image")(self._ctx, src.ctypes.data, p, c, n), cap)
+
+    def jpeg_coefficients(self):
+        """The quantised blocks of the last encode: blocks x 64 int16 in zigzag order, in stream order (MCU by MCU)."""
+        n = C.c_uint32()
+        self._check(self._fn("read_jpeg_coefficients")(self._ctx, None, 0, C.byref(n)))
+        out = np.empty((n.value, 64), np.int16)
+        self._check(self._fn("read_jpeg_coefficients")(self._ctx, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     # ---- noise estimate (include/rfwhip.h, rfwhip_get_noise; setting noise_estimate = 1) ---------------------------
     def get_noise(self):
         """The noise of the accumulated image as a dict: samples, pixels, converged, mean_error, max_error, threshold.
@@ -629,10 +686,11 @@ class CoreBinding:
     PRIMARY_ORDER = 11  # ... and of the primary wave's ordering pass (one count per rewrite of the camera-ordered node table)
     BLOOM = 12  # ... and of bloom (one count per launch of a chain: 2 x the levels it ran)
     GRADE = 13  # ... and of the graded display kernel (one launch per displayed image with display_grade = 1)
+    JPEG = 14  # ... and of the JPEG encoder (four launches per stream)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -785,7 +843,10 @@ class RenderGroup:
                                 ("group_get_adaptive", i32, [vp, C.POINTER(abi.AdaptiveStats)]),
                                 ("group_get_meter", i32, [vp, C.POINTER(abi.MeterStats)]),
                                 ("group_set_display_lut", i32, [vp, vp, u32]),
-                                ("group_set_display_lut_cube", i32, [vp, C.c_char_p, C.c_size_t])]:
+                                ("group_set_display_lut_cube", i32, [vp, C.c_char_p, C.c_size_t]),
+                                ("group_read_display_jpeg", i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+                                ("group_present_jpeg_async", i32, [vp, i32]),
+                                ("group_present_jpeg_wait", i32, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -904,6 +965,31 @@ class RenderGroup:
         if fmt.value == 0:
             return np.frombuffer((C.c_uint8 * n).from_address(ptr.value), dtype=np.uint8).reshape(self.height, self.width, 4)
         return np.frombuffer((C.c_float * n).from_address(ptr.value), dtype=np.float32).reshape(self.height, self.width, 4)
+
+    def jpeg_bound(self):
+        return self.contexts[0].jpeg_bound()
+
+    def display_jpeg(self, cap=None):
+        """gather + the display stage + the JPEG encoder on the root + wait: the stream as bytes (CoreBinding.display_jpeg)."""
+        return self.contexts[0]._jpeg_call(lambda p, c, n: self._check_code(self._fn("group_read_display_jpeg")(self._g, p, c, n)), cap)
+
+    def save_jpeg(self, path):
+        data = self.display_jpeg()
+        with open(path, "wb") as f:
+            f.write(data)
+        return len(data)
+
+    def _check_code(self, code):
+        self._check(code)
+        return 0
+
+    def present_jpeg_async(self, slot):
+        """present_async with the display stage and the JPEG encoder behind the gather: only the record travels until the wait."""
+        self._check(self._fn("group_present_jpeg_async")(self._g, int(slot)))
+
+    def present_jpeg_wait(self, slot, cap=None):
+        """Block until slot's stream is encoded; copies exactly its bytes -> bytes."""
+        return self.contexts[0]._jpeg_call(lambda p, c, n: self._check_code(self._fn("group_present_jpeg_wait")(self._g, int(slot), p, c, n)), cap)
 
     def framebuffer_device(self):
         """(device pointer, device ordinal) of the root-side image of the last completed gather."""

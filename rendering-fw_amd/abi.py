@@ -183,6 +183,14 @@ class MeterStats(C.Structure):
 METER_BINS = 256
 
 
+class JpegStats(C.Structure):
+    """rfwhip_jpeg_stats (include/rfwhip.h, rfwhip_get_jpeg): the JPEG encoder's 32-byte record."""
+    _fields_ = [(n, C.c_uint32) for n in ("bytes", "intervals", "mcus", "blocks", "stuffed_bytes", "overflow", "header_bytes", "reserved")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class AdaptiveStats(C.Structure):
     """rfwhip_adaptive_stats (include/rfwhip.h, rfwhip_get_adaptive)."""
     _fields_ = [(n, C.c_uint64) for n in ("tiles", "active_tiles", "pixels", "active_pixels", "samples_taken", "samples_uniform")]

@@ -76,6 +76,12 @@ class RenderComm:
         (wait(), or an event).  out: width * height * 4 bytes ("rgba8") or * 16 ("rgba32f") of device memory."""
         self._ctx.display_stream(full_rgba_device_ptr, out_device_ptr, format, stream)
 
+    def display_jpeg(self, rgba8_device_ptr, out_device_ptr, cap, record_device_ptr, stream=0):
+        """Root only: the JPEG encoder (rfwhip_display_jpeg_stream) on the RGBA8 image display() wrote, enqueued on the same
+        stream behind it.  out: cap bytes of device memory (ctx.jpeg_bound() always suffices); record: 32 bytes whose first
+        word is the stream's length once the stream has run."""
+        self._ctx.display_jpeg_stream(rgba8_device_ptr, out_device_ptr, cap, record_device_ptr, stream)
+
     def destroy(self):
         if self._c:
             self._lib.rfwhip_comm_destroy(self._c)

@@ -169,6 +169,39 @@ struct GradeView
 	float sat;
 };
 
+// Baseline JPEG of the RGBA8 display image (display_jpeg.h).  JP_HEADER: the bytes in front of the entropy data, built by the host;
+// JP_BLOCK_BYTES: the worst case of one block in an interval's slot — a block's code is at most JP_STRIP_WORDS x 32 bits = 208
+// bytes, and every byte may be an 0xFF with a 0x00 behind it
+constexpr uint32_t JP_HEADER = 613u, JP_STRIP_WORDS = 52u, JP_BLOCK_BYTES = 8u * JP_STRIP_WORDS;
+// the constant tables, built once by the host: K = the DCT's integer matrix, row by row; zz[z] = the natural index of zigzag
+// position z, izz its inverse; dc / ac[table][symbol] = the Annex K.3 Huffman code in the low 16 bits, its length above
+struct JpegTables
+{
+	int32_t K[64];
+	uint8_t zz[64], izz[64];
+	uint32_t dc[2][12], ac[2][256];
+};
+// what k_jpeg_offsets leaves (= rfwhip_jpeg_stats): bytes = the whole stream, header and markers included, also when it did not fit
+struct JpegRecord
+{
+	uint32_t bytes, intervals, mcus, blocks, stuffed, overflow, header, pad;
+};
+// rgba: W x H RGBA8, R in the lowest byte; sub: 0 = "444", 1 = "420"; bpm = blocks per MCU (3 | 6); ri = MCUs per restart interval;
+// q[table][natural index] = the scaled quantisation tables; coef: blocks x 64 int16; slots: blocks x JP_BLOCK_BYTES + 3 x intervals
+// bytes; counts: per interval its bytes and its stuffed bytes; offsets: per interval its place in `out`; out: cap bytes
+struct JpegView
+{
+	const uint32_t *rgba;
+	uint32_t W, H, sub, mcus_x, mcus, bpm, blocks, ri, intervals, cap;
+	const JpegTables *tab;
+	uint16_t q[2][64];
+	int16_t *coef;
+	uint8_t *slots;
+	uint32_t *counts, *offsets;
+	JpegRecord *rec;
+	uint8_t *out;
+};
+
 // The noise estimate (noise.h).  One record per NZ_TILE_X x NZ_TILE_Y noise tile (= rfwhip_noise_tile) and the one record k_noise_final leaves
 constexpr uint32_t NZ_TILE_X = 32, NZ_TILE_Y = 8;
 struct NoiseTile
@@ -295,6 +328,11 @@ void launch_bloom_apply(const BloomApplyView &v, const BloomParams &b, stream_t 
 // kernel k_kat_grade: n records of three floats, which = 0 (white balance, CDL, saturation) | 1 (the LUT)
 void launch_display_graded(const DisplayView &v, const GradeView &g, stream_t s);
 void launch_kat_grade(const GradeView &g, int which, const float *in, float *out, uint32_t n, stream_t s);
+// baseline JPEG (display_jpeg.h), in this order on one stream: k_jpeg_blocks, k_jpeg_entropy, k_jpeg_offsets, k_jpeg_pack
+void launch_jpeg_blocks(const JpegView &v, stream_t s);
+void launch_jpeg_entropy(const JpegView &v, stream_t s);
+void launch_jpeg_offsets(const JpegView &v, stream_t s);
+void launch_jpeg_pack(const JpegView &v, stream_t s);
 // a guide record's normal, unpacked on the host (rfwhip_read_denoise_guides)
 rt::f3 dn_normal(uint32_t octahedral);
 void launch_deinterleave(const rt::f4 *gathered, rt::f4 *out, uint32_t W, uint32_t H, uint32_t local_rows,

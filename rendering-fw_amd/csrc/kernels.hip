@@ -980,6 +980,8 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 #include "bloom.h"
 // colour grading and dither: white balance, CDL, 3D LUT, ordered dither (work items shared with the emulation)
 #include "display_grade.h"
+// baseline JPEG of the RGBA8 display image: the work items shared with the emulation, and the four kernels
+#include "display_jpeg.h"
 // moving emitters: the area lights of emissive geometry and the light tree's refit (work items shared with the emulation)
 #include "light_follow.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }

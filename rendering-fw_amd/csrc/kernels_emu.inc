@@ -644,6 +644,77 @@ void launch_kat_grade(const GradeView &g, int which, const float *in, float *out
 	for (uint32_t i = 0; i < n; i++)
 		dg_kat_item(g, which, in, out, i);
 }
+// baseline JPEG (display_jpeg.h): the same items block by block; an interval's blocks are appended bit by bit, then stuffed
+void launch_jpeg_blocks(const JpegView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_jpeg_blocks(v, s));
+	const uint32_t M = jp_mcu_size(v);
+	uint32_t px[256];
+	for (uint32_t m = 0; m < v.mcus; m++)
+	{
+		for (uint32_t y = 0; y < M; y++)
+			for (uint32_t x = 0; x < M; x++)
+				px[y * M + x] = jp_pixel(v, m, x, y);
+		for (uint32_t k = 0; k < v.bpm; k++)
+			jp_block_item(v, px, k, v.coef + ((size_t)m * v.bpm + k) * 64u);
+	}
+}
+void launch_jpeg_entropy(const JpegView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_jpeg_entropy(v, s));
+	for (uint32_t i = 0; i < v.intervals; i++)
+	{
+		const uint32_t first = jp_interval_first(v, i), n = jp_interval_blocks(v, i);
+		uint8_t *slot = v.slots + jp_slot(v, i);
+		uint32_t out = 0u, stuffed = 0u, acc = 0u, have = 0u;
+		const auto byte = [&](uint32_t b) {
+			slot[out++] = (uint8_t)b;
+			if (b == 255u)
+				slot[out++] = 0u, stuffed++;
+		};
+		for (uint32_t b = first; b < first + n; b++)
+		{
+			uint32_t strip[JP_STRIP_WORDS];
+			const uint32_t k = b % v.bpm, p = jp_prev_block(v.sub, b, first);
+			const uint32_t len = jp_encode_block(*v.tab, v.coef + (size_t)b * 64u, p == ~0u ? 0 : (int)v.coef[(size_t)p * 64u],
+												 v.sub ? (k >= 4u) : (k >= 1u), strip, 1u);
+			for (uint32_t t = 0; t < len; t++)
+			{
+				acc = (acc << 1) | ((strip[t >> 5] >> (31u - (t & 31u))) & 1u);
+				if (++have == 8u)
+					byte(acc & 255u), acc = 0u, have = 0u;
+			}
+		}
+		if (have)
+			byte(((acc << (8u - have)) | ((1u << (8u - have)) - 1u)) & 255u);
+		v.counts[2u * i] = out, v.counts[2u * i + 1u] = stuffed;
+	}
+}
+void launch_jpeg_offsets(const JpegView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_jpeg_offsets(v, s));
+	uint64_t run = JP_HEADER;
+	uint32_t stuffed = 0u;
+	for (uint32_t i = 0; i < v.intervals; i++)
+	{
+		v.offsets[i] = run > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)run;
+		run += (uint64_t)v.counts[2u * i] + 2u, stuffed += v.counts[2u * i + 1u];
+	}
+	jp_record(v, run, stuffed);
+}
+void launch_jpeg_pack(const JpegView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_jpeg_pack(v, s));
+	if (v.rec->overflow)
+		return;
+	for (uint32_t i = 0; i < v.intervals; i++)
+	{
+		const uint32_t n = v.counts[2u * i];
+		uint8_t *dst = v.out + v.offsets[i];
+		memcpy(dst, v.slots + jp_slot(v, i), n);
+		dst[n] = 0xFFu, dst[n + 1u] = (uint8_t)jp_marker(v, i);
+	}
+}
 // the exposure meter (metering.h): the same partial records, range by range, and the same fold
 uint32_t meter_records(uint32_t pixels) { return (uint32_t)(((size_t)pixels + MT_RANGE - 1u) / MT_RANGE); }
 void launch_meter_hist(const MeterView &v, stream_t s)

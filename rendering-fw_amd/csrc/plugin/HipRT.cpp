@@ -36,6 +36,11 @@
 // RFWHIP_GRADE_LUT=<path of a .cube file> (rfwhip_group_set_display_lut_cube) and RFWHIP_DITHER=1|0 (display_dither); a value the
 // setting refuses, or a file that cannot be read, ends the constructor with the message.
 //
+// JPEG: hiprtReadJpeg hands a headless host the display image as a baseline JPEG encoded on the device (include/rfwhip.h,
+// rfwhip_read_display_jpeg): a few hundred kilobytes instead of 4 bytes per pixel.  RFWHIP_JPEG_QUALITY (display_jpeg_quality,
+// 1 .. 100), RFWHIP_JPEG_SUBSAMPLING (444 | 420) and RFWHIP_JPEG_RESTART (display_jpeg_restart) are optional; a value the setting
+// refuses ends the constructor with the message.  Nothing is allocated or launched until hiprtReadJpeg is called.
+//
 // Noise estimate: RFWHIP_NOISE=1 (unset by default: nothing changes) turns the setting noise_estimate on (include/rfwhip.h,
 // rfwhip_get_noise); a host asks hiprtGetNoise when to stop converging.  It answers for the accumulator — with frames in flight,
 // for the newest frame enqueued, not the one render_frame handed out.
@@ -154,6 +159,12 @@ class Context final : public rfw::RenderContext
 			std::fclose(f);
 			HIPRT_CHECK(rfwhip_group_set_display_lut_cube(m_Group, text.data(), text.size()));
 		}
+		if (const char *jq = std::getenv("RFWHIP_JPEG_QUALITY"))
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_jpeg_quality", jq));
+		if (const char *js = std::getenv("RFWHIP_JPEG_SUBSAMPLING"))
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_jpeg_subsampling", js));
+		if (const char *jr = std::getenv("RFWHIP_JPEG_RESTART"))
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_jpeg_restart", jr));
 		if (const char *nz = std::getenv("RFWHIP_NOISE"))
 		{
 			if (std::string(nz) != "0" && std::string(nz) != "1")
@@ -313,6 +324,11 @@ class Context final : public rfw::RenderContext
 		}
 		return rfwhip_group_read_display(m_Group, RFWHIP_DISPLAY_RGBA8, rgba8);
 	}
+
+	// ... and the display image of the newest frame as a baseline JPEG, encoded on the device and read now (with frames in flight
+	// that is the newest frame enqueued, not the one render_frame handed out); bound: the capacity that always suffices
+	int read_jpeg(void *out, size_t cap, size_t *bytes) { return rfwhip_group_read_display_jpeg(m_Group, out, cap, bytes); }
+	int jpeg_bound(size_t *bytes) { return rfwhip_display_jpeg_bound(m_Cores[0], bytes); }
 
 	// the noise of the accumulated image (RFWHIP_NOISE=1; else RFWHIP_ERR_STATE)
 	int get_noise(rfwhip_noise_stats *stats) { return rfwhip_group_get_noise(m_Group, stats); }
@@ -478,6 +494,16 @@ HIPRT_EXPORT int hiprtReadFramebuffer(rfw::RenderContext *ptr, float *rgba)
 HIPRT_EXPORT int hiprtReadDisplay(rfw::RenderContext *ptr, uint8_t *rgba8)
 {
 	return static_cast<Context *>(ptr)->read_display(rgba8);
+}
+// ... and the same image as a baseline JPEG (include/rfwhip.h rfwhip_read_display_jpeg): at most `cap` bytes into `out`, *bytes = the
+// stream's length (also when cap is too small: RFWHIP_ERR_INVALID_ARGUMENT, nothing written); hiprtJpegBound: the cap that always suffices
+HIPRT_EXPORT int hiprtReadJpeg(rfw::RenderContext *ptr, void *out, size_t cap, size_t *bytes)
+{
+	return static_cast<Context *>(ptr)->read_jpeg(out, cap, bytes);
+}
+HIPRT_EXPORT int hiprtJpegBound(rfw::RenderContext *ptr, size_t *bytes)
+{
+	return static_cast<Context *>(ptr)->jpeg_bound(bytes);
 }
 // ... and how noisy the accumulated image still is (the noise estimate, include/rfwhip.h rfwhip_get_noise): 0, or an rfwhip_status
 // (rfwhip_last_error has the text) — without RFWHIP_NOISE=1, or before the second sample

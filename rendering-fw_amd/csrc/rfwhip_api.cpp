@@ -215,7 +215,8 @@ enum KernelFamily
 						   // without stage_timing (the milliseconds only with it)
 	KF_BLOOM = 12, // bloom (bloom.h): the down, up and apply passes of a chain, one count per launch
 	KF_GRADE = 13, // colour grading (display_grade.h): k_display_graded in place of family 7's kernel, one count per displayed image
-	KF_COUNT = 14
+	KF_JPEG = 14,  // baseline JPEG of the display image (display_jpeg.h): four launches per stream, one count each
+	KF_COUNT = 15
 };
 
 // A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
@@ -428,6 +429,18 @@ struct rfwhip_context
 	DevBuf d_grade_lut;
 	dm::event_t ev_grade; // behind the last graded display kernel that read the LUT on a caller's stream
 	bool ev_grade_ready = false, grade_pending = false;
+	// baseline JPEG (display_jpeg.h): the display_jpeg_* settings; every buffer is allocated by the first encode: d_jpeg_tab = the
+	// constant tables, d_jpeg_coef = the quantised blocks, d_jpeg_slots = the intervals' stuffed bytes, d_jpeg_counts / _offsets = the
+	// interval tables, d_jpeg_rec / d_jpeg_out = the record and the stream of the calls that read back themselves
+	int jpeg_quality = 90, jpeg_sub = 1, jpeg_restart = 8;
+	DevBuf d_jpeg_tab, d_jpeg_coef, d_jpeg_slots, d_jpeg_counts, d_jpeg_offsets, d_jpeg_rec, d_jpeg_out;
+	rtk::JpegRecord jpeg_rec_host = {0, 0, 0, 0, 0, 0, 0, 0}; // the last record this library read back
+	uint32_t jpeg_coef_blocks = 0;						   // blocks of the last encode (rfwhip_read_jpeg_coefficients)
+	float jpeg_kind_ms[4] = {};			 // family KF_JPEG by kernel: k_jpeg_blocks, k_jpeg_entropy, k_jpeg_offsets, k_jpeg_pack ...
+	uint32_t jpeg_kind_launches[4] = {}; // ... (stage_timing = 1; the read-only setting display_jpeg_time)
+	dm::event_t ev_jpeg;				 // behind the last encode: its stream is jpeg_stream (another stream waits for it: one scratch)
+	void *jpeg_stream = nullptr;
+	bool ev_jpeg_ready = false, jpeg_pending = false;
 	// the noise estimate (noise.h): d_noise = two moments per local pixel, allocated while noise_estimate is on.  noise_live: the
 	// moments cover every sample of the accumulator (the setting was on at the last RESET / rfwhip_init and ever since)
 	int noise_estimate = 0;
@@ -663,6 +676,7 @@ static void free_all(rfwhip_context *c)
 					  &c->d_present, &c->d_dn_guides, &c->d_dn_img, &c->d_dn_var, &c->d_dn_prev, &c->d_dn_ids, &c->d_dn_hist,
 					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
 					  &c->d_meter_rec, &c->d_meter_hist, &c->d_meter_part, &c->d_bloom_pyr, &c->d_bloom_out, &c->d_bloom_one, &c->d_grade_lut,
+					  &c->d_jpeg_tab, &c->d_jpeg_coef, &c->d_jpeg_slots, &c->d_jpeg_counts, &c->d_jpeg_offsets, &c->d_jpeg_rec, &c->d_jpeg_out,
 					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in,
 					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask, &c->d_lf_inst, &c->d_lf_bound, &c->d_lf_count, &c->d_lt_touched};
 	for (DevBuf *b : bufs)
@@ -678,6 +692,9 @@ static void free_all(rfwhip_context *c)
 	c->lut_host.clear(), c->lut_n = 0, c->grade_pending = false;
 	if (c->ev_grade_ready)
 		dm::event_destroy(c->ev_grade), c->ev_grade_ready = false;
+	c->jpeg_pending = false, c->jpeg_stream = nullptr, c->jpeg_coef_blocks = 0;
+	if (c->ev_jpeg_ready)
+		dm::event_destroy(c->ev_jpeg), c->ev_jpeg_ready = false;
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->dn_inst_ver_stale = true;
@@ -2337,6 +2354,11 @@ static int sync_all(rfwhip_context *c)
 		RF_TRY(dm::event_sync(c->ev_grade));
 		c->grade_pending = false;
 	}
+	if (c->jpeg_pending) // (an encode on a caller's stream writes the JPEG scratch)
+	{
+		RF_TRY(dm::event_sync(c->ev_jpeg));
+		c->jpeg_pending = false;
+	}
 	return 0;
 }
 
@@ -3042,6 +3064,10 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 		case KF_BLOOM:
 			if (sp.depth >= 0 && sp.depth < 4)
 				c->bloom_kind_ms[sp.depth] += ms, c->bloom_kind_launches[sp.depth]++;
+			break;
+		case KF_JPEG:
+			if (sp.depth >= 0 && sp.depth < 4)
+				c->jpeg_kind_ms[sp.depth] += ms, c->jpeg_kind_launches[sp.depth]++;
 			break;
 		default:
 			break;
@@ -3767,6 +3793,293 @@ extern "C" int rfwhip_display_image(rfwhip_context *c, const float *rgba_in, flo
 	return dm::sync(c->stream);
 }
 
+// ---- baseline JPEG (settings "display_jpeg_*"; work items and kernels: display_jpeg.h) ----------------------------------------------
+static_assert(sizeof(rfwhip_jpeg_stats) == sizeof(rtk::JpegRecord) && sizeof(rtk::JpegRecord) == 32, "rfwhip.h: the JPEG record is the kernels' (kernels.h)");
+// T.81 Annex K.1 (natural order), the zigzag sequence, Annex K.3 (BITS and HUFFVAL; the two DC tables share their values)
+static const uint8_t k_jpeg_q[2][64] = {
+	{16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+	 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+	{17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+	 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+static const uint8_t k_jpeg_zz[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+									  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+static const uint8_t k_jpeg_bits[4][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},	  // DC luminance
+										   {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},  // AC luminance
+										   {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0},	  // DC chrominance
+										   {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}}; // AC chrominance
+static const uint8_t k_jpeg_dc_val[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static const uint8_t k_jpeg_ac_val[2][162] = {
+	{0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1,
+	 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+	 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a,
+	 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+	 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3,
+	 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+	{0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1,
+	 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+	 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+	 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+	 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca,
+	 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+// the scaled table of a quality (IJG): s = 5000 / quality below 50, else 200 - 2 quality; Q = clamp((base s + 50) / 100, 1, 255)
+static void jpeg_quant_table(int table, int quality, uint16_t out[64])
+{
+	const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+	for (int i = 0; i < 64; i++)
+		out[i] = (uint16_t)std::min(std::max(((int)k_jpeg_q[table][i] * s + 50) / 100, 1), 255);
+}
+// canonical codes of one table: out[symbol] = code | length << 16 (0: the symbol has no code)
+static void jpeg_huffman(const uint8_t bits[16], const uint8_t *vals, uint32_t *out, size_t out_n)
+{
+	for (size_t i = 0; i < out_n; i++)
+		out[i] = 0u;
+	uint32_t code = 0u;
+	size_t k = 0;
+	for (uint32_t len = 1; len <= 16u; len++, code <<= 1)
+		for (uint32_t n = 0; n < bits[len - 1u]; n++, k++, code++)
+			if (vals[k] < out_n)
+				out[vals[k]] = code | (len << 16);
+}
+static void jpeg_tables(rtk::JpegTables &t)
+{
+	// K[u][x] = round(8192 a(u) cos((2 x + 1) u pi / 16)): 8192 / sqrt(8) in row 0, below it 4096 cos(n pi / 16) for n = 1 .. 7
+	static const int cs[8] = {4096, 4017, 3784, 3406, 2896, 2276, 1567, 799};
+	for (int u = 0; u < 8; u++)
+		for (int x = 0; x < 8; x++)
+		{
+			int n = ((2 * x + 1) * u) % 32, sign = 1;
+			if (n > 16)
+				n = 32 - n;
+			if (n > 8)
+				n = 16 - n, sign = -1;
+			t.K[u * 8 + x] = u == 0 ? 2896 : sign * (n == 8 ? 0 : cs[n]);
+		}
+	for (int z = 0; z < 64; z++)
+		t.zz[z] = k_jpeg_zz[z], t.izz[k_jpeg_zz[z]] = (uint8_t)z;
+	for (int table = 0; table < 2; table++)
+	{
+		jpeg_huffman(k_jpeg_bits[2 * table], k_jpeg_dc_val, t.dc[table], 12);
+		jpeg_huffman(k_jpeg_bits[2 * table + 1], k_jpeg_ac_val[table], t.ac[table], 256);
+	}
+}
+// SOI, APP0, DQT, SOF0, DHT, DRI, SOS: JP_HEADER bytes
+static void jpeg_header(const rfwhip_context *c, uint8_t *h)
+{
+	size_t n = 0;
+	const auto put8 = [&](uint32_t b) { h[n++] = (uint8_t)b; };
+	const auto put16 = [&](uint32_t w) { put8(w >> 8), put8(w & 255u); };
+	put16(0xFFD8);
+	put16(0xFFE0), put16(16);
+	for (const uint8_t b : {0x4A, 0x46, 0x49, 0x46, 0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00})
+		put8(b);
+	put16(0xFFDB), put16(2 + 2 * 65);
+	for (int table = 0; table < 2; table++)
+	{
+		uint16_t q[64];
+		jpeg_quant_table(table, c->jpeg_quality, q);
+		put8((uint32_t)table);
+		for (int z = 0; z < 64; z++)
+			put8(q[k_jpeg_zz[z]]);
+	}
+	put16(0xFFC0), put16(17), put8(8), put16(c->H), put16(c->W), put8(3);
+	put8(1), put8(c->jpeg_sub ? 0x22 : 0x11), put8(0), put8(2), put8(0x11), put8(1), put8(3), put8(0x11), put8(1);
+	put16(0xFFC4), put16(2 + 2 * (17 + 12) + 2 * (17 + 162));
+	for (int k = 0; k < 4; k++) // DC0, AC0, DC1, AC1
+	{
+		put8((uint32_t)((k & 1) << 4 | (k >> 1)));
+		for (int i = 0; i < 16; i++)
+			put8(k_jpeg_bits[k][i]);
+		if (k & 1)
+			for (int i = 0; i < 162; i++)
+				put8(k_jpeg_ac_val[k >> 1][i]);
+		else
+			for (int i = 0; i < 12; i++)
+				put8(k_jpeg_dc_val[i]);
+	}
+	put16(0xFFDD), put16(4), put16((uint32_t)c->jpeg_restart);
+	put16(0xFFDA), put16(12), put8(3), put8(1), put8(0x00), put8(2), put8(0x11), put8(3), put8(0x11), put8(0), put8(63), put8(0);
+	(void)n; // == JP_HEADER (tests/test_display_jpeg.py holds the header to the model's byte for byte)
+}
+// the geometry of the target under the current settings, and the capacity that always suffices: the header, every block at its
+// worst case, two marker bytes per interval
+static void jpeg_geometry(const rfwhip_context *c, rtk::JpegView &v)
+{
+	const uint32_t M = c->jpeg_sub ? 16u : 8u;
+	v.W = c->W, v.H = c->H, v.sub = (uint32_t)c->jpeg_sub;
+	v.mcus_x = (c->W + M - 1u) / M, v.mcus = v.mcus_x * ((c->H + M - 1u) / M);
+	v.bpm = c->jpeg_sub ? 6u : 3u, v.blocks = v.mcus * v.bpm;
+	v.ri = (uint32_t)c->jpeg_restart, v.intervals = (v.mcus + v.ri - 1u) / v.ri;
+}
+static uint64_t jpeg_bound(const rtk::JpegView &v) { return (uint64_t)rtk::JP_HEADER + (uint64_t)v.blocks * rtk::JP_BLOCK_BYTES + 2ull * v.intervals; }
+static int jpeg_check_target(const rfwhip_context *c, const char *who)
+{
+	if (!c->W)
+		return set_error(RFWHIP_ERR_STATE, "no render target");
+	if (c->W > 65535u || c->H > 65535u)
+		return set_error(RFWHIP_ERR_UNSUPPORTED, "%s: a JPEG is at most 65535 pixels wide and high, the target is %u x %u", who, c->W, c->H);
+	return RFWHIP_OK;
+}
+// the four kernels on `stream`: W x H RGBA8 at `rgba8` -> the stream at `out` (cap bytes, >= JP_HEADER) and the record at `rec`
+static int jpeg_enqueue(rfwhip_context *c, const void *rgba8, void *out, size_t cap, void *rec, void *stream)
+{
+	rtk::JpegView v;
+	memset(&v, 0, sizeof(v));
+	jpeg_geometry(c, v);
+	if (jpeg_bound(v) + 3ull * v.intervals > 0xFFFFFFFFull)
+		return set_error(RFWHIP_ERR_UNSUPPORTED, "display_jpeg: a %u x %u target is too large for the encoder's 32-bit offsets", c->W, c->H);
+	// one scratch: an encode on another stream has to be through with it
+	if (c->jpeg_pending && c->jpeg_stream != stream)
+	{
+		RF_TRY(dm::event_sync(c->ev_jpeg));
+		c->jpeg_pending = false;
+	}
+	if (!c->d_jpeg_tab.p)
+	{
+		rtk::JpegTables t;
+		jpeg_tables(t);
+		RF_TRY(c->d_jpeg_tab.ensure(sizeof(t)));
+		RF_TRY(dm::h2d(c->d_jpeg_tab.p, &t, sizeof(t), c->stream));
+		RF_TRY(dm::sync(c->stream));
+	}
+	const size_t need[4] = {(size_t)v.blocks * 128u, (size_t)v.blocks * rtk::JP_BLOCK_BYTES + 3u * (size_t)v.intervals, (size_t)v.intervals * 8u, (size_t)v.intervals * 4u};
+	DevBuf *buf[4] = {&c->d_jpeg_coef, &c->d_jpeg_slots, &c->d_jpeg_counts, &c->d_jpeg_offsets};
+	for (int k = 0; k < 4; k++)
+		if (need[k] > buf[k]->cap || !buf[k]->p)
+		{
+			RF_TRY(sync_all(c)); // (an encode in flight uses the buffer this reallocates)
+			if (stream != c->stream)
+				RF_TRY(dm::sync(stream));
+			RF_TRY(buf[k]->ensure(need[k]));
+		}
+	v.rgba = (const uint32_t *)rgba8, v.tab = c->d_jpeg_tab.as<rtk::JpegTables>();
+	jpeg_quant_table(0, c->jpeg_quality, v.q[0]), jpeg_quant_table(1, c->jpeg_quality, v.q[1]);
+	v.coef = c->d_jpeg_coef.as<int16_t>(), v.slots = c->d_jpeg_slots.as<uint8_t>();
+	v.counts = c->d_jpeg_counts.as<uint32_t>(), v.offsets = c->d_jpeg_offsets.as<uint32_t>();
+	v.rec = (rtk::JpegRecord *)rec, v.out = (uint8_t *)out, v.cap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu);
+	uint8_t header[rtk::JP_HEADER];
+	jpeg_header(c, header);
+	RF_TRY(dm::h2d(out, header, sizeof(header), stream));
+	void (*const launch[4])(const rtk::JpegView &, void *) = {rtk::launch_jpeg_blocks, rtk::launch_jpeg_entropy, rtk::launch_jpeg_offsets, rtk::launch_jpeg_pack};
+	for (int k = 0; k < 4; k++)
+	{
+		StageTimer t(c, KF_JPEG, k, stream);
+		launch[k](v, stream);
+		t.stop(1);
+		RF_TRY(dm::last_launch_error());
+	}
+	c->jpeg_coef_blocks = v.blocks;
+	if (!c->ev_jpeg_ready)
+	{
+		RF_TRY(dm::event_create(&c->ev_jpeg, false));
+		c->ev_jpeg_ready = true;
+	}
+	RF_TRY(dm::event_record(c->ev_jpeg, stream));
+	c->jpeg_pending = true, c->jpeg_stream = stream;
+	return 0;
+}
+
+extern "C" int rfwhip_display_jpeg_bound(rfwhip_context *c, size_t *bytes)
+{
+	CTX_ENTER(c);
+	if (!bytes)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_display_jpeg_bound: null argument");
+	RF_TRY(jpeg_check_target(c, "rfwhip_display_jpeg_bound"));
+	rtk::JpegView v;
+	memset(&v, 0, sizeof(v));
+	jpeg_geometry(c, v);
+	*bytes = (size_t)jpeg_bound(v);
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_display_jpeg_stream(rfwhip_context *c, const void *rgba8_device, void *out_device, size_t cap, void *record_device, void *hip_stream)
+{
+	CTX_ENTER(c);
+	if (!rgba8_device || !out_device || !record_device)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_display_jpeg_stream: null argument");
+	RF_TRY(jpeg_check_target(c, "rfwhip_display_jpeg_stream"));
+	if (cap < rtk::JP_HEADER)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_display_jpeg_stream: cap = %zu bytes does not hold the header of %u bytes", cap, rtk::JP_HEADER);
+	return jpeg_enqueue(c, rgba8_device, out_device, cap, record_device, hip_stream);
+}
+
+// the RGBA8 image in d_display -> the stream in `out_host`: the record first, then exactly its bytes
+static int jpeg_read_back(rfwhip_context *c, const char *who, void *out_host, size_t cap, size_t *bytes)
+{
+	rtk::JpegView v;
+	memset(&v, 0, sizeof(v));
+	jpeg_geometry(c, v);
+	// (the device's capacity: the caller's, never more than the bound and never less than the header — the record then names the
+	// stream's length whether it fitted or not)
+	const size_t dev_cap = (size_t)std::min<uint64_t>(jpeg_bound(v), std::max<uint64_t>(cap, rtk::JP_HEADER));
+	RF_TRY(c->d_jpeg_rec.ensure(sizeof(rtk::JpegRecord)));
+	if (dev_cap > c->d_jpeg_out.cap || !c->d_jpeg_out.p)
+	{
+		RF_TRY(sync_all(c));
+		RF_TRY(c->d_jpeg_out.ensure(dev_cap));
+	}
+	RF_TRY(jpeg_enqueue(c, c->d_display.p, c->d_jpeg_out.p, dev_cap, c->d_jpeg_rec.p, c->stream));
+	rtk::JpegRecord r;
+	RF_TRY(dm::d2h(&r, c->d_jpeg_rec.p, sizeof(r), c->stream));
+	c->jpeg_pending = false; // (the stream is idle)
+	c->jpeg_rec_host = r;
+	if (bytes)
+		*bytes = r.bytes;
+	if (r.overflow || (size_t)r.bytes > cap)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: the stream has %u bytes, cap is %zu", who, r.bytes, cap);
+	return dm::d2h(out_host, c->d_jpeg_out.p, r.bytes, c->stream);
+}
+
+extern "C" int rfwhip_read_display_jpeg(rfwhip_context *c, void *out_host, size_t cap, size_t *bytes)
+{
+	CTX_ENTER(c);
+	if (!out_host && cap)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_display_jpeg: null destination");
+	RF_TRY(jpeg_check_target(c, "rfwhip_read_display_jpeg"));
+	// present -> denoise when on -> display (RGBA8) -> encode
+	RF_TRY(c->d_display.ensure((size_t)c->W * c->H * 4u));
+	RF_TRY(rfwhip_read_display_device(c, RFWHIP_DISPLAY_RGBA8, c->d_display.p));
+	return jpeg_read_back(c, "rfwhip_read_display_jpeg", out_host, cap, bytes);
+}
+
+extern "C" int rfwhip_jpeg_image(rfwhip_context *c, const void *rgba8_in, void *out_host, size_t cap, size_t *bytes)
+{
+	CTX_ENTER(c);
+	if (!rgba8_in || (!out_host && cap))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_jpeg_image: null image");
+	RF_TRY(jpeg_check_target(c, "rfwhip_jpeg_image"));
+	RF_TRY(sync_all(c));
+	const size_t px = (size_t)c->W * c->H;
+	RF_TRY(c->d_display.ensure(px * 4u));
+	RF_TRY(dm::h2d(c->d_display.p, rgba8_in, px * 4u, c->stream));
+	return jpeg_read_back(c, "rfwhip_jpeg_image", out_host, cap, bytes);
+}
+
+extern "C" int rfwhip_get_jpeg(rfwhip_context *c, rfwhip_jpeg_stats *stats)
+{
+	CTX_ENTER(c);
+	if (!stats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_get_jpeg: null argument");
+	if (!c->jpeg_rec_host.header)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_get_jpeg: no stream has been read back");
+	memcpy(stats, &c->jpeg_rec_host, sizeof(*stats));
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_jpeg_coefficients(rfwhip_context *c, int16_t *out, size_t cap_blocks, uint32_t *blocks)
+{
+	CTX_ENTER(c);
+	if (!c->jpeg_coef_blocks)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_jpeg_coefficients: nothing has been encoded");
+	if (blocks)
+		*blocks = c->jpeg_coef_blocks;
+	if (!out)
+		return RFWHIP_OK; // (the count alone)
+	if (cap_blocks < c->jpeg_coef_blocks)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_jpeg_coefficients: %u blocks, room for %zu", c->jpeg_coef_blocks, cap_blocks);
+	RF_TRY(sync_all(c));
+	return dm::d2h(out, c->d_jpeg_coef.p, (size_t)c->jpeg_coef_blocks * 128u, c->stream);
+}
+
 extern "C" int rfwhip_bloom_image(rfwhip_context *c, const float *rgba_in, float exposure, float *rgba_out)
 {
 	CTX_ENTER(c);
@@ -4448,6 +4761,15 @@ static int set_int_in(int &dst, const char *key, const char *value, int lo, int 
 	dst = n;
 	return RFWHIP_OK;
 }
+static int set_whole_in(int &dst, const char *key, const char *value, long lo, long hi) // strict: the whole of `value` is one whole number in [lo, hi]
+{
+	char *end = nullptr;
+	const long n = strtol(value, &end, 10);
+	if (!end || *end || end == value || n < lo || n > hi)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be a whole number in [%ld, %ld]", key, lo, hi);
+	dst = (int)n;
+	return RFWHIP_OK;
+}
 static int parse_01(const char *key, const char *value, bool *on) // strict: exactly "0" or "1"
 {
 	if (strcmp(value, "0") && strcmp(value, "1"))
@@ -4766,6 +5088,17 @@ static const Setting k_settings[] = {
 	{"display_lut", nullptr, GET { return put(out, cap, "%u", c->lut_n); }, false},
 	// (read-only, stage_timing = 1) family 13 since its last reset: the milliseconds of k_display_graded, then its launches
 	{"display_grade_time", nullptr, GET { return put(out, cap, "%.6f %u", c->kernel_ms[KF_GRADE], c->kernel_launches[KF_GRADE]); }, false},
+	// baseline JPEG (display_jpeg.h): strict whole numbers; a refused value leaves the setting as it was
+	{"display_jpeg_quality", SET { return set_whole_in(c->jpeg_quality, key, value, 1, 100); }, GET_INT(jpeg_quality), false},
+	{"display_jpeg_subsampling", SET { return set_enum2(c->jpeg_sub, key, value, "444", "420"); },
+	 GET { return put(out, cap, "%s", c->jpeg_sub ? "420" : "444"); }, false},
+	{"display_jpeg_restart", SET { return set_whole_in(c->jpeg_restart, key, value, 1, 65535); }, GET_INT(jpeg_restart), false},
+	// (read-only) the length of the last stream this library read back (rfwhip_read_display_jpeg, rfwhip_jpeg_image), 0 before
+	{"display_jpeg_bytes", nullptr, GET { return put(out, cap, "%u", c->jpeg_rec_host.bytes); }, false},
+	// (read-only, stage_timing = 1) family 14 by kernel since its last reset: the milliseconds of k_jpeg_blocks, k_jpeg_entropy,
+	// k_jpeg_offsets, k_jpeg_pack, then their launches
+	{"display_jpeg_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %u %u %u %u", c->jpeg_kind_ms[0], c->jpeg_kind_ms[1], c->jpeg_kind_ms[2], c->jpeg_kind_ms[3],
+													 c->jpeg_kind_launches[0], c->jpeg_kind_launches[1], c->jpeg_kind_launches[2], c->jpeg_kind_launches[3]); }, false},
 	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
 	{"noise_estimate", SET {
 		 bool on;
@@ -4920,7 +5253,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)
@@ -4930,6 +5263,9 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	if (reset && which == KF_BLOOM)
 		for (int k = 0; k < 4; k++)
 			c->bloom_kind_ms[k] = 0.0f, c->bloom_kind_launches[k] = 0;
+	if (reset && which == KF_JPEG)
+		for (int k = 0; k < 4; k++)
+			c->jpeg_kind_ms[k] = 0.0f, c->jpeg_kind_launches[k] = 0;
 	return RFWHIP_OK;
 }
 

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 
 #if !defined(RFWHIP_HOST_EMULATION)
@@ -143,9 +144,18 @@ struct rfwhip_group
 	dm::event_t host_ready[SLOTS], slot_done[SLOTS];
 	bool host_events = false, host_pending[SLOTS] = {};
 	// display stage (rfwhip_group_read_display / _present_display_*): the root's display image of a read, of each slot, and what a
-	// slot was last presented with: SLOT_NONE, SLOT_FLOAT, or SLOT_DISPLAY + the format
-	static constexpr int SLOT_NONE = -2, SLOT_FLOAT = -1, SLOT_DISPLAY = 0;
+	// slot was last presented with: SLOT_NONE, SLOT_FLOAT, SLOT_DISPLAY + the format, or SLOT_JPEG
+	static constexpr int SLOT_NONE = -2, SLOT_FLOAT = -1, SLOT_DISPLAY = 0, SLOT_JPEG = 2;
 	void *disp = nullptr, *slot_disp[SLOTS] = {};
+	// baseline JPEG (rfwhip_group_read_display_jpeg / _present_jpeg_*): the root's stream and 32-byte record of a read and of each
+	// slot, jpeg_cap bytes each (the bound when they were allocated)
+	void *jpeg = nullptr, *jpeg_rec = nullptr, *slot_jpeg[SLOTS] = {}, *slot_jrec[SLOTS] = {};
+	size_t jpeg_cap = 0, slot_jpeg_cap[SLOTS] = {};
+	// the copy of a slot's stream is enqueued before its length is known: the record, and behind it (at JPEG_HOST_OFFSET of the slot's
+	// pinned image) the first slot_jpeg_copied bytes — jpeg_guess: an eighth more than the last stream waited for, one byte per pixel
+	// before the first.  A stream that turns out longer is copied again by the wait.
+	static constexpr size_t JPEG_HOST_OFFSET = 64;
+	size_t jpeg_guess = 0, slot_jpeg_copied[SLOTS] = {};
 	int slot_kind[SLOTS] = {SLOT_NONE, SLOT_NONE, SLOT_NONE, SLOT_NONE};
 	size_t chunk_bytes() const { return (size_t)local_rows * W * PIXEL_BYTES; }
 };
@@ -167,15 +177,17 @@ void release_buffers(rfwhip_group *g)
 	if (g->root_local >= 0)
 	{
 		(void)dm::use(g->ep[g->root_local].device);
-		dm::release(g->staging), dm::release(g->full), dm::release(g->disp);
+		dm::release(g->staging), dm::release(g->full), dm::release(g->disp), dm::release(g->jpeg), dm::release(g->jpeg_rec);
 	}
-	g->staging = g->full = g->disp = nullptr;
+	g->staging = g->full = g->disp = g->jpeg = g->jpeg_rec = nullptr, g->jpeg_cap = 0;
 	g->staging_read_valid = false;
 	for (int k = 0; k < rfwhip_group::SLOTS; k++)
 	{
 		dm::host_free(g->host_img[k]), g->host_img[k] = nullptr, g->host_pending[k] = false;
 		dm::release(g->slot_img[k]), g->slot_img[k] = nullptr;
 		dm::release(g->slot_disp[k]), g->slot_disp[k] = nullptr, g->slot_kind[k] = rfwhip_group::SLOT_NONE;
+		dm::release(g->slot_jpeg[k]), dm::release(g->slot_jrec[k]), g->slot_jpeg[k] = g->slot_jrec[k] = nullptr, g->slot_jpeg_cap[k] = 0;
+		g->slot_jpeg_copied[k] = 0;
 	}
 }
 
@@ -590,7 +602,29 @@ extern "C" int rfwhip_group_read_framebuffer(rfwhip_group *g, float *rgba_host)
 static_assert(rfwhip_group::SLOTS == 4, "slot_kind's initialiser");
 static size_t display_bytes(int format) { return format == RFWHIP_DISPLAY_RGBA8 ? 4u : PIXEL_BYTES; }
 
-// kind: SLOT_FLOAT, or SLOT_DISPLAY + format: the display stage runs behind the gather (and the root's denoiser) on the root's
+// room on the root's device for a JPEG stream of the current bound and its record (reallocated when the settings raised the bound)
+static int jpeg_room(rfwhip_group *g, Endpoint &root, void **stream_buf, void **rec, size_t *cap)
+{
+	size_t bound = 0;
+	if (rfwhip_display_jpeg_bound(root.ctx, &bound))
+		return RFWHIP_ERR_STATE; // (the context's message stands)
+	GR_TRY(dm::use(root.device));
+	if (!*rec)
+		GR_TRY(dm::alloc(rec, sizeof(rfwhip_jpeg_stats)));
+	if (bound > *cap)
+	{
+		GR_TRY(wait_all(g)); // (an encode or a copy in flight may use the buffer this replaces)
+		if (g->copy_stream)
+			GR_TRY(dm::sync(g->copy_stream));
+		GR_TRY(dm::use(root.device));
+		dm::release(*stream_buf), *stream_buf = nullptr, *cap = 0;
+		GR_TRY(dm::alloc(stream_buf, bound));
+		*cap = bound;
+	}
+	return RFWHIP_OK;
+}
+
+// kind: SLOT_FLOAT, SLOT_DISPLAY + format, or SLOT_JPEG: the display stage runs behind the gather (and the root's denoiser) on the root's
 // gather stream, and the copy carries its output
 static int present_async(rfwhip_group *g, int slot, int kind, const char *who)
 {
@@ -612,24 +646,35 @@ static int present_async(rfwhip_group *g, int slot, int kind, const char *who)
 		g->host_events = true;
 	}
 	if (!g->host_img[slot])
-		GR_TRY(dm::host_alloc(&g->host_img[slot], bytes)); // (sized for the float image: either kind fits)
+		GR_TRY(dm::host_alloc(&g->host_img[slot], bytes + rfwhip_group::JPEG_HOST_OFFSET)); // (sized for the float image: every kind fits)
 	if (!g->slot_img[slot])
 		GR_TRY(dm::alloc(&g->slot_img[slot], bytes));
-	const bool display = kind != rfwhip_group::SLOT_FLOAT;
+	const bool display = kind != rfwhip_group::SLOT_FLOAT, jpeg = kind == rfwhip_group::SLOT_JPEG;
 	if (display && !g->slot_disp[slot])
 		GR_TRY(dm::alloc(&g->slot_disp[slot], bytes));
+	if (jpeg)
+		GR_TRY(jpeg_room(g, root, &g->slot_jpeg[slot], &g->slot_jrec[slot], &g->slot_jpeg_cap[slot]));
 	// the slot's device images are rewritten only after the slot's previous copy to the host has read them
 	if (g->host_pending[slot])
 		GR_TRY(dm::stream_wait_event(root.stream, g->host_ready[slot]));
 	GR_TRY(gather(g, g->slot_img[slot]));
-	if (display && rfwhip_display_stream(root.ctx, g->slot_img[slot], g->slot_disp[slot], kind, root.stream))
+	if (display && rfwhip_display_stream(root.ctx, g->slot_img[slot], g->slot_disp[slot], jpeg ? RFWHIP_DISPLAY_RGBA8 : kind, root.stream))
 		return RFWHIP_ERR_STATE; // (the context's message stands)
+	if (jpeg && rfwhip_display_jpeg_stream(root.ctx, g->slot_disp[slot], g->slot_jpeg[slot], g->slot_jpeg_cap[slot], g->slot_jrec[slot], root.stream))
+		return RFWHIP_ERR_STATE;
 	GR_TRY(dm::use(root.device));
 	GR_TRY(dm::event_record(g->slot_done[slot], root.stream));
 	// ... and the copy rides its own stream: the next frame's present / transfer / de-interleave do not queue behind 33 MB of PCIe
 	// (a display image: 8 MB as RGBA8)
 	GR_TRY(dm::stream_wait_event(g->copy_stream, g->slot_done[slot]));
-	if (display)
+	if (jpeg) // (the record and a guess at the stream: rfwhip_group_present_jpeg_wait copies again if the stream is longer)
+	{
+		GR_TRY(dm::d2h_async(g->host_img[slot], g->slot_jrec[slot], sizeof(rfwhip_jpeg_stats), g->copy_stream));
+		const size_t guess = g->jpeg_guess ? g->jpeg_guess : (size_t)g->W * g->H;
+		g->slot_jpeg_copied[slot] = std::min(std::min(guess, g->slot_jpeg_cap[slot]), bytes);
+		GR_TRY(dm::d2h_async((char *)g->host_img[slot] + rfwhip_group::JPEG_HOST_OFFSET, g->slot_jpeg[slot], g->slot_jpeg_copied[slot], g->copy_stream));
+	}
+	else if (display)
 		GR_TRY(dm::d2h_async(g->host_img[slot], g->slot_disp[slot], (size_t)g->W * g->H * display_bytes(kind), g->copy_stream));
 	else
 		GR_TRY(dm::d2h_async(g->host_img[slot], g->slot_img[slot], bytes, g->copy_stream));
@@ -638,13 +683,18 @@ static int present_async(rfwhip_group *g, int slot, int kind, const char *who)
 	return RFWHIP_OK;
 }
 
-static int present_wait(rfwhip_group *g, int slot, bool display, const char *who)
+// want: 0 a float image, 1 a display image, 2 a JPEG stream
+static int present_wait(rfwhip_group *g, int slot, int want, const char *who)
 {
 	if (g->slot_kind[slot] == rfwhip_group::SLOT_NONE || !g->host_img[slot])
 		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "%s: nothing was presented into slot %d", who, slot);
-	if ((g->slot_kind[slot] != rfwhip_group::SLOT_FLOAT) != display)
-		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "%s: slot %d holds a %s image (presented with rfwhip_group_present_%sasync)", who,
-										 slot, display ? "float" : "display", display ? "" : "display_");
+	const int holds = g->slot_kind[slot] == rfwhip_group::SLOT_FLOAT ? 0 : g->slot_kind[slot] == rfwhip_group::SLOT_JPEG ? 2 : 1;
+	if (holds != want)
+	{
+		static const char *const what[3] = {"a float image", "a display image", "a JPEG stream"}, *const call[3] = {"", "display_", "jpeg_"};
+		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "%s: slot %d holds %s (presented with rfwhip_group_present_%sasync)", who, slot,
+										 what[holds], call[holds]);
+	}
 	if (g->host_pending[slot])
 	{
 		GR_TRY(dm::use(g->ep[(size_t)g->root_local].device));
@@ -663,7 +713,7 @@ extern "C" int rfwhip_group_present_wait(rfwhip_group *g, int slot, const float 
 {
 	if (!g || slot < 0 || slot >= rfwhip_group::SLOTS || !rgba_host)
 		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_wait: bad arguments");
-	GR_TRY(present_wait(g, slot, false, "rfwhip_group_present_wait"));
+	GR_TRY(present_wait(g, slot, 0, "rfwhip_group_present_wait"));
 	*rgba_host = (const float *)g->host_img[slot];
 	return RFWHIP_OK;
 }
@@ -679,7 +729,7 @@ extern "C" int rfwhip_group_present_display_wait(rfwhip_group *g, int slot, cons
 {
 	if (!g || slot < 0 || slot >= rfwhip_group::SLOTS || !out_host)
 		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_display_wait: bad arguments");
-	GR_TRY(present_wait(g, slot, true, "rfwhip_group_present_display_wait"));
+	GR_TRY(present_wait(g, slot, 1, "rfwhip_group_present_display_wait"));
 	*out_host = g->host_img[slot];
 	if (format)
 		*format = g->slot_kind[slot];
@@ -704,6 +754,58 @@ extern "C" int rfwhip_group_read_display(rfwhip_group *g, int format, void *out_
 	GR_TRY(wait_all(g));
 	GR_TRY(dm::use(root.device));
 	return dm::d2h(out_host, g->disp, (size_t)g->W * g->H * display_bytes(format), root.stream);
+}
+
+extern "C" int rfwhip_group_read_display_jpeg(rfwhip_group *g, void *out_host, size_t cap, size_t *bytes)
+{
+	if (!g || (!out_host && cap))
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null argument");
+	if (g->root_local < 0 || !g->full)
+		return rfwhip_internal_set_error(RFWHIP_ERR_STATE, "no render target");
+	Endpoint &root = g->ep[(size_t)g->root_local];
+	GR_TRY(dm::use(root.device));
+	if (!g->disp)
+		GR_TRY(dm::alloc(&g->disp, (size_t)g->W * g->H * PIXEL_BYTES));
+	GR_TRY(jpeg_room(g, root, &g->jpeg, &g->jpeg_rec, &g->jpeg_cap));
+	GR_TRY(gather(g, nullptr));
+	if (rfwhip_display_stream(root.ctx, g->full, g->disp, RFWHIP_DISPLAY_RGBA8, root.stream) ||
+		rfwhip_display_jpeg_stream(root.ctx, g->disp, g->jpeg, g->jpeg_cap, g->jpeg_rec, root.stream))
+		return RFWHIP_ERR_STATE; // (the context's message stands)
+	GR_TRY(wait_all(g));
+	GR_TRY(dm::use(root.device));
+	rfwhip_jpeg_stats st;
+	GR_TRY(dm::d2h(&st, g->jpeg_rec, sizeof(st), root.stream));
+	if (bytes)
+		*bytes = st.bytes;
+	if (st.overflow || (size_t)st.bytes > cap)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_read_display_jpeg: the stream has %u bytes, cap is %zu", st.bytes, cap);
+	return dm::d2h(out_host, g->jpeg, st.bytes, root.stream);
+}
+
+extern "C" int rfwhip_group_present_jpeg_async(rfwhip_group *g, int slot)
+{
+	return present_async(g, slot, rfwhip_group::SLOT_JPEG, "rfwhip_group_present_jpeg_async");
+}
+
+extern "C" int rfwhip_group_present_jpeg_wait(rfwhip_group *g, int slot, void *out_host, size_t cap, size_t *bytes)
+{
+	if (!g || slot < 0 || slot >= rfwhip_group::SLOTS || (!out_host && cap))
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_jpeg_wait: bad arguments");
+	GR_TRY(present_wait(g, slot, 2, "rfwhip_group_present_jpeg_wait"));
+	const rfwhip_jpeg_stats st = *(const rfwhip_jpeg_stats *)g->host_img[slot];
+	if (bytes)
+		*bytes = st.bytes;
+	if (st.overflow || (size_t)st.bytes > cap)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_group_present_jpeg_wait: the stream has %u bytes, cap is %zu", st.bytes, cap);
+	g->jpeg_guess = (size_t)st.bytes + st.bytes / 8u + 4096u;
+	if ((size_t)st.bytes <= g->slot_jpeg_copied[slot]) // the usual case: the stream came with the record
+	{
+		memcpy(out_host, (const char *)g->host_img[slot] + rfwhip_group::JPEG_HOST_OFFSET, st.bytes);
+		return RFWHIP_OK;
+	}
+	// (the record has landed, so the encode behind it is complete: the copy needs no further ordering)
+	GR_TRY(dm::use(g->ep[(size_t)g->root_local].device));
+	return dm::d2h(out_host, g->slot_jpeg[slot], st.bytes, g->copy_stream);
 }
 
 extern "C" int rfwhip_group_get_noise(rfwhip_group *g, rfwhip_noise_stats *stats)

@@ -9,7 +9,8 @@ number into every local label (.LBB<f>_<n>, BB<f>_<n> in loop comments, .Lfunc_e
 above ends with the section header of whatever function follows it: a kernel added or removed elsewhere changes both without
 changing an instruction.  With --labels the function number is taken out of the labels and the lines that open the following
 function's section (.section / .protected / .weak / .hidden, and the "-- Begin function" comment) are dropped; a kernel's text ends
-with its resource summary ("; Kernel info:" comments), and only kernels are compared."""
+with its resource summary ("; Kernel info:" comments), only kernels are compared, and the blanks in front of a trailing comment
+(padding to a column, which moves when a function number gains a digit) count as one."""
 import re
 import sys
 
@@ -24,7 +25,8 @@ def normal(l):
         return l
     if re.match(r"\s*\.(section|protected|weak|hidden)\s", l) or "-- Begin function" in l:
         return None
-    return re.sub(r"(\.LBB|\bBB|\.Lfunc_end|\.Lfunc_begin|\.LJTI)\d+", r"\1", l)
+    # (the blanks in front of a label's trailing comment pad it to a column: a function number with one digit more moves them)
+    return re.sub(r"\s+;", " ;", re.sub(r"(\.LBB|\bBB|\.Lfunc_end|\.Lfunc_begin|\.LJTI)\d+", r"\1", l))
 
 
 def kernels(path):
