@@ -382,6 +382,81 @@ RFWHIP_API int rfwhip_get_jpeg(rfwhip_context *ctx, rfwhip_jpeg_stats *stats);
 RFWHIP_API int rfwhip_jpeg_image(rfwhip_context *ctx, const void *rgba8_in, void *out_host, size_t cap, size_t *bytes);
 RFWHIP_API int rfwhip_read_jpeg_coefficients(rfwhip_context *ctx, int16_t *out, size_t cap_blocks, uint32_t *blocks);
 
+/* ---- image textures: JPEG decode and the mip chain on the device (csrc/texture_decode.h) ---------------------
+ * In the reference a texture file is decoded, flipped, linearised and given its mip chain by rfw::texture (texture.cpp of the system
+ * layer, FreeImage); a backend sees texels only (rfwhip_set_textures).  These calls take the file instead: the bytes of a baseline
+ * JPEG, or a PNG's RGBA8 pixels, and build the texture's slot of the one texel table on the device (kernel family 15).  Level 0 of a
+ * JPEG never crosses the bus as texels.
+ * ACCEPTED STREAMS  SOF0, or SOF1 with 8-bit samples and Huffman coding; 1 component, or 3 in one interleaved scan with luma sampling
+ *   1x1, 2x1 or 2x2 over chroma 1x1; 8-bit quantisation tables; up to four DC and four AC Huffman tables in any number of DHT segments;
+ *   DRI or none; APPn, COM and fill bytes are skipped.  Everything else (progressive, arithmetic, 12-bit, 4 components, several scans,
+ *   other sampling, an APP14 that declares RGB or CMYK) is RFWHIP_ERR_UNSUPPORTED with a message naming the form; a malformed stream
+ *   is RFWHIP_ERR_INVALID_ARGUMENT.
+ * THE DECODE is defined in integers (an implementation of this text agrees with the device, and with the common decoders' defaults,
+ *   byte for byte):
+ *   Coefficients: blocks of 64 int16 in zigzag order, MCU by MCU: the luma blocks row by row, then Cb, Cr.  The entropy data of a
+ *     stream with restart intervals is decoded on the device, a lane per interval; of a stream without on the host (one interval is
+ *     serial), its coefficients uploaded.  Setting texture_entropy = auto | host | device forces either; both give the same words.
+ *   Inverse DCT: dequantise; the 13-bit-constant "slow integer" transform (even part from 4433, 6270, 15137; odd part from 2446, 3196,
+ *     7373, 9633, 12299, 16069, 16819, 20995, 25172), columns first with a descale by 11 bits, rows with 18, each rounding half up;
+ *     + 128; clamp.  All in wrapping 32-bit arithmetic.
+ *   Chroma: the component at its own size ceil(w / 2) x ceil(h / 2), edges replicated.  2x2: v = 3 near + far vertically, then
+ *     (3 this + left + 8) >> 4 for even and (3 this + right + 7) >> 4 for odd columns.  2x1: (3 this + left + 1) >> 2 and
+ *     (3 this + right + 2) >> 2.  A component at most 2 columns wide is replicated instead.
+ *   Colour, with FIX(x) = int(x 65536 + 0.5), Cb and Cr centred on 0:  R = Y + ((FIX(1.402) Cr + 32768) >> 16),
+ *     B = Y + ((FIX(1.772) Cb + 32768) >> 16),  G = Y + ((-FIX(0.34414) Cb + 32768 - FIX(0.71414) Cr) >> 16), clamped; grey: R = G = B = Y;
+ *     alpha 255.  Then the flags (rfwhip_abi.h): flip, linearise.  Texel = r | g << 8 | b << 16 | a << 24.
+ *   Mips: five levels (MIPLEVELCOUNT), level i is (w >> i) x (h >> i), back to back behind level 0; a colour channel is the truncated
+ *     quarter of the aligned 2 x 2 quad's sum, alpha the minimum of the four (construct_mipmaps, texture.cpp:163-209).
+ * rfwhip_set_texture_sources: rfwhip_set_textures for mixed sources (replaces rfw::texture's constructors, texture.cpp:16-138): parses
+ *   every header, lays out the one table, uploads TEXELS entries as they are, decodes and mips the others on the context's stream.
+ *   All or nothing: on any error the previous textures stay in place and the message names the texture's index.
+ * rfwhip_image_info (host only; replaces FreeImage's header queries, texture.cpp:34-49): RFWHIP_OK with supported = 1, or with
+ *   supported = 0 and the reason for a well-formed stream of a form not decoded here; RFWHIP_ERR_INVALID_ARGUMENT for a malformed one.
+ * rfwhip_get_texture_decode: the record of texture `index` of the current table (zeros for a TEXELS entry); alpha_zero is what the
+ *   reference derives HAS_ALPHA from (texture.cpp:52-58).  index = (size_t)-1: the record of the last rfwhip_decode_image.
+ * rfwhip_read_texture: all levels of one texture, *texels of them (may be null; 4 bytes each, 16 for a FLOAT4 texture); out null: the
+ *   count alone; cap_texels too small: RFWHIP_ERR_INVALID_ARGUMENT.
+ * rfwhip_png_unfilter (host only; replaces FreeImage's PNG reader, texture.cpp:41): undoes PNG's row filters — `rows` scanlines of a
+ *   filter byte and row_bytes bytes each -> the rows alone; bpp = bytes per whole pixel.
+ * Hooks: rfwhip_decode_image decodes level 0 alone into host memory (cap_texels too small or out null: *w, *h alone) and needs no
+ *   scene; rfwhip_read_texture_coefficients copies the coefficients of the last decode, as rfwhip_read_jpeg_coefficients does.
+ * Unlisted settings: texture_entropy; texture_decode_time (read-only, stage_timing = 1): family 15 by kernel — the milliseconds of
+ *   k_texdec_zero, k_texdec_entropy, k_texdec_idct, k_texdec_color, k_tex_mips, k_texdec_finish, then their launches. */
+enum rfwhip_texture_decode_error
+{
+	RFWHIP_TEXDEC_ERR_TRUNCATED = 1, /* an interval's data ended inside a code */
+	RFWHIP_TEXDEC_ERR_RUN = 2,		 /* a zero run past coefficient 63 */
+	RFWHIP_TEXDEC_ERR_NOCODE = 4,	 /* 16 bits that are no code of the table */
+	RFWHIP_TEXDEC_ERR_MARKER = 8	 /* an 0xFF inside an interval that is not followed by 0x00 */
+};
+typedef struct rfwhip_texture_decode_record /* 32 bytes: the record as it lies on the device */
+{
+	uint32_t width, height;
+	uint32_t blocks, intervals; /* 8 x 8 blocks and restart intervals decoded (0 for RGBA8 and TEXELS) */
+	uint32_t errors;			/* rfwhip_texture_decode_error bits, ORed over the intervals */
+	uint32_t alpha_zero;		/* level-0 texels with alpha 0 */
+	uint32_t path;				/* 0: nothing to decode, 1: entropy decoding on the host, 2: on the device */
+	uint32_t reserved;
+} rfwhip_texture_decode_record;
+typedef struct rfwhip_image_info_t
+{
+	uint32_t width, height, components;
+	uint32_t h_sampling, v_sampling; /* of the luma component: 1 1, 2 1 or 2 2 */
+	uint32_t restart_interval;		 /* Ri in MCUs, 0 without DRI */
+	uint32_t intervals;
+	uint32_t supported;
+	char reason[96]; /* empty when supported */
+} rfwhip_image_info_t;
+RFWHIP_API int rfwhip_set_texture_sources(rfwhip_context *ctx, const rfwhip_texture_source *sources, size_t count);
+RFWHIP_API int rfwhip_image_info(const void *data, size_t bytes, rfwhip_image_info_t *info);
+RFWHIP_API int rfwhip_get_texture_decode(rfwhip_context *ctx, size_t index, rfwhip_texture_decode_record *record);
+RFWHIP_API int rfwhip_read_texture(rfwhip_context *ctx, size_t index, void *out, size_t cap_texels, size_t *texels);
+RFWHIP_API int rfwhip_png_unfilter(const uint8_t *in, size_t rows, size_t row_bytes, size_t bpp, uint8_t *out);
+RFWHIP_API int rfwhip_decode_image(rfwhip_context *ctx, const void *data, size_t bytes, uint32_t flags, void *out_rgba8_host, size_t cap_texels,
+								   uint32_t *w, uint32_t *h);
+RFWHIP_API int rfwhip_read_texture_coefficients(rfwhip_context *ctx, int16_t *out, size_t cap_blocks, uint32_t *blocks);
+
 /* ---- noise estimate: when has a progressive render converged? ---------------------------------------------------------------
  * With noise_estimate = 1 the resolve of every rfwhip_render (its variant k_resolve_noise) keeps two floats per pixel beside the
  * accumulator — sumY, the sum of the luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel's samples (a sample's value is what
@@ -551,6 +626,9 @@ RFWHIP_API int rfwhip_group_get_adaptive(rfwhip_group *group, rfwhip_adaptive_st
 RFWHIP_API int rfwhip_group_get_meter(rfwhip_group *group, rfwhip_meter_stats *stats);
 /* The LUT of the display stage (rfwhip_set_display_lut above), for the root's context: the display kernel runs there. */
 RFWHIP_API int rfwhip_group_set_display_lut(rfwhip_group *group, const float *rgb, uint32_t n);
+/* rfwhip_set_texture_sources on every member: each decodes its own replica of the table on its own device.  The sources are parsed by
+ * every member alike, so a refused table is refused by all of them and every member keeps its previous one. */
+RFWHIP_API int rfwhip_group_set_texture_sources(rfwhip_group *group, const rfwhip_texture_source *sources, size_t count);
 RFWHIP_API int rfwhip_group_set_display_lut_cube(rfwhip_group *group, const char *text, size_t len);
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);

@@ -132,6 +132,32 @@ typedef struct rfwhip_texture
 } rfwhip_texture;
 RFWHIP_STATIC_ASSERT(sizeof(rfwhip_texture) == 32, "TextureData must be 32 B");
 
+/* A texture as a host has it before rfw::texture (texture.cpp of the reference's system layer, which a backend never sees) has
+ * decoded it: finished texels, an encoded JPEG file, or a file's RGBA8 pixels (rfwhip_set_texture_sources, rfwhip.h). */
+enum rfwhip_texture_source_kind
+{
+	RFWHIP_TEXSRC_TEXELS = 0, /* as rfwhip_texture: type, width, height, texelCount, data */
+	RFWHIP_TEXSRC_JPEG = 1,	  /* data / bytes: a baseline JPEG stream; width, height, type, texelCount are ignored */
+	RFWHIP_TEXSRC_RGBA8 = 2	  /* data: width x height pixels r, g, b, a in file order (top row first); bytes = 4 width height */
+};
+enum rfwhip_texture_source_flags
+{
+	RFWHIP_TEXSRC_FLIP_ROWS = 1,		   /* texel row 0 is the image's bottom row (texture.cpp:83-86, FLIPPED) */
+	RFWHIP_TEXSRC_LINEARIZE_REFERENCE = 2, /* c c >> 8 per colour byte, before the mips (texture.cpp:6-14,90, LINEARIZED) */
+	RFWHIP_TEXSRC_LINEARIZE_SRGB = 4	   /* the exact sRGB EOTF per colour byte, rounded to nearest, before the mips */
+};
+typedef struct rfwhip_texture_source
+{
+	uint32_t kind;
+	uint32_t flags;
+	const void *data;
+	size_t bytes;
+	uint32_t width, height;
+	uint32_t type;
+	uint32_t texelCount;
+} rfwhip_texture_source;
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_texture_source) == 40, "rfwhip_texture_source must be 40 B");
+
 typedef struct rfwhip_light_count
 {
 	uint32_t areaLightCount, pointLightCount, spotLightCount, directionalLightCount;

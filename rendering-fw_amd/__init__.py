@@ -11,10 +11,11 @@ from . import _binding, abi, scenes
 from . import gltf
 from . import obj
 from . import lut
+from . import images
 from .abi import CONVERGE, RESET
 from .camera import Camera
 from .context import LIB_PATH, RenderComm, RenderContext, comm_unique_id, load_library, render_group
 from .build import build as build_native
 from .build import build_strict
 
-__all__ = ["abi", "scenes", "gltf", "obj", "lut", "Camera", "RenderContext", "load_library", "render_group", "RenderComm", "comm_unique_id", "LIB_PATH", "build_native", "build_strict", "RESET", "CONVERGE"]
+__all__ = ["abi", "scenes", "gltf", "obj", "lut", "images", "Camera", "RenderContext", "load_library", "render_group", "RenderComm", "comm_unique_id", "LIB_PATH", "build_native", "build_strict", "RESET", "CONVERGE"]

@@ -16,6 +16,34 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _texture_source_array(textures):
+    """The rfwhip_texture_source array of a list of texture dicts (CoreBinding.set_textures) and the arrays it points into."""
+    arr = (abi.TextureSource * max(1, len(textures)))()
+    keep = []
+    for i, t in enumerate(textures):
+        kind = t.get("kind", "texels")
+        flags = int(t.get("flags", 0))
+        if kind == "jpeg":
+            data = np.frombuffer(bytes(t["data"]), np.uint8)
+            arr[i] = abi.TextureSource(abi.TEXSRC_JPEG, flags, data.ctypes.data, data.size, 0, 0, abi.TEX_UINT, 0)
+        elif kind == "rgba8":
+            data = np.ascontiguousarray(t["data"], dtype=np.uint8)
+            h, w = data.shape[:2]
+            arr[i] = abi.TextureSource(abi.TEXSRC_RGBA8, flags, data.ctypes.data, data.size, w, h, abi.TEX_UINT, 0)
+        elif kind == "texels":
+            data = np.ascontiguousarray(t["data"])
+            per = 4 if t["type"] == abi.TEX_FLOAT4 else 1
+            arr[i] = abi.TextureSource(abi.TEXSRC_TEXELS, 0, data.ctypes.data, data.nbytes, t["width"], t["height"], t["type"], data.size // per)
+        else:
+            raise ValueError("texture %d: unknown kind %r" % (i, kind))
+        keep.append(data)
+    return arr, keep
+
+
+def _texture_source_types(textures):
+    return [t["type"] if t.get("kind", "texels") == "texels" else abi.TEX_UINT for t in textures]
+
+
 class CoreBinding:
     def __init__(self, lib, prefix, device=0, rank=0, world=1, borrowed=None):
         """borrowed: an existing context pointer owned by somebody else (a RenderGroup): used, never destroyed."""
@@ -110,6 +138,13 @@ class CoreBinding:
                                   "get_jpeg": (i32, [vp, C.POINTER(abi.JpegStats)]),
                                   "jpeg_image": (i32, [vp, vp, vp, sz, C.POINTER(sz)]),
                                   "read_jpeg_coefficients": (i32, [vp, vp, sz, C.POINTER(u32)]),
+                                  "set_texture_sources": (i32, [vp, vp, sz]),
+                                  "image_info": (i32, [vp, sz, C.POINTER(abi.ImageInfo)]),
+                                  "get_texture_decode": (i32, [vp, sz, C.POINTER(abi.TextureDecodeRecord)]),
+                                  "read_texture": (i32, [vp, sz, vp, sz, C.POINTER(sz)]),
+                                  "png_unfilter": (i32, [vp, sz, sz, sz, vp]),
+                                  "decode_image": (i32, [vp, vp, sz, u32, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
+                                  "read_texture_coefficients": (i32, [vp, vp, sz, C.POINTER(u32)]),
                                   "get_noise": (i32, [vp, C.POINTER(abi.NoiseStats)]),
                                   "read_noise_map": (i32, [vp, vp]),
                                   "read_noise_tiles": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
@@ -178,7 +213,12 @@ class CoreBinding:
         self._check(self._fn("set_materials")(self._ctx, m.ctypes.data, t.ctypes.data, len(m)))
 
     def set_textures(self, textures):
-        """textures: list of dicts {type, width, height, data(np.ndarray)}; data may include appended mip levels."""
+        """textures: list of dicts {type, width, height, data(np.ndarray)}; data may include appended mip levels.  A dict with a
+        "kind" (images.texture_from_file: "jpeg" with the file's bytes, "rgba8" with H x W x 4 pixels in file order; "flags") is an
+        image the device decodes and mips: with one in the list the whole list goes through rfwhip_set_texture_sources."""
+        if any("kind" in t for t in textures):
+            return self._set_texture_sources(textures)
+        self._texture_types = [t["type"] for t in textures]  # (read_texture)
         arr = (abi.Texture * max(1, len(textures)))()
         keep = []
         for i, t in enumerate(textures):
@@ -187,6 +227,46 @@ class CoreBinding:
             per = 4 if t["type"] == abi.TEX_FLOAT4 else 1
             arr[i] = abi.Texture(t["type"], t["width"], t["height"], data.size // per, 0, 0, data.ctypes.data)
         self._check(self._fn("set_textures")(self._ctx, C.cast(arr, C.c_void_p), len(textures)))
+
+    def _set_texture_sources(self, textures):
+        arr, keep = _texture_source_array(textures)
+        self._check(self._fn("set_texture_sources")(self._ctx, C.cast(arr, C.c_void_p), len(textures)))
+        self._texture_types = _texture_source_types(textures)
+        del keep
+
+    # ---- image textures (include/rfwhip.h, rfwhip_set_texture_sources; rendering_fw_amd.images) ------------------------------
+    def decode_image(self, data, flags=0):
+        """Known-answer hook: a JPEG stream decoded on the device -> H x W x 4 uint8 (level 0 alone; needs no scene)."""
+        src = np.frombuffer(bytes(data), np.uint8)
+        w, h = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("decode_image")(self._ctx, src.ctypes.data, src.size, int(flags), None, 0, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, 4), np.uint8)
+        self._check(self._fn("decode_image")(self._ctx, src.ctypes.data, src.size, int(flags), out.ctypes.data, w.value * h.value, C.byref(w), C.byref(h)))
+        return out
+
+    def read_texture(self, index):
+        """All levels of texture `index` of the current table, back to back: uint32 texels (float32 x 4 for a FLOAT4 texture)."""
+        n = C.c_size_t()
+        self._check(self._fn("read_texture")(self._ctx, int(index), None, 0, C.byref(n)))
+        raw = np.empty(n.value * 16, np.uint8)
+        self._check(self._fn("read_texture")(self._ctx, int(index), raw.ctypes.data, n.value, C.byref(n)))
+        if self._texture_types[int(index)] == abi.TEX_FLOAT4:
+            return raw.view(np.float32).reshape(-1, 4)
+        return raw[:n.value * 4].view(np.uint32).copy()
+
+    def texture_record(self, index=None):
+        """The decode record of texture `index` as a dict (abi.TextureDecodeRecord); None: of the last decode_image."""
+        r = abi.TextureDecodeRecord()
+        self._check(self._fn("get_texture_decode")(self._ctx, C.c_size_t(-1).value if index is None else int(index), C.byref(r)))
+        return r.as_dict()
+
+    def texture_coefficients(self):
+        """The coefficients of the last decode: blocks x 64 int16 in zigzag order, in stream order (MCU by MCU)."""
+        n = C.c_uint32()
+        self._check(self._fn("read_texture_coefficients")(self._ctx, None, 0, C.byref(n)))
+        out = np.empty((n.value, 64), np.int16)
+        self._check(self._fn("read_texture_coefficients")(self._ctx, out.ctypes.data, n.value, C.byref(n)))
+        return out
 
     def set_mesh(self, index, vertices, triangles, indices=None):
         v = _f32(vertices).reshape(-1, 4)
@@ -687,10 +767,11 @@ class CoreBinding:
     BLOOM = 12  # ... and of bloom (one count per launch of a chain: 2 x the levels it ran)
     GRADE = 13  # ... and of the graded display kernel (one launch per displayed image with display_grade = 1)
     JPEG = 14  # ... and of the JPEG encoder (four launches per stream)
+    TEXDEC = 15  # ... and of the image-texture decoder (one count per launch of a decode or mip chain)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.TEXDEC if which == "texture_decode" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -846,7 +927,8 @@ class RenderGroup:
                                 ("group_set_display_lut_cube", i32, [vp, C.c_char_p, C.c_size_t]),
                                 ("group_read_display_jpeg", i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
                                 ("group_present_jpeg_async", i32, [vp, i32]),
-                                ("group_present_jpeg_wait", i32, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)])]:
+                                ("group_present_jpeg_wait", i32, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+                                ("group_set_texture_sources", i32, [vp, vp, C.c_size_t])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -876,6 +958,19 @@ class RenderGroup:
 
     def load_cube(self, path):
         self.set_display_lut_cube(_read_file(path))
+
+    def set_textures(self, textures):
+        """CoreBinding.set_textures on every member; a list with image sources goes through rfwhip_group_set_texture_sources: every
+        member decodes its own replica."""
+        if not any("kind" in t for t in textures):
+            for c in self.contexts:
+                c.set_textures(textures)
+            return
+        arr, keep = _texture_source_array(textures)
+        self._check(self._fn("group_set_texture_sources")(self._g, C.cast(arr, C.c_void_p), len(textures)))
+        for c in self.contexts:
+            c._texture_types = _texture_source_types(textures)
+        del keep
 
     def __getattr__(self, name):
         # scene setters and friends: the same call on every context (set_sky, set_mesh, set_lights, set_blue_noise, ...)

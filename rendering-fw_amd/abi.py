@@ -114,6 +114,30 @@ class Texture(C.Structure):
                 ("texAddr", C.c_uint32), ("_pad", C.c_uint32), ("data", C.c_void_p)]
 
 
+# rfwhip_texture_source (include/rfwhip_abi.h): a texture as finished texels, an encoded JPEG file, or a file's RGBA8 pixels
+TEXSRC_TEXELS, TEXSRC_JPEG, TEXSRC_RGBA8 = 0, 1, 2
+TEXSRC_FLIP_ROWS, TEXSRC_LINEARIZE_REFERENCE, TEXSRC_LINEARIZE_SRGB = 1, 2, 4
+
+
+class TextureSource(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("data", C.c_void_p), ("bytes", C.c_size_t), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("type", C.c_uint32), ("texelCount", C.c_uint32)]
+
+
+class TextureDecodeRecord(C.Structure):
+    """rfwhip_texture_decode_record (include/rfwhip.h, rfwhip_get_texture_decode): the decoder's 32-byte record."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "blocks", "intervals", "errors", "alpha_zero", "path", "reserved")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class ImageInfo(C.Structure):
+    """rfwhip_image_info_t (include/rfwhip.h, rfwhip_image_info)."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "components", "h_sampling", "v_sampling", "restart_interval", "intervals",
+                                          "supported")] + [("reason", C.c_char * 96)]
+
+
 class LightCount(C.Structure):
     _fields_ = [("areaLightCount", C.c_uint32), ("pointLightCount", C.c_uint32), ("spotLightCount", C.c_uint32),
                 ("directionalLightCount", C.c_uint32)]

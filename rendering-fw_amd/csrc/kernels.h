@@ -429,4 +429,17 @@ struct LightTreeLevels
 void launch_light_tree_refit(rt::LightTreeNode *nodes, const LightTreeLevels &lv, const rt::AreaLight *area, uint32_t n_area,
 							 const unsigned char *bound, unsigned char *touched, stream_t s);
 
+// image textures (texture_decode.h, kernel family 15), in this order on one stream: k_texdec_zero, k_texdec_entropy (the device path of
+// the entropy decoding), k_texdec_idct, k_texdec_color (with v.src: the modifiers over an RGBA8 source), k_tex_mips, k_texdec_finish
+struct TexdecView;
+void launch_texdec_zero(const TexdecView &v, stream_t s);
+void launch_texdec_entropy(const TexdecView &v, stream_t s);
+void launch_texdec_idct(const TexdecView &v, stream_t s);
+void launch_texdec_color(const TexdecView &v, stream_t s);
+void launch_tex_mips(const TexdecView &v, stream_t s);
+void launch_texdec_finish(const TexdecView &v, stream_t s);
+
 } // namespace rtk
+
+// the types, the marker walk and the work items of the image textures (part 1 of the file)
+#include "texture_decode.h"

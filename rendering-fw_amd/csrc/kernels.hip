@@ -982,6 +982,9 @@ RT_FN void leaf_bounds(const Node &n, const f4 *tri_verts, float mn[3], float mx
 #include "display_grade.h"
 // baseline JPEG of the RGBA8 display image: the work items shared with the emulation, and the four kernels
 #include "display_jpeg.h"
+// image textures: JPEG decode and the mip chain (part 2 of the file: the kernels and launchers, or the emulation's launchers)
+#define TEXTURE_DECODE_LAUNCHERS
+#include "texture_decode.h"
 // moving emitters: the area lights of emissive geometry and the light tree's refit (work items shared with the emulation)
 #include "light_follow.h"
 rt::f3 dn_normal(uint32_t e) { return dn_oct_decode(e); }

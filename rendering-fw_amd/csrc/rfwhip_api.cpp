@@ -216,7 +216,8 @@ enum KernelFamily
 	KF_BLOOM = 12, // bloom (bloom.h): the down, up and apply passes of a chain, one count per launch
 	KF_GRADE = 13, // colour grading (display_grade.h): k_display_graded in place of family 7's kernel, one count per displayed image
 	KF_JPEG = 14,  // baseline JPEG of the display image (display_jpeg.h): four launches per stream, one count each
-	KF_COUNT = 15
+	KF_TEXDEC = 15, // image textures (texture_decode.h): the kernels of a decode and of a mip chain, one count per launch
+	KF_COUNT = 16
 };
 
 // A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
@@ -441,6 +442,18 @@ struct rfwhip_context
 	dm::event_t ev_jpeg;				 // behind the last encode: its stream is jpeg_stream (another stream waits for it: one scratch)
 	void *jpeg_stream = nullptr;
 	bool ev_jpeg_ready = false, jpeg_pending = false;
+	// image textures (texture_decode.h): texture_entropy = 0 auto | 1 host | 2 device; the scratch of a decode, allocated by the first
+	// one (the stream, the intervals' ranges, the tables, the coefficients, the intervals' flags, the components' planes, the mip
+	// tiles' alpha counts, an RGBA8 source, the sRGB table, the image of rfwhip_decode_image); d_td_rec: a record per texture
+	int td_entropy = 0;
+	DevBuf d_td_stream, d_td_ranges, d_td_tab, d_td_coef, d_td_flags, d_td_planes, d_td_alpha, d_td_src, d_td_lin, d_td_out, d_td_rec;
+	std::vector<rtk::TexRecord> td_records; // of the current table's textures (zeros for textures that came as texels)
+	std::vector<rt::TexDesc> tex_desc_host; // the current table's descriptors (rfwhip_read_texture)
+	uint32_t td_coef_blocks = 0;			// blocks of the last decode (rfwhip_read_texture_coefficients)
+	rtk::TexRecord td_hook_record = {0, 0, 0, 0, 0, 0, 0, 0}; // of the last rfwhip_decode_image (rfwhip_get_texture_decode, index -1)
+	bool td_hook_ran = false;
+	float td_kind_ms[6] = {};				// family KF_TEXDEC by kernel: zero, entropy, idct, color, mips, finish ...
+	uint32_t td_kind_launches[6] = {};		// ... (stage_timing = 1; the read-only setting texture_decode_time)
 	// the noise estimate (noise.h): d_noise = two moments per local pixel, allocated while noise_estimate is on.  noise_live: the
 	// moments cover every sample of the accumulator (the setting was on at the last RESET / rfwhip_init and ever since)
 	int noise_estimate = 0;
@@ -677,6 +690,8 @@ static void free_all(rfwhip_context *c)
 					  &c->d_dn_inst_ver, &c->d_dn_surf, &c->d_dn_minst, &c->d_sky_alias, &c->d_lt_nodes, &c->d_lt_paths, &c->d_display,
 					  &c->d_meter_rec, &c->d_meter_hist, &c->d_meter_part, &c->d_bloom_pyr, &c->d_bloom_out, &c->d_bloom_one, &c->d_grade_lut,
 					  &c->d_jpeg_tab, &c->d_jpeg_coef, &c->d_jpeg_slots, &c->d_jpeg_counts, &c->d_jpeg_offsets, &c->d_jpeg_rec, &c->d_jpeg_out,
+					  &c->d_td_stream, &c->d_td_ranges, &c->d_td_tab, &c->d_td_coef, &c->d_td_flags, &c->d_td_planes, &c->d_td_alpha, &c->d_td_src,
+					  &c->d_td_lin, &c->d_td_out, &c->d_td_rec,
 					  &c->d_noise, &c->d_noise_map, &c->d_noise_tiles, &c->d_noise_total, &c->d_noise_in,
 					  &c->d_ad_n, &c->d_ad_active, &c->d_ad_mask, &c->d_lf_inst, &c->d_lf_bound, &c->d_lf_count, &c->d_lt_touched};
 	for (DevBuf *b : bufs)
@@ -692,6 +707,7 @@ static void free_all(rfwhip_context *c)
 	c->lut_host.clear(), c->lut_n = 0, c->grade_pending = false;
 	if (c->ev_grade_ready)
 		dm::event_destroy(c->ev_grade), c->ev_grade_ready = false;
+	c->td_records.clear(), c->tex_desc_host.clear(), c->td_coef_blocks = 0;
 	c->jpeg_pending = false, c->jpeg_stream = nullptr, c->jpeg_coef_blocks = 0;
 	if (c->ev_jpeg_ready)
 		dm::event_destroy(c->ev_jpeg), c->ev_jpeg_ready = false;
@@ -924,6 +940,7 @@ extern "C" int rfwhip_set_textures(rfwhip_context *c, const rfwhip_texture *tex,
 	RF_TRY(dm::h2d(c->d_tex_f4.p, f4s.data(), f4s.size() * sizeof(f4), c->stream));
 	RF_TRY(dm::sync(c->stream));
 	c->texture_count = (uint32_t)count;
+	c->tex_desc_host = desc, c->td_records.assign(count, rtk::TexRecord{0, 0, 0, 0, 0, 0, 0, 0}); // (rfwhip_read_texture, rfwhip_get_texture_decode)
 	c->scene_dirty = true;
 	return RFWHIP_OK;
 }
@@ -3069,6 +3086,10 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 			if (sp.depth >= 0 && sp.depth < 4)
 				c->jpeg_kind_ms[sp.depth] += ms, c->jpeg_kind_launches[sp.depth]++;
 			break;
+		case KF_TEXDEC:
+			if (sp.depth >= 0 && sp.depth < 6)
+				c->td_kind_ms[sp.depth] += ms, c->td_kind_launches[sp.depth]++;
+			break;
 		default:
 			break;
 		}
@@ -4078,6 +4099,350 @@ extern "C" int rfwhip_read_jpeg_coefficients(rfwhip_context *c, int16_t *out, si
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_jpeg_coefficients: %u blocks, room for %zu", c->jpeg_coef_blocks, cap_blocks);
 	RF_TRY(sync_all(c));
 	return dm::d2h(out, c->d_jpeg_coef.p, (size_t)c->jpeg_coef_blocks * 128u, c->stream);
+}
+
+// ---- image textures (work items and kernels: texture_decode.h) -----------------------------------------------------------------------
+static_assert(sizeof(rfwhip_texture_decode_record) == sizeof(rtk::TexRecord) && sizeof(rtk::TexRecord) == 32, "rfwhip.h: the decode record is the kernels' (texture_decode.h)");
+static_assert(rtk::TD_INVALID == RFWHIP_ERR_INVALID_ARGUMENT && rtk::TD_UNSUPPORTED == RFWHIP_ERR_UNSUPPORTED, "texture_decode.h answers rfwhip.h's codes");
+static_assert(rtk::TD_FLIP_ROWS == RFWHIP_TEXSRC_FLIP_ROWS && rtk::TD_LINEARIZE_REFERENCE == RFWHIP_TEXSRC_LINEARIZE_REFERENCE &&
+				  rtk::TD_LINEARIZE_SRGB == RFWHIP_TEXSRC_LINEARIZE_SRGB && rtk::TD_ERR_TRUNCATED == RFWHIP_TEXDEC_ERR_TRUNCATED &&
+				  rtk::TD_ERR_RUN == RFWHIP_TEXDEC_ERR_RUN && rtk::TD_ERR_NOCODE == RFWHIP_TEXDEC_ERR_NOCODE && rtk::TD_ERR_MARKER == RFWHIP_TEXDEC_ERR_MARKER,
+			  "texture_decode.h restates rfwhip.h's flags");
+
+// one source of a decode: a walked JPEG stream, or RGBA8 pixels
+struct TdJob
+{
+	bool jpeg = false;
+	const void *data = nullptr;
+	size_t bytes = 0;
+	uint32_t W = 0, H = 0, mods = 0;
+	rtk::TdInfo info;
+};
+// host arrays an enqueued copy still reads: alive until the stream has been waited for
+struct TdKeep
+{
+	std::vector<std::vector<int16_t>> coef;
+	std::vector<std::vector<uint32_t>> words;
+};
+static int td_check_flags(const char *who, uint32_t flags)
+{
+	if (flags & ~7u)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x", who, flags);
+	if ((flags & RFWHIP_TEXSRC_LINEARIZE_REFERENCE) && (flags & RFWHIP_TEXSRC_LINEARIZE_SRGB))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: two linearisations at once", who);
+	return 0;
+}
+// the scratch for every job of a call, sized once (a growing buffer waits for the work in flight first)
+static int td_reserve(rfwhip_context *c, const std::vector<TdJob> &jobs)
+{
+	size_t need[8] = {0, 0, sizeof(rtk::TdTables), 0, 0, 0, 0, 0};
+	bool srgb = false;
+	for (const TdJob &j : jobs)
+	{
+		srgb = srgb || (j.mods & rtk::TD_LINEARIZE_SRGB);
+		need[6] = std::max(need[6], (size_t)rtk::td_tiles(j.W, j.H) * 4u);
+		if (!j.jpeg)
+		{
+			need[7] = std::max(need[7], (size_t)j.W * j.H * 4u);
+			continue;
+		}
+		rtk::TexdecView v;
+		size_t planes = 0;
+		rtk::td_view_geometry(j.info, v, &planes);
+		need[0] = std::max(need[0], j.bytes), need[1] = std::max(need[1], j.info.ranges.size() * 4u);
+		need[3] = std::max(need[3], (size_t)j.info.blocks * 128u), need[4] = std::max(need[4], (size_t)j.info.intervals * 4u);
+		need[5] = std::max(need[5], planes);
+	}
+	DevBuf *buf[8] = {&c->d_td_stream, &c->d_td_ranges, &c->d_td_tab, &c->d_td_coef, &c->d_td_flags, &c->d_td_planes, &c->d_td_alpha, &c->d_td_src};
+	for (int k = 0; k < 8; k++)
+		if (need[k] && (need[k] > buf[k]->cap || !buf[k]->p))
+		{
+			RF_TRY(sync_all(c));
+			RF_TRY(buf[k]->ensure(need[k]));
+		}
+	if (srgb && !c->d_td_lin.p)
+	{
+		uint8_t lin[256];
+		rtk::td_srgb_table(lin);
+		RF_TRY(c->d_td_lin.ensure(sizeof(lin)));
+		RF_TRY(dm::h2d(c->d_td_lin.p, lin, sizeof(lin), c->stream));
+		RF_TRY(dm::sync(c->stream));
+	}
+	return 0;
+}
+// one job on the context's stream: level 0 (and with `mips` the chain behind it) at `out`, the record at `rec`
+static int td_enqueue(rfwhip_context *c, const TdJob &j, uint32_t *out, rtk::TexRecord *rec, bool mips, TdKeep &keep)
+{
+	void *const s = c->stream;
+	rtk::TexdecView v;
+	memset(&v, 0, sizeof(v));
+	v.W = j.W, v.H = j.H, v.mods = j.mods, v.out = out, v.rec = rec, v.alpha = c->d_td_alpha.as<uint32_t>();
+	v.lin = c->d_td_lin.as<uint8_t>(), v.tiles = mips ? rtk::td_tiles(j.W, j.H) : 0u, v.path = rtk::TD_PATH_NONE;
+	const auto run = [&](int kind, void (*launch)(const rtk::TexdecView &, void *)) {
+		StageTimer t(c, KF_TEXDEC, kind, s);
+		launch(v, s);
+		t.stop(1);
+		return dm::last_launch_error();
+	};
+	if (j.jpeg)
+	{
+		rtk::td_view_geometry(j.info, v, nullptr);
+		v.coef = c->d_td_coef.as<int16_t>(), v.flags = c->d_td_flags.as<uint32_t>(), v.planes = c->d_td_planes.as<uint8_t>();
+		v.tab = c->d_td_tab.as<rtk::TdTables>();
+		RF_TRY(dm::h2d(c->d_td_tab.p, &j.info.tab, sizeof(rtk::TdTables), s));
+		const bool device = c->td_entropy == 2 || (c->td_entropy == 0 && j.info.ri != 0u);
+		v.path = device ? rtk::TD_PATH_DEVICE : rtk::TD_PATH_HOST;
+		if (device)
+		{
+			v.stream = c->d_td_stream.as<uint8_t>(), v.ranges = c->d_td_ranges.as<uint32_t>();
+			RF_TRY(dm::h2d(c->d_td_stream.p, j.data, j.bytes, s));
+			RF_TRY(dm::h2d(c->d_td_ranges.p, j.info.ranges.data(), j.info.ranges.size() * 4u, s));
+			RF_TRY(run(0, rtk::launch_texdec_zero));
+			RF_TRY(run(1, rtk::launch_texdec_entropy));
+		}
+		else // the same item, serially over the host's arrays; the words go up
+		{
+			keep.coef.emplace_back((size_t)v.blocks * 64u, (int16_t)0);
+			keep.words.emplace_back((size_t)v.intervals, 0u);
+			rtk::TexdecView h = v;
+			h.stream = (const uint8_t *)j.data, h.ranges = j.info.ranges.data(), h.tab = &j.info.tab;
+			h.coef = keep.coef.back().data(), h.flags = keep.words.back().data();
+			rtk::td_host_entropy(h);
+			RF_TRY(dm::h2d(c->d_td_coef.p, h.coef, (size_t)v.blocks * 128u, s));
+			RF_TRY(dm::h2d(c->d_td_flags.p, h.flags, (size_t)v.intervals * 4u, s));
+		}
+		RF_TRY(run(2, rtk::launch_texdec_idct));
+		c->td_coef_blocks = v.blocks;
+	}
+	else
+	{
+		v.src = c->d_td_src.as<uint32_t>();
+		RF_TRY(dm::h2d(c->d_td_src.p, j.data, (size_t)j.W * j.H * 4u, s));
+	}
+	RF_TRY(run(3, rtk::launch_texdec_color));
+	if (mips)
+		RF_TRY(run(4, rtk::launch_tex_mips));
+	return run(5, rtk::launch_texdec_finish);
+}
+static int td_error_of_record(const char *who, size_t index, const rtk::TexRecord &r)
+{
+	if (!r.errors)
+		return 0;
+	return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: texture %zu: the entropy data is corrupt (%s%s%s%s)", who, index,
+					 (r.errors & rtk::TD_ERR_TRUNCATED) ? " an interval ends inside a code;" : "", (r.errors & rtk::TD_ERR_RUN) ? " a zero run passes coefficient 63;" : "",
+					 (r.errors & rtk::TD_ERR_NOCODE) ? " bits that are no Huffman code;" : "", (r.errors & rtk::TD_ERR_MARKER) ? " a marker inside an interval;" : "");
+}
+
+extern "C" int rfwhip_image_info(const void *data, size_t bytes, rfwhip_image_info_t *info)
+{
+	if (!data || !info)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_image_info: null argument");
+	rtk::TdInfo t;
+	const int rc = rtk::td_walk((const uint8_t *)data, bytes, t);
+	memset(info, 0, sizeof(*info));
+	info->width = t.W, info->height = t.H, info->components = t.ncomp, info->h_sampling = t.hs, info->v_sampling = t.vs;
+	info->restart_interval = t.ri, info->intervals = t.intervals, info->supported = rc == rtk::TD_OK;
+	snprintf(info->reason, sizeof(info->reason), "%s", t.msg);
+	if (rc == rtk::TD_INVALID)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_image_info: %s", t.msg);
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_png_unfilter(const uint8_t *in, size_t rows, size_t row_bytes, size_t bpp, uint8_t *out)
+{
+	if (!in || !out || !bpp)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_png_unfilter: null argument");
+	if (rtk::td_png_unfilter(in, rows, row_bytes, bpp, out))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_png_unfilter: a filter type above 4");
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_set_texture_sources(rfwhip_context *c, const rfwhip_texture_source *src, size_t count)
+{
+	CTX_ENTER(c);
+	const char *const who = "rfwhip_set_texture_sources";
+	if (count && !src)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: null array", who);
+	// 1. every header, and the layout of the one table
+	std::vector<rt::TexDesc> desc(count);
+	std::vector<TdJob> jobs(count);
+	std::vector<f4> f4s;
+	uint64_t n_u32 = 0;
+	for (size_t i = 0; i < count; i++)
+	{
+		const rfwhip_texture_source &t = src[i];
+		rt::TexDesc &d = desc[i];
+		TdJob &j = jobs[i];
+		memset(&d, 0, sizeof(d));
+		if (!t.data)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: texture %zu has no data", who, i);
+		if (t.kind == RFWHIP_TEXSRC_TEXELS)
+		{
+			d.type = t.type, d.width = t.width, d.height = t.height, d.texelCount = t.texelCount;
+			if (!t.texelCount || (t.type != RFWHIP_TEX_UINT && t.type != RFWHIP_TEX_FLOAT4))
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: texture %zu has no texels or an unknown type %u", who, i, t.type);
+			if (t.type == RFWHIP_TEX_FLOAT4)
+			{
+				d.offset = (uint32_t)f4s.size();
+				f4s.insert(f4s.end(), (const f4 *)t.data, (const f4 *)t.data + t.texelCount);
+				continue;
+			}
+		}
+		else if (t.kind == RFWHIP_TEXSRC_JPEG || t.kind == RFWHIP_TEXSRC_RGBA8)
+		{
+			if (td_check_flags(who, t.flags))
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: texture %zu: flags 0x%x", who, i, t.flags);
+			j.jpeg = t.kind == RFWHIP_TEXSRC_JPEG, j.data = t.data, j.bytes = t.bytes, j.mods = t.flags, j.W = t.width, j.H = t.height;
+			if (j.jpeg)
+			{
+				const int rc = rtk::td_walk((const uint8_t *)t.data, t.bytes, j.info);
+				if (rc)
+					return set_error(rc, "%s: texture %zu: %s", who, i, j.info.msg);
+				j.W = j.info.W, j.H = j.info.H;
+			}
+			else if (!j.W || !j.H || j.W > 65535u || j.H > 65535u || t.bytes != (size_t)j.W * j.H * 4u)
+				return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: texture %zu: %u x %u RGBA8 pixels in %zu bytes", who, i, j.W, j.H, t.bytes);
+			if ((uint64_t)j.W * j.H > 0x3FFFFFFFull)
+				return set_error(RFWHIP_ERR_UNSUPPORTED, "%s: texture %zu: %u x %u texels", who, i, j.W, j.H);
+			d.type = RFWHIP_TEX_UINT, d.width = j.W, d.height = j.H, d.texelCount = rtk::td_chain_texels(j.W, j.H);
+		}
+		else
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: texture %zu has unknown kind %u", who, i, t.kind);
+		d.offset = (uint32_t)n_u32, n_u32 += d.texelCount;
+		if (n_u32 > 0xFFFFFFFFull)
+			return set_error(RFWHIP_ERR_UNSUPPORTED, "%s: more than 2^32 texels", who);
+	}
+	// 2. a new table beside the current one: the current one stays whatever happens below
+	RF_TRY(sync_all(c));
+	std::vector<TdJob> work;
+	for (const TdJob &j : jobs)
+		if (j.data)
+			work.push_back(j);
+	RF_TRY(td_reserve(c, work));
+	DevBuf n_desc, n_tex, n_f4, n_rec;
+	const auto drop = [&](int rc) {
+		(void)dm::sync(c->stream);
+		n_desc.free_(), n_tex.free_(), n_f4.free_(), n_rec.free_();
+		return rc;
+	};
+	std::vector<rtk::TexRecord> records(count, rtk::TexRecord{0, 0, 0, 0, 0, 0, 0, 0});
+	TdKeep keep;
+	int rc = n_desc.ensure(desc.size() * sizeof(rt::TexDesc));
+	rc = rc ? rc : n_tex.ensure((size_t)n_u32 * 4u);
+	rc = rc ? rc : n_f4.ensure(f4s.size() * sizeof(f4));
+	rc = rc ? rc : n_rec.ensure(count * sizeof(rtk::TexRecord));
+	rc = rc ? rc : dm::h2d(n_desc.p, desc.data(), desc.size() * sizeof(rt::TexDesc), c->stream);
+	rc = rc ? rc : dm::h2d(n_f4.p, f4s.data(), f4s.size() * sizeof(f4), c->stream);
+	rc = rc ? rc : dm::h2d(n_rec.p, records.data(), count * sizeof(rtk::TexRecord), c->stream);
+	for (size_t i = 0; i < count && !rc; i++)
+	{
+		uint32_t *slot = n_tex.as<uint32_t>() + desc[i].offset;
+		if (src[i].kind == RFWHIP_TEXSRC_TEXELS)
+			rc = src[i].type == RFWHIP_TEX_UINT ? dm::h2d(slot, src[i].data, (size_t)desc[i].texelCount * 4u, c->stream) : 0;
+		else
+			rc = td_enqueue(c, jobs[i], slot, n_rec.as<rtk::TexRecord>() + i, true, keep);
+	}
+	rc = rc ? rc : dm::d2h(records.data(), n_rec.p, count * sizeof(rtk::TexRecord), c->stream);
+	if (rc)
+		return drop(rc);
+	for (size_t i = 0; i < count; i++)
+		if (td_error_of_record(who, i, records[i]))
+			return drop(RFWHIP_ERR_INVALID_ARGUMENT);
+	// 3. the new table takes the place of the old one
+	std::swap(c->d_textures, n_desc), std::swap(c->d_tex_u32, n_tex), std::swap(c->d_tex_f4, n_f4), std::swap(c->d_td_rec, n_rec);
+	n_desc.free_(), n_tex.free_(), n_f4.free_(), n_rec.free_();
+	c->texture_count = (uint32_t)count, c->tex_desc_host = desc, c->td_records = records;
+	c->scene_dirty = true;
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_get_texture_decode(rfwhip_context *c, size_t index, rfwhip_texture_decode_record *record)
+{
+	CTX_ENTER(c);
+	if (record && index == (size_t)-1 && c->td_hook_ran) // the record of the last rfwhip_decode_image
+	{
+		memcpy(record, &c->td_hook_record, sizeof(*record));
+		return RFWHIP_OK;
+	}
+	if (!record || index >= c->td_records.size())
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_get_texture_decode: texture %zu of %zu", index, c->td_records.size());
+	memcpy(record, &c->td_records[index], sizeof(*record));
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_texture(rfwhip_context *c, size_t index, void *out, size_t cap_texels, size_t *texels)
+{
+	CTX_ENTER(c);
+	if (index >= c->tex_desc_host.size())
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_texture: texture %zu of %zu", index, c->tex_desc_host.size());
+	const rt::TexDesc &d = c->tex_desc_host[index];
+	if (texels)
+		*texels = d.texelCount;
+	if (!out)
+		return RFWHIP_OK;
+	if (cap_texels < d.texelCount)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_texture: %u texels, room for %zu", d.texelCount, cap_texels);
+	RF_TRY(sync_all(c));
+	if (d.type == RFWHIP_TEX_FLOAT4)
+		return dm::d2h(out, c->d_tex_f4.as<f4>() + d.offset, (size_t)d.texelCount * sizeof(f4), c->stream);
+	return dm::d2h(out, c->d_tex_u32.as<uint32_t>() + d.offset, (size_t)d.texelCount * 4u, c->stream);
+}
+
+extern "C" int rfwhip_decode_image(rfwhip_context *c, const void *data, size_t bytes, uint32_t flags, void *out_rgba8_host, size_t cap_texels,
+								   uint32_t *w, uint32_t *h)
+{
+	CTX_ENTER(c);
+	if (!data)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_decode_image: null stream");
+	RF_TRY(td_check_flags("rfwhip_decode_image", flags));
+	std::vector<TdJob> job(1);
+	TdJob &j = job[0];
+	j.jpeg = true, j.data = data, j.bytes = bytes, j.mods = flags;
+	const int rc = rtk::td_walk((const uint8_t *)data, bytes, j.info);
+	if (rc)
+		return set_error(rc, "rfwhip_decode_image: %s", j.info.msg);
+	j.W = j.info.W, j.H = j.info.H;
+	if (w)
+		*w = j.W;
+	if (h)
+		*h = j.H;
+	const size_t px = (size_t)j.W * j.H;
+	if (!out_rgba8_host)
+		return RFWHIP_OK;
+	if (cap_texels < px)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_decode_image: %zu texels, room for %zu", px, cap_texels);
+	RF_TRY(sync_all(c));
+	RF_TRY(td_reserve(c, job));
+	if (px * 4u + 32u > c->d_td_out.cap || !c->d_td_out.p)
+		RF_TRY(c->d_td_out.ensure(px * 4u + 32u));
+	TdKeep keep;
+	rtk::TexRecord *rec = (rtk::TexRecord *)(c->d_td_out.as<uint8_t>() + px * 4u);
+	int e = td_enqueue(c, j, c->d_td_out.as<uint32_t>(), rec, false, keep);
+	rtk::TexRecord r;
+	e = e ? e : dm::d2h(&r, rec, sizeof(r), c->stream);
+	if (e)
+	{
+		(void)dm::sync(c->stream);
+		return e;
+	}
+	c->td_hook_record = r, c->td_hook_ran = true;
+	RF_TRY(td_error_of_record("rfwhip_decode_image", 0, r));
+	return dm::d2h(out_rgba8_host, c->d_td_out.p, px * 4u, c->stream);
+}
+
+extern "C" int rfwhip_read_texture_coefficients(rfwhip_context *c, int16_t *out, size_t cap_blocks, uint32_t *blocks)
+{
+	CTX_ENTER(c);
+	if (!c->td_coef_blocks)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_texture_coefficients: nothing has been decoded");
+	if (blocks)
+		*blocks = c->td_coef_blocks;
+	if (!out)
+		return RFWHIP_OK; // (the count alone)
+	if (cap_blocks < c->td_coef_blocks)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_texture_coefficients: %u blocks, room for %zu", c->td_coef_blocks, cap_blocks);
+	RF_TRY(sync_all(c));
+	return dm::d2h(out, c->d_td_coef.p, (size_t)c->td_coef_blocks * 128u, c->stream);
 }
 
 extern "C" int rfwhip_bloom_image(rfwhip_context *c, const float *rgba_in, float exposure, float *rgba_out)
@@ -5099,6 +5464,20 @@ static const Setting k_settings[] = {
 	// k_jpeg_offsets, k_jpeg_pack, then their launches
 	{"display_jpeg_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %u %u %u %u", c->jpeg_kind_ms[0], c->jpeg_kind_ms[1], c->jpeg_kind_ms[2], c->jpeg_kind_ms[3],
 													 c->jpeg_kind_launches[0], c->jpeg_kind_launches[1], c->jpeg_kind_launches[2], c->jpeg_kind_launches[3]); }, false},
+	// image textures (texture_decode.h): which side decodes the entropy data; auto = the device when the stream
+	// has restart intervals, the host when it has none
+	{"texture_entropy", SET {
+		 const int k = !strcmp(value, "auto") ? 0 : !strcmp(value, "host") ? 1 : !strcmp(value, "device") ? 2 : -1;
+		 if (k < 0)
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be auto, host or device", key);
+		 c->td_entropy = k;
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%s", c->td_entropy == 1 ? "host" : c->td_entropy == 2 ? "device" : "auto"); }, false},
+	// (read-only, stage_timing = 1) family 15 by kernel since its last reset: the milliseconds of k_texdec_zero, k_texdec_entropy,
+	// k_texdec_idct, k_texdec_color, k_tex_mips, k_texdec_finish, then their launches
+	{"texture_decode_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %.6f %.6f %u %u %u %u %u %u", c->td_kind_ms[0], c->td_kind_ms[1], c->td_kind_ms[2],
+													   c->td_kind_ms[3], c->td_kind_ms[4], c->td_kind_ms[5], c->td_kind_launches[0], c->td_kind_launches[1],
+													   c->td_kind_launches[2], c->td_kind_launches[3], c->td_kind_launches[4], c->td_kind_launches[5]); }, false},
 	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
 	{"noise_estimate", SET {
 		 bool on;
@@ -5253,7 +5632,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14 && KF_TEXDEC == 15, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)
@@ -5266,6 +5645,9 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	if (reset && which == KF_JPEG)
 		for (int k = 0; k < 4; k++)
 			c->jpeg_kind_ms[k] = 0.0f, c->jpeg_kind_launches[k] = 0;
+	if (reset && which == KF_TEXDEC)
+		for (int k = 0; k < 6; k++)
+			c->td_kind_ms[k] = 0.0f, c->td_kind_launches[k] = 0;
 	return RFWHIP_OK;
 }
 

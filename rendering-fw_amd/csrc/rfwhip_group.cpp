@@ -842,6 +842,18 @@ extern "C" int rfwhip_group_get_meter(rfwhip_group *g, rfwhip_meter_stats *stats
 }
 
 // the LUT of the display stage belongs to the root's context: the display kernel runs there, on the gathered image
+extern "C" int rfwhip_group_set_texture_sources(rfwhip_group *g, const rfwhip_texture_source *sources, size_t count)
+{
+	if (!g)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null group");
+	for (auto &e : g->ep)
+	{
+		GR_TRY(dm::use(e.device));
+		GR_TRY(rfwhip_set_texture_sources(e.ctx, sources, count)); // (the member's message stands)
+	}
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_group_set_display_lut(rfwhip_group *g, const float *rgb, uint32_t n)
 {
 	if (!g)

@@ -13,8 +13,12 @@ What it restates from the reference (which parses with tinygltf, a third-party l
                     (mesh.cpp:127-147; poses built at object.cpp:463-497); weights from the mesh / node defaults and from
                     "weights" animation channels (animation.cpp:201,231-257,365-367: sampleFloat over `count` targets)
   * containers      .gltf (json + external / data-uri buffers) and binary .glb (12-byte header, JSON chunk, BIN chunk)
-Not covered: cameras, KHR extensions, sparse accessors, image decoding (no image library in this environment: textures are
-referenced by index only); materials map baseColorFactor / metallic / roughness only.  File parsing itself is plain
+  * images          with load_images=True: `images` (uri, data-uri, bufferView) -> `textures` -> the material's baseColorTexture
+                    and normalTexture become texture sources (images.py): a JPEG stays encoded and is decoded, linearised and
+                    mipped on the device (rfwhip_set_texture_sources), a PNG's pixels likewise.  glTF's uv origin is the image's
+                    top-left corner and the sampler's row 0 is v = 0, so the rows are NOT flipped.  Off by default.
+Not covered: cameras, KHR extensions, sparse accessors, texture transforms and samplers' wrap modes; materials map
+baseColorFactor / metallic / roughness and, with load_images, the two textures above.  File parsing itself is plain
 json + base64 / external buffers + numpy.
 """
 import base64
@@ -25,7 +29,7 @@ import struct
 
 import numpy as np
 
-from . import scenes
+from . import images, scenes
 
 _COMPONENT = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
 _WIDTH = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
@@ -231,6 +235,29 @@ class Gltf:
         inv = np.linalg.inv(self.combined(node_index))
         return np.stack([inv @ self.combined(j) @ ibm[k] for k, j in enumerate(skin["joints"])]).astype(np.float32)
 
+    # ---- images ----------------------------------------------------------------------------------------------------
+    def image_bytes(self, idx):
+        """The encoded file of image `idx`: a data-uri, a file beside the .gltf, or a bufferView."""
+        im = self.doc["images"][idx]
+        if "uri" in im:
+            if im["uri"].startswith("data:"):
+                return base64.b64decode(im["uri"].split(",", 1)[1])
+            with open(os.path.join(self.dir, im["uri"]), "rb") as f:
+                return f.read()
+        v = self.doc["bufferViews"][im["bufferView"]]
+        off = v.get("byteOffset", 0)
+        return bytes(self.buffers[v["buffer"]][off:off + v["byteLength"]])
+
+    def material_images(self, idx):
+        """(image index of the base colour texture, of the normal texture), None where the material carries none."""
+        if idx < 0:
+            return None, None
+        m = self.doc["materials"][idx]
+        out = []
+        for ref in (m.get("pbrMetallicRoughness", {}).get("baseColorTexture"), m.get("normalTexture")):
+            out.append(None if ref is None else self.doc["textures"][ref["index"]].get("source"))
+        return tuple(out)
+
     def material(self, idx):
         if idx < 0:
             return scenes.host_material()
@@ -240,19 +267,32 @@ class Gltf:
                                     roughness=float(pbr.get("roughnessFactor", 1.0)))
 
 
-def load_scene(path, width=480, height=270):
+def load_scene(path, width=480, height=270, load_images=False):
     """A Scene with one mesh + instance per mesh node (first primitive), the node transforms as instance transforms, and
     per mesh node the rig (joints, weights, bind normals) when it is skinned.  Returns (scene, gltf, rigs) with
-    rigs = {scene mesh index: (node index, joints, weights, normals)}."""
+    rigs = {scene mesh index: (node index, joints, weights, normals)}.  load_images: the materials' base colour (sRGB -> linear)
+    and normal textures become texture sources the device decodes (module docstring)."""
     g = Gltf(path)
     s = scenes.Scene()
     s.name = os.path.basename(path)
     rigs = {}
     mats = {}
+    texs = {}
+
+    def texture(image, linearize):
+        if image is None:
+            return -1
+        if (image, linearize) not in texs:
+            texs[(image, linearize)] = s.add_texture(images.texture_from_bytes(g.image_bytes(image), flip=False, linearize=linearize))
+        return texs[(image, linearize)]
     for ni in g.mesh_nodes():
         prim = g.primitive(g.nodes[ni]["mesh"])
         if prim["material"] not in mats:
-            mats[prim["material"]] = s.add_material(**g.material(prim["material"]))
+            kw = g.material(prim["material"])
+            if load_images:
+                base, normal = g.material_images(prim["material"])
+                kw["texture"], kw["normalmap"] = texture(base, "srgb"), texture(normal, None)
+            mats[prim["material"]] = s.add_material(**kw)
         m = s.add_mesh(prim["positions"], prim["indices"], normals=prim["normals"], uvs=prim["uvs"], material=mats[prim["material"]])
         # skinned meshes are posed in mesh space by the joint matrices; the node transform places the instance
         s.add_instance(m, g.combined(ni).astype(np.float32))

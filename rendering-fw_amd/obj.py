@@ -10,7 +10,7 @@ core (object.cpp:1105-1123): assimp splits an object wherever the material chang
   * normals from the file when every corner of the mesh has one, else smooth normals generated per POSITION: the sum of the
     incident face normals, area-weighted (GenSmoothNormals; assimp's exact weighting depends on its version);
   * materials from the .mtl: Kd -> colour, Ns -> roughness = sqrt(2 / (Ns + 2)), d / Tr -> ignored, map_Kd is recorded by name
-    only (no image decoder in this environment); a face before any `usemtl` gets a default material.
+    and, with load_scene(load_images=True), loaded as the material's diffuse texture (images.py); a face before any `usemtl` gets a default material.
 
 Smoothing groups (`s`) do not change the result: with vn records the file's normals are used as they are, without them
 GenSmoothNormals smooths over every shared position regardless of group.
@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from . import scenes
+from . import images, scenes
 
 
 def parse_mtl(path):
@@ -117,15 +117,25 @@ def load_obj(path):
     return materials, meshes
 
 
-def load_scene(path, width=480, height=270):
-    """A Scene with one mesh + identity instance per material group of the file."""
+def load_scene(path, width=480, height=270, load_images=False):
+    """A Scene with one mesh + identity instance per material group of the file.  load_images: a material's map_Kd, resolved beside
+    the .mtl (the .obj's directory), becomes a texture source the device decodes (images.py; sRGB -> linear).  OBJ's v = 0 is the
+    image's bottom row and the sampler's row 0 is v = 0, so the rows ARE flipped.  Off by default."""
     materials, meshes = load_obj(path)
     s = scenes.Scene()
     s.name = os.path.basename(path)
     ids = []
+    texs = {}
+    base = os.path.dirname(os.path.abspath(path))
     for name, m in materials:
         rough = 1.0 if m["Ns"] is None else max(0.05, min(1.0, math.sqrt(2.0 / (m["Ns"] + 2.0))))
-        ids.append(s.add_material(color=tuple(m["Kd"]), roughness=rough))
+        tex = -1
+        if load_images and m["map_Kd"]:
+            file = os.path.join(base, m["map_Kd"].replace("\\", "/"))
+            if file not in texs:
+                texs[file] = s.add_texture(images.texture_from_file(file, flip=True, linearize="srgb"))
+            tex = texs[file]
+        ids.append(s.add_material(color=tuple(m["Kd"]), roughness=rough, texture=tex))
     for me in meshes:
         s.add_instance(s.add_mesh(me["vertices"], me["indices"], normals=me["normals"], uvs=me["uvs"], material=ids[me["material"]]))
     return s, materials, meshes
