@@ -872,8 +872,16 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   "shadow_bins_per_run", "shadow_packets_on", "sky" (the last update left p > 0: the shade waves run the sky variant),
  *   "light_tree" (nodes of the light tree the next render would use; 0: none, or light_sampling is not "tree"),
  *   "lights_bound" (area lights the last refresh of lights_follow_geometry found bound; 0 while that setting is off),
- *   "light_tree_refits" (refits of the light tree on the device since it was last built).
+ *   "light_tree_refits" (refits of the light tree on the device since it was last built), "primary_entry_on" (the primary wave of
+ *   the last render call started from its entry snapshot: see primary_entry).
  *   Not listed by rfwhip_get_settings, but settable:
+ *   primary_entry = "-1" (default) | "0" | "1": the entry snapshot of the pt primary wave in packet form.  Where the camera-ordered
+ *                  node table is used (kernel family 11 below), the camera has no lens (aperture 0) and count_traversal is 0, a pass
+ *                  walks the top of the tree once per 64-slot group of path slots — with sample groups of 64: once per pixel — and
+ *                  every wave of that group, in every sample group and sub-batch and in every later call with the same view, starts
+ *                  its walk from the record the pass left instead of at the root.  "1": records for every view; "-1": for calls of
+ *                  at least 720 paths per record, and for smaller calls from the second call with the same view on (a camera at rest);
+ *                  "0": never.  No pixel depends on it.  The passes are kernel family 16 of rfwhip_get_kernel_time.
  *   light_sampling = "reference" (default: the reference's estimator, the default kernels) | "linear" (its potentials, consistent
  *                  weights) | "tree" (the light tree, O(log lights) per next-event vertex, the same weights): rfwhip_get_light_tree
  *                  below has the formulas.  The parity integrator ignores it.
@@ -921,7 +929,8 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * call when the camera position or a tree has changed since — `launches` counts those passes, one per rewrite, with or without
  * stage_timing; the image does not depend on it.  12 bloom: one count per launch of a chain, 2 x the levels it ran (the down
  * passes, the up passes and the apply pass).  13 grade: k_display_graded, one launch per displayed image with display_grade = 1 (in
- * place of family 7's).  14 jpeg: the four kernels of a JPEG encode, one count each. */
+ * place of family 7's).  14 jpeg: the four kernels of a JPEG encode, one count each.  15 the image-texture decoder.  16 the
+ * primary wave's entry snapshot pass k_primary_entry (setting primary_entry): one count per pass, with or without stage_timing. */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

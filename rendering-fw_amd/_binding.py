@@ -768,10 +768,11 @@ class CoreBinding:
     GRADE = 13  # ... and of the graded display kernel (one launch per displayed image with display_grade = 1)
     JPEG = 14  # ... and of the JPEG encoder (four launches per stream)
     TEXDEC = 15  # ... and of the image-texture decoder (one count per launch of a decode or mip chain)
+    PRIMARY_ENTRY = 16  # ... and of the primary wave's entry snapshot pass (one count per rewrite of the records)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.TEXDEC if which == "texture_decode" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.TEXDEC if which == "texture_decode" else self.PRIMARY_ENTRY if which == "primary_entry" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 

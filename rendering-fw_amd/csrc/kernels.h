@@ -360,6 +360,12 @@ void launch_expand4(const rt::Node4c *nodes4, rt::Node4f *out, uint32_t count4, 
 // the primary wave's ordering pass (primary_order.h): nodes first .. first + count - 1 of `in` into the same nodes of `out`, their
 // children near to far as seen from `origin` (ordered = false: copied as they are)
 void launch_order4f(const rt::Node4f *in, rt::Node4f *out, uint32_t first, uint32_t count, const float origin[3], bool ordered, stream_t s);
+// the primary wave's entry snapshot pass (primary_entry.h): the records of groups 0 .. groups - 1 of the frame's slot layout
+// (groups = (fr.slots << fr.sgroup_log2) / 64) into out, primary_entry_words() words each; nodes: the camera-ordered table, root:
+// SceneView::tlas_root_entry, PRIMARY_ENTRY_NO_ROOT without instances
+constexpr uint32_t PRIMARY_ENTRY_NO_ROOT = 0xFFFFFFFEu; // (= ENTRY_DONE of rt_core.h, which the host side does not see)
+uint32_t primary_entry_words();
+void launch_primary_entry(const rt::Node4f *nodes, uint32_t root, const rt::CamView &cam, const rt::FrameView &fr, uint32_t *out, uint32_t groups, stream_t s);
 // BVH construction on the device (lbvh.hip), end to end in mesh-local arrays (node_base = tri_base = n4_base = 0):
 //   nodes / parents / flags   2 n entries   BVH2 in the reference's layout, device entries, one triangle per leaf
 //   nodes4 / src4             <= n / 4 n    the compressed 4-wide nodes the rays fetch, breadth-first, + their BVH2 sources

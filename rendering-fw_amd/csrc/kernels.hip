@@ -941,6 +941,7 @@ RT_FN void expand4_item(const Node4c *nodes4, Node4f *out, uint32_t i)
 
 // the primary wave's ordering pass: a node's children near to far as seen from the camera (the work item shared with the emulation)
 #include "primary_order.h"
+#include "primary_entry.h"
 
 // refit, pass 1: rewrite the leaf-ordered triangle vertices from the new mesh vertices
 RT_FN void refit_tris_item(f4 *tri_verts, const f4 *verts, const uint32_t *indices, uint32_t slot)
@@ -1553,8 +1554,11 @@ __device__ __forceinline__ uint32_t packet_key(float tk_lane, unsigned long long
 // ORDERED (closest hit only): sc.nodes4f is the camera-ordered table (primary_order.h) — every node's children stand near to far
 // as seen from where the wave's rays leave, and are taken as they come, like ANY's: no keys, no comparators, ref_lane unused.
 // The leaf phase is the closest-hit one, so every lane still finds ITS nearest hit whatever the order.
+// entry (ORDERED, wave-uniform; null: the root): the wave's record of the entry snapshot (primary_entry.h) — the walk starts with the
+// record's candidates on the stack, below the chain from the root that every ray of the group shares, instead of at the root.
 template <bool COUNT, bool ANY = false, bool ORDERED = false>
-__device__ __forceinline__ void trace_packet(const SceneView &sc, const bool active, const f3 O, const f3 D, const float t_min, Hit &hit, TStat &st)
+__device__ __forceinline__ void trace_packet(const SceneView &sc, const bool active, const f3 O, const f3 D, const float t_min, Hit &hit, TStat &st,
+											 const uint32_t *entry = nullptr)
 {
 	unsigned long long act = __ballot(active);
 	// a lane without a ray — or, ANY, one that has found its occluder — never enters a box: its ray is degenerate (PacketSpace::enter,
@@ -1572,6 +1576,19 @@ __device__ __forceinline__ void trace_packet(const SceneView &sc, const bool act
 	PacketStack stk;
 	int cur_inst = -1;
 	uint32_t cur = sc.instance_count ? sc.tlas_root_entry : ENTRY_DONE;
+	if (ORDERED && entry)
+	{
+		// one coalesced load: lane j + 1 takes word j, lane 0 keeps ENTRY_DONE; the used words are the stack, the top one comes first
+		// (the byte offset is made here, behind a barrier: hoisted out of the kernel's loops it costs two registers the kernel does not have)
+		uint32_t off = (__lane_id() - 1u) * 4u;
+		asm volatile("" : "+v"(off));
+		uint32_t w = ENTRY_DONE;
+		if (off < PRIMARY_ENTRY_K * 4u)
+			w = *(const uint32_t *)((const char *)entry + off);
+		stk.s0 = (int)w;
+		stk.sp = 1u + (uint32_t)__popcll(__ballot(w != ENTRY_DONE));
+		cur = stk.pop();
+	}
 	if (COUNT && active && cur != ENTRY_DONE) // (the root: popped by every ray)
 	{
 		if (!(cur & ENTRY_LEAF))
@@ -2101,6 +2118,22 @@ void launch_order4f(const Node4f *in, Node4f *out, uint32_t first, uint32_t coun
 	if (count)
 		hipLaunchKernelGGL(k_order4f, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, in, out, first, count, origin[0], origin[1],
 						   origin[2], ordered);
+}
+
+// the entry snapshot pass of the primary wave (primary_entry.h): a thread per 64-slot group of one sample group; its candidate list
+// lives in LDS, one column per thread (bank = thread % 32)
+__global__ void __launch_bounds__(BLOCK) k_primary_entry(const Node4f *nodes, uint32_t root, const CamView cam, const FrameView fr, uint32_t *out, uint32_t groups)
+{
+	__shared__ uint32_t list[PRIMARY_ENTRY_K * BLOCK];
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < groups)
+		primary_entry_item(nodes, root, cam, fr, i, out + (size_t)i * PRIMARY_ENTRY_K, list + threadIdx.x, BLOCK);
+}
+uint32_t primary_entry_words() { return PRIMARY_ENTRY_K; }
+void launch_primary_entry(const Node4f *nodes, uint32_t root, const CamView &cam, const FrameView &fr, uint32_t *out, uint32_t groups, stream_t s)
+{
+	if (groups)
+		hipLaunchKernelGGL(k_primary_entry, dim3((groups + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, nodes, root, cam, fr, out, groups);
 }
 
 // Grid of the persistent kernels: more workgroups than fit on the chip at once (4-7 per CU).  The queue-driven kernels

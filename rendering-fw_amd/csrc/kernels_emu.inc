@@ -87,7 +87,9 @@ static unsigned long long g_cost_nodes = 0, g_cost_tris = 0;
 #endif
 // ORDERED: the node table holds every node's children near to far as seen from the camera (primary_order.h) — they are taken as
 // they come (device: trace_packet<COUNT, false, true>, k_primary_packet; ORDERED = false: k_primary_packet_sorting)
-template <bool COUNT, bool ORDERED = false> void trace(const SceneView &sc, const bool *active, const f3 *O, const f3 *D, float t_min, Hit *hit, TStat &st)
+// entry (ORDERED; null: the root): the group's record of the entry snapshot (primary_entry.h), where the walk starts
+template <bool COUNT, bool ORDERED = false>
+void trace(const SceneView &sc, const bool *active, const f3 *O, const f3 *D, float t_min, Hit *hit, TStat &st, const uint32_t *entry = nullptr)
 {
 	unsigned long long act = 0;
 	for (int l = 0; l < WAVE; l++)
@@ -108,6 +110,15 @@ template <bool COUNT, bool ORDERED = false> void trace(const SceneView &sc, cons
 	Stack stk;
 	int cur_inst = -1;
 	uint32_t cur = sc.instance_count ? sc.tlas_root_entry : ENTRY_DONE;
+	if (ORDERED && entry) // (device: lane j + 1 takes word j, sp from a ballot of the used words)
+	{
+		for (uint32_t j = 0; j < PRIMARY_ENTRY_K; j++)
+		{
+			stk.s0[j + 1u] = entry[j];
+			stk.sp += entry[j] != ENTRY_DONE ? 1u : 0u;
+		}
+		cur = stk.pop();
+	}
 	if (COUNT && cur != ENTRY_DONE)
 	{
 		if (!(cur & ENTRY_LEAF))
@@ -281,7 +292,10 @@ template <bool COUNT, bool ORDERED = false> void primary(const Params &p, uint32
 			}
 			h[l].t = 1e34f, h[l].u = 0.0f, h[l].v = 0.0f, h[l].prim = -1, h[l].inst = -1;
 		}
-		trace<COUNT, ORDERED>(p.sc, active, O, D, 1e-5f, h, st);
+		const uint32_t *entry = nullptr; // (device: primary_packet_body.h)
+		if (ORDERED && !COUNT && p.wv.primary_entry)
+			entry = p.wv.primary_entry + (size_t)((base - fast_div(base, p.fr.div_group) * (p.fr.slots << p.fr.sgroup_log2)) >> 6) * PRIMARY_ENTRY_K;
+		trace<COUNT, ORDERED>(p.sc, active, O, D, 1e-5f, h, st, entry);
 		for (int l = 0; l < WAVE; l++)
 			if (active[l])
 			{
@@ -825,6 +839,16 @@ void launch_expand4(const Node4c *nodes4, Node4f *out, uint32_t count4, stream_t
 	EMU_DEFER(s, launch_expand4(nodes4, out, count4, s));
 	for (uint32_t i = 0; i < count4; i++)
 		expand4_item(nodes4, out, i);
+}
+uint32_t primary_entry_words() { return PRIMARY_ENTRY_K; }
+void launch_primary_entry(const Node4f *nodes, uint32_t root, const CamView &cam, const FrameView &fr, uint32_t *out, uint32_t groups, stream_t s)
+{
+	EMU_DEFER(s, launch_primary_entry(nodes, root, cam, fr, out, groups, s));
+	for (uint32_t i = 0; i < groups; i++)
+	{
+		uint32_t list[PRIMARY_ENTRY_K];
+		primary_entry_item(nodes, root, cam, fr, i, out + (size_t)i * PRIMARY_ENTRY_K, list, 1u);
+	}
 }
 void launch_order4f(const Node4f *in, Node4f *out, uint32_t first, uint32_t count, const float origin[3], bool ordered, stream_t s)
 {

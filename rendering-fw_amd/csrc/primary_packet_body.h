@@ -1,6 +1,9 @@
 // primary_packet_body.h — the body of k_primary_packet and of k_primary_packet_masked (kernels.hip), included by both like
 // shade_pt_body.h by the shade kernels: p, count, COUNT, ORDERED (the node table is camera-ordered: trace_packet); MASKED and `mask` (adaptive.h: one byte per slot tile) — with MASKED = false
 // the kernel is the code it was before the masked one existed.  A group of a retired tile leaves void hit records and traces nothing.
+// The ORDERED kernels, masked or not, start a group's walk from its record of the entry snapshot (primary_entry.h) where the launch
+// carries the table (p.wv.primary_entry; null: the root); the sorting kernels and the counting ones (COUNT: the per-ray counters
+// keep the meaning of a walk from the root) always start at the root.
 	clock_in(p.wv.counters, 0);
 	uint32_t *const head = &p.wv.counters->work[p.queue][0];
 	const uint32_t lane = __lane_id();
@@ -50,7 +53,16 @@
 			}
 			Hit h;
 			h.t = 1e34f, h.u = 0.0f, h.v = 0.0f, h.prim = -1, h.inst = -1;
-			trace_packet<COUNT, false, ORDERED>(fresh_params().sc, active, O, D, 1e-5f, h, st);
+			const uint32_t *entry = nullptr;
+			if (ORDERED && !COUNT)
+			{
+				// (base is wave-uniform: scalar arithmetic) the group within its sample group: (slot mod (g * slots)) / 64
+				const Params &q = fresh_params();
+				const uint32_t *const table = q.wv.primary_entry;
+				if (table)
+					entry = table + (size_t)((base - fast_div(base, q.fr.div_group) * (q.fr.slots << q.fr.sgroup_log2)) >> 6) * PRIMARY_ENTRY_K;
+			}
+			trace_packet<COUNT, false, ORDERED>(fresh_params().sc, active, O, D, 1e-5f, h, st, entry);
 			if (active)
 			{
 				primary_finish_item(fresh_params(), idx, D, h); // (hit record, or the sky term of a miss)

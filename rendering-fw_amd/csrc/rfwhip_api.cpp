@@ -217,7 +217,9 @@ enum KernelFamily
 	KF_GRADE = 13, // colour grading (display_grade.h): k_display_graded in place of family 7's kernel, one count per displayed image
 	KF_JPEG = 14,  // baseline JPEG of the display image (display_jpeg.h): four launches per stream, one count each
 	KF_TEXDEC = 15, // image textures (texture_decode.h): the kernels of a decode and of a mip chain, one count per launch
-	KF_COUNT = 16
+	KF_PRIMARY_ENTRY = 16, // the primary wave's entry snapshot pass k_primary_entry (primary_entry.h): one count per pass, with or without
+						   // stage_timing (the milliseconds only with it)
+	KF_COUNT = 17
 };
 
 // A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
@@ -377,6 +379,17 @@ struct rfwhip_context
 	dm::event_t ev_order;
 	uint64_t order_serial = 0, order_seen[MAX_SUB] = {};
 	bool ord_reader[MAX_SUB] = {}; // a primary wave of this sub-batch slot has read the table since its last rewrite
+	// the primary wave's entry snapshot (primary_entry.h): one record per 64-slot group of one sample group, for the
+	// view, frame layout and ordered table of ent_key; rewritten like the ordered table, on the main stream behind the ordering pass
+	int primary_entry = -1; // setting: 0 never, 1 wherever the ordered table is used without a lens, -1 where the pass also pays (ensure_primary_entry)
+	uint32_t ent_last_key[32] = {}; // the key of the previous call that could have used records: the same again = the view is at rest
+	bool primary_entry_last = false; // did the last render call's primary wave start from the snapshot?
+	DevBuf d_primary_entry;
+	bool ent_valid = false;
+	uint32_t ent_key[32] = {};
+	dm::event_t ev_entry;
+	uint64_t entry_serial = 0, entry_seen[MAX_SUB] = {};
+	bool ent_reader[MAX_SUB] = {};
 	DevBuf d_nodes, d_nodes4, d_nodes4_src, d_tri_verts, d_tri_shade, d_tri_uv, d_tlas_prims, d_instances;
 	size_t blas_nodes4 = 0, node4_capacity = 0; // d_nodes4 = [all BLAS 4-wide nodes | TLAS 4-wide nodes | spare]
 	DevBuf d_materials, d_textures, d_tex_u32, d_tex_f4, d_sky, d_area, d_point, d_spot, d_dir;
@@ -680,7 +693,7 @@ static void free_all(rfwhip_context *c)
 	}
 	c->d_lbvh_scratch.free_(), c->d_blue_noise.free_();
 	c->have_blue_noise = false;
-	DevBuf *bufs[] = {&c->d_nodes4, &c->d_nodes4f, &c->d_nodes4f_ord, &c->d_nodes4_src, &c->d_nodes, &c->d_tri_verts, &c->d_tri_shade, &c->d_tri_uv, &c->d_tlas_prims, &c->d_instances,
+	DevBuf *bufs[] = {&c->d_nodes4, &c->d_nodes4f, &c->d_nodes4f_ord, &c->d_primary_entry, &c->d_nodes4_src, &c->d_nodes, &c->d_tri_verts, &c->d_tri_shade, &c->d_tri_uv, &c->d_tlas_prims, &c->d_instances,
 					  &c->d_materials, &c->d_textures, &c->d_tex_u32, &c->d_tex_f4, &c->d_sky, &c->d_area, &c->d_point,
 					  &c->d_spot, &c->d_dir, &c->d_org[0], &c->d_org[1], &c->d_dir2[0], &c->d_dir2[1], &c->d_thr[0],
 					  &c->d_thr[1], &c->d_hit, &c->d_hit_inst, &c->d_hit0, &c->d_hit0_inst, &c->d_hit0_done, &c->d_sh_org[0], &c->d_sh_org[1],
@@ -697,7 +710,7 @@ static void free_all(rfwhip_context *c)
 	for (DevBuf *b : bufs)
 		b->free_();
 	c->noise_live = false, c->adaptive_live = false;
-	c->ord_valid = false;
+	c->ord_valid = false, c->ent_valid = false;
 	c->meter_have = false, c->meter_manual_stale = true, c->meter_pending = false;
 	if (c->ev_meter_ready)
 		dm::event_destroy(c->ev_meter), c->ev_meter_ready = false;
@@ -725,7 +738,7 @@ static void free_all(rfwhip_context *c)
 		for (int r = 0; r < rfwhip_context::MAX_RING; r++)
 			dm::event_destroy(c->ev_resolve[r]);
 		dm::event_destroy(c->ev_present_in), dm::event_destroy(c->ev_present_out), dm::event_destroy(c->ev_dn);
-		dm::event_destroy(c->ev_adaptive), dm::event_destroy(c->ev_order);
+		dm::event_destroy(c->ev_adaptive), dm::event_destroy(c->ev_order), dm::event_destroy(c->ev_entry);
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			dm::event_destroy(c->ev_sub_done[i]), dm::event_destroy(c->ev_conn_last[i]);
@@ -2083,7 +2096,7 @@ extern "C" int rfwhip_update(rfwhip_context *c)
 	// the trees the primary wave's ordering pass can order (primary_order.h): a mesh tree exactly one instance walks (in that
 	// instance's object space; a flat instance's is the world), the world tree and the top-level tree
 	{
-		c->ord_ranges.clear(), c->ord_valid = false;
+		c->ord_ranges.clear(), c->ord_valid = false, c->ent_valid = false;
 		std::vector<uint32_t> uses(c->meshes.size(), 0u), who(c->meshes.size(), 0u);
 		for (uint32_t i : live)
 			if (i != WORLD_ID)
@@ -2391,6 +2404,7 @@ static int ensure_sub_batches(rfwhip_context *c, int subs)
 		RF_TRY(dm::event_create(&c->ev_dn));
 		RF_TRY(dm::event_create(&c->ev_adaptive));
 		RF_TRY(dm::event_create(&c->ev_order));
+		RF_TRY(dm::event_create(&c->ev_entry));
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			RF_TRY(dm::event_create(&c->ev_sub_done[i]));
@@ -2529,6 +2543,67 @@ static int ensure_primary_order(rfwhip_context *c, const rt::f3 &pos)
 	c->order_serial++;
 	c->ord_valid = true, c->ord_version = c->nodes4f_version;
 	memcpy(c->ord_cam, bits, sizeof(bits));
+	return 0;
+}
+
+// ---- the primary wave's entry snapshot (primary_entry.h) --------------------------------------------------------------------------
+// It rides on the ordered table (the caller has just made that current) and needs ONE origin for a group's rays: no lens.  The per-ray
+// counters of count_traversal keep the meaning of a walk from the root, so a counting call starts there.
+// The pass is a thread per record that walks some ten nodes in double precision: 0.57 ms for the 2.07 M records of a 1080p frame in
+// groups of 64 (0.28 ns per record), against 19.6 ps per path of the primary wave that starts from them (2.6 ms per 133 M;
+// DESIGN_LOG.md, round 9) — 2 % of the call's primary wave from 720 paths per record.  Below that a pass per call would eat a fifth
+// of what it saves or more, so by the rule (-1) a smaller call gets records only when its view is the previous call's: a camera at
+// rest, whose calls all reuse them (a converging render: 256 spp per call and record on the bench).  1 makes them for every view.
+constexpr size_t PRIMARY_ENTRY_PATHS_PER_RECORD = 720;
+static bool primary_entry_wanted(const rfwhip_context *c, const rtk::Params &base)
+{
+	return c->primary_entry != 0 && base.cam.aperture == 0.0f && c->count_traversal == 0;
+}
+
+// The records for this view, frame and table, rewritten on the main stream when any of them has changed (compared by their bits).
+// Readers and the rewrite are ordered like the ordered table's (ensure_primary_order).
+// *use: the call's primary wave starts from the records
+static int ensure_primary_entry(rfwhip_context *c, const rtk::Params &base, size_t paths, bool *use)
+{
+	*use = false;
+	uint32_t key[32] = {};
+	static_assert(sizeof(rt::f3) == 12, "four vectors of the view");
+	memcpy(&key[0], &base.cam.pos, 12), memcpy(&key[3], &base.cam.p1, 12), memcpy(&key[6], &base.cam.right, 12), memcpy(&key[9], &base.cam.up, 12);
+	memcpy(&key[12], &base.fr.inv_w, 4), memcpy(&key[13], &base.fr.inv_h, 4);
+	key[14] = base.fr.W, key[15] = base.fr.H, key[16] = base.fr.tiles_x, key[17] = base.fr.slots, key[18] = base.fr.sgroup_log2;
+	key[19] = base.fr.local_rows, key[20] = base.fr.rank, key[21] = base.fr.world;
+	key[22] = (uint32_t)c->order_serial, key[23] = (uint32_t)(c->order_serial >> 32);
+	key[24] = base.sc.instance_count ? base.sc.tlas_root_entry : rtk::PRIMARY_ENTRY_NO_ROOT;
+	const bool at_rest = !memcmp(key, c->ent_last_key, sizeof(key));
+	memcpy(c->ent_last_key, key, sizeof(key));
+	*use = true;
+	if (c->ent_valid && !memcmp(key, c->ent_key, sizeof(key)))
+		return 0;
+	const uint32_t groups = (uint32_t)(((size_t)base.fr.slots << base.fr.sgroup_log2) >> 6);
+	if (c->primary_entry < 0 && !at_rest && paths < PRIMARY_ENTRY_PATHS_PER_RECORD * groups)
+	{
+		*use = false;
+		return 0;
+	}
+	const size_t bytes = (size_t)groups * rtk::primary_entry_words() * 4;
+	if (bytes > c->d_primary_entry.cap)
+		RF_TRY(sync_all(c)); // (the buffer moves)
+	RF_TRY(c->d_primary_entry.ensure(bytes));
+	for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
+		if (c->ent_reader[i])
+		{
+			RF_TRY(dm::stream_wait_event(c->stream, c->ev_sub_done[i]));
+			c->ent_reader[i] = false;
+		}
+	StageTimer t(c, KF_PRIMARY_ENTRY, -1);
+	rtk::launch_primary_entry(c->d_nodes4f_ord.as<rt::Node4f>(), key[24], base.cam, base.fr, c->d_primary_entry.as<uint32_t>(), groups, c->stream);
+	t.stop(0);
+	c->kernel_launches[KF_PRIMARY_ENTRY]++;
+	RF_TRY(dm::last_launch_error());
+	RF_TRY(dm::event_record(c->ev_entry, c->stream));
+	c->entry_serial++;
+	c->ent_valid = true;
+	memcpy(c->ent_key, key, sizeof(key));
 	return 0;
 }
 
@@ -2708,6 +2783,17 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		RF_TRY(ensure_primary_order(c, base.cam.pos));
 		ordered = c->d_nodes4f_ord.as<rt::Node4f>();
 	}
+	// ... and the entry snapshot of this view, behind it (primary_entry_wanted)
+	const uint32_t *entry = nullptr;
+	if (ordered && primary_entry_wanted(c, base))
+	{
+		bool use = false;
+		RF_TRY(ensure_primary_entry(c, base, paths, &use));
+		if (use)
+			entry = c->d_primary_entry.as<uint32_t>();
+	}
+	c->primary_entry_last = entry != nullptr;
+	base.wv.primary_entry = entry;
 	base.wv.rad = alternate ? c->d_rad[0].as<f4>() + paths * par : c->d_rad[par].as<f4>();
 	// the connections always add into their own buffer, on a side stream or not: the image is then bit-identical whichever way
 	// a call is scheduled (e.g. the ranks of a strip split against the single-rank image)
@@ -2741,6 +2827,11 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		{
 			RF_TRY(dm::stream_wait_event(s, c->ev_order));
 			c->order_seen[i] = c->order_serial;
+		}
+		if (entry && c->entry_seen[i] != c->entry_serial) // ... and so were the snapshot's records
+		{
+			RF_TRY(dm::stream_wait_event(s, c->ev_entry));
+			c->entry_seen[i] = c->entry_serial;
 		}
 		rtk::Params p = base;
 		const size_t off_rad = (size_t)c->fr.slots * s_begin; // this sub-batch's slice of the radiance buffers of the call
@@ -2814,6 +2905,8 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 					rtk::launch_extend(p, d == 0 ? rtk::GEN_PT : rtk::GEN_BUFFER, count, d == 0 ? n : n_ext, s, d == 0 ? ordered : nullptr);
 				if (d == 0 && ordered)
 					c->ord_reader[i] = true;
+				if (d == 0 && entry)
+					c->ent_reader[i] = true;
 				pa_pending = false;
 				te.stop();
 				if (side && d >= 2 && d < c->max_depth) // connect(d - 2) read the buffers shade(d) is about to write
@@ -5332,6 +5425,16 @@ static const Setting k_settings[] = {
 	{"arm", SET { return RFWHIP_OK; }, GET { return put(out, cap, "0"); }, false},
 	// read-only: would the next large pt call take the packet form of the depth-0 connection wave?
 	{"shadow_packets_on", nullptr, GET { return put(out, cap, "%d", (c->shadow_packets > 0 || (c->shadow_packets < 0 && c->shadow_packets_auto_on)) && c->packet_ok && c->nodes4f_current && (c->refill & 8) ? 1 : 0); }, false},
+	// the primary wave's entry snapshot (primary_entry.h): 1 wherever the camera-ordered table is used, without a lens and without
+	// count_traversal (primary_entry_wanted; no value forces it where those fail); -1 there too, where the pass pays: calls of 720
+	// paths per record or more, and smaller ones from the second call with the same view on (ensure_primary_entry); 0 never
+	{"primary_entry", SET {
+		 const int v = atoi(value);
+		 c->primary_entry = v < 0 ? -1 : (v != 0);
+		 return RFWHIP_OK; },
+	 GET_INT(primary_entry), false},
+	// read-only: did the primary wave of the last render call start from the snapshot?
+	{"primary_entry_on", nullptr, GET { return put(out, cap, "%d", c->primary_entry_last ? 1 : 0); }, false},
 	// read-only: light bins per sorted run of the last waited frames, see shadow_packets
 	{"shadow_bins_per_run", nullptr, GET { return put(out, cap, "%.3f", c->shadow_bins_per_run); }, false},
 	// read-only: which kernel variants the render calls launch (for hosts that label their measurements: bench.py)
@@ -5632,7 +5735,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14 && KF_TEXDEC == 15, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14 && KF_TEXDEC == 15 && KF_PRIMARY_ENTRY == 16, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)
@@ -6383,6 +6486,25 @@ extern "C" RFWHIP_API int rfwhip_emu_order4f(const void *in, void *out, uint32_t
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_emu_order4f: two node arrays and an origin");
 	rtk::launch_order4f((const rt::Node4f *)in, (rt::Node4f *)out, 0u, n, origin, ordered != 0, nullptr);
 	return dm::sync(nullptr); // (the deferred-stream variant: stream 0 — a context's main stream — has run it)
+}
+// the entry snapshot of the context's last render call that made one (primary_entry.h; tests/test_primary_entry.py): what the pass
+// read and what it wrote.  info[0..31] = the key of the records (view, frame, table serial, root: ensure_primary_entry), info[32] =
+// words per record, info[33] = records, info[34] = nodes of the camera-ordered table, info[35] = 1 if there are records at all.
+// nodes / records (either may be null): the table and the records, as many bytes / words as the caps allow
+extern "C" RFWHIP_API int rfwhip_emu_primary_entry(rfwhip_context *c, uint32_t *info, void *nodes, size_t nodes_cap_bytes, uint32_t *records,
+												   size_t records_cap_words)
+{
+	if (!c || !info)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_emu_primary_entry: a context and 36 words");
+	RF_TRY(sync_all(c));
+	memcpy(info, c->ent_key, sizeof(c->ent_key));
+	const size_t groups = c->ent_valid ? (((size_t)c->ent_key[17] << c->ent_key[18]) >> 6) : 0;
+	info[32] = rtk::primary_entry_words(), info[33] = (uint32_t)groups, info[34] = (uint32_t)c->nodes4_live, info[35] = c->ent_valid ? 1u : 0u;
+	if (nodes && c->ent_valid)
+		memcpy(nodes, c->d_nodes4f_ord.p, std::min(nodes_cap_bytes, c->nodes4_live * sizeof(rt::Node4f)));
+	if (records && c->ent_valid)
+		memcpy(records, c->d_primary_entry.p, std::min(records_cap_words, groups * info[32]) * 4);
+	return RFWHIP_OK;
 }
 #endif
 

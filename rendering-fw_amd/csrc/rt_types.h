@@ -496,6 +496,9 @@ struct WaveView
 				 // they must not read-modify-write the same words); null: connections add into `rad`
 	f4 *acc;	 // per local pixel accumulator (row-major local_rows x W)
 	const uint32_t *packet_rng; // parity integrator: xor128 state per (sample, packet), 4 x u32
+	// the entry snapshot of the primary wave's packet form (primary_entry.h): PRIMARY_ENTRY_K words per 64-slot group of one sample
+	// group, where the walk of the group's waves starts.  Null: at the root
+	const uint32_t *primary_entry;
 	WaveCounters *counters;
 };
 
