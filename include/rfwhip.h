@@ -457,6 +457,78 @@ RFWHIP_API int rfwhip_decode_image(rfwhip_context *ctx, const void *data, size_t
 								   uint32_t *w, uint32_t *h);
 RFWHIP_API int rfwhip_read_texture_coefficients(rfwhip_context *ctx, int16_t *out, size_t cap_blocks, uint32_t *blocks);
 
+/* ---- the sky's loaders: Radiance HDR files, and the alias table of sky_sampling on the device ----------------------------------
+ * (csrc/sky_load.h, kernel family 17)  rfw::skybox::load reads a .hdr file through FreeImage; a host of this
+ * library hands over the file's bytes and the device decodes them into the sky.
+ * rfwhip_set_sky_hdr(ctx, data, bytes, flags): the file `data` becomes the sky, as rfwhip_set_sky does for finished texels.
+ *   Accepted: the magic "#?RADIANCE" or "#?RGBE", header lines up to a blank one, among them FORMAT=32-bit_rle_rgbe (EXPOSURE= is
+ *   reported by rfwhip_hdr_info and not applied, the rest is skipped), the resolution line "-Y H +X W", and per scanline either
+ *   new-style RLE (2 2 hi lo with hi lo = W, for 8 <= W <= 32767: four component planes of count bytes, above 128 a run of
+ *   count - 128, otherwise `count` literal bytes, none across a plane's end) or W flat RGBE quadruples; the two may mix in a file.
+ *   A texel is rgb = mantissa * 2^(e - 136), all three 0 when e = 0 (FreeImage's rgbe_RGBEToFloat), w = 0: exact in float.  Row 0
+ *   of the sky is the file's first scanline (what the reference's loader has after flipping FreeImage's bottom-up bitmap);
+ *   RFWHIP_SKYSRC_FLIP_ROWS turns the rows over.
+ *   Not decoded — RFWHIP_ERR_UNSUPPORTED, the message names the form: other orientations (+Y, X-major), 32-bit_rle_xyze, old-style
+ *   run pixels (1 1 1 n).  Malformed — RFWHIP_ERR_INVALID_ARGUMENT, the message names the scanline: a count byte of 0, a run or
+ *   literal that overruns its plane, a scanline header whose width is not W, a buffer that ends early, a header without a blank
+ *   line.  The call is all or nothing: whatever it answers but RFWHIP_OK, the previous sky is in place.
+ * rfwhip_hdr_info (host only): width, height, the product of the EXPOSURE lines, whether any scanline is RLE, supported and the
+ *   reason; RFWHIP_OK with supported = 0 for a form that is not decoded, RFWHIP_ERR_INVALID_ARGUMENT for a malformed file.
+ * rfwhip_read_sky: the sky's texels back to the host, 4 floats each (r, g, b, 0); out null: *width, *height alone.
+ *
+ * sky_table = "host" (default) | "device" (unlisted): who builds the alias table of sky_sampling = 1.  "host": the sky is read
+ *   back, one core runs Walker / Vose, the table goes up — every byte and every image as before.  "device": seven kernels on the
+ *   context's stream and a 32-byte record back.  With n = W H, w_k = lum_k omega_row(k) (double; lum = 0.2126 r + 0.7152 g +
+ *   0.0722 b, 0 when negative or NaN; omega the row's solid angle from the host), S = sum w, mu = S / n, texel k heavy when w_k > mu,
+ *   d_k = max(mu - w_k, 0), e_k = max(w_k - mu, 0) and D, E their inclusive prefix sums:
+ *     light k: a = the first index with E_a > D_k - d_k: keep = (float)(w_k / mu), alias = a; no such a (rounding): keep = 1,
+ *              alias = k — or, for w_k = 0, keep = 0, alias = the heaviest texel;
+ *     heavy k: nxt = the first index with E_nxt > E_k, i = the first index with D_i >= E_k: keep = (float)clamp(1 - (D_i - E_k) / mu,
+ *              0, 1), alias = nxt; either missing: keep = 1, alias = k.
+ *   Every alias is a heavy texel; a texel of weight 0 has keep = 0 and is nobody's alias: it is never drawn.  Sums and prefix sums
+ *   have a fixed shape (no atomics; csrc/sky_load.h), the prefix sums are non-decreasing by construction.  The table describes the
+ *   same distribution as the host's, not the same bytes.  S = 0 or not finite: no table and p = 0, as with "host".
+ * rfwhip_read_sky_table: the current table (sky_sampling = 1; built now if a setting or the sky changed since the last update) and
+ *   its record; out null or cap too small: *entries and the record alone.  A host-built table reports S and RFWHIP_SKYTAB_VALID only.
+ * rfwhip_sky_alias_from_weights (hook): the total, scan and assign stages over n given weights (negative or NaN: 0), n < 2^31.
+ * sky_load_time (read-only, stage_timing = 1): family 17 by kernel — the milliseconds of k_skyhdr_planes, k_skyhdr_texels,
+ *   k_skytab_weights, k_skytab_total, k_skytab_scan_block, k_skytab_scan_super, k_skytab_scan_top, k_skytab_scan_apply,
+ *   k_skytab_assign, then their launches. */
+enum rfwhip_sky_hdr_error /* what k_skyhdr_planes flags (the host's walk refuses the same streams before any launch) */
+{
+	RFWHIP_SKYHDR_ERR_ZERO = 1,	   /* a count byte of 0 */
+	RFWHIP_SKYHDR_ERR_OVERRUN = 2, /* a run or literal past the plane's W bytes */
+	RFWHIP_SKYHDR_ERR_TRUNCATED = 4 /* the plane's bytes ended early */
+};
+enum rfwhip_sky_table_flags
+{
+	RFWHIP_SKYTAB_VALID = 1, /* S is positive and finite: there is a table */
+	RFWHIP_SKYTAB_DEVICE = 2 /* built by the kernels: heaviest, light and heavy are filled */
+};
+typedef struct rfwhip_hdr_info_t
+{
+	uint32_t width, height;
+	float exposure; /* the product of the header's EXPOSURE lines (1 without one); not applied */
+	uint32_t rle;	/* some scanline is run-length encoded */
+	uint32_t supported;
+	char reason[96]; /* empty when supported */
+} rfwhip_hdr_info_t;
+typedef struct rfwhip_sky_table_record /* 32 bytes: the record as it lies on the device */
+{
+	double S;			/* the sum of the weights */
+	uint32_t heaviest;	/* the first texel of the largest weight */
+	uint32_t light;		/* texels with w <= mu */
+	uint32_t heavy;		/* texels with w > mu */
+	uint32_t flags;		/* rfwhip_sky_table_flags */
+	uint32_t reserved[2];
+} rfwhip_sky_table_record;
+RFWHIP_API int rfwhip_set_sky_hdr(rfwhip_context *ctx, const void *data, size_t bytes, uint32_t flags);
+RFWHIP_API int rfwhip_hdr_info(const void *data, size_t bytes, rfwhip_hdr_info_t *info);
+RFWHIP_API int rfwhip_read_sky(rfwhip_context *ctx, float *out_rgba, size_t cap_texels, uint32_t *width, uint32_t *height);
+RFWHIP_API int rfwhip_read_sky_table(rfwhip_context *ctx, rfwhip_sky_alias *out, size_t cap_entries, size_t *entries, rfwhip_sky_table_record *record);
+RFWHIP_API int rfwhip_sky_alias_from_weights(rfwhip_context *ctx, const double *weights, size_t n, rfwhip_sky_alias *table_out,
+											 rfwhip_sky_table_record *record_out);
+
 /* ---- noise estimate: when has a progressive render converged? ---------------------------------------------------------------
  * With noise_estimate = 1 the resolve of every rfwhip_render (its variant k_resolve_noise) keeps two floats per pixel beside the
  * accumulator — sumY, the sum of the luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel's samples (a sample's value is what
@@ -629,6 +701,8 @@ RFWHIP_API int rfwhip_group_set_display_lut(rfwhip_group *group, const float *rg
 /* rfwhip_set_texture_sources on every member: each decodes its own replica of the table on its own device.  The sources are parsed by
  * every member alike, so a refused table is refused by all of them and every member keeps its previous one. */
 RFWHIP_API int rfwhip_group_set_texture_sources(rfwhip_group *group, const rfwhip_texture_source *sources, size_t count);
+/* rfwhip_set_sky_hdr on every member: each decodes its own replica of the sky on its own device; a refused file is refused by all. */
+RFWHIP_API int rfwhip_group_set_sky_hdr(rfwhip_group *group, const void *data, size_t bytes, uint32_t flags);
 RFWHIP_API int rfwhip_group_set_display_lut_cube(rfwhip_group *group, const char *text, size_t len);
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
@@ -930,7 +1004,8 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * stage_timing; the image does not depend on it.  12 bloom: one count per launch of a chain, 2 x the levels it ran (the down
  * passes, the up passes and the apply pass).  13 grade: k_display_graded, one launch per displayed image with display_grade = 1 (in
  * place of family 7's).  14 jpeg: the four kernels of a JPEG encode, one count each.  15 the image-texture decoder.  16 the
- * primary wave's entry snapshot pass k_primary_entry (setting primary_entry): one count per pass, with or without stage_timing. */
+ * primary wave's entry snapshot pass k_primary_entry (setting primary_entry): one count per pass, with or without stage_timing.  17 the
+ * sky's loaders (rfwhip_set_sky_hdr, sky_table = device): one count per launch; by kernel: the setting sky_load_time. */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

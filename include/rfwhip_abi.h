@@ -158,6 +158,20 @@ typedef struct rfwhip_texture_source
 } rfwhip_texture_source;
 RFWHIP_STATIC_ASSERT(sizeof(rfwhip_texture_source) == 40, "rfwhip_texture_source must be 40 B");
 
+/* A sky as a host has it before rfw::skybox::load has decoded it: the bytes of a Radiance .hdr file (rfwhip_set_sky_hdr, rfwhip.h). */
+enum rfwhip_sky_source_flags
+{
+	RFWHIP_SKYSRC_FLIP_ROWS = 1 /* sky row 0 is the file's last scanline */
+};
+/* One bucket of the sky's alias table (sky_sampling; rfwhip_read_sky_table, rfwhip.h): texel k is kept with probability keep, texel
+ * alias is handed out otherwise.  The layout of rt::SkyAlias, which the shade kernel reads. */
+typedef struct rfwhip_sky_alias
+{
+	float keep;
+	uint32_t alias;
+} rfwhip_sky_alias;
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_sky_alias) == 8, "rfwhip_sky_alias must be 8 B");
+
 typedef struct rfwhip_light_count
 {
 	uint32_t areaLightCount, pointLightCount, spotLightCount, directionalLightCount;

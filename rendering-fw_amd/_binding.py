@@ -145,6 +145,11 @@ class CoreBinding:
                                   "png_unfilter": (i32, [vp, sz, sz, sz, vp]),
                                   "decode_image": (i32, [vp, vp, sz, u32, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
                                   "read_texture_coefficients": (i32, [vp, vp, sz, C.POINTER(u32)]),
+                                  "set_sky_hdr": (i32, [vp, vp, sz, u32]),
+                                  "hdr_info": (i32, [vp, sz, C.POINTER(abi.HdrInfo)]),
+                                  "read_sky": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
+                                  "read_sky_table": (i32, [vp, vp, sz, C.POINTER(sz), C.POINTER(abi.SkyTableRecord)]),
+                                  "sky_alias_from_weights": (i32, [vp, vp, sz, vp, C.POINTER(abi.SkyTableRecord)]),
                                   "get_noise": (i32, [vp, C.POINTER(abi.NoiseStats)]),
                                   "read_noise_map": (i32, [vp, vp]),
                                   "read_noise_tiles": (i32, [vp, vp, sz, C.POINTER(u32), C.POINTER(u32)]),
@@ -289,6 +294,38 @@ class CoreBinding:
         p = _f32(pixels).reshape(-1, 3)
         assert len(p) == width * height
         self._check(self._fn("set_sky")(self._ctx, p.ctypes.data, int(width), int(height)))
+
+    # ---- the sky's loaders (include/rfwhip.h, rfwhip_set_sky_hdr; rendering_fw_amd.images.load_hdr) ----------------------------
+    def set_sky_hdr(self, data, flip=False):
+        """The bytes of a Radiance .hdr file become the sky: the device decodes them.  All or nothing: a refused file raises
+        RuntimeError and the previous sky stays."""
+        src = np.frombuffer(bytes(data), np.uint8)
+        self._check(self._fn("set_sky_hdr")(self._ctx, src.ctypes.data, src.size, abi.SKYSRC_FLIP_ROWS if flip else 0))
+
+    def read_sky(self):
+        """The sky's texels: H x W x 4 float32 (r, g, b, 0); a context without a sky: 0 x 0 x 4."""
+        w, h = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("read_sky")(self._ctx, None, 0, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, 4), np.float32)
+        if out.size:
+            self._check(self._fn("read_sky")(self._ctx, out.ctypes.data, w.value * h.value, C.byref(w), C.byref(h)))
+        return out
+
+    def read_sky_table(self):
+        """The alias table of sky_sampling = 1 as (entries of abi.SKY_ALIAS_DTYPE, the record as a dict); no entries without a table."""
+        n, rec = C.c_size_t(), abi.SkyTableRecord()
+        self._check(self._fn("read_sky_table")(self._ctx, None, 0, C.byref(n), C.byref(rec)))
+        out = np.empty(n.value, abi.SKY_ALIAS_DTYPE)
+        if n.value:
+            self._check(self._fn("read_sky_table")(self._ctx, out.ctypes.data, n.value, C.byref(n), C.byref(rec)))
+        return out, rec.as_dict()
+
+    def sky_alias_from_weights(self, weights):
+        """Known-answer hook: the device's alias table over the given float64 weights -> (entries, record)."""
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        out, rec = np.empty(len(w), abi.SKY_ALIAS_DTYPE), abi.SkyTableRecord()
+        self._check(self._fn("sky_alias_from_weights")(self._ctx, w.ctypes.data, len(w), out.ctypes.data, C.byref(rec)))
+        return out, rec.as_dict()
 
     def set_mesh_skin(self, index, joints, weights, base_normals):
         """Device skinning: per-vertex joints (V x 4 uint32), weights (V x 4) and bind-pose normals (V x 3|4) of mesh
@@ -769,10 +806,11 @@ class CoreBinding:
     JPEG = 14  # ... and of the JPEG encoder (four launches per stream)
     TEXDEC = 15  # ... and of the image-texture decoder (one count per launch of a decode or mip chain)
     PRIMARY_ENTRY = 16  # ... and of the primary wave's entry snapshot pass (one count per rewrite of the records)
+    SKY_LOAD = 17  # ... and of the sky's loaders (one count per launch of an HDR decode or of the alias table's chain)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.TEXDEC if which == "texture_decode" else self.PRIMARY_ENTRY if which == "primary_entry" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.TEXDEC if which == "texture_decode" else self.PRIMARY_ENTRY if which == "primary_entry" else self.SKY_LOAD if which == "sky_load" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -929,7 +967,8 @@ class RenderGroup:
                                 ("group_read_display_jpeg", i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
                                 ("group_present_jpeg_async", i32, [vp, i32]),
                                 ("group_present_jpeg_wait", i32, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
-                                ("group_set_texture_sources", i32, [vp, vp, C.c_size_t])]:
+                                ("group_set_texture_sources", i32, [vp, vp, C.c_size_t]),
+                                ("group_set_sky_hdr", i32, [vp, vp, C.c_size_t, u32])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -972,6 +1011,11 @@ class RenderGroup:
         for c in self.contexts:
             c._texture_types = _texture_source_types(textures)
         del keep
+
+    def set_sky_hdr(self, data, flip=False):
+        """CoreBinding.set_sky_hdr through rfwhip_group_set_sky_hdr: every member decodes its own replica of the sky."""
+        src = np.frombuffer(bytes(data), np.uint8)
+        self._check(self._fn("group_set_sky_hdr")(self._g, src.ctypes.data, src.size, abi.SKYSRC_FLIP_ROWS if flip else 0))
 
     def __getattr__(self, name):
         # scene setters and friends: the same call on every context (set_sky, set_mesh, set_lights, set_blue_noise, ...)

@@ -138,6 +138,27 @@ class ImageInfo(C.Structure):
                                           "supported")] + [("reason", C.c_char * 96)]
 
 
+# the sky's loaders (include/rfwhip.h, rfwhip_set_sky_hdr / rfwhip_read_sky_table)
+SKYSRC_FLIP_ROWS = 1
+SKYTAB_VALID, SKYTAB_DEVICE = 1, 2
+SKY_ALIAS_DTYPE = np.dtype([("keep", np.float32), ("alias", np.uint32)])  # rfwhip_sky_alias
+
+
+class HdrInfo(C.Structure):
+    """rfwhip_hdr_info_t (include/rfwhip.h, rfwhip_hdr_info)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("exposure", C.c_float), ("rle", C.c_uint32), ("supported", C.c_uint32),
+                ("reason", C.c_char * 96)]
+
+
+class SkyTableRecord(C.Structure):
+    """rfwhip_sky_table_record (include/rfwhip.h, rfwhip_read_sky_table): the 32-byte record of the alias table's chain."""
+    _fields_ = [("S", C.c_double), ("heaviest", C.c_uint32), ("light", C.c_uint32), ("heavy", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return dict(S=float(self.S), heaviest=int(self.heaviest), light=int(self.light), heavy=int(self.heavy), flags=int(self.flags))
+
+
 class LightCount(C.Structure):
     _fields_ = [("areaLightCount", C.c_uint32), ("pointLightCount", C.c_uint32), ("spotLightCount", C.c_uint32),
                 ("directionalLightCount", C.c_uint32)]

@@ -445,7 +445,24 @@ void launch_texdec_color(const TexdecView &v, stream_t s);
 void launch_tex_mips(const TexdecView &v, stream_t s);
 void launch_texdec_finish(const TexdecView &v, stream_t s);
 
+// the sky's loaders (sky_load.h, kernel family 17).  A Radiance HDR decode: k_skyhdr_planes (skipped when every scanline is flat),
+// k_skyhdr_texels.  The alias table: k_skytab_weights, k_skytab_total, k_skytab_scan_block, k_skytab_scan_super, k_skytab_scan_top,
+// k_skytab_scan_apply, k_skytab_assign, in this order on one stream
+struct SkyHdrView;
+struct SkyTabView;
+void launch_skyhdr_planes(const SkyHdrView &v, stream_t s);
+void launch_skyhdr_texels(const SkyHdrView &v, stream_t s);
+void launch_skytab_weights(const SkyTabView &v, stream_t s);
+void launch_skytab_total(const SkyTabView &v, stream_t s);
+void launch_skytab_scan_block(const SkyTabView &v, stream_t s);
+void launch_skytab_scan_super(const SkyTabView &v, stream_t s);
+void launch_skytab_scan_top(const SkyTabView &v, stream_t s);
+void launch_skytab_scan_apply(const SkyTabView &v, stream_t s);
+void launch_skytab_assign(const SkyTabView &v, stream_t s);
+
 } // namespace rtk
 
 // the types, the marker walk and the work items of the image textures (part 1 of the file)
 #include "texture_decode.h"
+// the types, the header walk and the work items of the sky's loaders (part 1 of the file)
+#include "sky_load.h"

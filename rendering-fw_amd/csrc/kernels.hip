@@ -3209,4 +3209,9 @@ void launch_kat_grade(const GradeView &g, int which, const float *in, float *out
 #include "kernels_emu.inc"
 #endif
 
+// the sky's loaders: Radiance HDR decode and the alias table on the device (part 2 of the file: the kernels and launchers, or the
+// emulation's launchers; behind everything else, so that no existing kernel moves)
+#define SKY_LOAD_LAUNCHERS
+#include "sky_load.h"
+
 } // namespace rtk

@@ -41,6 +41,11 @@
 // 1 .. 100), RFWHIP_JPEG_SUBSAMPLING (444 | 420) and RFWHIP_JPEG_RESTART (display_jpeg_restart) are optional; a value the setting
 // refuses ends the constructor with the message.  Nothing is allocated or launched until hiprtReadJpeg is called.
 //
+// Sky: RFWHIP_SKY_HDR=<path of a Radiance .hdr file> loads a sky at construction (include/rfwhip.h, rfwhip_group_set_sky_hdr: every
+// device decodes its own replica; the system's set_sky replaces it as usual), RFWHIP_SKY_TABLE=host|device sets sky_table — who
+// builds the alias table of sky_sampling; the key is listed by get_settings() as well.  A file that cannot be read or decoded, or a
+// value the setting refuses, ends the constructor with the message.
+//
 // Noise estimate: RFWHIP_NOISE=1 (unset by default: nothing changes) turns the setting noise_estimate on (include/rfwhip.h,
 // rfwhip_get_noise); a host asks hiprtGetNoise when to stop converging.  It answers for the accumulator — with frames in flight,
 // for the newest frame enqueued, not the one render_frame handed out.
@@ -170,6 +175,20 @@ class Context final : public rfw::RenderContext
 			if (std::string(nz) != "0" && std::string(nz) != "1")
 				throw std::runtime_error("HipRT: RFWHIP_NOISE must be \"0\" or \"1\"");
 			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "noise_estimate", nz));
+		}
+		if (const char *st = std::getenv("RFWHIP_SKY_TABLE"))
+			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "sky_table", st));
+		if (const char *sh = std::getenv("RFWHIP_SKY_HDR"))
+		{
+			std::string bytes;
+			FILE *f = std::fopen(sh, "rb");
+			if (!f)
+				throw std::runtime_error(std::string("HipRT: RFWHIP_SKY_HDR: cannot read ") + sh);
+			char buf[65536];
+			for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;)
+				bytes.append(buf, n);
+			std::fclose(f);
+			HIPRT_CHECK(rfwhip_group_set_sky_hdr(m_Group, bytes.data(), bytes.size(), 0));
 		}
 		const char *integ = std::getenv("RFWHIP_INTEGRATOR");
 		HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "integrator", integ ? integ : "pt"));
@@ -407,9 +426,9 @@ class Context final : public rfw::RenderContext
 	rfw::AvailableRenderSettings get_settings() const override
 	{
 		rfw::AvailableRenderSettings s;
-		s.settingKeys = {"integrator", "jitter", "spp", "max_depth", "DENOISE", "DENOISE_TEMPORAL", "sky_sampling", "DENOISE_MOTION"};
+		s.settingKeys = {"integrator", "jitter", "spp", "max_depth", "DENOISE", "DENOISE_TEMPORAL", "sky_sampling", "DENOISE_MOTION", "sky_table"};
 		s.settingValues = {{"pt", "parity"}, {"xor128", "center"}, {"1", "2", "4", "8", "16"}, {"0", "1", "2", "3", "4"}, {"0", "1"},
-						   {"0", "1"}, {"0", "1"}, {"0", "1"}};
+						   {"0", "1"}, {"0", "1"}, {"0", "1"}, {"host", "device"}};
 		return s;
 	}
 

@@ -219,7 +219,8 @@ enum KernelFamily
 	KF_TEXDEC = 15, // image textures (texture_decode.h): the kernels of a decode and of a mip chain, one count per launch
 	KF_PRIMARY_ENTRY = 16, // the primary wave's entry snapshot pass k_primary_entry (primary_entry.h): one count per pass, with or without
 						   // stage_timing (the milliseconds only with it)
-	KF_COUNT = 17
+	KF_SKYLOAD = 17, // the sky's loaders (sky_load.h): the kernels of an HDR decode and of the alias table's chain, one count per launch
+	KF_COUNT = 18
 };
 
 // A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
@@ -402,6 +403,12 @@ struct rfwhip_context
 	uint64_t sky_table_of = ~0ull; // the sky_version d_sky_alias was built from (~0: none)
 	double sky_total = 0.0;		 // S of that table (0: no texel with a positive weight)
 	DevBuf d_sky_alias;			 // allocated only while sky_sampling is on
+	// the sky's loaders (sky_load.h): sky_table = 0 host | 1 device: who builds d_sky_alias; the record of the current table
+	int sky_table = 0;
+	int sky_table_by = -1; // the sky_table value d_sky_alias was built with (-1: none)
+	rtk::SkyTabRecord sky_record = {0.0, 0, 0, 0, 0, {0, 0}};
+	float sl_kind_ms[9] = {};		  // family KF_SKYLOAD by kernel: planes, texels, weights, total, scan_block, scan_super, scan_top,
+	uint32_t sl_kind_launches[9] = {}; // scan_apply, assign (stage_timing = 1; the read-only setting sky_load_time)
 	rt::SkyView sky_view{};		 // pick == 0: the default kernels run
 	bool sky_stale = false;		 // a sky setting changed since: the next render (or update) refreshes the view
 	// light sampling (light_tree.h): 0 reference, 1 linear, 2 tree; the tree of the lights of the last rfwhip_set_lights
@@ -1600,6 +1607,9 @@ static int prepare_world(rfwhip_context *c, bool &changed)
 
 // sky_sampling: the alias table (rebuilt when the sky or the setting changed) and p (the lights may have changed).  Called by
 // rfwhip_update, and by a render or rfwhip_kat after a sky setting changed (they run on the scene of the last update).
+// sky_table = device (sky_load.h; defined with the sky's loaders below): the table of the sky's n texels — or of n given weights —
+// built by the kernels on the context's stream into `table`; the record comes back, the scratch is freed
+static int sky_table_on_device(rfwhip_context *c, const double *weights, uint32_t n, DevBuf &table, rtk::SkyTabRecord *record);
 static int update_sky_sampling(rfwhip_context *c)
 {
 	c->sky_stale = false;
@@ -1608,33 +1618,47 @@ static int update_sky_sampling(rfwhip_context *c)
 		if (c->d_sky_alias.p)
 			RF_TRY(sync_all(c)); // (frames in flight may still read the table)
 		c->d_sky_alias.free_(), c->sky_table_of = ~0ull, c->sky_total = 0.0;
+		c->sky_table_by = -1, c->sky_record = rtk::SkyTabRecord{0.0, 0, 0, 0, 0, {0, 0}};
 		c->sky_view = rt::SkyView{};
 		return RFWHIP_OK;
 	}
 	const size_t n = (size_t)c->sky_w * c->sky_h;
 	if (n >= (1ull << 31))
 		return set_error(RFWHIP_ERR_UNSUPPORTED, "sky_sampling: a sky of %u x %u texels is too large", c->sky_w, c->sky_h);
-	if (c->sky_table_of != c->sky_version)
+	if (c->sky_table_of != c->sky_version || c->sky_table_by != c->sky_table)
 	{
 		RF_TRY(sync_all(c)); // (frames in flight may still read the table)
 		c->sky_total = 0.0;
-		std::vector<rt::SkyAlias> table;
-		if (n)
+		c->sky_record = rtk::SkyTabRecord{0.0, 0, 0, 0, 0, {0, 0}};
+		if (n && c->sky_table == 1) // the kernels build it in place: nothing but the record comes back
 		{
-			std::vector<f4> px(n);
-			RF_TRY(dm::d2h(px.data(), c->d_sky.p, n * sizeof(f4), c->stream));
-			RF_TRY(dm::sync(c->stream));
-			c->sky_total = skysamp::build_alias(px.data(), c->sky_w, c->sky_h, table);
+			RF_TRY(sky_table_on_device(c, nullptr, (uint32_t)n, c->d_sky_alias, &c->sky_record));
+			if (c->sky_record.flags & rtk::SKYTAB_VALID)
+				c->sky_total = c->sky_record.S;
+			else
+				c->d_sky_alias.free_();
 		}
-		if (table.empty())
-			c->d_sky_alias.free_();
-		else
+		else // the host builds it: the sky comes down, the table goes up
 		{
-			RF_TRY(c->d_sky_alias.ensure(table.size() * sizeof(rt::SkyAlias)));
-			RF_TRY(dm::h2d(c->d_sky_alias.p, table.data(), table.size() * sizeof(rt::SkyAlias), c->stream));
-			RF_TRY(dm::sync(c->stream));
+			std::vector<rt::SkyAlias> table;
+			if (n)
+			{
+				std::vector<f4> px(n);
+				RF_TRY(dm::d2h(px.data(), c->d_sky.p, n * sizeof(f4), c->stream));
+				RF_TRY(dm::sync(c->stream));
+				c->sky_total = skysamp::build_alias(px.data(), c->sky_w, c->sky_h, table);
+			}
+			if (table.empty())
+				c->d_sky_alias.free_();
+			else
+			{
+				RF_TRY(c->d_sky_alias.ensure(table.size() * sizeof(rt::SkyAlias)));
+				RF_TRY(dm::h2d(c->d_sky_alias.p, table.data(), table.size() * sizeof(rt::SkyAlias), c->stream));
+				RF_TRY(dm::sync(c->stream));
+				c->sky_record.S = c->sky_total, c->sky_record.flags = rtk::SKYTAB_VALID;
+			}
 		}
-		c->sky_table_of = c->sky_version;
+		c->sky_table_of = c->sky_version, c->sky_table_by = c->sky_table;
 	}
 	// p: forced to 0 without a usable sky (the default kernels run: bit-identical to sky_sampling=0)
 	float pick = c->sky_pick >= 0.0f ? c->sky_pick : (total_light_count(c) ? 0.5f : 1.0f);
@@ -3183,6 +3207,10 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 			if (sp.depth >= 0 && sp.depth < 6)
 				c->td_kind_ms[sp.depth] += ms, c->td_kind_launches[sp.depth]++;
 			break;
+		case KF_SKYLOAD:
+			if (sp.depth >= 0 && sp.depth < 9)
+				c->sl_kind_ms[sp.depth] += ms, c->sl_kind_launches[sp.depth]++;
+			break;
 		default:
 			break;
 		}
@@ -4538,6 +4566,197 @@ extern "C" int rfwhip_read_texture_coefficients(rfwhip_context *c, int16_t *out,
 	return dm::d2h(out, c->d_td_coef.p, (size_t)c->td_coef_blocks * 128u, c->stream);
 }
 
+// ---- the sky's loaders (work items and kernels: sky_load.h) -----------------------------------------------------------------------
+static_assert(sizeof(rfwhip_sky_table_record) == sizeof(rtk::SkyTabRecord) && sizeof(rfwhip_sky_alias) == sizeof(rtk::SkyAliasEntry) &&
+				  sizeof(rtk::SkyAliasEntry) == sizeof(rt::SkyAlias) && sizeof(rtk::SkyF4) == sizeof(f4),
+			  "rfwhip.h: the sky table's records are the kernels' (sky_load.h, rt_types.h)");
+static_assert(rtk::SKY_INVALID == RFWHIP_ERR_INVALID_ARGUMENT && rtk::SKY_UNSUPPORTED == RFWHIP_ERR_UNSUPPORTED && rtk::SKY_FLIP_ROWS == RFWHIP_SKYSRC_FLIP_ROWS &&
+				  rtk::SKY_ERR_ZERO == RFWHIP_SKYHDR_ERR_ZERO && rtk::SKY_ERR_OVERRUN == RFWHIP_SKYHDR_ERR_OVERRUN &&
+				  rtk::SKY_ERR_TRUNCATED == RFWHIP_SKYHDR_ERR_TRUNCATED && rtk::SKYTAB_VALID == RFWHIP_SKYTAB_VALID && rtk::SKYTAB_DEVICE == RFWHIP_SKYTAB_DEVICE,
+			  "sky_load.h restates rfwhip.h's codes and flags");
+
+extern "C" int rfwhip_hdr_info(const void *data, size_t bytes, rfwhip_hdr_info_t *info)
+{
+	if (!data || !info)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_hdr_info: null argument");
+	rtk::SkyHdrInfo t;
+	const int rc = rtk::skyhdr_walk((const uint8_t *)data, bytes, t);
+	memset(info, 0, sizeof(*info));
+	info->width = t.W, info->height = t.H, info->exposure = t.exposure, info->rle = t.rle_lines != 0u, info->supported = rc == rtk::SKY_OK;
+	snprintf(info->reason, sizeof(info->reason), "%s", t.msg);
+	if (rc == rtk::SKY_INVALID)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_hdr_info: %s", t.msg);
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_set_sky_hdr(rfwhip_context *c, const void *data, size_t bytes, uint32_t flags)
+{
+	CTX_ENTER(c);
+	const char *const who = "rfwhip_set_sky_hdr";
+	if (!data)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: null file", who);
+	if (flags & ~(uint32_t)RFWHIP_SKYSRC_FLIP_ROWS)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x", who, flags);
+	rtk::SkyHdrInfo info;
+	const int walked = rtk::skyhdr_walk((const uint8_t *)data, bytes, info);
+	if (walked)
+		return set_error(walked, "%s: %s", who, info.msg);
+	// a new sky beside the current one: the current one stays whatever happens below
+	RF_TRY(sync_all(c));
+	void *const s = c->stream;
+	const size_t n = (size_t)info.W * info.H, items = (size_t)info.H * 4u;
+	DevBuf n_sky, d_stream, d_ranges, d_planes, d_flags;
+	const auto drop = [&](int rc) {
+		(void)dm::sync(s);
+		n_sky.free_(), d_stream.free_(), d_ranges.free_(), d_planes.free_(), d_flags.free_();
+		return rc;
+	};
+	int rc = n_sky.ensure(n * sizeof(f4));
+	rc = rc ? rc : d_stream.ensure(bytes);
+	rc = rc ? rc : d_ranges.ensure(info.ranges.size() * 4u);
+	rc = rc ? rc : d_flags.ensure(items * 4u);
+	if (info.rle_lines)
+		rc = rc ? rc : d_planes.ensure(items * info.W);
+	rc = rc ? rc : dm::h2d(d_stream.p, data, bytes, s);
+	rc = rc ? rc : dm::h2d(d_ranges.p, info.ranges.data(), info.ranges.size() * 4u, s);
+	if (rc)
+		return drop(rc);
+	rtk::SkyHdrView v;
+	memset(&v, 0, sizeof(v));
+	v.stream = d_stream.as<uint8_t>(), v.ranges = d_ranges.as<uint32_t>(), v.planes = d_planes.as<uint8_t>(), v.flags = d_flags.as<uint32_t>();
+	v.out = n_sky.as<rtk::SkyF4>(), v.W = info.W, v.H = info.H, v.mods = flags;
+	const auto run = [&](int kind, void (*launch)(const rtk::SkyHdrView &, void *)) {
+		StageTimer t(c, KF_SKYLOAD, kind, s);
+		launch(v, s);
+		t.stop(1);
+		return dm::last_launch_error();
+	};
+	std::vector<uint32_t> words;
+	if (info.rle_lines) // (a file of flat scanlines has no planes to expand)
+	{
+		words.resize(items);
+		rc = run(0, rtk::launch_skyhdr_planes);
+	}
+	rc = rc ? rc : run(1, rtk::launch_skyhdr_texels);
+	if (!rc && info.rle_lines)
+		rc = dm::d2h(words.data(), d_flags.p, items * 4u, s);
+	rc = rc ? rc : dm::sync(s);
+	if (rc)
+		return drop(rc);
+	for (size_t i = 0; i < words.size(); i++)
+		if (words[i]) // (the walk refuses these streams: a flag here is the kernel disagreeing with it)
+			return drop(set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: scanline %zu: component %zu is corrupt (flags 0x%x)", who, i / 4u, i % 4u, words[i]));
+	std::swap(c->d_sky, n_sky);
+	drop(0);
+	c->sky_w = info.W, c->sky_h = info.H;
+	c->sky_version++;
+	c->scene_dirty = true;
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_sky(rfwhip_context *c, float *out_rgba, size_t cap_texels, uint32_t *width, uint32_t *height)
+{
+	CTX_ENTER(c);
+	if (width)
+		*width = c->sky_w;
+	if (height)
+		*height = c->sky_h;
+	if (!out_rgba)
+		return RFWHIP_OK; // (the sizes alone)
+	const size_t n = (size_t)c->sky_w * c->sky_h;
+	if (cap_texels < n)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_read_sky: %zu texels, room for %zu", n, cap_texels);
+	RF_TRY(sync_all(c));
+	return dm::d2h(out_rgba, c->d_sky.p, n * sizeof(f4), c->stream);
+}
+
+static int sky_table_on_device(rfwhip_context *c, const double *weights, uint32_t n, DevBuf &table, rtk::SkyTabRecord *record)
+{
+	void *const s = c->stream;
+	const uint32_t nb1 = rtk::skytab_blocks(n), nb2 = rtk::skytab_blocks(nb1);
+	DevBuf b_w, b_d, b_e, b_part, b_t1d, b_t1e, b_t2d, b_t2e, b_c1, b_c2, b_omega, b_rec;
+	DevBuf *const all[12] = {&b_w, &b_d, &b_e, &b_part, &b_t1d, &b_t1e, &b_t2d, &b_t2e, &b_c1, &b_c2, &b_omega, &b_rec};
+	const size_t need[12] = {(size_t)n * 8u, (size_t)n * 8u, (size_t)n * 8u, (size_t)nb1 * sizeof(rtk::SkyPartial), (size_t)nb1 * 8u, (size_t)nb1 * 8u,
+							 (size_t)nb2 * 8u, (size_t)nb2 * 8u, (size_t)nb1 * 4u, (size_t)nb2 * 4u, weights ? 0u : (size_t)c->sky_h * 8u, sizeof(rtk::SkyTabRecord)};
+	const auto drop = [&](int rc) {
+		(void)dm::sync(s);
+		for (DevBuf *b : all)
+			b->free_();
+		return rc;
+	};
+	int rc = table.ensure((size_t)n * sizeof(rtk::SkyAliasEntry));
+	for (int k = 0; k < 12 && !rc; k++)
+		rc = need[k] ? all[k]->ensure_exact(need[k]) : 0;
+	std::vector<double> omega; // the rows' solid angles, as skysamp::build_alias has them: no device cos enters the numbers
+	if (!rc && weights)
+		rc = dm::h2d(b_w.p, weights, (size_t)n * 8u, s);
+	else if (!rc)
+	{
+		const double pi = 3.14159265358979323846;
+		omega.resize(c->sky_h);
+		for (uint32_t j = 0; j < c->sky_h; j++)
+			omega[j] = (2.0 * pi / c->sky_w) * (std::cos(pi * j / c->sky_h) - std::cos(pi * (j + 1) / c->sky_h));
+		rc = dm::h2d(b_omega.p, omega.data(), omega.size() * 8u, s);
+	}
+	if (rc)
+		return drop(rc);
+	rtk::SkyTabView v;
+	memset(&v, 0, sizeof(v));
+	v.sky = weights ? nullptr : c->d_sky.as<rtk::SkyF4>(), v.omega = b_omega.as<double>(), v.W = weights ? 1u : c->sky_w;
+	v.w = b_w.as<double>(), v.D = b_d.as<double>(), v.E = b_e.as<double>(), v.part = b_part.as<rtk::SkyPartial>();
+	v.t1d = b_t1d.as<double>(), v.t1e = b_t1e.as<double>(), v.t2d = b_t2d.as<double>(), v.t2e = b_t2e.as<double>();
+	v.c1 = b_c1.as<uint32_t>(), v.c2 = b_c2.as<uint32_t>(), v.rec = b_rec.as<rtk::SkyTabRecord>(), v.table = table.as<rtk::SkyAliasEntry>();
+	v.n = n, v.nb1 = nb1, v.nb2 = nb2;
+	void (*const chain[7])(const rtk::SkyTabView &, void *) = {rtk::launch_skytab_weights, rtk::launch_skytab_total, rtk::launch_skytab_scan_block,
+																rtk::launch_skytab_scan_super, rtk::launch_skytab_scan_top, rtk::launch_skytab_scan_apply,
+																rtk::launch_skytab_assign};
+	for (int k = 0; k < 7 && !rc; k++)
+	{
+		StageTimer t(c, KF_SKYLOAD, 2 + k, s);
+		chain[k](v, s);
+		t.stop(1);
+		rc = dm::last_launch_error();
+	}
+	rc = rc ? rc : dm::d2h(record, b_rec.p, sizeof(*record), s);
+	return drop(rc);
+}
+
+extern "C" int rfwhip_read_sky_table(rfwhip_context *c, rfwhip_sky_alias *out, size_t cap_entries, size_t *entries, rfwhip_sky_table_record *record)
+{
+	CTX_ENTER(c);
+	if (!c->sky_sampling)
+		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_sky_table: sky_sampling is off, there is no table");
+	if (c->sky_stale || c->sky_table_of != c->sky_version || c->sky_table_by != c->sky_table)
+		RF_TRY(update_sky_sampling(c));
+	const size_t n = c->sky_total > 0.0 ? (size_t)c->sky_w * c->sky_h : 0u;
+	if (entries)
+		*entries = n;
+	if (record)
+		memcpy(record, &c->sky_record, sizeof(*record));
+	if (!out || cap_entries < n || !n)
+		return RFWHIP_OK; // (the count and the record alone)
+	RF_TRY(sync_all(c));
+	return dm::d2h(out, c->d_sky_alias.p, n * sizeof(rt::SkyAlias), c->stream);
+}
+
+extern "C" int rfwhip_sky_alias_from_weights(rfwhip_context *c, const double *weights, size_t n, rfwhip_sky_alias *table_out, rfwhip_sky_table_record *record_out)
+{
+	CTX_ENTER(c);
+	if (!weights || !table_out || !record_out || !n)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_sky_alias_from_weights: null argument or no weights");
+	if (n >= (1ull << 31))
+		return set_error(RFWHIP_ERR_UNSUPPORTED, "rfwhip_sky_alias_from_weights: %zu weights (the table indexes 2^31)", n);
+	RF_TRY(sync_all(c));
+	DevBuf table;
+	rtk::SkyTabRecord r;
+	int rc = sky_table_on_device(c, weights, (uint32_t)n, table, &r);
+	rc = rc ? rc : dm::d2h(table_out, table.p, n * sizeof(rt::SkyAlias), c->stream);
+	table.free_();
+	if (!rc)
+		memcpy(record_out, &r, sizeof(r));
+	return rc;
+}
+
 extern "C" int rfwhip_bloom_image(rfwhip_context *c, const float *rgba_in, float exposure, float *rgba_out)
 {
 	CTX_ENTER(c);
@@ -5581,6 +5800,26 @@ static const Setting k_settings[] = {
 	{"texture_decode_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %.6f %.6f %u %u %u %u %u %u", c->td_kind_ms[0], c->td_kind_ms[1], c->td_kind_ms[2],
 													   c->td_kind_ms[3], c->td_kind_ms[4], c->td_kind_ms[5], c->td_kind_launches[0], c->td_kind_launches[1],
 													   c->td_kind_launches[2], c->td_kind_launches[3], c->td_kind_launches[4], c->td_kind_launches[5]); }, false},
+	// the sky's loaders (sky_load.h): who builds the alias table of sky_sampling; a change rebuilds it
+	{"sky_table", SET {
+		 const int k = !strcmp(value, "host") ? 0 : !strcmp(value, "device") ? 1 : -1;
+		 if (k < 0)
+			 return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s must be host or device", key);
+		 c->sky_table = k;
+		 c->sky_stale = true;
+		 return RFWHIP_OK; },
+	 GET { return put(out, cap, "%s", c->sky_table == 1 ? "device" : "host"); }, false},
+	// (read-only, stage_timing = 1) family 17 by kernel since its last reset: the milliseconds of k_skyhdr_planes, k_skyhdr_texels,
+	// k_skytab_weights, k_skytab_total, k_skytab_scan_block, k_skytab_scan_super, k_skytab_scan_top, k_skytab_scan_apply,
+	// k_skytab_assign, then their launches
+	{"sky_load_time", nullptr, GET {
+		 int at = 0;
+		 char line[512];
+		 for (int k = 0; k < 9; k++)
+			 at += snprintf(line + at, sizeof(line) - (size_t)at, "%.6f ", c->sl_kind_ms[k]);
+		 for (int k = 0; k < 9; k++)
+			 at += snprintf(line + at, sizeof(line) - (size_t)at, k < 8 ? "%u " : "%u", c->sl_kind_launches[k]);
+		 return put(out, cap, "%s", line); }, false},
 	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
 	{"noise_estimate", SET {
 		 bool on;
@@ -5735,7 +5974,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14 && KF_TEXDEC == 15 && KF_PRIMARY_ENTRY == 16, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14 && KF_TEXDEC == 15 && KF_PRIMARY_ENTRY == 16 && KF_SKYLOAD == 17, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)
@@ -5751,6 +5990,9 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	if (reset && which == KF_TEXDEC)
 		for (int k = 0; k < 6; k++)
 			c->td_kind_ms[k] = 0.0f, c->td_kind_launches[k] = 0;
+	if (reset && which == KF_SKYLOAD)
+		for (int k = 0; k < 9; k++)
+			c->sl_kind_ms[k] = 0.0f, c->sl_kind_launches[k] = 0;
 	return RFWHIP_OK;
 }
 

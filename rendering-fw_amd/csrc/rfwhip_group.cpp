@@ -854,6 +854,18 @@ extern "C" int rfwhip_group_set_texture_sources(rfwhip_group *g, const rfwhip_te
 	return RFWHIP_OK;
 }
 
+extern "C" int rfwhip_group_set_sky_hdr(rfwhip_group *g, const void *data, size_t bytes, uint32_t flags)
+{
+	if (!g)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null group");
+	for (auto &e : g->ep)
+	{
+		GR_TRY(dm::use(e.device));
+		GR_TRY(rfwhip_set_sky_hdr(e.ctx, data, bytes, flags)); // (the member's message stands)
+	}
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_group_set_display_lut(rfwhip_group *g, const float *rgb, uint32_t n)
 {
 	if (!g)

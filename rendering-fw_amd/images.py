@@ -1,6 +1,7 @@
 """Image files as texture sources (include/rfwhip.h, rfwhip_set_texture_sources): a JPEG stays encoded — the device decodes it —
 and a PNG becomes RGBA8 pixels here (zlib and the row filters), which the device flips, linearises and mips.  What the reference's
-rfw::texture does with FreeImage (texture.cpp of its system layer) on the host."""
+rfw::texture does with FreeImage (texture.cpp of its system layer) on the host.  Radiance .hdr files for the sky (rfwhip_set_sky_hdr)
+stay encoded as well: load_hdr / hdr_info, and write_hdr, a numpy encoder."""
 import ctypes as C
 import struct
 import zlib
@@ -137,3 +138,100 @@ def texture_from_bytes(data, flip=False, linearize=None, lib=None):
 def texture_from_file(path, flip=False, linearize=None, lib=None):
     with open(path, "rb") as f:
         return texture_from_bytes(f.read(), flip, linearize, lib)
+
+
+# ---- Radiance .hdr files (include/rfwhip.h, rfwhip_set_sky_hdr): the sky's loader, and an encoder for linear images ---------------
+def hdr_info(data, lib=None):
+    """The header of a Radiance .hdr file as a dict: width, height, exposure (the product of the EXPOSURE lines, not applied), rle,
+    supported, reason.  Host only (rfwhip_hdr_info); a malformed file raises RuntimeError."""
+    lib = lib or _lib()
+    src = np.frombuffer(bytes(data), np.uint8)
+    info = abi.HdrInfo()
+    lib.rfwhip_hdr_info.restype, lib.rfwhip_hdr_info.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(abi.HdrInfo)]
+    if lib.rfwhip_hdr_info(src.ctypes.data, src.size, C.byref(info)) != 0:
+        lib.rfwhip_last_error.restype = C.c_char_p
+        raise RuntimeError((lib.rfwhip_last_error() or b"unknown error").decode(errors="replace"))
+    return dict(width=int(info.width), height=int(info.height), exposure=float(info.exposure), rle=bool(info.rle),
+                supported=bool(info.supported), reason=info.reason.decode(errors="replace"))
+
+
+def load_hdr(path, ctx, flip=False):
+    """The file `path` becomes the sky of `ctx` (a RenderContext or a group): the device decodes it.  Returns hdr_info's dict."""
+    with open(path, "rb") as f:
+        data = f.read()
+    info = hdr_info(data, getattr(ctx, "_lib", None))
+    if not info["supported"]:
+        raise ValueError("HDR: not a form the device decodes: " + info["reason"])
+    ctx.set_sky_hdr(data, flip=flip)
+    return info
+
+
+def rgbe_from_float(rgb):
+    """H x W x 3 linear floats -> H x W x 4 uint8 RGBE, Ward's float2rgbe: the shared exponent of the largest component, the
+    mantissas truncated; a pixel whose largest component is below 1e-32 (or negative, or NaN) is 0 0 0 0."""
+    rgb = np.asarray(rgb, np.float64)
+    big = np.nan_to_num(rgb, nan=0.0, posinf=3.0e38).clip(0.0, 3.0e38)
+    v = big.max(-1)
+    m, e = np.frexp(v)  # v = m 2^e, m in [0.5, 1)
+    scale = np.where(v < 1e-32, 0.0, np.ldexp(256.0, -e))
+    out = np.zeros(rgb.shape[:2] + (4,), np.uint8)
+    out[..., :3] = np.minimum(big * scale[..., None], 255.0).astype(np.uint8)
+    out[..., 3] = np.where(v < 1e-32, 0, np.clip(e + 128, 0, 255)).astype(np.uint8)
+    out[out[..., 3] == 0] = 0
+    return out
+
+
+def _rle_plane(row):
+    """One component plane of a scanline -> its count bytes: runs of at least 4 equal bytes as (128 + n, value) with n <= 127,
+    everything else as literals of at most 128 bytes."""
+    out, n, i, lit = bytearray(), len(row), 0, 0
+    row = bytes(row)
+
+    def flush(upto):
+        nonlocal lit
+        while lit < upto:
+            k = min(128, upto - lit)
+            out.append(k)
+            out.extend(row[lit:lit + k])
+            lit += k
+    while i < n:
+        j = i + 1
+        while j < n and row[j] == row[i] and j - i < 127:
+            j += 1
+        if j - i >= 4:
+            flush(i)
+            out.append(128 + (j - i))
+            out.append(row[i])
+            lit = j
+        i = j
+    flush(n)
+    return bytes(out)
+
+
+def encode_hdr(rgbe, rle=True, exposure=None):
+    """H x W x 4 uint8 RGBE -> the bytes of a Radiance .hdr file (-Y H +X W).  rle: new-style run-length encoding where the format
+    allows it (8 <= W <= 32767), flat quadruples otherwise."""
+    rgbe = np.ascontiguousarray(rgbe, np.uint8)
+    h, w = rgbe.shape[:2]
+    head = b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n" + (b"EXPOSURE=%g\n" % exposure if exposure is not None else b"") + b"\n-Y %d +X %d\n" % (h, w)
+    if not rle or w < 8 or w > 32767:
+        # (a flat scanline that begins 2 2 hi<128 would read as an RLE header, a pixel 1 1 1 e as an old-style run)
+        first = rgbe[:, 0]
+        if (8 <= w <= 32767 and ((first[:, 0] == 2) & (first[:, 1] == 2) & (first[:, 2] < 128)).any()) or \
+                ((rgbe[..., 0] == 1) & (rgbe[..., 1] == 1) & (rgbe[..., 2] == 1)).any():
+            raise ValueError("HDR: these texels cannot be written flat (a scanline would read as run-length encoded): use rle=True")
+        return head + rgbe.tobytes()
+    body = bytearray()
+    for y in range(h):
+        body += bytes((2, 2, w >> 8, w & 255))
+        for c in range(4):
+            body += _rle_plane(rgbe[y, :, c])
+    return head + bytes(body)
+
+
+def write_hdr(path, rgb, rle=True):
+    """Save H x W x 3 (or x 4: the fourth channel is dropped) linear floats as a Radiance .hdr file — a sky for load_hdr, or a linear
+    render (framebuffer()[..., :3]).  Values are stored as RGBE: 8-bit mantissas under a shared exponent."""
+    rgb = np.asarray(rgb)[..., :3]
+    with open(path, "wb") as f:
+        f.write(encode_hdr(rgbe_from_float(rgb), rle=rle))
