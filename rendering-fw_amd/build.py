@@ -53,7 +53,7 @@ def build(force=False, verbose=False):
         host_src = os.path.join(os.path.dirname(HERE), "tests", "plugin", "plugin_host.cpp")
         if os.path.exists(host_src):
             host = os.path.join(os.path.dirname(HERE), "tests", "plugin", "plugin_host")
-            if force or _stale(host, deps + [host_src]):
+            if force or _stale(host, deps + [host_src, os.path.join(os.path.dirname(host_src), "host_common.h")]):
                 _run(["g++", "-O1", "-std=c++17", "-I" + INCLUDE, "-I" + os.path.join(CSRC, "plugin"), host_src, "-o", host,
                       "-ldl"], verbose)
             outs.append(host)

@@ -91,6 +91,53 @@ namespace
 			fail(#call);           \
 	} while (0)
 
+// The launcher's environment, one row per variable: a new RFWHIP_* variable that sets a setting is one more row here.  The rows are
+// applied top to bottom at construction, and settings are order-dependent in the core: keep the order.  Two allowed values
+// mean the plugin judges the value itself ("HipRT: <name> must be ..."); none, that it is passed through and the core judges it.
+// A row without a key names a file that is read whole and handed to the core.
+enum EnvFile
+{
+	NO_FILE,
+	CUBE_FILE, // rfwhip_group_set_display_lut_cube
+	HDR_FILE   // rfwhip_group_set_sky_hdr
+};
+struct EnvVar
+{
+	const char *name, *key = nullptr, *a = nullptr, *b = nullptr;
+	EnvFile file = NO_FILE;
+};
+const EnvVar kEnv[] = {
+	{"RFWHIP_DISPLAY", "display_tonemap", "aces", "none"}, // (and Context::m_Display)
+	{"RFWHIP_EXPOSURE", "display_exposure", "auto", "manual"},
+	{"RFWHIP_EXPOSURE_SPEED", "display_exposure_speed"},
+	{"RFWHIP_BLOOM", "display_bloom", "0", "1"},
+	{"RFWHIP_GRADE", "display_grade", "0", "1"},
+	{"RFWHIP_GRADE_TEMPERATURE", "display_wb_temperature"},
+	{"RFWHIP_GRADE_SATURATION", "display_grade_saturation"},
+	{"RFWHIP_DITHER", "display_dither", "0", "1"},
+	{"RFWHIP_GRADE_LUT", nullptr, nullptr, nullptr, CUBE_FILE},
+	{"RFWHIP_JPEG_QUALITY", "display_jpeg_quality"},
+	{"RFWHIP_JPEG_SUBSAMPLING", "display_jpeg_subsampling"},
+	{"RFWHIP_JPEG_RESTART", "display_jpeg_restart"},
+	{"RFWHIP_NOISE", "noise_estimate", "0", "1"},
+	{"RFWHIP_SKY_TABLE", "sky_table"},
+	{"RFWHIP_SKY_HDR", nullptr, nullptr, nullptr, HDR_FILE},
+};
+
+// the whole file at `path`, named by the variable `name`
+std::string read_file(const char *name, const char *path)
+{
+	FILE *f = std::fopen(path, "rb");
+	if (!f)
+		throw std::runtime_error(std::string("HipRT: ") + name + ": cannot read " + path);
+	std::string bytes;
+	char buf[65536];
+	for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;)
+		bytes.append(buf, n);
+	std::fclose(f);
+	return bytes;
+}
+
 class Context final : public rfw::RenderContext
 {
   public:
@@ -113,83 +160,27 @@ class Context final : public rfw::RenderContext
 			m_Cores.push_back(rfwhip_group_context(m_Group, i));
 		if (const char *f = std::getenv("RFWHIP_FRAMES_IN_FLIGHT"))
 			m_InFlight = std::max(1, std::min(RFWHIP_PRESENT_SLOTS, std::atoi(f)));
-		if (const char *d = std::getenv("RFWHIP_DISPLAY"))
+		for (const EnvVar &v : kEnv)
 		{
-			const std::string mode = d;
-			if (mode != "aces" && mode != "none")
-				throw std::runtime_error("HipRT: RFWHIP_DISPLAY must be \"aces\" or \"none\"");
-			m_Display = true;
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_tonemap", mode.c_str()));
+			const char *value = std::getenv(v.name);
+			if (!value)
+				continue;
+			if (v.a && std::strcmp(value, v.a) != 0 && std::strcmp(value, v.b) != 0)
+				throw std::runtime_error(std::string("HipRT: ") + v.name + " must be \"" + v.a + "\" or \"" + v.b + "\"");
+			if (v.key)
+				HIPRT_CHECK(rfwhip_group_set_setting(m_Group, v.key, value));
+			else if (v.file == CUBE_FILE)
+			{
+				const std::string text = read_file(v.name, value);
+				HIPRT_CHECK(rfwhip_group_set_display_lut_cube(m_Group, text.data(), text.size()));
+			}
+			else
+			{
+				const std::string bytes = read_file(v.name, value);
+				HIPRT_CHECK(rfwhip_group_set_sky_hdr(m_Group, bytes.data(), bytes.size(), 0));
+			}
 		}
-		if (const char *x = std::getenv("RFWHIP_EXPOSURE"))
-		{
-			const std::string mode = x;
-			if (mode != "auto" && mode != "manual")
-				throw std::runtime_error("HipRT: RFWHIP_EXPOSURE must be \"auto\" or \"manual\"");
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_exposure", mode.c_str()));
-		}
-		if (const char *sp = std::getenv("RFWHIP_EXPOSURE_SPEED"))
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_exposure_speed", sp));
-		if (const char *bl = std::getenv("RFWHIP_BLOOM"))
-		{
-			if (std::string(bl) != "0" && std::string(bl) != "1")
-				throw std::runtime_error("HipRT: RFWHIP_BLOOM must be \"0\" or \"1\"");
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_bloom", bl));
-		}
-		if (const char *gr = std::getenv("RFWHIP_GRADE"))
-		{
-			if (std::string(gr) != "0" && std::string(gr) != "1")
-				throw std::runtime_error("HipRT: RFWHIP_GRADE must be \"0\" or \"1\"");
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_grade", gr));
-		}
-		if (const char *gt = std::getenv("RFWHIP_GRADE_TEMPERATURE"))
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_wb_temperature", gt));
-		if (const char *gs = std::getenv("RFWHIP_GRADE_SATURATION"))
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_grade_saturation", gs));
-		if (const char *dt = std::getenv("RFWHIP_DITHER"))
-		{
-			if (std::string(dt) != "0" && std::string(dt) != "1")
-				throw std::runtime_error("HipRT: RFWHIP_DITHER must be \"0\" or \"1\"");
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_dither", dt));
-		}
-		if (const char *gl = std::getenv("RFWHIP_GRADE_LUT"))
-		{
-			std::string text;
-			FILE *f = std::fopen(gl, "rb");
-			if (!f)
-				throw std::runtime_error(std::string("HipRT: RFWHIP_GRADE_LUT: cannot read ") + gl);
-			char buf[65536];
-			for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;)
-				text.append(buf, n);
-			std::fclose(f);
-			HIPRT_CHECK(rfwhip_group_set_display_lut_cube(m_Group, text.data(), text.size()));
-		}
-		if (const char *jq = std::getenv("RFWHIP_JPEG_QUALITY"))
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_jpeg_quality", jq));
-		if (const char *js = std::getenv("RFWHIP_JPEG_SUBSAMPLING"))
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_jpeg_subsampling", js));
-		if (const char *jr = std::getenv("RFWHIP_JPEG_RESTART"))
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "display_jpeg_restart", jr));
-		if (const char *nz = std::getenv("RFWHIP_NOISE"))
-		{
-			if (std::string(nz) != "0" && std::string(nz) != "1")
-				throw std::runtime_error("HipRT: RFWHIP_NOISE must be \"0\" or \"1\"");
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "noise_estimate", nz));
-		}
-		if (const char *st = std::getenv("RFWHIP_SKY_TABLE"))
-			HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "sky_table", st));
-		if (const char *sh = std::getenv("RFWHIP_SKY_HDR"))
-		{
-			std::string bytes;
-			FILE *f = std::fopen(sh, "rb");
-			if (!f)
-				throw std::runtime_error(std::string("HipRT: RFWHIP_SKY_HDR: cannot read ") + sh);
-			char buf[65536];
-			for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;)
-				bytes.append(buf, n);
-			std::fclose(f);
-			HIPRT_CHECK(rfwhip_group_set_sky_hdr(m_Group, bytes.data(), bytes.size(), 0));
-		}
+		m_Display = std::getenv("RFWHIP_DISPLAY") != nullptr; // render_frame presents the display image
 		const char *integ = std::getenv("RFWHIP_INTEGRATOR");
 		HIPRT_CHECK(rfwhip_group_set_setting(m_Group, "integrator", integ ? integ : "pt"));
 		if (m_InFlight >= RFWHIP_PRESENT_SLOTS) // four frames in flight need four sets of wave buffers (the default ring is three)

@@ -3,36 +3,23 @@ RFWHIP_DISPLAY the bytes hiprtReadDisplay returns are the float64 models' (bloom
 C ABI gives for the same frame; with the variable unset, or "0", they are the C ABI's display bytes of a context that never touched
 a display_bloom* setting; a value the variable does not have is refused."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_bloom as cpu
-from conftest import ROOT
+from plugin_hosts import build_host, run_host
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def host(pkg, tmp_path_factory):
-    lib_dir = os.path.dirname(pkg.LIB_PATH)
-    exe = str(tmp_path_factory.mktemp("plugin") / "bloom_host")
-    src = os.path.join(ROOT, "tests", "plugin", "bloom_host.cpp")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "rendering-fw_amd", "csrc", "plugin"), src, "-o", exe, "-L" + lib_dir, "-lrfwhip",
-                        "-Wl,-rpath," + lib_dir, "-ldl"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout
-    if not os.path.exists(os.path.join(lib_dir, "HipRT.so")):
-        pytest.fail("the plugin is not built")
-    return exe, lib_dir
+    return build_host(pkg, tmp_path_factory, "bloom_host")
 
 
 def _run(host, out, **env):
-    exe, lib_dir = host
-    base = {k: v for k, v in os.environ.items() if k != "RFWHIP_BLOOM"}
-    return subprocess.run([exe, lib_dir, str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
-                          env=dict(base, RFWHIP_DISPLAY="aces", **env))
+    return run_host(host, out, drop=("RFWHIP_BLOOM",), RFWHIP_DISPLAY="aces", **env)
 
 
 def _images(r, out):

@@ -3,13 +3,12 @@
 gives for the same frame under the same settings; with the variables unset they are the ungraded display bytes; a value a variable
 does not have, or a file that is not there, is refused."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import display_grade_model as gm
-from conftest import ROOT
+from plugin_hosts import build_host, run_host
 
 pytestmark = pytest.mark.gpu
 VARS = ("RFWHIP_GRADE", "RFWHIP_GRADE_TEMPERATURE", "RFWHIP_GRADE_SATURATION", "RFWHIP_GRADE_LUT", "RFWHIP_DITHER", "RFWHIP_BLOOM", "RFWHIP_EXPOSURE")
@@ -17,23 +16,11 @@ VARS = ("RFWHIP_GRADE", "RFWHIP_GRADE_TEMPERATURE", "RFWHIP_GRADE_SATURATION", "
 
 @pytest.fixture(scope="module")
 def host(pkg, tmp_path_factory):
-    lib_dir = os.path.dirname(pkg.LIB_PATH)
-    exe = str(tmp_path_factory.mktemp("plugin") / "grade_host")
-    src = os.path.join(ROOT, "tests", "plugin", "grade_host.cpp")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "rendering-fw_amd", "csrc", "plugin"), src, "-o", exe, "-L" + lib_dir, "-lrfwhip",
-                        "-Wl,-rpath," + lib_dir, "-ldl"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout
-    if not os.path.exists(os.path.join(lib_dir, "HipRT.so")):
-        pytest.fail("the plugin is not built")
-    return exe, lib_dir
+    return build_host(pkg, tmp_path_factory, "grade_host")
 
 
 def _run(host, out, **env):
-    exe, lib_dir = host
-    base = {k: v for k, v in os.environ.items() if k not in VARS}
-    return subprocess.run([exe, lib_dir, str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
-                          env=dict(base, RFWHIP_DISPLAY="aces", **env))
+    return run_host(host, out, drop=VARS, RFWHIP_DISPLAY="aces", **env)
 
 
 def _images(r, out):

@@ -2,13 +2,12 @@
 hiprtReadJpeg returns is the numpy model's stream (tests/jpeg_model.py) of the bytes hiprtReadDisplay returns for the same frame,
 under the settings the RFWHIP_JPEG_* variables name and under the defaults; a value a variable does not have is refused."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import jpeg_model as jm
-from conftest import ROOT
+from plugin_hosts import build_host, run_host
 
 pytestmark = pytest.mark.gpu
 VARS = ("RFWHIP_JPEG_QUALITY", "RFWHIP_JPEG_SUBSAMPLING", "RFWHIP_JPEG_RESTART", "RFWHIP_GRADE", "RFWHIP_BLOOM", "RFWHIP_EXPOSURE")
@@ -16,23 +15,11 @@ VARS = ("RFWHIP_JPEG_QUALITY", "RFWHIP_JPEG_SUBSAMPLING", "RFWHIP_JPEG_RESTART",
 
 @pytest.fixture(scope="module")
 def host(pkg, tmp_path_factory):
-    lib_dir = os.path.dirname(pkg.LIB_PATH)
-    exe = str(tmp_path_factory.mktemp("plugin") / "jpeg_host")
-    src = os.path.join(ROOT, "tests", "plugin", "jpeg_host.cpp")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "rendering-fw_amd", "csrc", "plugin"), src, "-o", exe, "-L" + lib_dir, "-lrfwhip",
-                        "-Wl,-rpath," + lib_dir, "-ldl"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout
-    if not os.path.exists(os.path.join(lib_dir, "HipRT.so")):
-        pytest.fail("the plugin is not built")
-    return exe, lib_dir
+    return build_host(pkg, tmp_path_factory, "jpeg_host")
 
 
 def _run(host, out, **env):
-    exe, lib_dir = host
-    base = {k: v for k, v in os.environ.items() if k not in VARS}
-    return subprocess.run([exe, lib_dir, str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
-                          env=dict(base, RFWHIP_DISPLAY="aces", **env))
+    return run_host(host, out, drop=VARS, RFWHIP_DISPLAY="aces", **env)
 
 
 def _check(r, out, quality, sub, ri):

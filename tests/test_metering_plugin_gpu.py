@@ -2,34 +2,20 @@
 RFWHIP_EXPOSURE=auto beside RFWHIP_DISPLAY, the bytes hiprtReadDisplay returns after every render_frame — with 2 frames in flight,
 and with 1 — are the bytes the C ABI's rfwhip_group_read_display gives for the same frame, hiprtGetExposure reports one step per
 frame and the C ABI's record, and a value the variable does not have is refused."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+from plugin_hosts import build_host, run_host
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def host(pkg, tmp_path_factory):
-    lib_dir = os.path.dirname(pkg.LIB_PATH)
-    exe = str(tmp_path_factory.mktemp("plugin") / "exposure_host")
-    src = os.path.join(ROOT, "tests", "plugin", "exposure_host.cpp")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "rendering-fw_amd", "csrc", "plugin"), src, "-o", exe, "-L" + lib_dir, "-lrfwhip",
-                        "-Wl,-rpath," + lib_dir, "-ldl"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout
-    if not os.path.exists(os.path.join(lib_dir, "HipRT.so")):
-        pytest.fail("the plugin is not built")
-    return exe, lib_dir
+    return build_host(pkg, tmp_path_factory, "exposure_host")
 
 
 def _run(host, **env):
-    exe, lib_dir = host
-    return subprocess.run([exe, lib_dir], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
-                          env=dict(os.environ, RFWHIP_DISPLAY="aces", **env))
+    return run_host(host, RFWHIP_DISPLAY="aces", **env)
 
 
 @pytest.mark.parametrize("in_flight", [2, 1])

@@ -1,14 +1,12 @@
 """The noise estimate on the device (k_resolve_noise, k_noise_merge, k_noise_tiles, k_noise_final; work items: csrc/noise.h): the
 checks of tests/test_noise.py on the HIP kernels at the same small shapes, held to the float64 model of tests/noise_model.py (not
 to the emulation), one full-size metric, a group of two contexts on one device, and the plugin's hiprtGetNoise."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import noise_model as nm
 import test_noise as tn
+from plugin_hosts import build_host, run_host
 
 pytestmark = pytest.mark.gpu
 
@@ -72,27 +70,14 @@ def test_group_on_one_device_equals_the_single_context(pkg, make_hip):
 
 @pytest.fixture(scope="module")
 def plugin_host(pkg, tmp_path_factory):
-    from conftest import ROOT
-    lib_dir = os.path.dirname(pkg.LIB_PATH)
-    exe = str(tmp_path_factory.mktemp("plugin") / "noise_host")
-    src = os.path.join(ROOT, "tests", "plugin", "noise_host.cpp")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "rendering-fw_amd", "csrc", "plugin"), src, "-o", exe, "-L" + lib_dir, "-lrfwhip",
-                        "-Wl,-rpath," + lib_dir, "-ldl"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout
-    return exe, lib_dir
+    return build_host(pkg, tmp_path_factory, "noise_host")
 
 
 @pytest.mark.parametrize("on", [1, 0])
 def test_plugin_reports_the_noise(plugin_host, on):
     """HipRT.so behind the stand-in for rfw::system (tests/plugin/noise_host.cpp): with RFWHIP_NOISE=1 hiprtGetNoise refuses after
     the first sample and then answers with the C ABI's record of the same frames, byte for byte; without the variable it refuses."""
-    exe, lib_dir = plugin_host
-    assert os.path.exists(os.path.join(lib_dir, "HipRT.so")), "run __graft_entry__.build() first"
-    env = {k: v for k, v in os.environ.items() if k != "RFWHIP_NOISE"}
-    if on:
-        env["RFWHIP_NOISE"] = "1"
-    r = subprocess.run([exe, lib_dir], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, env=env)
+    r = run_host(plugin_host, drop=("RFWHIP_NOISE",), **({"RFWHIP_NOISE": "1"} if on else {}))
     assert r.returncode == 0, (r.stdout, r.stderr)
     out = dict(line.split(" ", 1) for line in r.stdout.strip().splitlines())
     state_error = "4"  # RFWHIP_ERR_STATE
