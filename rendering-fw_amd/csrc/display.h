@@ -59,6 +59,8 @@ RT_FN f3 dp_tone(const DisplayView &d, const f4 &in)
 	return mk3(dp_clamp01(1.60475f * ir - 0.53108f * ig - 0.07367f * ib), dp_clamp01(-0.10208f * ir + 1.10813f * ig - 0.00605f * ib),
 			   dp_clamp01(-0.00327f * ir - 0.07276f * ig + 1.07602f * ib));
 }
+// the exposed display (metering.h): every colour channel times E in front of dp_tone, alpha untouched
+RT_FN f4 dp_exposed(const f4 &c, float E) { return mk4(c.x * E, c.y * E, c.z * E, c.w); }
 
 // a bilinear tap at c + (ox, oy), c the centre of pixel (x, y); fetch(xi, yi) = the tone-mapped texel, 0 <= xi < W, 0 <= yi < H.
 // u = q - 0.5 = x + ox: floor and fraction are taken of the OFFSET, so the weights keep the offset's precision at any x (the sum
@@ -77,9 +79,8 @@ template <typename Fetch> RT_FN f3 dp_tap(const Fetch &fetch, int W, int H, int 
 
 RT_FN float dp_srgb(float c) { return c < 0.0031308f ? 12.92f * c : 1.055f * powf(c, 1.0f / 2.4f) - 0.055f; }
 
-// steps 2 - 4 for pixel (x, y): FXAA over `fetch` (or the texel itself), the encoding, and the store in the view's format.
-// alpha: the pixel's own in.w, unclamped.
-template <bool FXAA, typename Fetch> RT_FN void dp_item(const DisplayView &d, const Fetch &fetch, int x, int y, float alpha)
+// steps 2 - 3 for pixel (x, y): FXAA over `fetch` (or the texel itself) and the encoding — the colour that a store quantises
+template <bool FXAA, typename Fetch> RT_FN f3 dp_encoded(const DisplayView &d, const Fetch &fetch, int x, int y)
 {
 	const int W = (int)d.W, H = (int)d.H;
 	f3 out = fetch(x, y);
@@ -103,6 +104,12 @@ template <bool FXAA, typename Fetch> RT_FN void dp_item(const DisplayView &d, co
 	}
 	if (d.srgb)
 		out = mk3(dp_srgb(out.x), dp_srgb(out.y), dp_srgb(out.z));
+	return out;
+}
+// steps 2 - 4 for pixel (x, y): dp_encoded and the store in the view's format.  alpha: the pixel's own in.w, unclamped.
+template <bool FXAA, typename Fetch> RT_FN void dp_item(const DisplayView &d, const Fetch &fetch, int x, int y, float alpha)
+{
+	const f3 out = dp_encoded<FXAA>(d, fetch, x, y);
 	const float a = dp_clamp01(alpha);
 	const size_t i = (size_t)y * d.W + (size_t)x;
 	if (d.format == 0u) // RFWHIP_DISPLAY_RGBA8

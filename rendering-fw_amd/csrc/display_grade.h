@@ -17,7 +17,7 @@
 //          in channel order r, g, b; V0 = L[i], V1 = one step along axis a, V2 = one further step along b, V3 = L[i + (1, 1, 1)];
 //          w = (1 - f_a, f_a - f_b, f_b - f_c, f_c);  out = fmaf(w3, V3, fmaf(w2, V2, fmaf(w1, V1, w0 V0)))
 //          L: n^3 float4 (r, g, b, 0), red fastest — one 16-byte load per vertex, the four fetched before the arithmetic
-//   FXAA, ENCODE: display.h's, restated in dg_item, on the graded values
+//   FXAA, ENCODE: display.h's dp_encoded, on the graded values
 //   DITHER (RGBA8, GR_DITHER): byte = clamp(rint(255 v + d(x, y) - 0.5), 0, 255) for r, g, b, EVALUATED EXACTLY (dg_byte: the
 //          product's rounding error is carried along, so a threshold is never decided by a rounding of 255 v + d); alpha as without.
 //          d(x, y) = (B + 0.5) / 256, B = the 16 x 16 Bayer index of (x & 15, y & 15): with q = x ^ y, bit b (0 .. 3) of q is bit
@@ -100,18 +100,17 @@ RT_FN f3 dg_tetra(const GradeView &g, f3 v)
 // one texel up to the LDS tile: exposure, the LINEAR block, the tone map, the LUT.  With flags = 0 this is dp_tone(v, in)
 // (the three routes in front of dp_tone are written out, each the expression of the kernel it stands for — k_display's, k_display_exposed's
 // — so that the compiler contracts x E + offset here where it does there)
-RT_FN f4 dg_exposed(const f4 &c, float E) { return mk4(c.x * E, c.y * E, c.z * E, c.w); }
 RT_FN f3 dg_texel(const DisplayView &v, const GradeView &g, const f4 &in, float E)
 {
 	f3 t;
 	if (g.flags & GR_LINEAR)
 	{
-		const f4 x = (g.flags & GR_EXPOSED) ? dg_exposed(in, E) : in;
+		const f4 x = (g.flags & GR_EXPOSED) ? dp_exposed(in, E) : in;
 		const f3 c = dg_linear(g, mk3(x.x, x.y, x.z));
 		t = dp_tone(v, mk4(c.x, c.y, c.z, in.w));
 	}
 	else if (g.flags & GR_EXPOSED)
-		t = dp_tone(v, dg_exposed(in, E));
+		t = dp_tone(v, dp_exposed(in, E));
 	else
 		t = dp_tone(v, in);
 	// (a LUT may hold entries outside [0, 1] — looks with overshoot are ordinary .cube files: what leaves this step keeps dp_tone's
@@ -149,32 +148,11 @@ RT_FN uint32_t dg_byte(float v, uint32_t B)
 	return (uint32_t)(byte < 0 ? 0 : (byte > 255 ? 255 : byte));
 }
 
-// display.h's dp_item with the dithered store: FXAA over `fetch` (or the texel itself), the encoding, and the store in the view's
-// format.  Restated here: dp_item and the kernels built from it keep their code.  alpha: the pixel's own in.w, unclamped.
+// display.h's dp_item with the dithered store: dp_encoded on the graded values, and the store in the view's format.
+// alpha: the pixel's own in.w, unclamped.
 template <bool FXAA, typename Fetch> RT_FN void dg_item(const DisplayView &d, const GradeView &g, const Fetch &fetch, int x, int y, float alpha)
 {
-	const int W = (int)d.W, H = (int)d.H;
-	f3 out = fetch(x, y);
-	if (FXAA)
-	{
-		const float nw = dp_luma(dp_tap(fetch, W, H, x, y, -0.75f, -0.75f)), ne = dp_luma(dp_tap(fetch, W, H, x, y, 0.25f, -0.75f)),
-					sw = dp_luma(dp_tap(fetch, W, H, x, y, -0.75f, 0.25f)), se = dp_luma(dp_tap(fetch, W, H, x, y, 0.25f, 0.25f)),
-					m = dp_luma(out);
-		const float lmin = fminf(m, fminf(fminf(nw, ne), fminf(sw, se))), lmax = fmaxf(m, fmaxf(fmaxf(nw, ne), fmaxf(sw, se)));
-		float dx = -((nw + ne) - (sw + se)), dy = (nw + sw) - (ne + se);
-		const float reduce = fmaxf((nw + ne + sw + se) * (0.25f / 8.0f), 1.0f / 64.0f);
-		const float rcp = 1.0f / (fminf(fabsf(dx), fabsf(dy)) + reduce);
-		dx = fminf(fmaxf(dx * rcp, -(float)DP_SPAN), (float)DP_SPAN), dy = fminf(fmaxf(dy * rcp, -(float)DP_SPAN), (float)DP_SPAN);
-		const float ax = dx * (1.0f / 6.0f), ay = dy * (1.0f / 6.0f), bx = dx * 0.5f, by = dy * 0.5f;
-		const f3 a0 = dp_tap(fetch, W, H, x, y, -ax, -ay), a1 = dp_tap(fetch, W, H, x, y, ax, ay);
-		const f3 b0 = dp_tap(fetch, W, H, x, y, -bx, -by), b1 = dp_tap(fetch, W, H, x, y, bx, by);
-		const f3 A = mk3(0.5f * (a0.x + a1.x), 0.5f * (a0.y + a1.y), 0.5f * (a0.z + a1.z));
-		const f3 B = mk3(0.5f * A.x + 0.25f * (b0.x + b1.x), 0.5f * A.y + 0.25f * (b0.y + b1.y), 0.5f * A.z + 0.25f * (b0.z + b1.z));
-		const float lb = dp_luma(B);
-		out = (lb < lmin || lb > lmax) ? A : B;
-	}
-	if (d.srgb)
-		out = mk3(dp_srgb(out.x), dp_srgb(out.y), dp_srgb(out.z));
+	const f3 out = dp_encoded<FXAA>(d, fetch, x, y);
 	const float a = dp_clamp01(alpha);
 	const size_t i = (size_t)y * d.W + (size_t)x;
 	if (d.format == 0u) // RFWHIP_DISPLAY_RGBA8

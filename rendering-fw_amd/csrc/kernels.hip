@@ -2585,7 +2585,8 @@ void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, in
 // and every store is one contiguous 256-byte (RGBA8) / 1 KiB (RGBA32F) run per wave.  k_display<false>: pointwise, no LDS. ----
 static_assert(BLOCK == 4 * DP_TILE_X && DP_TILE_Y % 4 == 0, "display workgroup = 4 waves, each a 64-pixel row segment at a time");
 static_assert(3 * DP_LDS_H * DP_PITCH * sizeof(float) <= 64 * 1024, "display tile in LDS");
-template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const DisplayView v)
+// texel(f4) -> f3: what goes into the tile (or, pointwise, into the item); item(fetch, x, y, alpha): what runs behind it
+template <bool FXAA, class Texel, class Item> __device__ __forceinline__ void display_body(const DisplayView &v, const Texel &texel, const Item &item)
 {
 	if constexpr (!FXAA)
 	{
@@ -2593,8 +2594,8 @@ template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const Di
 		if (i >= (size_t)v.W * v.H)
 			return;
 		const f4 c = v.in[i];
-		const f3 t = dp_tone(v, c);
-		dp_item<false>(v, [&](int, int) -> f3 { return t; }, (int)(i % v.W), (int)(i / v.W), c.w);
+		const f3 t = texel(c);
+		item([&](int, int) -> f3 { return t; }, (int)(i % v.W), (int)(i / v.W), c.w);
 	}
 	else
 	{
@@ -2606,7 +2607,7 @@ template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const Di
 			const int ly = k / DP_LDS_W, lx = k - ly * DP_LDS_W, gx = x0 + lx, gy = y0 + ly;
 			if (gx >= 0 && gx < W && gy >= 0 && gy < H) // (texels outside the image are never fetched: the taps clamp to the edge first)
 			{
-				const f3 t = dp_tone(v, v.in[(size_t)gy * v.W + (size_t)gx]);
+				const f3 t = texel(v.in[(size_t)gy * v.W + (size_t)gx]);
 				const int o = ly * DP_PITCH + lx;
 				s_rgb[0][o] = t.x, s_rgb[1][o] = t.y, s_rgb[2][o] = t.z;
 			}
@@ -2622,54 +2623,24 @@ template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const Di
 		if (x < W)
 			for (int r = 0; r < DP_TILE_Y / 4; r++)
 				if (yw + r < H)
-					dp_item<true>(v, fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
+					item(fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
 	}
 }
-// k_display_exposed (metering.h): k_display with every colour channel of a texel times E in front of dp_tone.  A kernel of its own,
-// its body restated: k_display keeps its code to the instruction.  (display_grade.h's dg_exposed / dg_texel restate this expression,
-// dp_tone(v, dp_exposed(c, E)), so that the compiler contracts x E + offset there as it does here: the defaults of display_grade = 1
-// are bit for bit this kernel's output, which tests/test_display_grade_gpu.py asserts.  Change the two together.)
-RT_FN f4 dp_exposed(const f4 &c, float E) { return mk4(c.x * E, c.y * E, c.z * E, c.w); }
+template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display(const DisplayView v)
+{
+	display_body<FXAA>(
+		v, [&](const f4 &c) -> f3 { return dp_tone(v, c); },
+		[&](const auto &fetch, int x, int y, float alpha) { dp_item<FXAA>(v, fetch, x, y, alpha); });
+}
+// k_display_exposed (metering.h): every colour channel of a texel times E in front of dp_tone.  (display_grade.h's dg_texel writes
+// this expression, dp_tone(v, dp_exposed(c, E)), out as one of its routes, so that the compiler contracts x E + offset there as it
+// does here: the defaults of display_grade = 1 are bit for bit this kernel's output, which tests/test_display_grade_gpu.py asserts.)
 template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display_exposed(const DisplayView v, const ExposureView e)
 {
 	const float E = e.rec->E; // (a uniform address: one scalar load)
-	if constexpr (!FXAA)
-	{
-		const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-		if (i >= (size_t)v.W * v.H)
-			return;
-		const f4 c = v.in[i];
-		const f3 t = dp_tone(v, dp_exposed(c, E));
-		dp_item<false>(v, [&](int, int) -> f3 { return t; }, (int)(i % v.W), (int)(i / v.W), c.w);
-	}
-	else
-	{
-		__shared__ float s_rgb[3][DP_LDS_H * DP_PITCH];
-		const int W = (int)v.W, H = (int)v.H;
-		const int x0 = (int)blockIdx.x * DP_TILE_X - DP_HALO, y0 = (int)blockIdx.y * DP_TILE_Y - DP_HALO;
-		for (int k = (int)threadIdx.x; k < DP_LDS_W * DP_LDS_H; k += BLOCK)
-		{
-			const int ly = k / DP_LDS_W, lx = k - ly * DP_LDS_W, gx = x0 + lx, gy = y0 + ly;
-			if (gx >= 0 && gx < W && gy >= 0 && gy < H) // (texels outside the image are never fetched: the taps clamp to the edge first)
-			{
-				const f3 t = dp_tone(v, dp_exposed(v.in[(size_t)gy * v.W + (size_t)gx], E));
-				const int o = ly * DP_PITCH + lx;
-				s_rgb[0][o] = t.x, s_rgb[1][o] = t.y, s_rgb[2][o] = t.z;
-			}
-		}
-		__syncthreads();
-		// (xi, yi) is inside the image and within DP_HALO of a pixel of this tile: inside the LDS tile
-		const auto fetch = [&](int xi, int yi) -> f3 {
-			const int o = (yi - y0) * DP_PITCH + (xi - x0);
-			return mk3(s_rgb[0][o], s_rgb[1][o], s_rgb[2][o]);
-		};
-		const int x = (int)blockIdx.x * DP_TILE_X + (int)(threadIdx.x & 63u);
-		const int yw = (int)blockIdx.y * DP_TILE_Y + (int)(threadIdx.x >> 6) * (DP_TILE_Y / 4);
-		if (x < W)
-			for (int r = 0; r < DP_TILE_Y / 4; r++)
-				if (yw + r < H)
-					dp_item<true>(v, fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
-	}
+	display_body<FXAA>(
+		v, [&](const f4 &c) -> f3 { return dp_tone(v, dp_exposed(c, E)); },
+		[&](const auto &fetch, int x, int y, float alpha) { dp_item<FXAA>(v, fetch, x, y, alpha); });
 }
 void launch_display(const DisplayView &v, stream_t s)
 {
@@ -2926,13 +2897,11 @@ __global__ void k_noise_merge(const float *samples_rgb, float *moments, uint32_t
 	if (i < pixels)
 		nz_merge_item(samples_rgb, moments, n_a, S, i);
 }
-__global__ void __launch_bounds__(BLOCK) k_noise_tiles(const NoiseView v)
+// the tile's record from its pixels: e the pixel's error, real whether the pixel exists
+__device__ __forceinline__ void noise_tile_reduce(const NoiseView &v, float e, bool real)
 {
 	__shared__ float s_sum[BLOCK / 64], s_max[BLOCK / 64];
 	__shared__ uint32_t s_pix[BLOCK / 64], s_conv[BLOCK / 64];
-	const uint32_t x = blockIdx.x * NZ_TILE_X + (threadIdx.x & (NZ_TILE_X - 1u)), yl = blockIdx.y * NZ_TILE_Y + threadIdx.x / NZ_TILE_X;
-	float e;
-	const bool real = nz_pixel_item(v, x, yl, e);
 	float sum = e, mx = e;
 	for (int m = 32; m >= 1; m >>= 1)
 		sum += __shfl_xor(sum, m, 64), mx = fmaxf(mx, __shfl_xor(mx, m, 64));
@@ -2949,6 +2918,13 @@ __global__ void __launch_bounds__(BLOCK) k_noise_tiles(const NoiseView v)
 		t.sum_e = fminf(t.sum_e, FLT_MAX);
 		v.tiles[blockIdx.y * gridDim.x + blockIdx.x] = t;
 	}
+}
+__global__ void __launch_bounds__(BLOCK) k_noise_tiles(const NoiseView v)
+{
+	const uint32_t x = blockIdx.x * NZ_TILE_X + (threadIdx.x & (NZ_TILE_X - 1u)), yl = blockIdx.y * NZ_TILE_Y + threadIdx.x / NZ_TILE_X;
+	float e;
+	const bool real = nz_pixel_item(v, x, yl, e);
+	noise_tile_reduce(v, e, real);
 }
 __global__ void __launch_bounds__(BLOCK) k_noise_final(const NoiseView v, uint32_t count)
 {
@@ -2993,33 +2969,13 @@ __global__ void __launch_bounds__(BLOCK) k_present_adaptive(const Params p, f4 *
 	for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
 		present_adaptive_item(p, out, a, full, i);
 }
-// k_noise_tiles with n per tile.  Its reduction is k_noise_tiles', line for line, and a change to one is a change to both.  It is a
-// copy because sharing it changes the code k_noise_tiles compiles to: with the reduction in one __forceinline__ function that both
-// kernels call, four v_add_u32 of k_noise_tiles' last fold come out with their operands exchanged (tools/dev/isa_same.py --labels:
-// 1 differs) — the same numbers, not the same code, and the kernels that exist stay instruction for instruction what they are
+// k_noise_tiles with n per tile
 __global__ void __launch_bounds__(BLOCK) k_noise_tiles_adaptive(const NoiseView v, const uint32_t *n_tile)
 {
-	__shared__ float s_sum[BLOCK / 64], s_max[BLOCK / 64];
-	__shared__ uint32_t s_pix[BLOCK / 64], s_conv[BLOCK / 64];
 	const uint32_t x = blockIdx.x * NZ_TILE_X + (threadIdx.x & (NZ_TILE_X - 1u)), yl = blockIdx.y * NZ_TILE_Y + threadIdx.x / NZ_TILE_X;
 	float e;
 	const bool real = ad_noise_pixel_item(v, n_tile, x, yl, e);
-	float sum = e, mx = e;
-	for (int m = 32; m >= 1; m >>= 1)
-		sum += __shfl_xor(sum, m, 64), mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-	const uint32_t pix = (uint32_t)__popcll(__ballot(real)), conv = (uint32_t)__popcll(__ballot(real && e <= v.threshold));
-	const uint32_t wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63u) == 0u)
-		s_sum[wave] = sum, s_max[wave] = mx, s_pix[wave] = pix, s_conv[wave] = conv;
-	__syncthreads();
-	if (threadIdx.x == 0u)
-	{
-		NoiseTile t = {0.0f, 0.0f, 0u, 0u};
-		for (uint32_t w = 0; w < BLOCK / 64; w++)
-			t.sum_e += s_sum[w], t.max_e = fmaxf(t.max_e, s_max[w]), t.pixels += s_pix[w], t.converged += s_conv[w];
-		t.sum_e = fminf(t.sum_e, FLT_MAX);
-		v.tiles[blockIdx.y * gridDim.x + blockIdx.x] = t;
-	}
+	noise_tile_reduce(v, e, real);
 }
 __global__ void k_adaptive_step(const AdaptiveView a, uint32_t add, int decide)
 {
@@ -3138,50 +3094,15 @@ void launch_light_tree_refit(LightTreeNode *nodes, const LightTreeLevels &lv, co
 		hipLaunchKernelGGL(k_lt_refit_top, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nodes, lv, top, area, n_area, bound, touched);
 }
 
-// ---- colour grading and dither (display_grade.h).  k_display_graded: k_display_exposed with dg_texel in place of dp_tone in front of
-// the LDS tile — the tile and its halo hold graded texels — and dg_item behind it.  A kernel of its own, its body restated: k_display
-// and k_display_exposed keep their code to the instruction.  The same tiling, the same contiguous run per wave and store; the LUT's
-// four vertices of a texel are four independent 16-byte loads from a table that stays in L2. ----
+// ---- colour grading and dither (display_grade.h).  k_display_graded: the display kernel's body with dg_texel in front of the LDS
+// tile — the tile and its halo hold graded texels — and dg_item behind it.  The same tiling, the same contiguous run per wave and
+// store; the LUT's four vertices of a texel are four independent 16-byte loads from a table that stays in L2. ----
 template <bool FXAA> __global__ void __launch_bounds__(BLOCK) k_display_graded(const DisplayView v, const GradeView g)
 {
 	const float E = (g.flags & GR_EXPOSED) ? g.rec->E : 1.0f; // (a uniform address: one scalar load)
-	if constexpr (!FXAA)
-	{
-		const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-		if (i >= (size_t)v.W * v.H)
-			return;
-		const f4 c = v.in[i];
-		const f3 t = dg_texel(v, g, c, E);
-		dg_item<false>(v, g, [&](int, int) -> f3 { return t; }, (int)(i % v.W), (int)(i / v.W), c.w);
-	}
-	else
-	{
-		__shared__ float s_rgb[3][DP_LDS_H * DP_PITCH];
-		const int W = (int)v.W, H = (int)v.H;
-		const int x0 = (int)blockIdx.x * DP_TILE_X - DP_HALO, y0 = (int)blockIdx.y * DP_TILE_Y - DP_HALO;
-		for (int k = (int)threadIdx.x; k < DP_LDS_W * DP_LDS_H; k += BLOCK)
-		{
-			const int ly = k / DP_LDS_W, lx = k - ly * DP_LDS_W, gx = x0 + lx, gy = y0 + ly;
-			if (gx >= 0 && gx < W && gy >= 0 && gy < H) // (texels outside the image are never fetched: the taps clamp to the edge first)
-			{
-				const f3 t = dg_texel(v, g, v.in[(size_t)gy * v.W + (size_t)gx], E);
-				const int o = ly * DP_PITCH + lx;
-				s_rgb[0][o] = t.x, s_rgb[1][o] = t.y, s_rgb[2][o] = t.z;
-			}
-		}
-		__syncthreads();
-		// (xi, yi) is inside the image and within DP_HALO of a pixel of this tile: inside the LDS tile
-		const auto fetch = [&](int xi, int yi) -> f3 {
-			const int o = (yi - y0) * DP_PITCH + (xi - x0);
-			return mk3(s_rgb[0][o], s_rgb[1][o], s_rgb[2][o]);
-		};
-		const int x = (int)blockIdx.x * DP_TILE_X + (int)(threadIdx.x & 63u);
-		const int yw = (int)blockIdx.y * DP_TILE_Y + (int)(threadIdx.x >> 6) * (DP_TILE_Y / 4);
-		if (x < W)
-			for (int r = 0; r < DP_TILE_Y / 4; r++)
-				if (yw + r < H)
-					dg_item<true>(v, g, fetch, x, yw + r, v.in[(size_t)(yw + r) * v.W + (size_t)x].w);
-	}
+	display_body<FXAA>(
+		v, [&](const f4 &c) -> f3 { return dg_texel(v, g, c, E); },
+		[&](const auto &fetch, int x, int y, float alpha) { dg_item<FXAA>(v, g, fetch, x, y, alpha); });
 }
 // rfwhip_grade_colors: one lane per colour
 __global__ void __launch_bounds__(BLOCK) k_kat_grade(const GradeView g, int which, const float *in, float *out, uint32_t n)

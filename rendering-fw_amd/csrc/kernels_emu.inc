@@ -482,10 +482,9 @@ void launch_noise_merge(const float *samples_rgb, float *moments, uint32_t pixel
 	for (uint32_t i = 0; i < pixels; i++)
 		nz_merge_item(samples_rgb, moments, n_a, S, i);
 }
-void launch_noise_metric(const NoiseView &v, stream_t s)
+// a tile's pixels in row-major order, the tiles in index order; pixel(x, yl, e) = the kernel's pixel item
+template <class Pixel> static void noise_tiles_loop(const NoiseView &v, bool final, const Pixel &pixel)
 {
-	EMU_DEFER(s, launch_noise_metric(v, s));
-	// a tile's pixels in row-major order, the tiles in index order
 	const uint32_t tx = noise_tiles_x(v.W), ty = v.local_rows / NZ_TILE_Y;
 	for (uint32_t k = 0; k < tx * ty; k++)
 	{
@@ -493,13 +492,19 @@ void launch_noise_metric(const NoiseView &v, stream_t s)
 		for (uint32_t j = 0; j < NZ_TILE_X * NZ_TILE_Y; j++)
 		{
 			float e;
-			if (nz_pixel_item(v, (k % tx) * NZ_TILE_X + j % NZ_TILE_X, (k / tx) * NZ_TILE_Y + j / NZ_TILE_X, e))
+			if (pixel((k % tx) * NZ_TILE_X + j % NZ_TILE_X, (k / tx) * NZ_TILE_Y + j / NZ_TILE_X, e))
 				t.sum_e += e, t.max_e = fmaxf(t.max_e, e), t.pixels++, t.converged += e <= v.threshold;
 		}
 		t.sum_e = fminf(t.sum_e, FLT_MAX);
 		v.tiles[k] = t;
 	}
-	nz_fold(v.tiles, tx * ty, 0u, 1u, *v.total);
+	if (final)
+		nz_fold(v.tiles, tx * ty, 0u, 1u, *v.total);
+}
+void launch_noise_metric(const NoiseView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_noise_metric(v, s));
+	noise_tiles_loop(v, true, [&](uint32_t x, uint32_t yl, float &e) { return nz_pixel_item(v, x, yl, e); });
 }
 void launch_resolve_adaptive(const Params &p, float *moments, const AdaptiveView &a, stream_t s)
 {
@@ -516,22 +521,7 @@ void launch_present_adaptive(const Params &p, f4 *out, const AdaptiveView &a, in
 void launch_noise_metric_adaptive(const NoiseView &v, const uint32_t *n_tile, bool final, stream_t s)
 {
 	EMU_DEFER(s, launch_noise_metric_adaptive(v, n_tile, final, s));
-	// (launch_noise_metric's loops with n per tile)
-	const uint32_t tx = noise_tiles_x(v.W), ty = v.local_rows / NZ_TILE_Y;
-	for (uint32_t k = 0; k < tx * ty; k++)
-	{
-		NoiseTile t = {0.0f, 0.0f, 0u, 0u};
-		for (uint32_t j = 0; j < NZ_TILE_X * NZ_TILE_Y; j++)
-		{
-			float e;
-			if (ad_noise_pixel_item(v, n_tile, (k % tx) * NZ_TILE_X + j % NZ_TILE_X, (k / tx) * NZ_TILE_Y + j / NZ_TILE_X, e))
-				t.sum_e += e, t.max_e = fmaxf(t.max_e, e), t.pixels++, t.converged += e <= v.threshold;
-		}
-		t.sum_e = fminf(t.sum_e, FLT_MAX);
-		v.tiles[k] = t;
-	}
-	if (final)
-		nz_fold(v.tiles, tx * ty, 0u, 1u, *v.total);
+	noise_tiles_loop(v, final, [&](uint32_t x, uint32_t yl, float &e) { return ad_noise_pixel_item(v, n_tile, x, yl, e); });
 }
 void launch_adaptive_connections(WaveCounters *c, uint32_t depth, stream_t s)
 {
@@ -603,54 +593,40 @@ void launch_denoise_filter(const DnView &d, const DnTemporal *t, const DnMotion 
 		for (uint32_t i = 0; i < d.W * d.H; i++)
 			dn_pass_item(d, 1u << k, k + 1u == d.iterations, d.img[k & 1u], d.var[k & 1u], d.img[(k + 1u) & 1u], d.var[(k + 1u) & 1u], i);
 }
-void launch_display(const DisplayView &v, stream_t s)
+// the direct fetch: texel(f4) is evaluated where the texel is read; item(fetch, x, y, alpha) = the kernel's item behind it
+template <class Texel, class Item> static void display_loop(const DisplayView &v, const Texel &texel, const Item &item)
 {
-	EMU_DEFER(s, launch_display(v, s));
-	// the direct fetch: the texel is tone-mapped where it is read
-	const auto fetch = [&](int xi, int yi) -> f3 { return dp_tone(v, v.in[(size_t)yi * v.W + (size_t)xi]); };
+	const auto fetch = [&](int xi, int yi) -> f3 { return texel(v.in[(size_t)yi * v.W + (size_t)xi]); };
 	for (uint32_t y = 0; y < v.H; y++)
 		for (uint32_t x = 0; x < v.W; x++)
 		{
 			const float a = v.in[(size_t)y * v.W + x].w;
-			if (v.fxaa)
-				dp_item<true>(v, fetch, (int)x, (int)y, a);
-			else
-				dp_item<false>(v, fetch, (int)x, (int)y, a);
+			item(fetch, (int)x, (int)y, a);
 		}
+}
+void launch_display(const DisplayView &v, stream_t s)
+{
+	EMU_DEFER(s, launch_display(v, s));
+	display_loop(
+		v, [&](const f4 &c) -> f3 { return dp_tone(v, c); },
+		[&](const auto &fetch, int x, int y, float a) { v.fxaa ? dp_item<true>(v, fetch, x, y, a) : dp_item<false>(v, fetch, x, y, a); });
 }
 void launch_display_exposed(const DisplayView &v, const ExposureView &e, stream_t s)
 {
 	EMU_DEFER(s, launch_display_exposed(v, e, s));
 	const float E = e.rec->E;
-	const auto fetch = [&](int xi, int yi) -> f3 {
-		const f4 c = v.in[(size_t)yi * v.W + (size_t)xi];
-		return dp_tone(v, mk4(c.x * E, c.y * E, c.z * E, c.w));
-	};
-	for (uint32_t y = 0; y < v.H; y++)
-		for (uint32_t x = 0; x < v.W; x++)
-		{
-			const float a = v.in[(size_t)y * v.W + x].w;
-			if (v.fxaa)
-				dp_item<true>(v, fetch, (int)x, (int)y, a);
-			else
-				dp_item<false>(v, fetch, (int)x, (int)y, a);
-		}
+	display_loop(
+		v, [&](const f4 &c) -> f3 { return dp_tone(v, dp_exposed(c, E)); },
+		[&](const auto &fetch, int x, int y, float a) { v.fxaa ? dp_item<true>(v, fetch, x, y, a) : dp_item<false>(v, fetch, x, y, a); });
 }
-// colour grading and dither (display_grade.h): the graded texel where it is read, the same item behind it
+// colour grading and dither (display_grade.h): the graded texel where it is read, dg_item behind it
 void launch_display_graded(const DisplayView &v, const GradeView &g, stream_t s)
 {
 	EMU_DEFER(s, launch_display_graded(v, g, s));
 	const float E = (g.flags & GR_EXPOSED) ? g.rec->E : 1.0f;
-	const auto fetch = [&](int xi, int yi) -> f3 { return dg_texel(v, g, v.in[(size_t)yi * v.W + (size_t)xi], E); };
-	for (uint32_t y = 0; y < v.H; y++)
-		for (uint32_t x = 0; x < v.W; x++)
-		{
-			const float a = v.in[(size_t)y * v.W + x].w;
-			if (v.fxaa)
-				dg_item<true>(v, g, fetch, (int)x, (int)y, a);
-			else
-				dg_item<false>(v, g, fetch, (int)x, (int)y, a);
-		}
+	display_loop(
+		v, [&](const f4 &c) -> f3 { return dg_texel(v, g, c, E); },
+		[&](const auto &fetch, int x, int y, float a) { v.fxaa ? dg_item<true>(v, g, fetch, x, y, a) : dg_item<false>(v, g, fetch, x, y, a); });
 }
 void launch_kat_grade(const GradeView &g, int which, const float *in, float *out, uint32_t n, stream_t s)
 {
