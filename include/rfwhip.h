@@ -106,6 +106,42 @@ RFWHIP_API int rfwhip_set_mesh_morph(rfwhip_context *ctx, size_t mesh_index, con
 									 const float *target_positions4, const float *target_normals4, size_t target_count,
 									 size_t vertex_count);
 RFWHIP_API int rfwhip_morph_mesh(rfwhip_context *ctx, size_t mesh_index, const float *weights, size_t weight_count);
+/* ---- animations on the device (extension: SceneAnimation::setTime, geometry/gltf/animation.cpp:231-322, 374-422, and the node
+ * hierarchy, node.cpp:54-116, run on the host in the reference).  The two pairs of calls above took the vertices out of the host's
+ * animation loop; these take the pose out of it: a host hands over a TIME, the device samples the keyframes, multiplies the
+ * hierarchy, and writes the joint matrices and morph weights that the skinning and morph kernels read (csrc/animation.h, kernel
+ * family 18).
+ * set_rig: the flat tables of rfwhip_rig (rfwhip_abi.h) become rig `rig_index`.  Everything is validated on the host before a byte
+ *   goes to the device; a refused rig leaves a message that names the node, skin or channel, and the previous rig of that index
+ *   stays in place with its bindings.  Refused: an index or offset out of range, a parent cycle, key_count 0, a key time that is not
+ *   finite or not greater than its predecessor, a value range whose length is not path x method x key_count, a weights channel on a
+ *   node without weights, a skin without joints, two channels of one animation on the same node and path.  An accepted rig replaces
+ *   the previous one of its index and drops that one's bindings.
+ * bind_rig: mesh `mesh_index` follows the rig: a mesh with rfwhip_set_mesh_skin takes the joint matrices of skin `skin_index`
+ *   (refused when the mesh refers to a joint the skin does not have), a mesh with rfwhip_set_mesh_morph the weights of node
+ *   `node_index` (refused unless the node has as many weights as the mesh has targets).  Several meshes may follow one rig; a mesh
+ *   follows at most one, binding it again replaces the binding.
+ * animate: every listed rig is evaluated at its own time in ONE launch (a workgroup per rig), then every mesh bound to a listed rig
+ *   is posed or morphed and refitted as by rfwhip_pose_mesh / rfwhip_morph_mesh — the same kernels, reading the rig's buffers — with
+ *   the same ordering and the same bookkeeping: lights_follow_geometry and denoise_motion see an animated mesh as they see a posed
+ *   one.  animations[i] == RFWHIP_RIG_BASE_POSE, or a rig without animations: the base pose.  A rig listed twice, a time that is not
+ *   finite and a bound mesh that is not resident are refused before anything runs.  Per rig, 12 bytes travel to the device and none
+ *   come back.  rfwhip_update() afterwards.
+ *   The rule (all float32, every product and sum of a fixed shape, csrc/animation.h): per channel time = fmodf(time, last key) when
+ *   time > last key > 0; the segment k = #{j in [1, n-2]: time > t_j}; f = (time - t_k) / (t_k+1 - t_k); one key or f <= 0: the first
+ *   key's value; STEP key k, LINEAR (1 - f) a + f b, CUBICSPLINE the Hermite form with tangents scaled by t_k+1 - t_k; rotations per
+ *   component, then normalised (no slerp); local = T R S M, world = world[parent] local, joint = inverse(world[mesh node])
+ *   world[joint] inverseBind with the affine closed-form inverse.  A sampled rotation of zero norm and a mesh node of zero
+ *   determinant give the identity and are counted in the status record.
+ * read_rig: values of the last evaluation of the rig into out[0 .. cap) floats: RFWHIP_RIG_READ_TRS 10 per node (translation,
+ *   rotation xyzw, scale), _WORLD 16 per node (column-major), _JOINTS the joint matrices of skin `index` (16 per joint, column-major),
+ *   _WEIGHTS the weights of node `index`, _STATUS the 8 words of rfwhip_rig_status.  For tests, and for hosts that move INSTANCES by
+ *   node animation: the top-level tree is built on the host, so such a host reads the node's world matrix and calls
+ *   rfwhip_set_instance as before. */
+RFWHIP_API int rfwhip_set_rig(rfwhip_context *ctx, size_t rig_index, const rfwhip_rig *rig);
+RFWHIP_API int rfwhip_bind_rig(rfwhip_context *ctx, size_t rig_index, size_t skin_index, size_t node_index, size_t mesh_index);
+RFWHIP_API int rfwhip_animate(rfwhip_context *ctx, const uint32_t *rigs, const uint32_t *animations, const float *times, size_t count);
+RFWHIP_API int rfwhip_read_rig(rfwhip_context *ctx, size_t rig_index, int what, size_t index, float *out, size_t cap);
 /* update(): once after a batch of set_* — builds the TLAS, uploads descriptors              context.h:108 */
 RFWHIP_API int rfwhip_update(rfwhip_context *ctx);
 
@@ -703,6 +739,11 @@ RFWHIP_API int rfwhip_group_set_display_lut(rfwhip_group *group, const float *rg
 RFWHIP_API int rfwhip_group_set_texture_sources(rfwhip_group *group, const rfwhip_texture_source *sources, size_t count);
 /* rfwhip_set_sky_hdr on every member: each decodes its own replica of the sky on its own device; a refused file is refused by all. */
 RFWHIP_API int rfwhip_group_set_sky_hdr(rfwhip_group *group, const void *data, size_t bytes, uint32_t flags);
+/* rfwhip_set_rig / rfwhip_bind_rig / rfwhip_animate on every member: each evaluates its own copy of the rig on its own device, as
+ * rfwhip_group_update does for the scene; nothing crosses the gather.  A refused rig or call is refused by all. */
+RFWHIP_API int rfwhip_group_set_rig(rfwhip_group *group, size_t rig_index, const rfwhip_rig *rig);
+RFWHIP_API int rfwhip_group_bind_rig(rfwhip_group *group, size_t rig_index, size_t skin_index, size_t node_index, size_t mesh_index);
+RFWHIP_API int rfwhip_group_animate(rfwhip_group *group, const uint32_t *rigs, const uint32_t *animations, const float *times, size_t count);
 RFWHIP_API int rfwhip_group_set_display_lut_cube(rfwhip_group *group, const char *text, size_t len);
 RFWHIP_API int rfwhip_group_read_display(rfwhip_group *group, int format, void *out_host);
 RFWHIP_API int rfwhip_group_present_display_async(rfwhip_group *group, int slot, int format);
@@ -1005,7 +1046,9 @@ RFWHIP_API int rfwhip_get_counters(rfwhip_context *ctx, rfwhip_counters *out, in
  * passes, the up passes and the apply pass).  13 grade: k_display_graded, one launch per displayed image with display_grade = 1 (in
  * place of family 7's).  14 jpeg: the four kernels of a JPEG encode, one count each.  15 the image-texture decoder.  16 the
  * primary wave's entry snapshot pass k_primary_entry (setting primary_entry): one count per pass, with or without stage_timing.  17 the
- * sky's loaders (rfwhip_set_sky_hdr, sky_table = device): one count per launch; by kernel: the setting sky_load_time. */
+ * sky's loaders (rfwhip_set_sky_hdr, sky_table = device): one count per launch; by kernel: the setting sky_load_time.  18 the rig
+ * kernel k_rig_evaluate (rfwhip_animate): one launch per call, however many rigs it lists; the vertex kernels and the refit behind
+ * it count as family 5, as they do for rfwhip_pose_mesh. */
 RFWHIP_API int rfwhip_get_kernel_time(rfwhip_context *ctx, int which, float *ms, uint32_t *launches, int reset);
 
 /* The denoiser's guides of the full image (see "denoise"), for the camera of the last render — the guide pass runs first if they are

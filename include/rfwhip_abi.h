@@ -172,6 +172,96 @@ typedef struct rfwhip_sky_alias
 } rfwhip_sky_alias;
 RFWHIP_STATIC_ASSERT(sizeof(rfwhip_sky_alias) == 8, "rfwhip_sky_alias must be 8 B");
 
+/* A rig: the animation data of a glTF file as flat tables (rfwhip_set_rig, rfwhip.h).  Matrices are 16 floats, column-major, like
+ * rfwhip_set_instance's. */
+enum rfwhip_rig_path
+{
+	RFWHIP_RIG_PATH_TRANSLATION = 0, /* 3 floats per key */
+	RFWHIP_RIG_PATH_ROTATION = 1,	 /* 4: xyzw */
+	RFWHIP_RIG_PATH_SCALE = 2,		 /* 3 */
+	RFWHIP_RIG_PATH_WEIGHTS = 3		 /* the node's weight_count */
+};
+enum rfwhip_rig_method
+{
+	RFWHIP_RIG_METHOD_STEP = 0,
+	RFWHIP_RIG_METHOD_LINEAR = 1,
+	RFWHIP_RIG_METHOD_CUBICSPLINE = 2 /* three times the floats per key: in-tangent, value, out-tangent (weights: per target) */
+};
+enum rfwhip_rig_read
+{
+	RFWHIP_RIG_READ_TRS = 0,
+	RFWHIP_RIG_READ_WORLD = 1,
+	RFWHIP_RIG_READ_JOINTS = 2,
+	RFWHIP_RIG_READ_WEIGHTS = 3,
+	RFWHIP_RIG_READ_STATUS = 4
+};
+#define RFWHIP_RIG_BASE_POSE 0xFFFFFFFFu /* rfwhip_animate: no animation, the base pose */
+typedef struct rfwhip_rig_node
+{
+	int32_t parent; /* -1: a root; nodes may come in any order */
+	float translation[3];
+	float rotation[4]; /* xyzw */
+	float scale[3];
+	uint32_t weight_offset; /* the node's base morph weights: weights[weight_offset .. + weight_count) */
+	float matrix[16];		/* the node's constant matrix: local = T R S matrix */
+	uint32_t weight_count;
+	uint32_t reserved[3];
+} rfwhip_rig_node;
+typedef struct rfwhip_rig_skin
+{
+	uint32_t mesh_node;					/* the node the skinned mesh hangs on */
+	uint32_t joint_offset, joint_count; /* joints[joint_offset .. + joint_count) and the same range of inverse_bind */
+	uint32_t reserved;
+} rfwhip_rig_skin;
+typedef struct rfwhip_rig_animation
+{
+	uint32_t channel_offset, channel_count;
+} rfwhip_rig_animation;
+typedef struct rfwhip_rig_channel
+{
+	uint32_t node, path, method;
+	uint32_t key_count;
+	uint32_t time_offset;				/* times[time_offset .. + key_count): finite, strictly increasing */
+	uint32_t value_offset, value_count; /* values[value_offset .. + value_count), value_count = floats per key x key_count (x 3) */
+	uint32_t reserved;
+} rfwhip_rig_channel;
+typedef struct rfwhip_rig
+{
+	const rfwhip_rig_node *nodes;
+	size_t node_count;
+	const float *weights;
+	size_t weight_count;
+	const rfwhip_rig_skin *skins;
+	size_t skin_count;
+	const uint32_t *joints;	   /* node indices */
+	const float *inverse_bind; /* 16 floats per entry of joints */
+	size_t joint_count;
+	const rfwhip_rig_animation *animations;
+	size_t animation_count;
+	const rfwhip_rig_channel *channels;
+	size_t channel_count;
+	const float *times;
+	size_t time_count;
+	const float *values;
+	size_t value_count;
+} rfwhip_rig;
+/* What an evaluation leaves beside its values (rfwhip_read_rig, RFWHIP_RIG_READ_STATUS). */
+typedef struct rfwhip_rig_status
+{
+	float time;					 /* the given time after the wrap of the animation's first channel; as given for a base pose */
+	uint32_t rotation_fallbacks; /* sampled rotations of zero or non-finite norm, replaced by the identity */
+	uint32_t inverse_fallbacks;	 /* skins whose mesh node had a zero or non-finite determinant, its inverse replaced by the identity */
+	uint32_t serial;			 /* the evaluations of this rig so far */
+	uint32_t animation;			 /* the animation evaluated, RFWHIP_RIG_BASE_POSE for the base pose */
+	uint32_t reserved[3];
+} rfwhip_rig_status;
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_rig_node) == 128, "rfwhip_rig_node must be 128 B");
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_rig_skin) == 16, "rfwhip_rig_skin must be 16 B");
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_rig_animation) == 8, "rfwhip_rig_animation must be 8 B");
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_rig_channel) == 32, "rfwhip_rig_channel must be 32 B");
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_rig) == 136, "rfwhip_rig must be 136 B");
+RFWHIP_STATIC_ASSERT(sizeof(rfwhip_rig_status) == 32, "rfwhip_rig_status must be 32 B");
+
 typedef struct rfwhip_light_count
 {
 	uint32_t areaLightCount, pointLightCount, spotLightCount, directionalLightCount;

@@ -103,6 +103,10 @@ class CoreBinding:
                                   "pose_mesh": (i32, [vp, sz, vp, sz]),
                                   "set_mesh_morph": (i32, [vp, sz, vp, vp, vp, sz, sz]),
                                   "morph_mesh": (i32, [vp, sz, vp, sz]),
+                                  "set_rig": (i32, [vp, sz, C.POINTER(abi.Rig)]),
+                                  "bind_rig": (i32, [vp, sz, sz, sz, sz]),
+                                  "animate": (i32, [vp, vp, vp, vp, sz]),
+                                  "read_rig": (i32, [vp, sz, i32, sz, vp, sz]),
                                   "read_framebuffer_device": (i32, [vp, vp]),
                                   "read_local_framebuffer_stream": (i32, [vp, vp, vp]),
                                   "deinterleave_stream": (i32, [vp, vp, vp, vp]),
@@ -360,6 +364,47 @@ class CoreBinding:
     def morph_mesh(self, index, weights):
         w = _f32(weights).reshape(-1)
         self._check(self._fn("morph_mesh")(self._ctx, int(index), w.ctypes.data, len(w)))
+
+    # ---- animations on the device (include/rfwhip.h, rfwhip_set_rig; rendering_fw_amd.gltf.Gltf.rig packs a file's tables) -------
+    def set_rig(self, index, rig):
+        """rig: the tables of abi.RIG_TABLES by name (a missing one is empty); inverse_bind holds 16 floats, column-major, per joint."""
+        pod, keep = _rig_pod(rig)
+        self._check(self._fn("set_rig")(self._ctx, int(index), C.byref(pod)))
+        if not hasattr(self, "_rigs"):
+            self._rigs = {}
+        self._rigs[int(index)] = (len(keep["nodes"]), keep["skins"]["joint_count"].copy(), keep["nodes"]["weight_count"].copy())
+
+    def bind_rig(self, rig, mesh, skin=0, node=0):
+        """Mesh `mesh` follows rig `rig`: a skinned mesh takes the joint matrices of `skin`, a morphed one the weights of `node`."""
+        self._check(self._fn("bind_rig")(self._ctx, int(rig), int(skin), int(node), int(mesh)))
+
+    def animate(self, rigs, times, animations=0):
+        """Evaluate the listed rigs at their times (one launch), pose / morph and refit every mesh bound to them.  animations: one
+        index for all or one per rig; None or abi.RIG_BASE_POSE: the base pose.  update() afterwards."""
+        r, t, a = _rig_calls(rigs, times, animations)
+        self._check(self._fn("animate")(self._ctx, r.ctypes.data, a.ctypes.data, t.ctypes.data, len(r)))
+
+    def read_rig(self, rig, what, index=0):
+        """Values of the rig's last evaluation: "trs" (N, 10), "world" (N, 4, 4) and "joints" of skin `index` (J, 4, 4) as row-major
+        matrices acting on column vectors (what pose_mesh takes), "weights" of node `index`, "status" a dict."""
+        nodes, joint_counts, weight_counts = self._rigs[int(rig)]
+        n = {"trs": nodes * 10, "world": nodes * 16, "status": 8}.get(what)
+        if what == "joints":
+            n = int(joint_counts[index]) * 16
+        elif what == "weights":
+            n = int(weight_counts[index])
+        out = np.zeros(max(n, 1), np.float32)
+        self._check(self._fn("read_rig")(self._ctx, int(rig), abi.RIG_READ[what], int(index), out.ctypes.data, n))
+        out = out[:n]
+        if what == "trs":
+            return out.reshape(-1, 10)
+        if what in ("world", "joints"):
+            return np.ascontiguousarray(out.reshape(-1, 4, 4).transpose(0, 2, 1))
+        if what == "status":
+            w = out.view(np.uint32)
+            return {"time": float(out[0]), "rotation_fallbacks": int(w[1]), "inverse_fallbacks": int(w[2]), "serial": int(w[3]),
+                    "animation": int(w[4])}
+        return out
 
     def set_blue_noise(self, table):
         """The reference's 5 x 65536-word blue-noise table (createBlueNoiseBuffer()); see scenes.synthetic_blue_noise."""
@@ -807,10 +852,11 @@ class CoreBinding:
     TEXDEC = 15  # ... and of the image-texture decoder (one count per launch of a decode or mip chain)
     PRIMARY_ENTRY = 16  # ... and of the primary wave's entry snapshot pass (one count per rewrite of the records)
     SKY_LOAD = 17  # ... and of the sky's loaders (one count per launch of an HDR decode or of the alias table's chain)
+    RIG = 18  # ... and of the rig kernel (one launch per animate, however many rigs it lists)
 
     def get_kernel_time(self, which, reset=False):
         ms, n = C.c_float(), C.c_uint32()
-        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.TEXDEC if which == "texture_decode" else self.PRIMARY_ENTRY if which == "primary_entry" else self.SKY_LOAD if which == "sky_load" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
+        idx = self.DENOISE if which == "denoise" else self.DISPLAY if which == "display" else self.NOISE if which == "noise" else self.METER_HIST if which == "meter_hist" else self.METER_REDUCE if which == "meter_reduce" else self.PRIMARY_ORDER if which == "primary_order" else self.BLOOM if which == "bloom" else self.GRADE if which == "grade" else self.JPEG if which == "jpeg" else self.TEXDEC if which == "texture_decode" else self.PRIMARY_ENTRY if which == "primary_entry" else self.SKY_LOAD if which == "sky_load" else self.RIG if which == "rig" else self.KERNELS.index(which) if isinstance(which, str) else int(which)
         self._check(self._fn("get_kernel_time")(self._ctx, idx, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
@@ -937,6 +983,27 @@ def _read_file(path):
         return f.read()
 
 
+def _rig_pod(rig):
+    """abi.Rig over contiguous copies of a rig's tables -> (pod, the arrays it points into)."""
+    keep = {name: np.ascontiguousarray(rig.get(name, ()), dtype=dt).reshape(-1) for name, dt in abi.RIG_TABLES}
+    if len(keep["inverse_bind"]) != 16 * len(keep["joints"]):
+        raise ValueError("inverse_bind holds %d floats for %d joints (16 each)" % (len(keep["inverse_bind"]), len(keep["joints"])))
+    pod = abi.Rig()
+    for name, _ in abi.RIG_TABLES:
+        setattr(pod, name, keep[name].ctypes.data if len(keep[name]) else None)
+        if name != "inverse_bind":
+            setattr(pod, name[:-1] + "_count", len(keep[name]))
+    return pod, keep
+
+
+def _rig_calls(rigs, times, animations):
+    r = np.ascontiguousarray(np.atleast_1d(rigs), dtype=np.uint32)
+    t = np.ascontiguousarray(np.broadcast_to(_f32(np.atleast_1d(times)), r.shape))
+    a = np.full(r.shape, abi.RIG_BASE_POSE, np.uint32) if animations is None else \
+        np.ascontiguousarray(np.broadcast_to(np.atleast_1d(animations), r.shape), dtype=np.uint32)
+    return r, t, a
+
+
 class RenderGroup:
     """n devices driven by ONE host thread through rfwhip_group_* (include/rfwhip.h): context i renders the strips of rank i
     of world n, one gather per presented frame lands the image on the root's device.  Looks like one RenderContext to the
@@ -968,7 +1035,10 @@ class RenderGroup:
                                 ("group_present_jpeg_async", i32, [vp, i32]),
                                 ("group_present_jpeg_wait", i32, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
                                 ("group_set_texture_sources", i32, [vp, vp, C.c_size_t]),
-                                ("group_set_sky_hdr", i32, [vp, vp, C.c_size_t, u32])]:
+                                ("group_set_sky_hdr", i32, [vp, vp, C.c_size_t, u32]),
+                                ("group_set_rig", i32, [vp, C.c_size_t, C.POINTER(abi.Rig)]),
+                                ("group_bind_rig", i32, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+                                ("group_animate", i32, [vp, vp, vp, vp, C.c_size_t])]:
             if hasattr(lib, prefix + name):
                 f = self._fn(name)
                 f.restype, f.argtypes = res, args
@@ -1016,6 +1086,22 @@ class RenderGroup:
         """CoreBinding.set_sky_hdr through rfwhip_group_set_sky_hdr: every member decodes its own replica of the sky."""
         src = np.frombuffer(bytes(data), np.uint8)
         self._check(self._fn("group_set_sky_hdr")(self._g, src.ctypes.data, src.size, abi.SKYSRC_FLIP_ROWS if flip else 0))
+
+    # animations (CoreBinding.set_rig / bind_rig / animate through rfwhip_group_*): every member evaluates its own copy
+    def set_rig(self, index, rig):
+        pod, keep = _rig_pod(rig)
+        self._check(self._fn("group_set_rig")(self._g, int(index), C.byref(pod)))
+        for c in self.contexts:
+            if not hasattr(c, "_rigs"):
+                c._rigs = {}
+            c._rigs[int(index)] = (len(keep["nodes"]), keep["skins"]["joint_count"].copy(), keep["nodes"]["weight_count"].copy())
+
+    def bind_rig(self, rig, mesh, skin=0, node=0):
+        self._check(self._fn("group_bind_rig")(self._g, int(rig), int(skin), int(node), int(mesh)))
+
+    def animate(self, rigs, times, animations=0):
+        r, t, a = _rig_calls(rigs, times, animations)
+        self._check(self._fn("group_animate")(self._g, r.ctypes.data, a.ctypes.data, t.ctypes.data, len(r)))
 
     def __getattr__(self, name):
         # scene setters and friends: the same call on every context (set_sky, set_mesh, set_lights, set_blue_noise, ...)

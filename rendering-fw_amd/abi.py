@@ -159,6 +159,36 @@ class SkyTableRecord(C.Structure):
         return dict(S=float(self.S), heaviest=int(self.heaviest), light=int(self.light), heavy=int(self.heavy), flags=int(self.flags))
 
 
+# animations (include/rfwhip_abi.h: rfwhip_rig and its records; rfwhip_set_rig / rfwhip_animate / rfwhip_read_rig)
+RIG_PATHS = {"translation": 0, "rotation": 1, "scale": 2, "weights": 3}
+RIG_METHODS = {"STEP": 0, "LINEAR": 1, "CUBICSPLINE": 2}
+RIG_READ = {"trs": 0, "world": 1, "joints": 2, "weights": 3, "status": 4}
+RIG_BASE_POSE = 0xFFFFFFFF
+RIG_NODE_DTYPE = np.dtype([("parent", "<i4"), ("translation", "<f4", 3), ("rotation", "<f4", 4), ("scale", "<f4", 3), ("weight_offset", "<u4"),
+                           ("matrix", "<f4", 16), ("weight_count", "<u4"), ("reserved", "<u4", 3)])
+RIG_SKIN_DTYPE = np.dtype([("mesh_node", "<u4"), ("joint_offset", "<u4"), ("joint_count", "<u4"), ("reserved", "<u4")])
+RIG_ANIMATION_DTYPE = np.dtype([("channel_offset", "<u4"), ("channel_count", "<u4")])
+RIG_CHANNEL_DTYPE = np.dtype([("node", "<u4"), ("path", "<u4"), ("method", "<u4"), ("key_count", "<u4"), ("time_offset", "<u4"),
+                              ("value_offset", "<u4"), ("value_count", "<u4"), ("reserved", "<u4")])
+assert (RIG_NODE_DTYPE.itemsize, RIG_SKIN_DTYPE.itemsize, RIG_ANIMATION_DTYPE.itemsize, RIG_CHANNEL_DTYPE.itemsize) == (128, 16, 8, 32)
+# the tables of a rig as numpy arrays, in the order of rfwhip_rig's (pointer, count) pairs; inverse_bind shares joints' count
+RIG_TABLES = (("nodes", RIG_NODE_DTYPE), ("weights", np.float32), ("skins", RIG_SKIN_DTYPE), ("joints", np.uint32),
+              ("inverse_bind", np.float32), ("animations", RIG_ANIMATION_DTYPE), ("channels", RIG_CHANNEL_DTYPE), ("times", np.float32),
+              ("values", np.float32))
+
+
+class Rig(C.Structure):
+    """rfwhip_rig (include/rfwhip_abi.h)."""
+    _fields_ = [("nodes", C.c_void_p), ("node_count", C.c_size_t), ("weights", C.c_void_p), ("weight_count", C.c_size_t),
+                ("skins", C.c_void_p), ("skin_count", C.c_size_t), ("joints", C.c_void_p), ("inverse_bind", C.c_void_p),
+                ("joint_count", C.c_size_t), ("animations", C.c_void_p), ("animation_count", C.c_size_t), ("channels", C.c_void_p),
+                ("channel_count", C.c_size_t), ("times", C.c_void_p), ("time_count", C.c_size_t), ("values", C.c_void_p),
+                ("value_count", C.c_size_t)]
+
+
+assert C.sizeof(Rig) == 136
+
+
 class LightCount(C.Structure):
     _fields_ = [("areaLightCount", C.c_uint32), ("pointLightCount", C.c_uint32), ("spotLightCount", C.c_uint32),
                 ("directionalLightCount", C.c_uint32)]

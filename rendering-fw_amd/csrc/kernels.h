@@ -460,9 +460,17 @@ void launch_skytab_scan_top(const SkyTabView &v, stream_t s);
 void launch_skytab_scan_apply(const SkyTabView &v, stream_t s);
 void launch_skytab_assign(const SkyTabView &v, stream_t s);
 
+// animations (animation.h, kernel family 18).  k_rig_evaluate: ONE launch, a workgroup per entry of `calls`; table: the context's
+// rigs by index (device memory, like calls)
+struct RigView;
+struct RigCall;
+void launch_rig_evaluate(const RigView *table, const RigCall *calls, uint32_t count, stream_t s);
+
 } // namespace rtk
 
 // the types, the marker walk and the work items of the image textures (part 1 of the file)
 #include "texture_decode.h"
 // the types, the header walk and the work items of the sky's loaders (part 1 of the file)
 #include "sky_load.h"
+// the types, the validator and the work items of the animations (part 1 of the file)
+#include "animation.h"

@@ -3134,5 +3134,8 @@ void launch_kat_grade(const GradeView &g, int which, const float *in, float *out
 // emulation's launchers; behind everything else, so that no existing kernel moves)
 #define SKY_LOAD_LAUNCHERS
 #include "sky_load.h"
+// animations: the rig kernel (part 2 of the file, behind the sky's loaders for the same reason)
+#define ANIMATION_LAUNCHERS
+#include "animation.h"
 
 } // namespace rtk

@@ -144,6 +144,21 @@ struct MeshRec
 	bool morphed = false;
 	DevBuf d_tgt_pos, d_tgt_nrm, d_morph_weights;
 	uint32_t target_count = 0;
+	// animations (rfwhip_bind_rig): the rig the mesh follows (-1: none) and the skin (a skinned mesh) or node (a morphed one) of it
+	int rig = -1;
+	uint32_t rig_item = 0;
+	uint32_t skin_max_joint = 0; // the largest joint index of the last rfwhip_set_mesh_skin
+};
+
+// A rig (rfwhip_set_rig; animation.h): the tables and the validator's plan in one device allocation, what an evaluation writes in
+// another, and what the host keeps to bind meshes and to size read-backs
+struct RigRec
+{
+	bool used = false, evaluated = false;
+	DevBuf d_tables, d_state;
+	rtk::RigView view{};
+	std::vector<uint32_t> node_weight_offset, node_weight_count, skin_joint_count, skin_first_item;
+	std::vector<size_t> meshes; // bound to it
 };
 
 // "denoise_motion": an instance as a guide pass traced it
@@ -220,7 +235,8 @@ enum KernelFamily
 	KF_PRIMARY_ENTRY = 16, // the primary wave's entry snapshot pass k_primary_entry (primary_entry.h): one count per pass, with or without
 						   // stage_timing (the milliseconds only with it)
 	KF_SKYLOAD = 17, // the sky's loaders (sky_load.h): the kernels of an HDR decode and of the alias table's chain, one count per launch
-	KF_COUNT = 18
+	KF_RIG = 18, // animations (animation.h): k_rig_evaluate, one launch per rfwhip_animate
+	KF_COUNT = 19
 };
 
 // A run of the float node table the ordering pass handles alike (primary_order.h): the nodes of one tree
@@ -504,6 +520,9 @@ struct rfwhip_context
 	uint32_t lights_bound = 0, lt_refits = 0;
 	rtk::LightTreeLevels lt_levels{};
 	DevBuf d_lf_inst, d_lf_bound, d_lf_count, d_lt_touched;
+	// animations (animation.h): the rigs by index, their views as the kernel reads them, the triples of the current call
+	std::vector<RigRec> rigs;
+	DevBuf d_rig_table, d_rig_calls;
 	uint32_t tlas_root_entry = 0, instance_count = 0;
 	rt::SceneView sv;
 
@@ -698,6 +717,9 @@ static void free_all(rfwhip_context *c)
 		for (DevBuf *b : mb)
 			b->free_();
 	}
+	for (auto &r : c->rigs)
+		r.d_tables.free_(), r.d_state.free_();
+	c->rigs.clear(), c->d_rig_table.free_(), c->d_rig_calls.free_();
 	c->d_lbvh_scratch.free_(), c->d_blue_noise.free_();
 	c->have_blue_noise = false;
 	DevBuf *bufs[] = {&c->d_nodes4, &c->d_nodes4f, &c->d_nodes4f_ord, &c->d_primary_entry, &c->d_nodes4_src, &c->d_nodes, &c->d_tri_verts, &c->d_tri_shade, &c->d_tri_uv, &c->d_tlas_prims, &c->d_instances,
@@ -1353,6 +1375,9 @@ extern "C" int rfwhip_set_mesh_skin(rfwhip_context *c, size_t index, const uint3
 	RF_TRY(dm::h2d(m.d_weights.p, weights4, n * sizeof(f4), c->stream));
 	RF_TRY(dm::sync(c->stream));
 	m.skinned = true;
+	m.skin_max_joint = 0; // (for rfwhip_bind_rig: the skin it binds to must have this joint)
+	for (size_t i = 0; i < 4 * n; i++)
+		m.skin_max_joint = std::max(m.skin_max_joint, joints4[i]);
 	return RFWHIP_OK;
 }
 
@@ -1437,6 +1462,289 @@ extern "C" int rfwhip_morph_mesh(rfwhip_context *c, size_t index, const float *w
 							   m.d_tgt_pos.as<f4>(), m.d_tgt_nrm.as<f4>(), m.d_morph_weights.as<float>(), m.target_count,
 							   (uint32_t)m.vertexCount, c->stream);
 	return refit_deformed(c, m, timer);
+}
+
+// ---- animations on the device (work items and kernel: animation.h) ---------------------------------------
+static_assert(sizeof(rfwhip_rig_node) == sizeof(rtk::RigNode) && sizeof(rfwhip_rig_skin) == sizeof(rtk::RigSkin) &&
+				  sizeof(rfwhip_rig_animation) == sizeof(rtk::RigAnim) && sizeof(rfwhip_rig_channel) == sizeof(rtk::RigChannel) &&
+				  sizeof(rfwhip_rig) == sizeof(rtk::RigSource) && sizeof(rfwhip_rig_status) == sizeof(rtk::RigStatus) &&
+				  offsetof(rfwhip_rig_node, matrix) == offsetof(rtk::RigNode, matrix) && offsetof(rfwhip_rig, values) == offsetof(rtk::RigSource, values),
+			  "rfwhip_abi.h: the rig's records are the kernel's (animation.h)");
+static_assert(rtk::RIG_INVALID == RFWHIP_ERR_INVALID_ARGUMENT && rtk::RIG_WEIGHTS == RFWHIP_RIG_PATH_WEIGHTS && rtk::RIG_ROTATION == RFWHIP_RIG_PATH_ROTATION &&
+				  rtk::RIG_CUBICSPLINE == RFWHIP_RIG_METHOD_CUBICSPLINE && rtk::RIG_LINEAR == RFWHIP_RIG_METHOD_LINEAR &&
+				  rtk::RIG_READ_STATUS == RFWHIP_RIG_READ_STATUS && rtk::RIG_READ_JOINTS == RFWHIP_RIG_READ_JOINTS && rtk::RIG_BASE_POSE == RFWHIP_RIG_BASE_POSE,
+			  "animation.h restates rfwhip_abi.h's codes");
+
+static void rig_unbind_all(rfwhip_context *c, size_t rig_index)
+{
+	for (size_t mi : c->rigs[rig_index].meshes)
+		if (mi < c->meshes.size() && c->meshes[mi].rig == (int)rig_index)
+			c->meshes[mi].rig = -1;
+	c->rigs[rig_index].meshes.clear();
+}
+
+extern "C" int rfwhip_set_rig(rfwhip_context *c, size_t rig_index, const rfwhip_rig *rig)
+{
+	CTX_ENTER(c);
+	const char *const who = "rfwhip_set_rig";
+	if (!rig)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: null rig", who);
+	if (rig_index >= (1u << 20))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig index %zu out of range", who, rig_index);
+	rtk::RigSource src;
+	memcpy(&src, rig, sizeof(src));
+	rtk::RigPlan plan;
+	if (rtk::rig_validate(src, plan))
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig %zu: %s", who, rig_index, plan.msg);
+	// the tables and the plan, one after the other at 16-byte offsets, in one allocation; the evaluation's values in another
+	std::vector<uint8_t> blob;
+	const auto put = [&](const void *p, size_t bytes) {
+		const size_t at = (blob.size() + 15u) & ~(size_t)15u;
+		blob.resize(at + bytes);
+		if (bytes)
+			memcpy(blob.data() + at, p, bytes);
+		return at;
+	};
+	const size_t n = src.node_count, items = plan.item_skin.size();
+	const size_t o_nodes = put(src.nodes, n * sizeof(rtk::RigNode)), o_bw = put(src.weights, src.weight_count * 4u);
+	const size_t o_skins = put(src.skins, src.skin_count * sizeof(rtk::RigSkin)), o_joints = put(src.joints, src.joint_count * 4u);
+	const size_t o_ibm = put(src.inverse_bind, src.joint_count * 64u), o_anims = put(src.animations, src.animation_count * sizeof(rtk::RigAnim));
+	const size_t o_chan = put(src.channels, src.channel_count * sizeof(rtk::RigChannel)), o_times = put(src.times, src.time_count * 4u);
+	const size_t o_values = put(src.values, src.value_count * 4u), o_order = put(plan.order.data(), n * 4u);
+	const size_t o_level = put(plan.level_first.data(), plan.level_first.size() * 4u), o_iskin = put(plan.item_skin.data(), items * 4u);
+	const size_t o_ijoint = put(plan.item_joint.data(), items * 4u);
+	size_t state = 0;
+	const auto room = [&](size_t bytes) {
+		const size_t at = state;
+		state = (state + bytes + 15u) & ~(size_t)15u;
+		return at;
+	};
+	const size_t s_trs = room(n * rtk::RIG_TRS * 4u), s_w = room(src.weight_count * 4u), s_world = room(n * 64u), s_local = room(n * 64u);
+	const size_t s_inv = room(src.skin_count * 64u), s_joint = room(items * 64u), s_flags = room((src.channel_count + src.skin_count) * 4u);
+	const size_t s_status = room(sizeof(rtk::RigStatus));
+	// a new rig beside the current one: the current one stays whatever happens below
+	RF_TRY(sync_all(c));
+	RigRec fresh;
+	const auto drop = [&](int rc) {
+		(void)dm::sync(c->stream);
+		fresh.d_tables.free_(), fresh.d_state.free_();
+		return rc;
+	};
+	int rc = fresh.d_tables.ensure(blob.size());
+	rc = rc ? rc : fresh.d_state.ensure(state);
+	rc = rc ? rc : dm::h2d(fresh.d_tables.p, blob.data(), blob.size(), c->stream);
+	rc = rc ? rc : dm::zero(fresh.d_state.p, state, c->stream);
+	if (rc)
+		return drop(rc);
+	const char *const T = (const char *)fresh.d_tables.p;
+	char *const S = (char *)fresh.d_state.p;
+	rtk::RigView &v = fresh.view;
+	memset(&v, 0, sizeof(v));
+	v.nodes = (const rtk::RigNode *)(T + o_nodes), v.base_weights = (const float *)(T + o_bw), v.skins = (const rtk::RigSkin *)(T + o_skins);
+	v.joints = (const uint32_t *)(T + o_joints), v.ibm = (const float *)(T + o_ibm), v.anims = (const rtk::RigAnim *)(T + o_anims);
+	v.channels = (const rtk::RigChannel *)(T + o_chan), v.times = (const float *)(T + o_times), v.values = (const float *)(T + o_values);
+	v.order = (const uint32_t *)(T + o_order), v.level_first = (const uint32_t *)(T + o_level);
+	v.item_skin = (const uint32_t *)(T + o_iskin), v.item_joint = (const uint32_t *)(T + o_ijoint);
+	v.trs = (float *)(S + s_trs), v.weights = (float *)(S + s_w), v.world = (float *)(S + s_world), v.local = (float *)(S + s_local);
+	v.inv = (float *)(S + s_inv), v.joint_mats = (float *)(S + s_joint), v.flags = (uint32_t *)(S + s_flags), v.status = (rtk::RigStatus *)(S + s_status);
+	v.node_count = (uint32_t)n, v.weight_count = (uint32_t)src.weight_count, v.skin_count = (uint32_t)src.skin_count, v.item_count = (uint32_t)items;
+	v.anim_count = (uint32_t)src.animation_count, v.channel_count = (uint32_t)src.channel_count, v.levels = plan.levels;
+	fresh.used = true;
+	for (size_t i = 0; i < n; i++)
+		fresh.node_weight_offset.push_back(src.nodes[i].weight_offset), fresh.node_weight_count.push_back(src.nodes[i].weight_count);
+	for (size_t s = 0; s < src.skin_count; s++)
+		fresh.skin_joint_count.push_back(src.skins[s].joint_count), fresh.skin_first_item.push_back(plan.out_offset[s]);
+	// the table of views the kernel indexes: every rig's, with this one's new view in its place
+	const size_t count = std::max(c->rigs.size(), rig_index + 1);
+	std::vector<rtk::RigView> table(count);
+	for (size_t i = 0; i < count; i++)
+		if (i == rig_index)
+			table[i] = v;
+		else if (i < c->rigs.size())
+			table[i] = c->rigs[i].view;
+		else
+			memset(&table[i], 0, sizeof(rtk::RigView));
+	DevBuf n_table;
+	rc = n_table.ensure(count * sizeof(rtk::RigView));
+	rc = rc ? rc : dm::h2d(n_table.p, table.data(), count * sizeof(rtk::RigView), c->stream);
+	rc = rc ? rc : dm::sync(c->stream);
+	if (rc)
+	{
+		n_table.free_();
+		return drop(rc);
+	}
+	if (c->rigs.size() < count)
+		c->rigs.resize(count);
+	rig_unbind_all(c, rig_index);
+	std::swap(c->rigs[rig_index], fresh);
+	std::swap(c->d_rig_table, n_table);
+	n_table.free_();
+	drop(0);
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_bind_rig(rfwhip_context *c, size_t rig_index, size_t skin_index, size_t node_index, size_t mesh_index)
+{
+	CTX_ENTER(c);
+	const char *const who = "rfwhip_bind_rig";
+	if (rig_index >= c->rigs.size() || !c->rigs[rig_index].used)
+		return set_error(RFWHIP_ERR_STATE, "%s: rig %zu has not been set (rfwhip_set_rig)", who, rig_index);
+	if (mesh_index >= c->meshes.size() || !c->meshes[mesh_index].used)
+		return set_error(RFWHIP_ERR_STATE, "%s: mesh %zu has not been set", who, mesh_index);
+	RigRec &r = c->rigs[rig_index];
+	MeshRec &m = c->meshes[mesh_index];
+	uint32_t item = 0;
+	if (m.skinned)
+	{
+		if (skin_index >= r.skin_joint_count.size())
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig %zu has %zu skins, no skin %zu", who, rig_index, r.skin_joint_count.size(), skin_index);
+		if (m.skin_max_joint >= r.skin_joint_count[skin_index])
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: mesh %zu refers to joint %u, skin %zu of rig %zu has %u joints", who, mesh_index,
+							 m.skin_max_joint, skin_index, rig_index, r.skin_joint_count[skin_index]);
+		item = (uint32_t)skin_index;
+	}
+	else if (m.morphed)
+	{
+		if (node_index >= r.node_weight_count.size())
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig %zu has %zu nodes, no node %zu", who, rig_index, r.node_weight_count.size(), node_index);
+		if (r.node_weight_count[node_index] != m.target_count)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: mesh %zu has %u targets, node %zu of rig %zu has %u weights", who, mesh_index,
+							 m.target_count, node_index, rig_index, r.node_weight_count[node_index]);
+		item = (uint32_t)node_index;
+	}
+	else
+		return set_error(RFWHIP_ERR_STATE, "%s: mesh %zu has neither a skin nor morph targets (rfwhip_set_mesh_skin / rfwhip_set_mesh_morph)", who, mesh_index);
+	if (m.rig >= 0 && (size_t)m.rig < c->rigs.size()) // binding it again replaces the binding
+	{
+		std::vector<size_t> &old = c->rigs[(size_t)m.rig].meshes;
+		old.erase(std::remove(old.begin(), old.end(), mesh_index), old.end());
+	}
+	m.rig = (int)rig_index, m.rig_item = item;
+	r.meshes.push_back(mesh_index);
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_animate(rfwhip_context *c, const uint32_t *rigs, const uint32_t *animations, const float *times, size_t count)
+{
+	CTX_ENTER(c);
+	const char *const who = "rfwhip_animate";
+	if (!rigs || !animations || !times || !count)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: null argument or no rigs", who);
+	std::vector<rtk::RigCall> calls(count);
+	std::vector<uint8_t> listed(c->rigs.size(), 0);
+	for (size_t i = 0; i < count; i++)
+	{
+		if (rigs[i] >= c->rigs.size() || !c->rigs[rigs[i]].used)
+			return set_error(RFWHIP_ERR_STATE, "%s: rig %u has not been set (rfwhip_set_rig)", who, rigs[i]);
+		const RigRec &r = c->rigs[rigs[i]];
+		if (listed[rigs[i]])
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig %u is listed twice", who, rigs[i]);
+		listed[rigs[i]] = 1;
+		if (animations[i] != RFWHIP_RIG_BASE_POSE && r.view.anim_count && animations[i] >= r.view.anim_count)
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig %u has %u animations, no animation %u", who, rigs[i], r.view.anim_count, animations[i]);
+		if (!(times[i] - times[i] == 0.0f))
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: the time of rig %u is not finite", who, rigs[i]);
+		for (size_t mi : r.meshes)
+		{
+			const MeshRec &m = c->meshes[mi];
+			if (!m.used || !(m.skinned || m.morphed))
+				return set_error(RFWHIP_ERR_STATE, "%s: mesh %zu, bound to rig %u, has lost its skin or morph targets", who, mi, rigs[i]);
+			if (!m.resident || m.dirty)
+				return set_error(RFWHIP_ERR_STATE, "%s: mesh %zu, bound to rig %u, is not resident yet (rfwhip_update first)", who, mi, rigs[i]);
+		}
+		calls[i].rig = rigs[i], calls[i].animation = r.view.anim_count ? animations[i] : RFWHIP_RIG_BASE_POSE, calls[i].time = times[i];
+	}
+	RF_TRY(sync_all(c));
+	for (size_t i = 0; i < count; i++)
+		for (size_t mi : c->rigs[rigs[i]].meshes)
+			RF_TRY(dn_snapshot_mesh(c, c->meshes[mi]));
+	RF_TRY(c->d_rig_calls.ensure(count * sizeof(rtk::RigCall)));
+	RF_TRY(dm::h2d(c->d_rig_calls.p, calls.data(), count * sizeof(rtk::RigCall), c->stream));
+	{
+		// (the rig kernel's own events, read behind the synchronisation of the first refit below — or, without a bound mesh, one of
+		// their own; only with stage_timing)
+		const bool timed = c->stage_timing != 0;
+		dm::event_t ea{}, eb{};
+		if (timed)
+			dm::event_create(&ea), dm::event_create(&eb), dm::event_record(ea, c->stream);
+		rtk::launch_rig_evaluate(c->d_rig_table.as<rtk::RigView>(), c->d_rig_calls.as<rtk::RigCall>(), (uint32_t)count, c->stream);
+		int rc = dm::last_launch_error();
+		if (timed)
+		{
+			dm::event_record(eb, c->stream);
+			rc = rc ? rc : dm::sync(c->stream);
+			if (!rc)
+				c->kernel_ms[KF_RIG] += dm::event_ms(ea, eb), c->kernel_launches[KF_RIG] += 1;
+			dm::event_destroy(ea), dm::event_destroy(eb);
+		}
+		RF_TRY(rc);
+	}
+	for (size_t i = 0; i < count; i++)
+	{
+		RigRec &r = c->rigs[rigs[i]];
+		r.evaluated = true;
+		for (size_t mi : r.meshes)
+		{
+			MeshRec &m = c->meshes[mi];
+			RefitTimer timer(c);
+			if (m.skinned)
+			{
+				m.joint_count = r.skin_joint_count[m.rig_item];
+				rtk::launch_skin_vertices(m.d_verts.as<f4>(), m.d_vnormals.as<f4>(), m.d_base_verts.as<f4>(), m.d_base_normals.as<f4>(),
+										  m.d_joints.as<uint32_t>(), m.d_weights.as<f4>(), r.view.joint_mats + 16u * (size_t)r.skin_first_item[m.rig_item],
+										  m.joint_count, (uint32_t)m.vertexCount, c->stream);
+			}
+			else
+				rtk::launch_morph_vertices(m.d_verts.as<f4>(), m.d_vnormals.as<f4>(), m.d_base_verts.as<f4>(), m.d_base_normals.as<f4>(),
+										   m.d_tgt_pos.as<f4>(), m.d_tgt_nrm.as<f4>(), r.view.weights + r.node_weight_offset[m.rig_item], m.target_count,
+										   (uint32_t)m.vertexCount, c->stream);
+			RF_TRY(refit_deformed(c, m, timer));
+		}
+	}
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_read_rig(rfwhip_context *c, size_t rig_index, int what, size_t index, float *out, size_t cap)
+{
+	CTX_ENTER(c);
+	const char *const who = "rfwhip_read_rig";
+	if (rig_index >= c->rigs.size() || !c->rigs[rig_index].used)
+		return set_error(RFWHIP_ERR_STATE, "%s: rig %zu has not been set (rfwhip_set_rig)", who, rig_index);
+	const RigRec &r = c->rigs[rig_index];
+	if (!r.evaluated)
+		return set_error(RFWHIP_ERR_STATE, "%s: rig %zu has not been evaluated (rfwhip_animate)", who, rig_index);
+	const void *from = nullptr;
+	size_t floats = 0;
+	switch (what)
+	{
+	case RFWHIP_RIG_READ_TRS:
+		from = r.view.trs, floats = (size_t)r.view.node_count * rtk::RIG_TRS;
+		break;
+	case RFWHIP_RIG_READ_WORLD:
+		from = r.view.world, floats = (size_t)r.view.node_count * 16u;
+		break;
+	case RFWHIP_RIG_READ_JOINTS:
+		if (index >= r.skin_joint_count.size())
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig %zu has %zu skins, no skin %zu", who, rig_index, r.skin_joint_count.size(), index);
+		from = r.view.joint_mats + 16u * (size_t)r.skin_first_item[index], floats = (size_t)r.skin_joint_count[index] * 16u;
+		break;
+	case RFWHIP_RIG_READ_WEIGHTS:
+		if (index >= r.node_weight_count.size())
+			return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: rig %zu has %zu nodes, no node %zu", who, rig_index, r.node_weight_count.size(), index);
+		from = r.view.weights + r.node_weight_offset[index], floats = r.node_weight_count[index];
+		break;
+	case RFWHIP_RIG_READ_STATUS:
+		from = r.view.status, floats = sizeof(rtk::RigStatus) / 4u;
+		break;
+	default:
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: unknown selector %d", who, what);
+	}
+	if (!out || cap < floats)
+		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "%s: %zu floats, room for %zu", who, floats, out ? cap : (size_t)0);
+	RF_TRY(sync_all(c));
+	if (!floats)
+		return RFWHIP_OK;
+	return dm::d2h(out, from, floats * 4u, c->stream);
 }
 
 // The float copy of the traversal nodes (rt::Node4f) — written only when its one reader, the packet form of the pt primary wave,
@@ -5974,7 +6282,7 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 	CTX_ENTER(c);
 	if (which < 0 || which >= KF_COUNT)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "kernel family %d out of range", which);
-	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14 && KF_TEXDEC == 15 && KF_PRIMARY_ENTRY == 16 && KF_SKYLOAD == 17, "rfwhip.h numbers the families");
+	static_assert(KF_METER_HIST == 9 && KF_METER_REDUCE == 10 && KF_PRIMARY_ORDER == 11 && KF_BLOOM == 12 && KF_GRADE == 13 && KF_JPEG == 14 && KF_TEXDEC == 15 && KF_PRIMARY_ENTRY == 16 && KF_SKYLOAD == 17 && KF_RIG == 18, "rfwhip.h numbers the families");
 	if (ms)
 		*ms = c->kernel_ms[which];
 	if (launches)

@@ -866,6 +866,43 @@ extern "C" int rfwhip_group_set_sky_hdr(rfwhip_group *g, const void *data, size_
 	return RFWHIP_OK;
 }
 
+// animations: every member holds and evaluates its own copy of a rig (each device holds the whole scene); nothing crosses the gather
+extern "C" int rfwhip_group_set_rig(rfwhip_group *g, size_t rig_index, const rfwhip_rig *rig)
+{
+	if (!g)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null group");
+	for (auto &e : g->ep)
+	{
+		GR_TRY(dm::use(e.device));
+		GR_TRY(rfwhip_set_rig(e.ctx, rig_index, rig)); // (the member's message stands)
+	}
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_group_bind_rig(rfwhip_group *g, size_t rig_index, size_t skin_index, size_t node_index, size_t mesh_index)
+{
+	if (!g)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null group");
+	for (auto &e : g->ep)
+	{
+		GR_TRY(dm::use(e.device));
+		GR_TRY(rfwhip_bind_rig(e.ctx, rig_index, skin_index, node_index, mesh_index));
+	}
+	return RFWHIP_OK;
+}
+
+extern "C" int rfwhip_group_animate(rfwhip_group *g, const uint32_t *rigs, const uint32_t *animations, const float *times, size_t count)
+{
+	if (!g)
+		return rfwhip_internal_set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null group");
+	for (auto &e : g->ep)
+	{
+		GR_TRY(dm::use(e.device));
+		GR_TRY(rfwhip_animate(e.ctx, rigs, animations, times, count));
+	}
+	return RFWHIP_OK;
+}
+
 extern "C" int rfwhip_group_set_display_lut(rfwhip_group *g, const float *rgb, uint32_t n)
 {
 	if (!g)

@@ -17,6 +17,10 @@ What it restates from the reference (which parses with tinygltf, a third-party l
                     and normalTexture become texture sources (images.py): a JPEG stays encoded and is decoded, linearised and
                     mipped on the device (rfwhip_set_texture_sources), a PNG's pixels likewise.  glTF's uv origin is the image's
                     top-left corner and the sampler's row 0 is v = 0, so the rows are NOT flipped.  Off by default.
+  * the device's animation path  `Gltf.rig()` packs nodes, skins, channels and keys into the flat tables of rfwhip_set_rig; the scene
+                    `load_scene` returns carries that rig and which mesh follows which skin or node, `bind_scene(ctx, scene)` hands
+                    them to a context, and a frame's animation is then `ctx.animate(0, time); ctx.update()` — set_time /
+                    joint_matrices below stay as the host's float64 statement of the same rule (include/rfwhip.h, rfwhip_animate)
 Not covered: cameras, KHR extensions, sparse accessors, texture transforms and samplers' wrap modes; materials map
 baseColorFactor / metallic / roughness and, with load_images, the two textures above.  File parsing itself is plain
 json + base64 / external buffers + numpy.
@@ -29,7 +33,7 @@ import struct
 
 import numpy as np
 
-from . import images, scenes
+from . import abi, images, scenes
 
 _COMPONENT = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
 _WIDTH = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
@@ -192,6 +196,53 @@ class Gltf:
             elif c["path"] == "rotation":
                 self.R[c["node"]] = v[:4] / np.linalg.norm(v[:4])  # sampleQuat normalises
 
+    def rig(self):
+        """The file's animation data as the flat tables of rfwhip_set_rig (include/rfwhip_abi.h: rfwhip_rig; abi.RIG_TABLES), from
+        the file alone — set_time's state is not read.  One rig skin per mesh node that carries a skin, in mesh_nodes() order
+        ("skin_of_node": mesh node -> rig skin); one rig animation per animation of the file, a sampler's keys copied per channel."""
+        n = len(self.nodes)
+        nodes = np.zeros(n, abi.RIG_NODE_DTYPE)
+        weights = []
+        for i, nd in enumerate(self.nodes):
+            nodes[i]["parent"] = self.parents[i]
+            nodes[i]["translation"] = nd.get("translation", (0, 0, 0))
+            nodes[i]["rotation"] = nd.get("rotation", (0, 0, 0, 1))
+            nodes[i]["scale"] = nd.get("scale", (1, 1, 1))
+            nodes[i]["matrix"] = nd.get("matrix", np.eye(4).reshape(-1))  # (the file's order is column-major already)
+            if "mesh" in nd:
+                mesh = self.doc["meshes"][nd["mesh"]]
+                w = nd.get("weights", mesh.get("weights", [0.0] * len(mesh["primitives"][0].get("targets", []))))
+                nodes[i]["weight_offset"], nodes[i]["weight_count"] = len(weights), len(w)
+                weights += [float(x) for x in w]
+        skins, joints, ibm, skin_of_node = [], [], [], {}
+        for ni in self.mesh_nodes():
+            if "skin" not in self.nodes[ni]:
+                continue
+            sk = self.doc["skins"][self.nodes[ni]["skin"]]
+            skin_of_node[ni] = len(skins)
+            skins.append((ni, len(joints), len(sk["joints"]), 0))
+            joints += list(sk["joints"])
+            ibm.append(self.accessor(sk["inverseBindMatrices"]).astype(np.float32).reshape(-1, 16) if "inverseBindMatrices" in sk
+                       else np.tile(np.eye(4, dtype=np.float32).reshape(-1), (len(sk["joints"]), 1)))
+        animations, channels, times, values = [], [], [], []
+        nt = nv = 0
+        for a in self.animations:
+            animations.append((len(channels), len(a["channels"])))
+            for c in a["channels"]:
+                smp = a["samplers"][c["sampler"]]
+                t, v = smp["times"].astype(np.float32), smp["keys"].astype(np.float32).reshape(-1)
+                channels.append((c["node"], abi.RIG_PATHS[c["path"]], abi.RIG_METHODS[smp["method"]], len(t), nt, nv, len(v), 0))
+                times.append(t), values.append(v)
+                nt, nv = nt + len(t), nv + len(v)
+
+        def cat(parts):
+            return np.concatenate(parts) if parts else np.zeros(0, np.float32)
+        return {"nodes": nodes, "weights": np.asarray(weights, np.float32), "skins": np.asarray(skins, np.uint32).view(abi.RIG_SKIN_DTYPE).reshape(-1),
+                "joints": np.asarray(joints, np.uint32), "inverse_bind": cat(ibm).reshape(-1),
+                "animations": np.asarray(animations, np.uint32).view(abi.RIG_ANIMATION_DTYPE).reshape(-1),
+                "channels": np.asarray(channels, np.uint32).view(abi.RIG_CHANNEL_DTYPE).reshape(-1), "times": cat(times), "values": cat(values),
+                "skin_of_node": skin_of_node}
+
     # ---- meshes / skins --------------------------------------------------------------------------------------------
     def mesh_nodes(self):
         return [i for i, n in enumerate(self.nodes) if "mesh" in n]
@@ -270,12 +321,14 @@ class Gltf:
 def load_scene(path, width=480, height=270, load_images=False):
     """A Scene with one mesh + instance per mesh node (first primitive), the node transforms as instance transforms, and
     per mesh node the rig (joints, weights, bind normals) when it is skinned.  Returns (scene, gltf, rigs) with
-    rigs = {scene mesh index: (node index, joints, weights, normals)}.  load_images: the materials' base colour (sRGB -> linear)
+    rigs = {scene mesh index: (node index, joints, weights, normals)}.  The scene also carries `rig` (Gltf.rig(), None when no mesh
+    is skinned or morphed) and `rig_bindings` for bind_scene.  load_images: the materials' base colour (sRGB -> linear)
     and normal textures become texture sources the device decodes (module docstring)."""
     g = Gltf(path)
     s = scenes.Scene()
     s.name = os.path.basename(path)
     rigs = {}
+    bindings = {}
     mats = {}
     texs = {}
 
@@ -298,4 +351,29 @@ def load_scene(path, width=480, height=270, load_images=False):
         s.add_instance(m, g.combined(ni).astype(np.float32))
         if prim["joints"] is not None and "skin" in g.nodes[ni]:
             rigs[m] = (ni, prim["joints"], prim["weights"], prim["normals"])
+            bindings[m] = {"skin": ni}
+        elif prim["targets"]:
+            bindings[m] = {"node": ni, "normals": prim["normals"], "target_positions": np.stack([t[0] for t in prim["targets"]]),
+                           "target_normals": np.stack([t[1] for t in prim["targets"]])}
+    # the device's animation path (rfwhip_set_rig / rfwhip_animate): the scene carries its rig and which mesh follows what
+    s.rig = g.rig() if bindings else None
+    s.rig_bindings = bindings
+    s.rig_skins = rigs
     return s, g, rigs
+
+
+def bind_scene(ctx, scene, rig_index=0):
+    """After scene.upload(ctx): hand the scene's rig to the context and bind its skinned and morphed meshes to it, so that
+    `ctx.animate(rig_index, time); ctx.update()` is a frame's whole animation.  Returns whether the scene has a rig."""
+    if scene.rig is None:
+        return False
+    ctx.set_rig(rig_index, scene.rig)
+    for m, b in scene.rig_bindings.items():
+        if "skin" in b:
+            _, joints, weights, normals = scene.rig_skins[m]
+            ctx.set_mesh_skin(m, joints, weights, normals)
+            ctx.bind_rig(rig_index, m, skin=scene.rig["skin_of_node"][b["skin"]])
+        else:
+            ctx.set_mesh_morph(m, b["normals"], b["target_positions"], b["target_normals"])
+            ctx.bind_rig(rig_index, m, node=b["node"])
+    return True
