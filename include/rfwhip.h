@@ -988,7 +988,8 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *   "light_tree" (nodes of the light tree the next render would use; 0: none, or light_sampling is not "tree"),
  *   "lights_bound" (area lights the last refresh of lights_follow_geometry found bound; 0 while that setting is off),
  *   "light_tree_refits" (refits of the light tree on the device since it was last built), "primary_entry_on" (the primary wave of
- *   the last render call started from its entry snapshot: see primary_entry).
+ *   the last render call started from its entry snapshot: see primary_entry), "material_maps_on" (the next render's pt shade waves
+ *   run the map kernels: material_maps is "1" and some material has a present alpha, roughness or metallic map).
  *   Not listed by rfwhip_get_settings, but settable:
  *   primary_entry = "-1" (default) | "0" | "1": the entry snapshot of the pt primary wave in packet form.  Where the camera-ordered
  *                  node table is used (kernel family 11 below), the camera has no lens (aperture 0) and count_traversal is 0, a pass
@@ -1008,6 +1009,28 @@ RFWHIP_API int rfwhip_get_stats(rfwhip_context *ctx, rfwhip_render_stats *stats)
  *                  and dither, see rfwhip_set_display_lut above.
  *   noise_estimate / noise_floor / noise_threshold = the noise estimate, see rfwhip_get_noise above.
  *   adaptive_sampling / adaptive_min_samples / adaptive_every = adaptive sampling, see rfwhip_get_adaptive above.
+ *   material_maps = "0" (default: map slots 6 - 9 of a material are ignored, as in the reference) | "1": the pt integrator reads the
+ *                  alpha mask of slot 9 and the roughness / metallic maps of slots 7 / 6.  The parity integrator ignores it.
+ *                  At a hit with interpolated (tu, tv) and the level of detail lambda of the colour layers, slot K's texel is the
+ *                  trilinear fetch of its own descriptor, as a colour layer's:
+ *                    texel_K = fetch(textures[map[K].addr], lambda, uscale_K (uoffs_K + tu), vscale_K (voffs_K + tv), width_K, height_K).
+ *                  A slot is PRESENT when its flag is set and map[K].addr < the textures of the last rfwhip_set_textures — with or
+ *                  without a diffuse map.
+ *                    alpha mask (HasAlphaMap, slot 9): a = min(texel_9.r, texel_9.a) — a grey mask with alpha 255 gives its grey, a
+ *                      white one with an alpha channel its alpha.  a < 0.5 is HasAlpha's pass-through, unchanged: the path goes on from
+ *                      I + 1e-5 D, its state untouched, one depth deeper, and nothing else of the surface is evaluated.  With
+ *                      HasAlpha as well, either test passes the ray through.
+ *                    roughness (HasRoughnessMap, slot 7): r = roughness * texel_7.g;  metallic (HasSpecularityMap, slot 6):
+ *                      m = metallic * texel_6.b, roughness and metallic the bytes of parameters[0] over 255 — glTF's packing, so a
+ *                      host points both slots at one metallic-roughness texture (with the same descriptor in both, one fetch serves
+ *                      both); a grey map scales the same two parameters.  Both go back into the 8 bits the BSDF reads,
+ *                      byte(v) = (uint32)(min(max(v, 0), 1) * 255 + 0.5), a NaN gives 0; the specular test (roughness < 0.01) and the
+ *                      BSDF then read the mapped bytes.  Emitters (a colour component > 1) and hits passed through read neither.
+ *                    slot 8 (colour mask) stays ignored.
+ *                  The map kernels (k_shade_pt_maps) run only while some material of the last rfwhip_set_materials has a present slot
+ *                  6, 7 or 9 ("material_maps_on"); otherwise the setting changes no byte of any image.  The denoiser's guide pass
+ *                  looks through the mask under the same condition, and a change of the setting makes the guides stale.
+ *                  RFWHIP_KAT_SURFACE_MAPS evaluates the rule on given hits whatever the setting is.
  *   lights_follow_geometry = "0" (default) | "1": rfwhip_update derives the area lights of emissive geometry on the device and
  *                  refits the light tree, see rfwhip_read_area_lights below.
  * Returns the number of keys; fills up to cap pointers with static strings. */

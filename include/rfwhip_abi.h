@@ -428,6 +428,8 @@ enum rfwhip_kat_function
 	 * pt_surface, pt_textures).  An index outside the scene's tables is an error. */
 	RFWHIP_KAT_TEX_FETCH = 15,		   /* [0] = texture (int), [1] = form (int: 0 = the trilinear fetch of a colour layer, 1 = the bilinear fetch at level 0 of a normal-map layer), [2] = lambda, [3..4] = tu, tv, [5..6] = width, height as the material's map descriptor gives them (ints, 1..65536) -> rgba */
 	RFWHIP_KAT_SURFACE_LAYERS = 16,   /* [0] = instance, [1] = triangle (ints), [2..3] = barycentrics u, v (weights of vertex 1, 2), [4..6] = D, [7] = t, [8] = the camera's spread angle -> [0..2] = colour after the texture layers, [3..5] = shading normal after the normal maps, [6] = flags (int): bit 0 alpha pass-through, bit 1 the material is textured */
+	/* what setting material_maps makes of the same hit, whatever the setting is (rt_core.h: pt_maps_alpha, pt_maps_params; rfwhip.h has the rule) */
+	RFWHIP_KAT_SURFACE_MAPS = 20,	   /* the input record of SURFACE_LAYERS -> [0] = the roughness byte, [1] = the metallic byte after their maps (ints; the material's own for a hit the mask passes through), [2] = a (1 without a mask), [3] = flags (int): bit 0 alpha pass-through by the mask, bit 1 slot 6 (metallic) present, bit 2 slot 7 (roughness) present, bit 3 slot 9 (alpha mask) present */
 	/* the light tree of light_sampling=tree (rt_core.h: lt_sample / lt_pick_prob); RFWHIP_ERR_STATE in any other mode */
 	RFWHIP_KAT_LT_SAMPLE = 17,		   /* [0..2] = I, [3..5] = N, [6] = r0, [7] = r1 -> [0..2] = P, [3] = q, [4] = lightPdf (area: dist^2 / (area LNdotL)), [5] = the light (int, -1: none), [6] = its rank in the order r1 walks through (int) */
 	RFWHIP_KAT_LT_PICK_PROB = 18, 	   /* [0..2] = I, [3..5] = N, [8] = light (int) -> q, bit for bit what LT_SAMPLE gives when it draws that light */

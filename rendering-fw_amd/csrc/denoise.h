@@ -82,14 +82,27 @@ RT_FN bool dn_pixel(uint32_t bx, uint32_t by, uint32_t t, uint32_t W, uint32_t H
 RT_FN void dn_guide_item(const Params &p, const DnView &d, uint32_t i, const TravStack &stk)
 {
 #define DN_BODY_SURF 0
+#define DN_BODY_MAPS 0
 #include "denoise_guide_body.h"
+#undef DN_BODY_MAPS
 #undef DN_BODY_SURF
 }
 // "denoise_motion": the same item, which also keeps the hit's primitive and barycentrics (surf[i] = (prim, u, v, 0))
 RT_FN void dn_guide_surf_item(const Params &p, const DnView &d, f4 *surf, uint32_t i, const TravStack &stk)
 {
 #define DN_BODY_SURF 1
+#define DN_BODY_MAPS 0
 #include "denoise_guide_body.h"
+#undef DN_BODY_MAPS
+#undef DN_BODY_SURF
+}
+// material_maps: the same item, which also lets the alpha mask pass the ray through (pt_maps_alpha); surf may be null
+RT_FN void dn_guide_maps_item(const Params &p, const DnView &d, f4 *surf, uint32_t i, const TravStack &stk)
+{
+#define DN_BODY_SURF 1
+#define DN_BODY_MAPS 1
+#include "denoise_guide_body.h"
+#undef DN_BODY_MAPS
 #undef DN_BODY_SURF
 }
 

@@ -1,6 +1,7 @@
 // denoise_guide_body.h — the body of the denoiser's guide item, included by its two functions in denoise.h: dn_guide_item
 // (DN_BODY_SURF 0, the default) and dn_guide_surf_item (DN_BODY_SURF 1, setting "denoise_motion": the kept hit's primitive and
-// barycentrics also go into surf[i] = (prim, u, v, 0); prim = -1 at an invalid pixel).  In scope there: p, d, i, stk and, with
+// barycentrics also go into surf[i] = (prim, u, v, 0); prim = -1 at an invalid pixel); dn_guide_maps_item (DN_BODY_MAPS 1, setting
+// "material_maps": the alpha mask passes the ray through as MF_ALPHA does; surf may be null).  In scope there: p, d, i, stk and, with
 // DN_BODY_SURF, surf.  Spelled out per function with the preprocessor, as shade_pt_body.h is per kernel: the default item's code,
 // and with it k_dn_guides, stays exactly what it was.
 // (no include guard: it is included once per function)
@@ -29,6 +30,13 @@
 		bool alpha_skip = false;
 		if (p.textured && pt_has_textures(p.sc, sf))
 			pt_textures(p.sc, p.cam, D, h.t, sf, color, iN, alpha_skip);
+#if DN_BODY_MAPS
+		if (!alpha_skip)
+		{
+			float a;
+			alpha_skip = pt_maps_alpha(p.sc, p.cam, D, h.t, sf, a);
+		}
+#endif
 		z += h.t;
 		if (alpha_skip)
 		{
@@ -55,5 +63,8 @@
 	if (d.id) // (the temporal stage's instance test)
 		d.id[i] = inst;
 #if DN_BODY_SURF
+#if DN_BODY_MAPS
+	if (surf)
+#endif
 	surf[i] = mk4(ubits(sprim), su, sv, 0.0f);
 #endif

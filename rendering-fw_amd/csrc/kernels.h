@@ -263,6 +263,9 @@ uint32_t queue_pad(uint32_t max_items); // extra slots per queue and launch for 
 void launch_shade_pt(const Params &p, const rt::SkyView &sky, uint32_t max_items, stream_t s);
 // light_sampling = linear | tree: k_shade_pt_lt (lt.nodes null: linear); sky as above (pick == 0: no sky sampling)
 void launch_shade_pt_lt(const Params &p, const rt::SkyView &sky, const rt::LightTreeView &lt, uint32_t max_items, stream_t s);
+// material_maps = 1 and a material with an alpha, roughness or metallic map: k_shade_pt_maps<SKY, LT> in place of either of the two
+// above (with_lt false: light_sampling = reference, lt unread; sky as above)
+void launch_shade_pt_maps(const Params &p, const rt::SkyView &sky, const rt::LightTreeView &lt, bool with_lt, uint32_t max_items, stream_t s);
 void launch_connect(const Params &p, bool count, uint32_t max_items, stream_t s);
 // the connection wave of depth 0 in packet form: runs of the shadow queue sorted by the chosen light's bin (FrameView::shadow_bins),
 // one wave-uniform occlusion traversal per 64 rays of the sorted order
@@ -294,12 +297,14 @@ void launch_adaptive_connections(rt::WaveCounters *c, uint32_t depth, stream_t s
 // rfwhip_kat: `function` (RFWHIP_KAT_*) on n records of 24 floats -> n records of 8 floats (device pointers)
 // (KAT_LT_*: the functions of k_kat_lt, RFWHIP_KAT_LT_* of rfwhip_abi.h; every other function runs in k_kat)
 constexpr int KAT_LT_SAMPLE = 17, KAT_LT_PICK_PROB = 18;
+constexpr int KAT_SURFACE_MAPS = 20; // (RFWHIP_KAT_SURFACE_MAPS: k_kat_maps)
 void launch_kat(const Params &p, const rt::SkyView &sky, const rt::LightTreeView &lt, int function, const float *in, float *out, uint32_t n, stream_t s);
 // out: local layout (local_rows x W) when full == 0, else full image (H x W; world must be 1)
 void launch_present(const Params &p, rt::f4 *out, float scale, int full, stream_t s);
 // the denoiser's guide pass (p: scene, camera and FrameView of the full image) = guide kernel + depth-gradient kernel
 // surf != null ("denoise_motion"): the guide kernel's variant that also writes the surface record per pixel
-void launch_denoise_guides(const Params &p, const DnView &d, rt::f4 *surf, stream_t s);
+// maps (material_maps = 1 and a material with an alpha mask): the variant that honours the mask, k_dn_guides_maps
+void launch_denoise_guides(const Params &p, const DnView &d, rt::f4 *surf, stream_t s, bool maps = false);
 // demodulation + variance (with t, then the temporal stage), d.iterations a-trous passes, remodulation into d.out:
 // 1 (+ 1 with t) + d.iterations launches
 // m != null (with t): the stage's motion variant k_dn_temporal_motion

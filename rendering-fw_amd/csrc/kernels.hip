@@ -382,7 +382,7 @@ struct ShadeSink
 
 // One entry of the wave of depth p.depth.  `active` = the lane holds a path (the device kernel's scan has checked that the entry is
 // a path's: not void, at depth 0 a real pixel's slot); h4 / hi = its hit record (the device kernel's scan has read them already).
-template <bool TEX, bool SKY, bool LT> RT_FN void shade_pt_item(const Params &p, const SkyView &sky, const LightTreeView &lt, uint32_t i, bool active, const f4 &h4, int hi, Ctx &ctx RT_ITEM_CLK)
+template <bool TEX, bool SKY, bool LT, bool MAPS> RT_FN void shade_pt_item(const Params &p, const SkyView &sky, const LightTreeView &lt, uint32_t i, bool active, const f4 &h4, int hi, Ctx &ctx RT_ITEM_CLK)
 {
 	RT_ITEM_TICK(0);
 	const uint32_t b = p.depth & 1u, nb = b ^ 1u;
@@ -416,7 +416,7 @@ template <bool TEX, bool SKY, bool LT> RT_FN void shade_pt_item(const Params &p,
 	}
 	const uint32_t slot = in.slot;
 	ShadeSink sink{p, ctx, slot};
-	pt_shade<TEX, SKY, LT>(p.sc, sky, lt, p.cam, p.fr, p.max_depth, active, in, h, out, ctx.pot, sink RT_CLK_ARG);
+	pt_shade<TEX, SKY, LT, MAPS>(p.sc, sky, lt, p.cam, p.fr, p.max_depth, active, in, h, out, ctx.pot, sink RT_CLK_ARG);
 	if (active)
 	{
 		// depth 0 initialises the slot (no clear pass); later depths accumulate.  One path per slot => no race.
@@ -667,6 +667,31 @@ template <bool LT> RT_FN void kat_item(const Params &p, const SkyView &sky, cons
 	default:
 		break;
 	}
+}
+// surface_maps (k_kat_maps alone runs it — k_kat keeps its code): what the MAPS variants make of a hit of the context's scene,
+// whatever the setting is.  The input record of surface_layers -> roughness byte, metallic byte (ints), a, flags (int: bit 0 alpha
+// pass-through by the mask, bits 1 / 2 / 3 slot 6 / 7 / 9 present)
+RT_FN void kat_maps_item(const Params &p, const float *in, float *out, uint32_t i)
+{
+	const float *r = in + (size_t)i * KAT_IN;
+	float *o = out + (size_t)i * KAT_OUT;
+	for (int k = 0; k < KAT_OUT; k++)
+		o[k] = 0.0f;
+	Hit h;
+	h.inst = (int)fbits(r[0]), h.prim = (int)fbits(r[1]), h.u = r[2], h.v = r[3], h.t = r[7];
+	Surface sf;
+	pt_surface(p.sc, h, sf);
+	CamView cam = p.cam;
+	cam.spread_angle = r[8];
+	const f3 D = mk3(r[4], r[5], r[6]);
+	float a;
+	const bool skip = pt_maps_alpha(p.sc, cam, D, h.t, sf, a);
+	uint32_t p0 = sf.mat->parameters[0];
+	if (!skip)
+		pt_maps_params(p.sc, cam, D, h.t, sf, p0);
+	o[0] = ubits(p0 >> 24), o[1] = ubits(p0 & 255u), o[2] = a;
+	o[3] = ubits((skip ? 1u : 0u) | (pt_map_present(p.sc, sf, MF_SPECULARITY_MAP, 6) ? 2u : 0u) | (pt_map_present(p.sc, sf, MF_ROUGHNESS_MAP, 7) ? 4u : 0u) |
+				 (pt_map_present(p.sc, sf, MF_ALPHA_MAP, 9) ? 8u : 0u));
 }
 
 // CUDART/src/Context.cpp:109: the connections of shade call d are traced only if depth d + 1 has extension rays
@@ -1926,7 +1951,7 @@ __global__ void __launch_bounds__(BLOCK, RT_TRAVERSAL_WAVES) k_shade_parity(cons
 
 template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt(const Params p)
 {
-	constexpr bool SKY = false, LT = false;
+	constexpr bool SKY = false, LT = false, MAPS = false;
 	const SkyView sky{};
 	const LightTreeView lt{};
 #include "shade_pt_body.h"
@@ -1935,7 +1960,7 @@ template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVE
 // argument of k_shade_pt: the measurements look the default kernels up by their names.
 template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt_sky(const Params p, const SkyView sky)
 {
-	constexpr bool SKY = true, LT = false;
+	constexpr bool SKY = true, LT = false, MAPS = false;
 	const LightTreeView lt{};
 #include "shade_pt_body.h"
 }
@@ -1944,7 +1969,15 @@ template <bool TEX> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVE
 // SKY = false is launched and `sky` is unread).
 template <bool TEX, bool SKY> __global__ void __launch_bounds__(BLOCK, TEX ? RT_SHADE_WAVES : RT_SHADE_WAVES_PLAIN) k_shade_pt_lt(const Params p, const SkyView sky, const LightTreeView lt)
 {
-	constexpr bool LT = true;
+	constexpr bool LT = true, MAPS = false;
+#include "shade_pt_body.h"
+}
+// material_maps = 1 and some material has an alpha, roughness or metallic map: the textured kernel with the map code (pt_shade<true,
+// SKY, LT, true>).  Kernels of their own, as the sky's and the light tree's are: the ones above keep their code and their names.
+// (both views are arguments whatever SKY and LT are: an unread one costs a few kernarg bytes)
+template <bool SKY, bool LT> __global__ void __launch_bounds__(BLOCK, RT_SHADE_WAVES) k_shade_pt_maps(const Params p, const SkyView sky, const LightTreeView lt)
+{
+	constexpr bool TEX = true, MAPS = true;
 #include "shade_pt_body.h"
 }
 
@@ -2324,6 +2357,23 @@ void launch_shade_pt(const Params &p, const SkyView &sky, uint32_t max_items, st
 		hipLaunchKernelGGL(k_shade_pt<false>, dim3(persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(false))), dim3(BLOCK), 0, (hipStream_t)s, p);
 }
 
+void launch_shade_pt_maps(const Params &p, const SkyView &sky, const LightTreeView &lt, bool with_lt, uint32_t max_items, stream_t s)
+{
+	const dim3 g(persistent_grid(max_items, RT_SHADE_BLOCKS_PER_CU(true))), b(BLOCK);
+	const bool with_sky = sky.pick > 0.0f;
+	if (with_lt)
+	{
+		if (with_sky)
+			hipLaunchKernelGGL((k_shade_pt_maps<true, true>), g, b, 0, (hipStream_t)s, p, sky, lt);
+		else
+			hipLaunchKernelGGL((k_shade_pt_maps<false, true>), g, b, 0, (hipStream_t)s, p, sky, lt);
+	}
+	else if (with_sky)
+		hipLaunchKernelGGL((k_shade_pt_maps<true, false>), g, b, 0, (hipStream_t)s, p, sky, lt);
+	else
+		hipLaunchKernelGGL((k_shade_pt_maps<false, false>), g, b, 0, (hipStream_t)s, p, sky, lt);
+}
+
 void launch_shadow_packets(const Params &p, bool count, uint32_t max_items, stream_t s)
 {
 	const dim3 g(persistent_grid(max_items));
@@ -2417,6 +2467,15 @@ __global__ void __launch_bounds__(BLOCK) k_dn_guides_surf(const Params p, const 
 	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
 		dn_guide_surf_item(p, d, surf, i, ctx.stk);
 }
+// material_maps: the guides look through what the alpha mask lets the paths through (surf: null without denoise_motion)
+__global__ void __launch_bounds__(BLOCK) k_dn_guides_maps(const Params p, const DnView d, f4 *surf)
+{
+	RT_STACK_DECL_CLOSEST
+	ctx.stk.overflow = d.overflow;
+	uint32_t i;
+	if (dn_pixel(blockIdx.x, blockIdx.y, threadIdx.x, d.W, d.H, i))
+		dn_guide_maps_item(p, d, surf, i, ctx.stk);
+}
 __global__ void __launch_bounds__(BLOCK) k_dn_gradient(const DnView d)
 {
 	uint32_t i;
@@ -2449,9 +2508,11 @@ __global__ void __launch_bounds__(BLOCK) k_dn_pass(const DnView d, uint32_t pass
 					 d.var[(pass + 1u) & 1u], i);
 }
 static dim3 dn_grid(const DnView &d) { return dim3((d.W + DN_TILE_X - 1) / DN_TILE_X, (d.H + DN_TILE_Y - 1) / DN_TILE_Y); }
-void launch_denoise_guides(const Params &p, const DnView &d, f4 *surf, stream_t s)
+void launch_denoise_guides(const Params &p, const DnView &d, f4 *surf, stream_t s, bool maps)
 {
-	if (surf)
+	if (maps)
+		hipLaunchKernelGGL(k_dn_guides_maps, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d, surf);
+	else if (surf)
 		hipLaunchKernelGGL(k_dn_guides_surf, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d, surf);
 	else
 		hipLaunchKernelGGL(k_dn_guides, dn_grid(d), dim3(BLOCK), 0, (hipStream_t)s, p, d);
@@ -2559,6 +2620,12 @@ __global__ void __launch_bounds__(BLOCK) k_kat_lt(const Params p, const SkyView 
 	if (i < n)
 		kat_item<true>(p, sky, lt, function, in, out, i, s_pot + threadIdx.x);
 }
+__global__ void __launch_bounds__(BLOCK) k_kat_maps(const Params p, const float *in, float *out, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+	if (i < n)
+		kat_maps_item(p, in, out, i);
+}
 // RFWHIP_KAT_METER_BIN (metering.h): a kernel of its own, k_kat keeps its code
 __global__ void __launch_bounds__(BLOCK) k_kat_meter(const float *in, float *out, uint32_t n)
 {
@@ -2572,6 +2639,8 @@ void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, in
 		return;
 	if (function == KAT_METER_BIN)
 		hipLaunchKernelGGL(k_kat_meter, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, in, out, n);
+	else if (function == KAT_SURFACE_MAPS)
+		hipLaunchKernelGGL(k_kat_maps, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, in, out, n);
 	else if (function == KAT_LT_SAMPLE || function == KAT_LT_PICK_PROB)
 		hipLaunchKernelGGL(k_kat_lt, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)s, p, sky, lt, function, in, out, n);
 	else

@@ -394,15 +394,15 @@ void launch_shade_pt(const Params &p, const SkyView &sky, uint32_t max_items, st
 		ClkProbe clk0;
 		clk0.last = 0, clk0.acc = nullptr;
 		if (sky.pick > 0.0f)
-			p.textured ? shade_pt_item<true, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0);
+			p.textured ? shade_pt_item<true, true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0);
 		else
-			p.textured ? shade_pt_item<true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0);
+			p.textured ? shade_pt_item<true, false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0) : shade_pt_item<false, false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx, &clk0);
 #else
 		// (sky sampling: what k_shade_pt_sky runs)
 		if (sky.pick > 0.0f)
-			p.textured ? shade_pt_item<true, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx) : shade_pt_item<false, true, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx);
+			p.textured ? shade_pt_item<true, true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx) : shade_pt_item<false, true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx);
 		else
-			p.textured ? shade_pt_item<true, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx) : shade_pt_item<false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx);
+			p.textured ? shade_pt_item<true, false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx) : shade_pt_item<false, false, false, false>(p, sky, LightTreeView{}, i, true, h4, insts[i], ctx);
 #endif
 	}
 	p.wv.counters->ext[p.depth + 1] += ctx.q_ext.rays, p.wv.counters->shadow[p.depth] += ctx.q_shadow.rays;
@@ -431,9 +431,40 @@ void launch_shade_pt_lt(const Params &p, const SkyView &sky, const LightTreeView
 			continue;
 		// (what k_shade_pt_lt<TEX, SKY> runs)
 		if (sky.pick > 0.0f)
-			p.textured ? shade_pt_item<true, true, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<false, true, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
+			p.textured ? shade_pt_item<true, true, true, false>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<false, true, true, false>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
 		else
-			p.textured ? shade_pt_item<true, false, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<false, false, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
+			p.textured ? shade_pt_item<true, false, true, false>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<false, false, true, false>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
+	}
+#undef RT_EMU_CLK
+	p.wv.counters->ext[p.depth + 1] += ctx.q_ext.rays, p.wv.counters->shadow[p.depth] += ctx.q_shadow.rays;
+}
+void launch_shade_pt_maps(const Params &p, const SkyView &sky, const LightTreeView &lt, bool with_lt, uint32_t max_items, stream_t s)
+{
+	EMU_DEFER(s, launch_shade_pt_maps(p, sky, lt, with_lt, max_items, s));
+	Ctx ctx;
+	const uint32_t n = p.wv.counters->ext_n[p.depth];
+	const f4 *const hits = p.depth == 0 ? p.wv.hit0 : p.wv.hit;
+	const int *const insts = p.depth == 0 ? p.wv.hit0_inst : p.wv.hit_inst;
+#if defined(RT_DIAG_SHADE_CLOCK)
+	ClkProbe clk0;
+	clk0.last = 0, clk0.acc = nullptr;
+#define RT_EMU_CLK , &clk0
+#else
+#define RT_EMU_CLK
+#endif
+	for (uint32_t i = 0; i < n; i++)
+	{
+		// (the entries launch_shade_pt passes over)
+		if (p.depth == 0 && !slot_to_pixel(p.fr, i).valid)
+			continue;
+		const f4 h4 = hits[i];
+		if ((int)fbits(h4.w) < -1)
+			continue;
+		// (what k_shade_pt_maps<SKY, LT> runs)
+		if (with_lt)
+			sky.pick > 0.0f ? shade_pt_item<true, true, true, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<true, false, true, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
+		else
+			sky.pick > 0.0f ? shade_pt_item<true, true, false, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK) : shade_pt_item<true, false, false, true>(p, sky, lt, i, true, h4, insts[i], ctx RT_EMU_CLK);
 	}
 #undef RT_EMU_CLK
 	p.wv.counters->ext[p.depth + 1] += ctx.q_ext.rays, p.wv.counters->shadow[p.depth] += ctx.q_shadow.rays;
@@ -552,13 +583,15 @@ void launch_deinterleave(const f4 *gathered, f4 *out, uint32_t W, uint32_t H, ui
 	for (uint32_t i = 0; i < W * H; i++)
 		deinterleave_item(gathered, out, W, H, local_rows, world, i);
 }
-void launch_denoise_guides(const Params &p, const DnView &d, f4 *surf, stream_t s)
+void launch_denoise_guides(const Params &p, const DnView &d, f4 *surf, stream_t s, bool maps)
 {
-	EMU_DEFER(s, launch_denoise_guides(p, d, surf, s));
+	EMU_DEFER(s, launch_denoise_guides(p, d, surf, s, maps));
 	Ctx ctx(p);
 	ctx.stk.overflow = d.overflow;
 	for (uint32_t i = 0; i < d.W * d.H; i++)
-		if (surf)
+		if (maps)
+			dn_guide_maps_item(p, d, surf, i, ctx.stk);
+		else if (surf)
 			dn_guide_surf_item(p, d, surf, i, ctx.stk);
 		else
 			dn_guide_item(p, d, i, ctx.stk);
@@ -775,6 +808,8 @@ void launch_kat(const Params &p, const SkyView &sky, const LightTreeView &lt, in
 	for (uint32_t i = 0; i < n; i++)
 		if (function == KAT_METER_BIN)
 			mt_kat_item(in, out, i);
+		else if (function == KAT_SURFACE_MAPS)
+			kat_maps_item(p, in, out, i);
 		else
 			kat_item<true>(p, sky, lt, function, in, out, i, pot);
 }

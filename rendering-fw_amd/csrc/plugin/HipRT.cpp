@@ -50,6 +50,10 @@
 // rfwhip_get_noise); a host asks hiprtGetNoise when to stop converging.  It answers for the accumulator — with frames in flight,
 // for the newest frame enqueued, not the one render_frame handed out.
 //
+// Material maps: RFWHIP_MATERIAL_MAPS=1 (unset by default: nothing changes) turns the setting material_maps on (include/rfwhip.h):
+// the path tracer reads the alpha mask and the roughness / metallic maps the system's materials carry.  hiprtGetSetting reads a
+// setting of the core back, the read-only ones included ("material_maps_on": do the next frame's shade waves run the map kernels?).
+//
 // Headless by default (RenderTarget::BUFFER, context.h:27-34): the GPU box has no OpenGL.  With
 // -DRFWHIP_PLUGIN_WITH_GL (needs GLEW, i.e. the reference's own build environment) render_frame also uploads the
 // float4 image into the GL texture handed to init(), the same way EmbreeRT presents (EmbreeRT/src/Context.cpp:289-297).
@@ -120,6 +124,7 @@ const EnvVar kEnv[] = {
 	{"RFWHIP_JPEG_SUBSAMPLING", "display_jpeg_subsampling"},
 	{"RFWHIP_JPEG_RESTART", "display_jpeg_restart"},
 	{"RFWHIP_NOISE", "noise_estimate", "0", "1"},
+	{"RFWHIP_MATERIAL_MAPS", "material_maps", "0", "1"},
 	{"RFWHIP_SKY_TABLE", "sky_table"},
 	{"RFWHIP_SKY_HDR", nullptr, nullptr, nullptr, HDR_FILE},
 };
@@ -465,6 +470,8 @@ class Context final : public rfw::RenderContext
 		return out;
 	}
 
+	int get_setting(const char *key, char *out, size_t cap) const { return rfwhip_get_setting(m_Cores[0], key, out, cap); }
+
 	rfwhip_group *group() const { return m_Group; }
 
   private:
@@ -526,4 +533,9 @@ HIPRT_EXPORT int hiprtGetNoise(rfw::RenderContext *ptr, rfwhip_noise_stats *stat
 HIPRT_EXPORT int hiprtGetExposure(rfw::RenderContext *ptr, rfwhip_meter_stats *stats)
 {
 	return static_cast<Context *>(ptr)->get_exposure(stats);
+}
+// ... and a setting of the core as text (include/rfwhip.h rfwhip_get_setting; every device holds the same): 0, or an rfwhip_status
+HIPRT_EXPORT int hiprtGetSetting(rfw::RenderContext *ptr, const char *key, char *out, size_t cap)
+{
+	return static_cast<Context *>(ptr)->get_setting(key, out, cap);
 }

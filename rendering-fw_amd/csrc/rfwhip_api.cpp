@@ -412,6 +412,12 @@ struct rfwhip_context
 	DevBuf d_materials, d_textures, d_tex_u32, d_tex_f4, d_sky, d_area, d_point, d_spot, d_dir;
 	uint32_t material_count = 0, texture_count = 0, sky_w = 0, sky_h = 0;
 	bool textured = false; // some material carries a map
+	// setting material_maps: the setting, and whether some material of the last rfwhip_set_materials has a
+	// present alpha, roughness or metallic map (present: the flag and a texture of the last rfwhip_set_textures) / a present mask
+	int material_maps = 0;
+	bool maps_present = false, mask_present = false;
+	struct MapSlots { uint32_t flags, addr6, addr7, addr9; };
+	std::vector<MapSlots> map_slots; // of the last rfwhip_set_materials, as resolved
 	// sky sampling (sky_sampling.h): the settings, and what the last rfwhip_update made of them
 	int sky_sampling = 0;
 	float sky_pick = -1.0f;		 // -1: auto (1 without lights, 0.5 with)
@@ -943,6 +949,20 @@ extern "C" int rfwhip_set_blue_noise(rfwhip_context *c, const uint32_t *table, s
 	return RFWHIP_OK;
 }
 
+// material_maps: is a slot 6, 7 or 9 of some material present (its flag bit 4, 5 or 13, and a texture behind its address)?
+static void update_maps_present(rfwhip_context *c)
+{
+	c->maps_present = false, c->mask_present = false;
+	for (const auto &m : c->map_slots)
+	{
+		const bool mask = (m.flags >> 13 & 1u) && m.addr9 < c->texture_count;
+		c->mask_present = c->mask_present || mask;
+		c->maps_present = c->maps_present || mask || ((m.flags >> 4 & 1u) && m.addr6 < c->texture_count) || ((m.flags >> 5 & 1u) && m.addr7 < c->texture_count);
+	}
+}
+// which kernels the next render runs: the MAPS variants (pt shade waves) / the guide pass's variant
+static bool material_maps_on(const rfwhip_context *c) { return c->material_maps && c->maps_present; }
+
 extern "C" int rfwhip_set_textures(rfwhip_context *c, const rfwhip_texture *tex, size_t count)
 {
 	CTX_ENTER(c);
@@ -982,6 +1002,7 @@ extern "C" int rfwhip_set_textures(rfwhip_context *c, const rfwhip_texture *tex,
 	RF_TRY(dm::h2d(c->d_tex_f4.p, f4s.data(), f4s.size() * sizeof(f4), c->stream));
 	RF_TRY(dm::sync(c->stream));
 	c->texture_count = (uint32_t)count;
+	update_maps_present(c);
 	c->tex_desc_host = desc, c->td_records.assign(count, rtk::TexRecord{0, 0, 0, 0, 0, 0, 0, 0}); // (rfwhip_read_texture, rfwhip_get_texture_decode)
 	c->scene_dirty = true;
 	return RFWHIP_OK;
@@ -1016,6 +1037,10 @@ extern "C" int rfwhip_set_materials(rfwhip_context *c, const rfwhip_material *ma
 	c->textured = false;
 	for (size_t i = 0; i < count; i++)
 		c->textured = c->textured || (mats[i].flags & 0x7BCu) != 0;
+	c->map_slots.resize(count);
+	for (size_t i = 0; i < count; i++)
+		c->map_slots[i] = {mats[i].flags, mats[i].map[6].addr, mats[i].map[7].addr, mats[i].map[9].addr};
+	update_maps_present(c);
 	c->scene_dirty = true;
 	return RFWHIP_OK;
 }
@@ -3244,7 +3269,9 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 				if (side && d >= 2 && d < c->max_depth) // connect(d - 2) read the buffers shade(d) is about to write
 					RF_TRY(dm::stream_wait_event(s, c->ev_conn[i][d - 2]));
 				StageTimer ts(c, KF_SHADE, -1, s);
-				if (c->light_sampling) // (linear | tree: k_shade_pt_lt; the view's nodes are null in linear)
+				if (material_maps_on(c)) // (k_shade_pt_maps<SKY, LT>)
+					rtk::launch_shade_pt_maps(p, c->sky_view, c->lt_view, c->light_sampling != 0, n_shade, s);
+				else if (c->light_sampling) // (linear | tree: k_shade_pt_lt; the view's nodes are null in linear)
 					rtk::launch_shade_pt_lt(p, c->sky_view, c->lt_view, n_shade, s);
 				else
 					rtk::launch_shade_pt(p, c->sky_view, n_shade, s);
@@ -3656,7 +3683,7 @@ static int dn_guides(rfwhip_context *c, void *stream)
 	RF_TRY(dm::zero(d.overflow, sizeof(uint32_t), stream));
 	StageTimer t(c, KF_DENOISE, -1, stream);
 	const bool motion = c->dn_temporal && c->dn_motion;
-	rtk::launch_denoise_guides(p, d, motion ? c->d_dn_surf.as<f4>() : nullptr, stream);
+	rtk::launch_denoise_guides(p, d, motion ? c->d_dn_surf.as<f4>() : nullptr, stream, c->material_maps && c->mask_present);
 	t.stop(2);
 	RF_TRY(dm::last_launch_error());
 	c->dn_g_rec_ok = motion;
@@ -4781,6 +4808,7 @@ extern "C" int rfwhip_set_texture_sources(rfwhip_context *c, const rfwhip_textur
 	std::swap(c->d_textures, n_desc), std::swap(c->d_tex_u32, n_tex), std::swap(c->d_tex_f4, n_f4), std::swap(c->d_td_rec, n_rec);
 	n_desc.free_(), n_tex.free_(), n_f4.free_(), n_rec.free_();
 	c->texture_count = (uint32_t)count, c->tex_desc_host = desc, c->td_records = records;
+	update_maps_present(c);
 	c->scene_dirty = true;
 	return RFWHIP_OK;
 }
@@ -5966,6 +5994,18 @@ static const Setting k_settings[] = {
 	{"shadow_bins_per_run", nullptr, GET { return put(out, cap, "%.3f", c->shadow_bins_per_run); }, false},
 	// read-only: which kernel variants the render calls launch (for hosts that label their measurements: bench.py)
 	{"textured", nullptr, GET { return put(out, cap, "%d", c->textured ? 1 : 0); }, false}, // some material carries a texture / normal map: k_shade_pt<true>
+	// material maps: the alpha mask of slot 9 and the roughness / metallic maps of slots 7 / 6 in the pt
+	// integrator.  A change makes the guides stale: the guide pass honours the mask
+	{"material_maps", SET {
+		 bool on;
+		 RF_TRY(parse_01(key, value, &on));
+		 if ((int)on != c->material_maps)
+			 c->guides_valid = false;
+		 c->material_maps = on;
+		 return RFWHIP_OK; },
+	 GET_INT(material_maps), false},
+	// read-only: the next render's pt shade waves run k_shade_pt_maps (the setting is on and some material has such a map)
+	{"material_maps_on", nullptr, GET { return put(out, cap, "%d", material_maps_on(c) ? 1 : 0); }, false},
 	// the pt primary wave runs in packet form (k_primary_packet) for sample groups >= 2 or large launches
 	{"packet", nullptr, GET { return put(out, cap, "%d", (c->packet_ok && (c->refill & 8)) ? 1 : 0); }, false},
 	// triangles in the world tree of the last rfwhip_update (0: none)
@@ -6755,6 +6795,7 @@ static_assert(sizeof(rfwhip_area_light) == sizeof(rt::AreaLight) && sizeof(rfwhi
 			  "rfwhip_set_lights hands its arrays to the light tree's builder as the kernels' records");
 static_assert(RFWHIP_KAT_LT_SAMPLE == rtk::KAT_LT_SAMPLE && RFWHIP_KAT_LT_PICK_PROB == rtk::KAT_LT_PICK_PROB, "kernels.h restates the light-tree functions");
 static_assert(RFWHIP_KAT_METER_BIN == rtk::KAT_METER_BIN, "kernels.h restates the meter's function");
+static_assert(RFWHIP_KAT_SURFACE_MAPS == rtk::KAT_SURFACE_MAPS, "kernels.h restates the material maps' function");
 static_assert(RFWHIP_KAT_IN == 24 && RFWHIP_KAT_OUT == 8, "kat_item's record layout (kernels.hip)");
 static_assert(RFWHIP_STRIP_ROWS == (int)rt::STRIP_ROWS, "rfwhip.h: rfwhip_row_owner() restates rt::strip_owner()");
 static_assert(sizeof(rfwhip_adaptive_stats) == 48, "rfwhip.h: six uint64");
@@ -6765,7 +6806,7 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 	CTX_ENTER(c);
 	if (n && (!in || !out))
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: null records");
-	if (function < 0 || function > RFWHIP_KAT_METER_BIN)
+	if (function < 0 || function > RFWHIP_KAT_SURFACE_MAPS)
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "rfwhip_kat: unknown function %d", function);
 	if ((function == RFWHIP_KAT_POINT_ON_LIGHT || function == RFWHIP_KAT_LIGHT_PICK_PROB) && c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the light functions use the lights of the last rfwhip_update()");
@@ -6790,10 +6831,11 @@ extern "C" int rfwhip_kat(rfwhip_context *c, int function, size_t n, const float
 	}
 	if (function == RFWHIP_KAT_BLUE_NOISE && !c->have_blue_noise)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: no blue-noise table (rfwhip_set_blue_noise)");
-	if ((function == RFWHIP_KAT_TEX_FETCH || function == RFWHIP_KAT_SURFACE_LAYERS) && c->scene_dirty)
+	const bool surface_fn = function == RFWHIP_KAT_SURFACE_LAYERS || function == RFWHIP_KAT_SURFACE_MAPS;
+	if ((function == RFWHIP_KAT_TEX_FETCH || surface_fn) && c->scene_dirty)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_kat: the texture functions use the scene of the last rfwhip_update()");
 	// (the kernel indexes the scene's tables with what the records name: every index is checked here)
-	for (size_t i = 0; i < n && (function == RFWHIP_KAT_TEX_FETCH || function == RFWHIP_KAT_SURFACE_LAYERS); i++)
+	for (size_t i = 0; i < n && (function == RFWHIP_KAT_TEX_FETCH || surface_fn); i++)
 	{
 		uint32_t ub[7];
 		memcpy(ub, in + i * RFWHIP_KAT_IN, sizeof(ub));

@@ -938,7 +938,11 @@ enum
 	MF_2ND_DIFFUSE_MAP = 9,
 	MF_3RD_DIFFUSE_MAP = 10,
 	MF_SMOOTH_NORMALS = 11,
-	MF_ALPHA = 12
+	MF_ALPHA = 12,
+	// (setting material_maps alone reads these three: the MAPS variants)
+	MF_SPECULARITY_MAP = 4,
+	MF_ROUGHNESS_MAP = 5,
+	MF_ALPHA_MAP = 13
 };
 
 RT_FN f3 mul_normal(const Instance &in, f3 n)
@@ -2066,24 +2070,30 @@ RT_FN bool pt_has_textures(const SceneView &sc, const Surface &sf)
 {
 	return mat_flag(sf.mflags, MF_DIFFUSE_MAP) && sf.mat->map[0].addr < sc.texture_count;
 }
+// the interpolated texture coordinates of a hit and the level of detail its cone asks for
+RT_FN void pt_tex_coords(const SceneView &sc, const CamView &cam, f3 D, float t, const Surface &sf, float &tu, float &tv, float &lambda)
+{
+	const TriUV &uv = sc.tri_uv[sf.shade_idx];
+	const f4 tu4 = uv.tu, tv4 = uv.tv;
+	tu = sf.bw0 * tu4.x + sf.bw1 * tu4.y + sf.bw2 * tu4.z;
+	tv = sf.bw0 * tv4.x + sf.bw1 * tv4.y + sf.bw2 * tv4.z;
+	const float coneWidth = cam.spread_angle * t;
+	lambda = sf.lod + m_log2f(coneWidth * m_rcp(fabsf(dot(D * -1.0f, sf.N))));
+}
+// map slots: 0-2 diffuse layers, 3-5 normal-map layers (structs.h:98-115); 6 specularity, 7 roughness, 9 alpha mask (pt_maps below)
+#define RT_LAYER(K) \
+	fetch_trilinear(sc, sc.textures[mat.map[K].addr], lambda,                                          \
+					half_to_float(mat.map[K].uscale) * (half_to_float(mat.map[K].uoffs) + tu),         \
+					half_to_float(mat.map[K].vscale) * (half_to_float(mat.map[K].voffs) + tv), mat.map[K].width, \
+					mat.map[K].height)
 // the texture layers of a textured hit: color = the material's colour on entry; Tg / Bt = the tangent frame of the unperturbed
 // shading normal (tools.h:204-211)
 RT_FN void pt_textures(const SceneView &sc, const CamView &cam, f3 D, float t, const Surface &sf, f3 &color, f3 &iN, bool &alpha_skip)
 {
 	const MaterialRec &mat = *sf.mat;
 	const uint32_t mflags = sf.mflags;
-	const TriUV &uv = sc.tri_uv[sf.shade_idx];
-	const f4 tu4 = uv.tu, tv4 = uv.tv;
-	const float tu = sf.bw0 * tu4.x + sf.bw1 * tu4.y + sf.bw2 * tu4.z;
-	const float tv = sf.bw0 * tv4.x + sf.bw1 * tv4.y + sf.bw2 * tv4.z;
-	const float coneWidth = cam.spread_angle * t;
-	const float lambda = sf.lod + m_log2f(coneWidth * m_rcp(fabsf(dot(D * -1.0f, sf.N))));
-	// map slots: 0-2 diffuse layers, 3-5 normal-map layers (structs.h:98-115)
-#define RT_LAYER(K) \
-	fetch_trilinear(sc, sc.textures[mat.map[K].addr], lambda,                                          \
-					half_to_float(mat.map[K].uscale) * (half_to_float(mat.map[K].uoffs) + tu),         \
-					half_to_float(mat.map[K].vscale) * (half_to_float(mat.map[K].voffs) + tv), mat.map[K].width, \
-					mat.map[K].height)
+	float tu, tv, lambda;
+	pt_tex_coords(sc, cam, D, t, sf, tu, tv, lambda);
 #define RT_NORMAL_LAYER(K) \
 	((xyz(fetch_texel(sc, sc.textures[mat.map[K].addr],                                                \
 					  half_to_float(mat.map[K].uscale) * (half_to_float(mat.map[K].uoffs) + tu),       \
@@ -2119,9 +2129,62 @@ RT_FN void pt_textures(const SceneView &sc, const CamView &cam, f3 D, float t, c
 		// getShadingData.h:150 and :206 both multiply by the texel
 		color = color * xyz(texel);
 	}
-#undef RT_LAYER
 #undef RT_NORMAL_LAYER
 }
+// ---- setting material_maps (include/rfwhip.h): the alpha mask of slot 9 and the roughness / metallic maps of
+// slots 7 / 6.  The MAPS variants of the shade kernels, the guide pass's and the known-answer function surface_maps alone call these.
+// A slot is present when its flag is set and its texture exists, whether or not the material has a diffuse map
+RT_FN bool pt_map_present(const SceneView &sc, const Surface &sf, int bit, int slot)
+{
+	return mat_flag(sf.mflags, bit) && sf.mat->map[slot].addr < sc.texture_count;
+}
+// the 8 bits the BSDF reads of a parameter: clamped to [0, 1], rounded to the nearest byte; a NaN gives 0
+RT_FN uint32_t pt_map_byte(float v)
+{
+	const float c = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f; // (= fminf(fmaxf(v, 0), 1) for every v, the NaN included)
+	return (uint32_t)(c * 255.0f + 0.5f);
+}
+// The mask: a = min(red, alpha) of slot 9's texel — a grey mask with alpha 255 gives its grey, a white one with an alpha channel its
+// alpha; a < 0.5 is MF_ALPHA's pass-through.  false, a = 1: the material has no mask.
+RT_FN bool pt_maps_alpha(const SceneView &sc, const CamView &cam, f3 D, float t, const Surface &sf, float &a)
+{
+	a = 1.0f;
+	if (!pt_map_present(sc, sf, MF_ALPHA_MAP, 9))
+		return false;
+	const MaterialRec &mat = *sf.mat;
+	float tu, tv, lambda;
+	pt_tex_coords(sc, cam, D, t, sf, tu, tv, lambda);
+	const f4 texel = RT_LAYER(9);
+	a = fminf(texel.x, texel.w);
+	return a < 0.5f;
+}
+// Roughness (the top byte of p0) times the green of slot 7's texel, metallic (the low byte) times the blue of slot 6's — glTF's
+// packing — requantised into p0; sd_*, and with them the specular test and the BSDF, read the mapped bytes.  A host points both slots
+// at one metallic-roughness texture: with the same descriptor in both, one fetch serves both (the same texel, to the bit).
+RT_FN void pt_maps_params(const SceneView &sc, const CamView &cam, f3 D, float t, const Surface &sf, uint32_t &p0)
+{
+	const bool has_m = pt_map_present(sc, sf, MF_SPECULARITY_MAP, 6), has_r = pt_map_present(sc, sf, MF_ROUGHNESS_MAP, 7);
+	if (!has_m && !has_r)
+		return;
+	const MaterialRec &mat = *sf.mat;
+	float tu, tv, lambda;
+	pt_tex_coords(sc, cam, D, t, sf, tu, tv, lambda);
+	const bool shared = has_m && has_r && mat.map[6].addr == mat.map[7].addr && mat.map[6].width == mat.map[7].width &&
+						mat.map[6].height == mat.map[7].height && mat.map[6].uscale == mat.map[7].uscale &&
+						mat.map[6].vscale == mat.map[7].vscale && mat.map[6].uoffs == mat.map[7].uoffs && mat.map[6].voffs == mat.map[7].voffs;
+	f4 tr = mk4(0, 0, 0, 0);
+	if (has_r)
+	{
+		tr = RT_LAYER(7);
+		p0 = (p0 & 0x00FFFFFFu) | (pt_map_byte(chan(p0, 24) * tr.y) << 24);
+	}
+	if (has_m)
+	{
+		const f4 tm = shared ? tr : RT_LAYER(6);
+		p0 = (p0 & 0xFFFFFF00u) | pt_map_byte(chan(p0, 0) * tm.z);
+	}
+}
+#undef RT_LAYER
 // One path vertex, in PHASES every lane of the calling wave passes through together (round 6: until then the function returned from
 // half a dozen places and handed both of its rays back at the end — the shadow ray's twelve registers stayed live across the BSDF
 // sampling, the tangent frame and the absorption across the light sampling):
@@ -2141,7 +2204,9 @@ RT_FN void pt_textures(const SceneView &sc, const CamView &cam, f3 D, float t, c
 // the light tree, or by today's potentials when lt.nodes is null — and the weights are consistent: an area light's next-event term
 // divides by shadowPdf + q p_omega with its solid-angle density p_omega, a delta light's by q lightPdf alone, and an emitter a BSDF
 // ray finds takes its q from the rule that picks.  Every line of it sits under LT.
-template <bool TEX, bool SKY, bool LT, class Sink>
+// MAPS = true (setting material_maps, and some material has such a map): the alpha mask joins MF_ALPHA's test, and a vertex that goes
+// on reads its roughness and metallic through their maps.  Every line of it sits under MAPS.
+template <bool TEX, bool SKY, bool LT, bool MAPS, class Sink>
 RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const LightTreeView &lt, const CamView &cam, const FrameView &fr, uint32_t max_depth, bool active,
 					const PathIn &in, const Hit &h, ShadeOut &out, float *pot_cache, Sink &sink RT_CLK_PARAM)
 {
@@ -2196,6 +2261,11 @@ RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const LightTreeView
 		bool alpha_skip = false;
 		if (TEX && pt_has_textures(sc, sf))
 			pt_textures(sc, cam, D, h.t, sf, sd.color, iN, alpha_skip);
+		if (MAPS && !alpha_skip)
+		{
+			float a;
+			alpha_skip = pt_maps_alpha(sc, cam, D, h.t, sf, a);
+		}
 		// the path's pixel and sample: the key of its random numbers (and the probe pixel of the primary wave)
 		const PixelRef pr = slot_to_pixel(fr, in.slot);
 		const uint32_t pixel = pr.y * fr.W + pr.x, sampleIdx = fr.sample_base + pr.sample;
@@ -2252,6 +2322,8 @@ RT_FN void pt_shade(const SceneView &sc, const SkyView &sky, const LightTreeView
 		{
 			regular = true;
 			RT_TICK(4);
+			if (MAPS)
+				pt_maps_params(sc, cam, D, h.t, sf, sd.p0);
 			if (sd_roughness(sd) < 0.01f)
 				flags |= 1u;
 			else

@@ -1,6 +1,6 @@
 // shade_pt_body.h — the body of the pt shade kernel, included by its kernels in kernels.hip: k_shade_pt<TEX> (SKY = false,
 // the default), k_shade_pt_sky<TEX> (SKY = true, setting sky_sampling) and k_shade_pt_lt<TEX, SKY> (LT = true, setting
-// light_sampling).  In scope there: TEX, SKY, LT, `p` (the kernel's Params), `sky` (the sky-sampling view; unread when SKY is
+// light_sampling); k_shade_pt_maps<SKY, LT> (MAPS = true, setting material_maps).  In scope there: TEX, SKY, LT, MAPS, `p` (the kernel's Params), `sky` (the sky-sampling view; unread when SKY is
 // false) and `lt` (the light-tree view; unread when LT is false).  The body is spelled out inside each kernel instead of living in a
 // function the kernels call: with the Params a function argument rather than the kernel's own, the compiler orders some
 // commutative operands differently, and the default kernels' code is meant to stay exactly what it was.
@@ -137,11 +137,11 @@
 			break;
 		__builtin_amdgcn_wave_barrier();
 #if defined(RT_DIAG_SHADE_CLOCK)
-		shade_pt_item<TEX, SKY, LT>(p, sky, lt, idx, act, h4, hi, ctx, &clk);
+		shade_pt_item<TEX, SKY, LT, MAPS>(p, sky, lt, idx, act, h4, hi, ctx, &clk);
 #else
 		// (the kernel's arguments read again from the kernarg segment — scalar loads — instead of staying live across the loop: with
 		// ~150 wave-uniform words of scene, wave buffers, camera and frame the compiler parks them in VGPR lanes, a v_readlane per use)
-		shade_pt_item<TEX, SKY, LT>(fresh_params(), sky, lt, idx, act, h4, hi, ctx);
+		shade_pt_item<TEX, SKY, LT, MAPS>(fresh_params(), sky, lt, idx, act, h4, hi, ctx);
 #endif
 	}
 #if defined(RT_DIAG_SHADE_CLOCK)

@@ -17,13 +17,17 @@ What it restates from the reference (which parses with tinygltf, a third-party l
                     and normalTexture become texture sources (images.py): a JPEG stays encoded and is decoded, linearised and
                     mipped on the device (rfwhip_set_texture_sources), a PNG's pixels likewise.  glTF's uv origin is the image's
                     top-left corner and the sampler's row 0 is v = 0, so the rows are NOT flipped.  Off by default.
+                    metallicRoughnessTexture becomes the material's roughness AND metallic map (G scales roughnessFactor, B scales
+                    metallicFactor: the setting material_maps, include/rfwhip.h) — a data texture, not linearised, as normal maps are
+  * alphaMode       "MASK" sets the material's alpha flag: the base colour texture's alpha below 0.5 lets a path through.  The
+                    cutoff is the core's 0.5; an alphaCutoff other than 0.5 is out of scope and is not read.  "BLEND" is opaque.
   * the device's animation path  `Gltf.rig()` packs nodes, skins, channels and keys into the flat tables of rfwhip_set_rig; the scene
                     `load_scene` returns carries that rig and which mesh follows which skin or node, `bind_scene(ctx, scene)` hands
                     them to a context, and a frame's animation is then `ctx.animate(0, time); ctx.update()` — set_time /
                     joint_matrices below stay as the host's float64 statement of the same rule (include/rfwhip.h, rfwhip_animate)
-Not covered: cameras, KHR extensions, sparse accessors, texture transforms and samplers' wrap modes; materials map
-baseColorFactor / metallic / roughness and, with load_images, the two textures above.  File parsing itself is plain
-json + base64 / external buffers + numpy.
+Not covered: cameras, KHR extensions, sparse accessors, texture transforms and samplers' wrap modes, emissive and occlusion
+textures, alphaMode BLEND and alphaCutoff; materials map baseColorFactor / metallic / roughness / alphaMode MASK and, with
+load_images, the three textures above.  File parsing itself is plain json + base64 / external buffers + numpy.
 """
 import base64
 import json
@@ -300,30 +304,33 @@ class Gltf:
         return bytes(self.buffers[v["buffer"]][off:off + v["byteLength"]])
 
     def material_images(self, idx):
-        """(image index of the base colour texture, of the normal texture), None where the material carries none."""
+        """(image index of the base colour texture, of the normal texture, of the metallic-roughness texture), None where the
+        material carries none."""
         if idx < 0:
-            return None, None
+            return None, None, None
         m = self.doc["materials"][idx]
+        pbr = m.get("pbrMetallicRoughness", {})
         out = []
-        for ref in (m.get("pbrMetallicRoughness", {}).get("baseColorTexture"), m.get("normalTexture")):
+        for ref in (pbr.get("baseColorTexture"), m.get("normalTexture"), pbr.get("metallicRoughnessTexture")):
             out.append(None if ref is None else self.doc["textures"][ref["index"]].get("source"))
         return tuple(out)
 
     def material(self, idx):
         if idx < 0:
             return scenes.host_material()
-        pbr = self.doc["materials"][idx].get("pbrMetallicRoughness", {})
+        m = self.doc["materials"][idx]
+        pbr = m.get("pbrMetallicRoughness", {})
         c = pbr.get("baseColorFactor", (1, 1, 1, 1))
         return scenes.host_material(color=tuple(float(v) for v in c[:3]), metallic=float(pbr.get("metallicFactor", 1.0)),
-                                    roughness=float(pbr.get("roughnessFactor", 1.0)))
+                                    roughness=float(pbr.get("roughnessFactor", 1.0)), alpha=m.get("alphaMode", "OPAQUE") == "MASK")
 
 
 def load_scene(path, width=480, height=270, load_images=False):
     """A Scene with one mesh + instance per mesh node (first primitive), the node transforms as instance transforms, and
     per mesh node the rig (joints, weights, bind normals) when it is skinned.  Returns (scene, gltf, rigs) with
     rigs = {scene mesh index: (node index, joints, weights, normals)}.  The scene also carries `rig` (Gltf.rig(), None when no mesh
-    is skinned or morphed) and `rig_bindings` for bind_scene.  load_images: the materials' base colour (sRGB -> linear)
-    and normal textures become texture sources the device decodes (module docstring)."""
+    is skinned or morphed) and `rig_bindings` for bind_scene.  load_images: the materials' base colour (sRGB -> linear),
+    normal and metallic-roughness textures (both as they are) become texture sources the device decodes (module docstring)."""
     g = Gltf(path)
     s = scenes.Scene()
     s.name = os.path.basename(path)
@@ -343,8 +350,9 @@ def load_scene(path, width=480, height=270, load_images=False):
         if prim["material"] not in mats:
             kw = g.material(prim["material"])
             if load_images:
-                base, normal = g.material_images(prim["material"])
+                base, normal, mr = g.material_images(prim["material"])
                 kw["texture"], kw["normalmap"] = texture(base, "srgb"), texture(normal, None)
+                kw["roughnessmap"] = kw["metallicmap"] = texture(mr, None)
             mats[prim["material"]] = s.add_material(**kw)
         m = s.add_mesh(prim["positions"], prim["indices"], normals=prim["normals"], uvs=prim["uvs"], material=mats[prim["material"]])
         # skinned meshes are posed in mesh space by the joint matrices; the node transform places the instance

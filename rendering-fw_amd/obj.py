@@ -9,8 +9,9 @@ core (object.cpp:1105-1123): assimp splits an object wherever the material chang
   * vertices joined per unique (position, texcoord, normal) index triple (JoinIdenticalVertices);
   * normals from the file when every corner of the mesh has one, else smooth normals generated per POSITION: the sum of the
     incident face normals, area-weighted (GenSmoothNormals; assimp's exact weighting depends on its version);
-  * materials from the .mtl: Kd -> colour, Ns -> roughness = sqrt(2 / (Ns + 2)), d / Tr -> ignored, map_Kd is recorded by name
-    and, with load_scene(load_images=True), loaded as the material's diffuse texture (images.py); a face before any `usemtl` gets a default material.
+  * materials from the .mtl: Kd -> colour, Ns -> roughness = sqrt(2 / (Ns + 2)), d / Tr -> ignored, map_Kd and map_d are recorded by
+    name and, with load_scene(load_images=True), loaded as the material's diffuse texture and alpha mask (images.py; the mask is read
+    with the setting material_maps); a face before any `usemtl` gets a default material.
 
 Smoothing groups (`s`) do not change the result: with vn records the file's normals are used as they are, without them
 GenSmoothNormals smooths over every shared position regardless of group.
@@ -33,13 +34,13 @@ def parse_mtl(path):
             if not t or t[0].startswith("#"):
                 continue
             if t[0] == "newmtl":
-                cur = mats.setdefault(" ".join(t[1:]), {"Kd": (0.6, 0.6, 0.6), "Ns": None, "map_Kd": None})
+                cur = mats.setdefault(" ".join(t[1:]), {"Kd": (0.6, 0.6, 0.6), "Ns": None, "map_Kd": None, "map_d": None})
             elif cur is not None and t[0] == "Kd" and len(t) >= 4:
                 cur["Kd"] = tuple(float(x) for x in t[1:4])
             elif cur is not None and t[0] == "Ns" and len(t) >= 2:
                 cur["Ns"] = float(t[1])
-            elif cur is not None and t[0] == "map_Kd":
-                cur["map_Kd"] = " ".join(t[1:])
+            elif cur is not None and t[0] in ("map_Kd", "map_d"):
+                cur[t[0]] = " ".join(t[1:])
     return mats
 
 
@@ -91,7 +92,7 @@ def load_obj(path):
         tris = groups[name]
         if not tris:
             continue
-        m = mtl.get(name, {"Kd": (0.6, 0.6, 0.6), "Ns": None, "map_Kd": None})
+        m = mtl.get(name, {"Kd": (0.6, 0.6, 0.6), "Ns": None, "map_Kd": None, "map_d": None})
         materials.append((name, m))
         corner = np.asarray(tris, np.int64).reshape(-1, 3)           # (3F, 3): position, texcoord, normal index
         uniq, inv = np.unique(corner, axis=0, return_inverse=True)   # JoinIdenticalVertices
@@ -119,8 +120,9 @@ def load_obj(path):
 
 def load_scene(path, width=480, height=270, load_images=False):
     """A Scene with one mesh + identity instance per material group of the file.  load_images: a material's map_Kd, resolved beside
-    the .mtl (the .obj's directory), becomes a texture source the device decodes (images.py; sRGB -> linear).  OBJ's v = 0 is the
-    image's bottom row and the sampler's row 0 is v = 0, so the rows ARE flipped.  Off by default."""
+    the .mtl (the .obj's directory), becomes a texture source the device decodes (images.py; sRGB -> linear), its map_d the alpha
+    mask (`alphamap`, as it is: a data texture).  OBJ's v = 0 is the image's bottom row and the sampler's row 0 is v = 0, so the rows
+    ARE flipped.  Off by default."""
     materials, meshes = load_obj(path)
     s = scenes.Scene()
     s.name = os.path.basename(path)
@@ -129,13 +131,14 @@ def load_scene(path, width=480, height=270, load_images=False):
     base = os.path.dirname(os.path.abspath(path))
     for name, m in materials:
         rough = 1.0 if m["Ns"] is None else max(0.05, min(1.0, math.sqrt(2.0 / (m["Ns"] + 2.0))))
-        tex = -1
-        if load_images and m["map_Kd"]:
-            file = os.path.join(base, m["map_Kd"].replace("\\", "/"))
-            if file not in texs:
-                texs[file] = s.add_texture(images.texture_from_file(file, flip=True, linearize="srgb"))
-            tex = texs[file]
-        ids.append(s.add_material(color=tuple(m["Kd"]), roughness=rough, texture=tex))
+        tex = {"map_Kd": -1, "map_d": -1}
+        for key, linearize in (("map_Kd", "srgb"), ("map_d", None)):
+            if load_images and m.get(key):
+                file = os.path.join(base, m[key].replace("\\", "/"))
+                if (file, linearize) not in texs:
+                    texs[(file, linearize)] = s.add_texture(images.texture_from_file(file, flip=True, linearize=linearize))
+                tex[key] = texs[(file, linearize)]
+        ids.append(s.add_material(color=tuple(m["Kd"]), roughness=rough, texture=tex["map_Kd"], alphamap=tex["map_d"]))
     for me in meshes:
         s.add_instance(s.add_mesh(me["vertices"], me["indices"], normals=me["normals"], uvs=me["uvs"], material=ids[me["material"]]))
     return s, materials, meshes

@@ -34,16 +34,18 @@ def host_material(color=(1.0, 1.0, 1.0), roughness=0.5, metallic=0.0, subsurface
                   anisotropic=0.0, sheen=0.0, sheenTint=0.0, clearcoat=0.0, clearcoatGloss=1.0, transmission=0.0,
                   eta=1.0, absorption=(0.0, 0.0, 0.0), smooth=True, texture=-1, uvscale=(1.0, 1.0),
                   uvoffset=(0.0, 0.0), texture1=-1, texture2=-1, normalmap=-1, normalmap1=-1, normalmap2=-1,
-                  alpha=False):
+                  alpha=False, roughnessmap=-1, metallicmap=-1, alphamap=-1):
     """HostMaterial with the reference's defaults (material_list.h:48-66).  texture/texture1/texture2 are the diffuse
     layers (map[TEXTURE0..2]), normalmap/normalmap1/normalmap2 the normal-map layers (map[NORMALMAP0..2]); all layers
-    share uvscale / uvoffset here.  alpha = the HASALPHA host flag."""
+    share uvscale / uvoffset here.  alpha = the HASALPHA host flag.  roughnessmap / metallicmap / alphamap are the maps the
+    setting material_maps reads (map[ROUGHNESS0], map[SPECULARITY], map[ALPHAMASK]): green scales roughness, blue scales metallic —
+    a glTF metallic-roughness texture goes to both — and min(red, alpha) < 0.5 lets a path through."""
     return dict(color=color, roughness=roughness, metallic=metallic, subsurface=subsurface, specular=specular,
                 specularTint=specularTint, anisotropic=anisotropic, sheen=sheen, sheenTint=sheenTint,
                 clearcoat=clearcoat, clearcoatGloss=clearcoatGloss, transmission=transmission, eta=eta,
                 absorption=absorption, smooth=smooth, texture=texture, uvscale=uvscale, uvoffset=uvoffset,
                 texture1=texture1, texture2=texture2, normalmap=normalmap, normalmap1=normalmap1,
-                normalmap2=normalmap2, alpha=alpha)
+                normalmap2=normalmap2, alpha=alpha, roughnessmap=roughnessmap, metallicmap=metallicmap, alphamap=alphamap)
 
 
 def pack_materials(host_materials, textures, faithful=False):
@@ -52,7 +54,8 @@ def pack_materials(host_materials, textures, faithful=False):
 
     faithful=True reproduces two quirks of the reference's packer: a second diffuse layer sets the Has2ndNormalMap
     bit instead of Has2ndDiffuseMap (:372), and every present map writes its texture id into texaddr0 (:385-455), so
-    only MaterialTexIds says which texture belongs to which slot.  The default packs what was meant."""
+    only MaterialTexIds says which texture belongs to which slot.  The default packs what was meant.  The quirk covers the roughness
+    and the specularity map (in that order, :441-460); the alpha mask's descriptor gets no address at all there (:471-478)."""
     out = np.zeros(len(host_materials), dtype=abi.MATERIAL_DTYPE)
     ids = np.full((len(host_materials), 11), -1, dtype=np.int32)
     for i, m in enumerate(host_materials):
@@ -70,13 +73,15 @@ def pack_materials(host_materials, textures, faithful=False):
             flags |= 1 << abi.MAT_HAS_SMOOTH_NORMALS
         if m.get("alpha", False):
             flags |= 1 << abi.MAT_HAS_ALPHA
-        # (host field, map slot = MaterialTexIds index, flag)
-        layers = [("texture", 0, abi.MAT_HAS_DIFFUSE_MAP),
-                  ("texture1", 1, abi.MAT_HAS_2ND_NORMAL_MAP if faithful else abi.MAT_HAS_2ND_DIFFUSE_MAP),
-                  ("texture2", 2, abi.MAT_HAS_3RD_DIFFUSE_MAP),
-                  ("normalmap", 3, abi.MAT_HAS_NORMAL_MAP), ("normalmap1", 4, abi.MAT_HAS_2ND_NORMAL_MAP),
-                  ("normalmap2", 5, abi.MAT_HAS_3RD_NORMAL_MAP)]
-        for field, slot, flag in layers:
+        # (host field, map slot, MaterialTexIds index, flag)
+        layers = [("texture", 0, 0, abi.MAT_HAS_DIFFUSE_MAP),
+                  ("texture1", 1, 1, abi.MAT_HAS_2ND_NORMAL_MAP if faithful else abi.MAT_HAS_2ND_DIFFUSE_MAP),
+                  ("texture2", 2, 2, abi.MAT_HAS_3RD_DIFFUSE_MAP),
+                  ("normalmap", 3, 3, abi.MAT_HAS_NORMAL_MAP), ("normalmap1", 4, 4, abi.MAT_HAS_2ND_NORMAL_MAP),
+                  ("normalmap2", 5, 5, abi.MAT_HAS_3RD_NORMAL_MAP),
+                  ("roughnessmap", 7, 7, abi.MAT_HAS_ROUGHNESS_MAP), ("metallicmap", 6, 6, abi.MAT_HAS_SPECULARITY_MAP),
+                  ("alphamap", 9, 10, abi.MAT_HAS_ALPHA_MAP)]
+        for field, slot, tex_id, flag in layers:
             t = m.get(field, -1)
             if t < 0:
                 continue
@@ -88,11 +93,11 @@ def pack_materials(host_materials, textures, faithful=False):
             d["width"], d["height"] = tex["width"], tex["height"]
             d["uscale"], d["vscale"] = np.float16(m["uvscale"][0]), np.float16(m["uvscale"][1])
             d["uoffs"], d["voffs"] = np.float16(m["uvoffset"][0]), np.float16(m["uvoffset"][1])
-            if faithful:
-                o["map"][0]["addr"] = t
-            else:
+            if not faithful:
                 d["addr"] = t
-            ids[i, slot] = t
+            elif slot != 9:
+                o["map"][0]["addr"] = t
+            ids[i, tex_id] = t
         o["flags"] = flags
     return out, ids.view(abi.MATERIAL_TEX_IDS_DTYPE).reshape(-1)
 
