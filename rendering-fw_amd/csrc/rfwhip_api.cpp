@@ -99,6 +99,103 @@ struct DevBuf
 	template <typename T> T *as() const { return (T *)p; }
 };
 
+// "Work I enqueued on a stream that is not mine may still be running": the record behind that work.  The context keeps every one of
+// them in rfwhip_context::marks, which sync_all (before anything frees or rewrites device memory) and free_all walk: a mark outside
+// that array does not exist.  `pending` is the host's view (nobody has waited for the record on the host); a stream that must run
+// behind the record waits for it on the device (wait_on), which leaves `pending` alone.
+struct StreamMark
+{
+	dm::event_t ev;
+	bool timed = false;		// how the event is created (set once, in rfwhip_create)
+	bool ready = false;		// ev exists: it is created by the first record, so it has held one ever since
+	bool pending = false;	// the last record has not been waited for on the host
+	void *stream = nullptr; // the stream of the last record
+	int record(void *s, bool host_wait)
+	{
+		if (!ready)
+		{
+			RF_TRY(dm::event_create(&ev, timed));
+			ready = true;
+		}
+		RF_TRY(dm::event_record(ev, s));
+		stream = s, pending = host_wait;
+		return 0;
+	}
+	int wait_on(void *s) { return ready ? dm::stream_wait_event(s, ev) : 0; } // device side: s runs behind the last record
+	int sync()																   // host side
+	{
+		if (pending)
+			RF_TRY(dm::event_sync(ev));
+		pending = false;
+		return 0;
+	}
+	void destroy()
+	{
+		if (ready)
+			dm::event_destroy(ev);
+		ready = false, pending = false, stream = nullptr;
+	}
+
+private:
+	StreamMark() {} // (only rfwhip_context::marks can hold one: a mark elsewhere does not compile)
+	friend struct rfwhip_context;
+};
+enum MarkId
+{
+	MK_PRESENT = 0, // a present on a caller's stream (rfwhip_read_local_framebuffer_stream) still reads the accumulator
+	MK_DENOISE,		// a denoise on a gather stream reads the scene and the guides
+	MK_METER,		// a meter step on a caller's stream writes the record and the histogram
+	MK_BLOOM,		// the last bloom chain and the display kernel that read its image, on any stream: they write / read the pyramid
+	MK_GRADE,		// a graded display kernel on a caller's stream reads the LUT
+	MK_JPEG,		// the last encode, on any stream: it writes the JPEG scratch
+	MK_COUNT
+};
+
+// A table that is rewritten on the main stream and read by primary waves on the sub-batch streams.  Behind a rewrite the main stream
+// records ev and the serial goes up (publish); a sub-batch stream that has not waited for that record yet does so before its next
+// primary wave (acquire); a stream whose wave reads the table says so (read_by), and the next rewrite waits for that sub-batch's
+// end first (before_rewrite).  ev is created and destroyed with the render loop's own events.
+constexpr int MAX_SUB_BATCHES = 8;
+struct rfwhip_context;
+struct Published
+{
+	dm::event_t ev;
+	uint64_t serial = 0, seen[MAX_SUB_BATCHES] = {};
+	bool reader[MAX_SUB_BATCHES] = {}; // a primary wave of this sub-batch slot has read the table since its last rewrite
+	int publish(void *main_stream)
+	{
+		RF_TRY(dm::event_record(ev, main_stream));
+		serial++;
+		return 0;
+	}
+	int acquire(int i, void *s)
+	{
+		if (seen[i] != serial)
+		{
+			RF_TRY(dm::stream_wait_event(s, ev));
+			seen[i] = serial;
+		}
+		return 0;
+	}
+	void read_by(int i) { reader[i] = true; }
+	int before_rewrite(rfwhip_context *c); // (below the context)
+};
+
+// The milliseconds and launches of one kernel family by kernel (stage_timing = 1), and the read-only setting that prints them
+struct KindTimes
+{
+	static constexpr int MAX_KINDS = 9;
+	int count = 0;
+	float ms[MAX_KINDS] = {};
+	uint32_t launches[MAX_KINDS] = {};
+	void add(int kind, float t) { ms[kind] += t, launches[kind]++; }
+	void reset()
+	{
+		for (int k = 0; k < MAX_KINDS; k++)
+			ms[k] = 0.0f, launches[k] = 0;
+	}
+};
+
 // =================================================================================================================
 // context
 // =================================================================================================================
@@ -259,7 +356,7 @@ struct rfwhip_context
 {
 	int device = 0, rank = 0, world = 1, cus = 256;
 	void *stream = nullptr; // main stream: scene uploads, refits, prologue, resolve, presents
-	static constexpr int MAX_SUB = 8;
+	static constexpr int MAX_SUB = MAX_SUB_BATCHES;
 	static constexpr int MAX_RING = 4;
 	// every sub-batch of a render call runs on its own stream, its connection (shadow) waves on a second one beside it
 	void *sub_stream[MAX_SUB] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -279,8 +376,10 @@ struct rfwhip_context
 	int ring_active = 0;	  // ring size of the calls in flight (2 for calls cut into sub-batches: radiance double-buffered)
 	size_t paths_active = 0;  // path slots per call of the calls in flight
 	int subs_active = 0;	  // ... and their sub-batch count
-	dm::event_t ev_present_in, ev_present_out; // hand-off to / from a caller's stream (rfwhip_*_stream)
-	bool present_pending = false;
+	dm::event_t ev_present_in; // hand-off to a caller's stream (rfwhip_*_stream); the way back is marks[MK_PRESENT]
+	// work enqueued on streams that are not this context's (StreamMark): every one of them, by MarkId.  When each records and who
+	// waits for it besides sync_all stands at its *_mark function or its recording site
+	StreamMark marks[MK_COUNT];
 	bool events_ready = false;
 	size_t last_wave_off = 0; // where the most recent call's first sub-batch keeps its per-path records
 	int subs_last = 1, subs_first = 0; // sub-batch slots of the most recent render call: subs_first .. subs_first + subs_last - 1
@@ -317,8 +416,8 @@ struct rfwhip_context
 									// stream, in front of it — what a per-stage timing wants)
 	bool shadow_packets_auto_on = true; // -1: what the last waited frame's bins per run said (reset to true by rfwhip_update)
 	double shadow_bins_per_run = 0.0;
-	unsigned long long sp_seen[MAX_SUB][2] = {};
-	unsigned long long fused_ticks_seen[MAX_SUB][rt::MAX_DEPTH_SLOTS][2] = {}; // WaveCounters::fused_ticks at the last rfwhip_wait, per counter set
+	unsigned long long sp_at_wait[MAX_SUB][2] = {};
+	unsigned long long fused_ticks_at_wait[MAX_SUB][rt::MAX_DEPTH_SLOTS][2] = {}; // WaveCounters::fused_ticks at the last rfwhip_wait, per counter set
 	long long flatten_bytes = 1ll << 28; // ... as long as the world-space copy stays below this many bytes (256 MiB = 2.4 M triangles:
 										 // the tree is built on the host inside rfwhip_update, ~0.2 s per million triangles on 16 cores)
 	WorldRec wtree;
@@ -338,8 +437,6 @@ struct rfwhip_context
 	bool have_last_cam = false;
 	unsigned long long scene_version = 0, guide_scene = 0; // scene_version: rfwhip_update calls
 	uint32_t guide_W = 0, guide_H = 0;
-	dm::event_t ev_dn;	  // behind the last denoise enqueued on a caller's stream (the group / comm gather)
-	bool dn_pending = false;
 	// ... its temporal stage (setting "denoise_temporal"): P = the last presented frame, F = the frame being presented
 	int dn_temporal = 0;
 	float dn_alpha = 0.2f;
@@ -386,16 +483,14 @@ struct rfwhip_context
 	size_t nodes4_live = 0;		  // 4-wide nodes in use: all mesh trees + the top-level tree
 	// the primary wave's camera-ordered copy of d_nodes4f (primary_order.h): same size, same indexing.  It holds
 	// the order for camera position ord_cam (bits) of table version ord_version; a render call whose primary wave wants it and finds it
-	// stale rewrites it on the main stream in front of its sub-batches, which wait for ev_order
+	// stale rewrites it on the main stream in front of its sub-batches, which wait for that (order_pub)
 	int primary_order = -1; // RFWHIP_PRIMARY_ORDER as the context was created: 0 never, 1 wherever the packet form runs, else by call size
 	DevBuf d_nodes4f_ord;
 	std::vector<OrderRange> ord_ranges; // the trees that have ONE origin, as the last rfwhip_update laid them out (the rest is copied)
 	unsigned long long nodes4f_version = 0, ord_version = 0; // nodes4f_version: rewrites of d_nodes4f
 	bool ord_valid = false;
 	uint32_t ord_cam[3] = {0, 0, 0};
-	dm::event_t ev_order;
-	uint64_t order_serial = 0, order_seen[MAX_SUB] = {};
-	bool ord_reader[MAX_SUB] = {}; // a primary wave of this sub-batch slot has read the table since its last rewrite
+	Published order_pub;
 	// the primary wave's entry snapshot (primary_entry.h): one record per 64-slot group of one sample group, for the
 	// view, frame layout and ordered table of ent_key; rewritten like the ordered table, on the main stream behind the ordering pass
 	int primary_entry = -1; // setting: 0 never, 1 wherever the ordered table is used without a lens, -1 where the pass also pays (ensure_primary_entry)
@@ -404,9 +499,7 @@ struct rfwhip_context
 	DevBuf d_primary_entry;
 	bool ent_valid = false;
 	uint32_t ent_key[32] = {};
-	dm::event_t ev_entry;
-	uint64_t entry_serial = 0, entry_seen[MAX_SUB] = {};
-	bool ent_reader[MAX_SUB] = {};
+	Published entry_pub;
 	DevBuf d_nodes, d_nodes4, d_nodes4_src, d_tri_verts, d_tri_shade, d_tri_uv, d_tlas_prims, d_instances;
 	size_t blas_nodes4 = 0, node4_capacity = 0; // d_nodes4 = [all BLAS 4-wide nodes | TLAS 4-wide nodes | spare]
 	DevBuf d_materials, d_textures, d_tex_u32, d_tex_f4, d_sky, d_area, d_point, d_spot, d_dir;
@@ -429,8 +522,8 @@ struct rfwhip_context
 	int sky_table = 0;
 	int sky_table_by = -1; // the sky_table value d_sky_alias was built with (-1: none)
 	rtk::SkyTabRecord sky_record = {0.0, 0, 0, 0, 0, {0, 0}};
-	float sl_kind_ms[9] = {};		  // family KF_SKYLOAD by kernel: planes, texels, weights, total, scan_block, scan_super, scan_top,
-	uint32_t sl_kind_launches[9] = {}; // scan_apply, assign (stage_timing = 1; the read-only setting sky_load_time)
+	KindTimes skyload_times{9};	 // family KF_SKYLOAD by kernel: planes, texels, weights, total, scan_block, scan_super, scan_top,
+								 // scan_apply, assign (the read-only setting sky_load_time)
 	rt::SkyView sky_view{};		 // pick == 0: the default kernels run
 	bool sky_stale = false;		 // a sky setting changed since: the next render (or update) refreshes the view
 	// light sampling (light_tree.h): 0 reference, 1 linear, 2 tree; the tree of the lights of the last rfwhip_set_lights
@@ -448,8 +541,6 @@ struct rfwhip_context
 	unsigned long long meter_serial = 0;
 	bool meter_manual_stale = true;		   // manual mode: the record's E is not (yet) exp2(display_exposure_ev)
 	float meter_manual_E = 1.0f;		   // ... the value the next exposed display uploads (kept here: the copy's source)
-	dm::event_t ev_meter;				   // behind the last step enqueued on a caller's stream (rfwhip_display_stream)
-	bool ev_meter_ready = false, meter_pending = false;
 	// bloom (bloom.h): the display_bloom* settings; d_bloom_pyr = the levels 1 .. 8 of the target's pyramid, one behind the other,
 	// d_bloom_out = the image the display kernel reads, d_bloom_one = a float 1 (the E of an unexposed display) — allocated when the
 	// setting is first on with a render target.  bloom_ran: the levels of the last chain (0: none since rfwhip_init)
@@ -457,11 +548,7 @@ struct rfwhip_context
 	float bloom_intensity = 0.2f, bloom_threshold = 1.0f, bloom_knee = 0.5f, bloom_scatter = 0.7f;
 	DevBuf d_bloom_pyr, d_bloom_out, d_bloom_one;
 	uint32_t bloom_ran = 0;
-	float bloom_kind_ms[4] = {};		   // family KF_BLOOM by kernel: k_bloom_down0, k_bloom_down, k_bloom_up, k_bloom_apply ...
-	uint32_t bloom_kind_launches[4] = {}; // ... (stage_timing = 1; the read-only setting display_bloom_time)
-	dm::event_t ev_bloom;			  // behind the last chain and the display kernel that read its image
-	void *bloom_stream = nullptr;	  // ... the stream they ran on
-	bool ev_bloom_ready = false, bloom_marked = false, bloom_pending = false;
+	KindTimes bloom_times{4}; // family KF_BLOOM by kernel: k_bloom_down0, k_bloom_down, k_bloom_up, k_bloom_apply (display_bloom_time)
 	// colour grading and dither (display_grade.h): the display_grade* settings; grade_wb = M_wb of the temperature, built in double;
 	// lut_host = the LUT as it was set (n^3 triples), d_grade_lut = its float4 copy, uploaded when it is set
 	int grade_on = 0, grade_dither = 0;
@@ -470,8 +557,6 @@ struct rfwhip_context
 	std::vector<float> lut_host;
 	uint32_t lut_n = 0;
 	DevBuf d_grade_lut;
-	dm::event_t ev_grade; // behind the last graded display kernel that read the LUT on a caller's stream
-	bool ev_grade_ready = false, grade_pending = false;
 	// baseline JPEG (display_jpeg.h): the display_jpeg_* settings; every buffer is allocated by the first encode: d_jpeg_tab = the
 	// constant tables, d_jpeg_coef = the quantised blocks, d_jpeg_slots = the intervals' stuffed bytes, d_jpeg_counts / _offsets = the
 	// interval tables, d_jpeg_rec / d_jpeg_out = the record and the stream of the calls that read back themselves
@@ -479,11 +564,7 @@ struct rfwhip_context
 	DevBuf d_jpeg_tab, d_jpeg_coef, d_jpeg_slots, d_jpeg_counts, d_jpeg_offsets, d_jpeg_rec, d_jpeg_out;
 	rtk::JpegRecord jpeg_rec_host = {0, 0, 0, 0, 0, 0, 0, 0}; // the last record this library read back
 	uint32_t jpeg_coef_blocks = 0;						   // blocks of the last encode (rfwhip_read_jpeg_coefficients)
-	float jpeg_kind_ms[4] = {};			 // family KF_JPEG by kernel: k_jpeg_blocks, k_jpeg_entropy, k_jpeg_offsets, k_jpeg_pack ...
-	uint32_t jpeg_kind_launches[4] = {}; // ... (stage_timing = 1; the read-only setting display_jpeg_time)
-	dm::event_t ev_jpeg;				 // behind the last encode: its stream is jpeg_stream (another stream waits for it: one scratch)
-	void *jpeg_stream = nullptr;
-	bool ev_jpeg_ready = false, jpeg_pending = false;
+	KindTimes jpeg_times{4}; // family KF_JPEG by kernel: k_jpeg_blocks, k_jpeg_entropy, k_jpeg_offsets, k_jpeg_pack (display_jpeg_time)
 	// image textures (texture_decode.h): texture_entropy = 0 auto | 1 host | 2 device; the scratch of a decode, allocated by the first
 	// one (the stream, the intervals' ranges, the tables, the coefficients, the intervals' flags, the components' planes, the mip
 	// tiles' alpha counts, an RGBA8 source, the sRGB table, the image of rfwhip_decode_image); d_td_rec: a record per texture
@@ -494,8 +575,7 @@ struct rfwhip_context
 	uint32_t td_coef_blocks = 0;			// blocks of the last decode (rfwhip_read_texture_coefficients)
 	rtk::TexRecord td_hook_record = {0, 0, 0, 0, 0, 0, 0, 0}; // of the last rfwhip_decode_image (rfwhip_get_texture_decode, index -1)
 	bool td_hook_ran = false;
-	float td_kind_ms[6] = {};				// family KF_TEXDEC by kernel: zero, entropy, idct, color, mips, finish ...
-	uint32_t td_kind_launches[6] = {};		// ... (stage_timing = 1; the read-only setting texture_decode_time)
+	KindTimes texdec_times{6}; // family KF_TEXDEC by kernel: zero, entropy, idct, color, mips, finish (texture_decode_time)
 	// the noise estimate (noise.h): d_noise = two moments per local pixel, allocated while noise_estimate is on.  noise_live: the
 	// moments cover every sample of the accumulator (the setting was on at the last RESET / rfwhip_init and ever since)
 	int noise_estimate = 0;
@@ -510,11 +590,10 @@ struct rfwhip_context
 	bool adaptive_live = false;
 	uint32_t adaptive_calls = 0; // render calls since the RESET
 	DevBuf d_ad_n, d_ad_active, d_ad_mask;
-	// the mask changed on the main stream (RESET, a decision call): ev_adaptive is recorded behind it, and a sub-batch stream that has
-	// not waited for that record yet (adaptive_seen[i] != adaptive_serial) does so before its next primary wave
-	dm::event_t ev_adaptive;
+	// the mask changed on the main stream (RESET, a decision call): it is published behind that, and a sub-batch stream acquires it
+	// before its next primary wave.  No reader is noted: a decision call rewrites it behind its own epilogue on the main stream
+	Published adaptive_pub;
 	bool adaptive_mask_moved = false;
-	uint64_t adaptive_serial = 0, adaptive_seen[MAX_SUB] = {};
 	DevBuf d_lt_nodes, d_lt_paths; // allocated only while light_sampling is tree
 	rt::LightTreeView lt_view{};   // nodes == nullptr: linear (or no light with a position)
 	bool lt_stale = false;		   // the setting changed since: the next render (or update) builds the tree
@@ -559,9 +638,31 @@ struct rfwhip_context
 	uint32_t kernel_launches[KF_COUNT] = {};
 	rfwhip_render_stats stats;
 	std::chrono::steady_clock::time_point render_t0;
-	bool render_pending = false;
+	bool render_in_flight = false; // rfwhip_render since the last rfwhip_wait
 	rfwhip_counters totals;
+	KindTimes *kind_times(int family) // the families that are timed by kernel
+	{
+		switch (family)
+		{
+		case KF_BLOOM: return &bloom_times;
+		case KF_JPEG: return &jpeg_times;
+		case KF_TEXDEC: return &texdec_times;
+		case KF_SKYLOAD: return &skyload_times;
+		default: return nullptr;
+		}
+	}
 };
+
+int Published::before_rewrite(rfwhip_context *c)
+{
+	for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
+		if (reader[i])
+		{
+			RF_TRY(dm::stream_wait_event(c->stream, c->ev_sub_done[i]));
+			reader[i] = false;
+		}
+	return 0;
+}
 
 // =================================================================================================================
 // small math
@@ -668,6 +769,7 @@ extern "C" int rfwhip_create(int device_ordinal, int rank, int world, rfwhip_con
 	RF_TRY(dm::init(device_ordinal, &cus));
 	rfwhip_context *c = new rfwhip_context();
 	c->device = device_ordinal, c->rank = rank, c->world = world, c->cus = cus;
+	c->marks[MK_PRESENT].timed = c->marks[MK_DENOISE].timed = true;
 	if (const char *e = getenv("RFWHIP_PRIMARY_ORDER")) // (an environment variable, read once per context: not a setting)
 		c->primary_order = e[0] == '0' && !e[1] ? 0 : (e[0] == '1' && !e[1] ? 1 : -1);
 	rtk::set_device_cus(cus);
@@ -746,19 +848,13 @@ static void free_all(rfwhip_context *c)
 		b->free_();
 	c->noise_live = false, c->adaptive_live = false;
 	c->ord_valid = false, c->ent_valid = false;
-	c->meter_have = false, c->meter_manual_stale = true, c->meter_pending = false;
-	if (c->ev_meter_ready)
-		dm::event_destroy(c->ev_meter), c->ev_meter_ready = false;
-	c->bloom_ran = 0, c->bloom_marked = false, c->bloom_pending = false, c->bloom_stream = nullptr;
-	if (c->ev_bloom_ready)
-		dm::event_destroy(c->ev_bloom), c->ev_bloom_ready = false;
-	c->lut_host.clear(), c->lut_n = 0, c->grade_pending = false;
-	if (c->ev_grade_ready)
-		dm::event_destroy(c->ev_grade), c->ev_grade_ready = false;
+	for (StreamMark &m : c->marks)
+		m.destroy();
+	c->meter_have = false, c->meter_manual_stale = true;
+	c->bloom_ran = 0;
+	c->lut_host.clear(), c->lut_n = 0;
 	c->td_records.clear(), c->tex_desc_host.clear(), c->td_coef_blocks = 0;
-	c->jpeg_pending = false, c->jpeg_stream = nullptr, c->jpeg_coef_blocks = 0;
-	if (c->ev_jpeg_ready)
-		dm::event_destroy(c->ev_jpeg), c->ev_jpeg_ready = false;
+	c->jpeg_coef_blocks = 0;
 	c->guides_valid = false;
 	dn_clear_history(c);
 	c->dn_inst_ver_stale = true;
@@ -772,15 +868,15 @@ static void free_all(rfwhip_context *c)
 		dm::event_destroy(c->ev_prologue);
 		for (int r = 0; r < rfwhip_context::MAX_RING; r++)
 			dm::event_destroy(c->ev_resolve[r]);
-		dm::event_destroy(c->ev_present_in), dm::event_destroy(c->ev_present_out), dm::event_destroy(c->ev_dn);
-		dm::event_destroy(c->ev_adaptive), dm::event_destroy(c->ev_order), dm::event_destroy(c->ev_entry);
+		dm::event_destroy(c->ev_present_in);
+		dm::event_destroy(c->adaptive_pub.ev), dm::event_destroy(c->order_pub.ev), dm::event_destroy(c->entry_pub.ev);
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			dm::event_destroy(c->ev_sub_done[i]), dm::event_destroy(c->ev_conn_last[i]);
 			for (int d = 0; d < rt::MAX_DEPTH_SLOTS; d++)
 				dm::event_destroy(c->ev_shade[i][d]), dm::event_destroy(c->ev_conn[i][d]);
 		}
-		c->events_ready = false, c->present_pending = false, c->dn_pending = false;
+		c->events_ready = false;
 	}
 	for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 	{
@@ -2714,38 +2810,10 @@ static int sync_all(rfwhip_context *c)
 			RF_TRY(dm::sync(c->conn_stream[i]));
 	}
 	RF_TRY(dm::sync(c->stream));
-	if (c->present_pending)
-	{
-		// a present enqueued on the CALLER's stream (rfwhip_read_local_framebuffer_stream) still reads the accumulator:
-		// resize, cleanup and the scene setters must not free or rewrite anything under it
-		RF_TRY(dm::event_sync(c->ev_present_out));
-		c->present_pending = false;
-	}
-	if (c->dn_pending) // (a denoise on a gather stream reads the scene and the guides)
-	{
-		RF_TRY(dm::event_sync(c->ev_dn));
-		c->dn_pending = false;
-	}
-	if (c->meter_pending) // (a meter step on a caller's stream writes the record and the histogram)
-	{
-		RF_TRY(dm::event_sync(c->ev_meter));
-		c->meter_pending = false;
-	}
-	if (c->bloom_pending) // (a bloom chain on a caller's stream writes the pyramid and the bloomed image)
-	{
-		RF_TRY(dm::event_sync(c->ev_bloom));
-		c->bloom_pending = false;
-	}
-	if (c->grade_pending) // (a graded display kernel on a caller's stream reads the LUT)
-	{
-		RF_TRY(dm::event_sync(c->ev_grade));
-		c->grade_pending = false;
-	}
-	if (c->jpeg_pending) // (an encode on a caller's stream writes the JPEG scratch)
-	{
-		RF_TRY(dm::event_sync(c->ev_jpeg));
-		c->jpeg_pending = false;
-	}
+	// what this context enqueued on a CALLER's stream still reads or writes its memory (MarkId says what): resize, cleanup and the
+	// scene setters must not free or rewrite anything under it
+	for (StreamMark &m : c->marks)
+		RF_TRY(m.sync());
 	return 0;
 }
 
@@ -2757,11 +2825,9 @@ static int ensure_sub_batches(rfwhip_context *c, int subs)
 		for (int r = 0; r < rfwhip_context::MAX_RING; r++)
 			RF_TRY(dm::event_create(&c->ev_resolve[r]));
 		RF_TRY(dm::event_create(&c->ev_present_in));
-		RF_TRY(dm::event_create(&c->ev_present_out));
-		RF_TRY(dm::event_create(&c->ev_dn));
-		RF_TRY(dm::event_create(&c->ev_adaptive));
-		RF_TRY(dm::event_create(&c->ev_order));
-		RF_TRY(dm::event_create(&c->ev_entry));
+		RF_TRY(dm::event_create(&c->adaptive_pub.ev));
+		RF_TRY(dm::event_create(&c->order_pub.ev));
+		RF_TRY(dm::event_create(&c->entry_pub.ev));
 		for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
 		{
 			RF_TRY(dm::event_create(&c->ev_sub_done[i]));
@@ -2847,12 +2913,7 @@ static int ensure_primary_order(rfwhip_context *c, const rt::f3 &pos)
 	if (bytes > c->d_nodes4f_ord.cap)
 		RF_TRY(sync_all(c)); // (the buffer moves)
 	RF_TRY(c->d_nodes4f_ord.ensure(bytes));
-	for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
-		if (c->ord_reader[i])
-		{
-			RF_TRY(dm::stream_wait_event(c->stream, c->ev_sub_done[i]));
-			c->ord_reader[i] = false;
-		}
+	RF_TRY(c->order_pub.before_rewrite(c));
 	const rt::Node4f *in = c->d_nodes4f.as<rt::Node4f>();
 	rt::Node4f *out = c->d_nodes4f_ord.as<rt::Node4f>();
 	StageTimer t(c, KF_PRIMARY_ORDER, -1);
@@ -2896,8 +2957,7 @@ static int ensure_primary_order(rfwhip_context *c, const rt::f3 &pos)
 	t.stop(0);
 	c->kernel_launches[KF_PRIMARY_ORDER]++;
 	RF_TRY(dm::last_launch_error());
-	RF_TRY(dm::event_record(c->ev_order, c->stream));
-	c->order_serial++;
+	RF_TRY(c->order_pub.publish(c->stream));
 	c->ord_valid = true, c->ord_version = c->nodes4f_version;
 	memcpy(c->ord_cam, bits, sizeof(bits));
 	return 0;
@@ -2929,7 +2989,7 @@ static int ensure_primary_entry(rfwhip_context *c, const rtk::Params &base, size
 	memcpy(&key[12], &base.fr.inv_w, 4), memcpy(&key[13], &base.fr.inv_h, 4);
 	key[14] = base.fr.W, key[15] = base.fr.H, key[16] = base.fr.tiles_x, key[17] = base.fr.slots, key[18] = base.fr.sgroup_log2;
 	key[19] = base.fr.local_rows, key[20] = base.fr.rank, key[21] = base.fr.world;
-	key[22] = (uint32_t)c->order_serial, key[23] = (uint32_t)(c->order_serial >> 32);
+	key[22] = (uint32_t)c->order_pub.serial, key[23] = (uint32_t)(c->order_pub.serial >> 32);
 	key[24] = base.sc.instance_count ? base.sc.tlas_root_entry : rtk::PRIMARY_ENTRY_NO_ROOT;
 	const bool at_rest = !memcmp(key, c->ent_last_key, sizeof(key));
 	memcpy(c->ent_last_key, key, sizeof(key));
@@ -2946,19 +3006,13 @@ static int ensure_primary_entry(rfwhip_context *c, const rtk::Params &base, size
 	if (bytes > c->d_primary_entry.cap)
 		RF_TRY(sync_all(c)); // (the buffer moves)
 	RF_TRY(c->d_primary_entry.ensure(bytes));
-	for (int i = 0; i < rfwhip_context::MAX_SUB; i++)
-		if (c->ent_reader[i])
-		{
-			RF_TRY(dm::stream_wait_event(c->stream, c->ev_sub_done[i]));
-			c->ent_reader[i] = false;
-		}
+	RF_TRY(c->entry_pub.before_rewrite(c));
 	StageTimer t(c, KF_PRIMARY_ENTRY, -1);
 	rtk::launch_primary_entry(c->d_nodes4f_ord.as<rt::Node4f>(), key[24], base.cam, base.fr, c->d_primary_entry.as<uint32_t>(), groups, c->stream);
 	t.stop(0);
 	c->kernel_launches[KF_PRIMARY_ENTRY]++;
 	RF_TRY(dm::last_launch_error());
-	RF_TRY(dm::event_record(c->ev_entry, c->stream));
-	c->entry_serial++;
+	RF_TRY(c->entry_pub.publish(c->stream));
 	c->ent_valid = true;
 	memcpy(c->ent_key, key, sizeof(key));
 	return 0;
@@ -3062,19 +3116,20 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 		break;
 	}
 	RF_TRY(ensure_sub_batches(c, alternate ? ring : subs));
-	const bool pipelined = c->render_pending; // the caller enqueues calls without waiting for them in between
-	if (!c->render_pending)
+	const bool pipelined = c->render_in_flight; // the caller enqueues calls without waiting for them in between
+	if (!c->render_in_flight)
 	{
 		c->render_t0 = std::chrono::steady_clock::now();
-		c->render_pending = true;
+		c->render_in_flight = true;
 	}
 	void *s0 = c->stream;
 	// ---- prologue on stream 0 ----
-	if (c->present_pending)
+	if (c->marks[MK_PRESENT].pending)
 	{
-		// a present enqueued on the caller's stream (rfwhip_read_local_framebuffer_stream) still reads the accumulator
-		RF_TRY(dm::stream_wait_event(s0, c->ev_present_out));
-		c->present_pending = false;
+		// a present enqueued on the caller's stream (rfwhip_read_local_framebuffer_stream) still reads the accumulator: the main
+		// stream runs behind it from here on, so whoever waits for the main stream has waited for the present
+		RF_TRY(c->marks[MK_PRESENT].wait_on(s0));
+		c->marks[MK_PRESENT].pending = false;
 	}
 	if (status == RFWHIP_RESET)
 	{
@@ -3088,8 +3143,8 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 	}
 	if (c->adaptive_live && c->adaptive_mask_moved)
 	{
-		RF_TRY(dm::event_record(c->ev_adaptive, s0));
-		c->adaptive_serial++, c->adaptive_mask_moved = false;
+		RF_TRY(c->adaptive_pub.publish(s0));
+		c->adaptive_mask_moved = false;
 	}
 	const rtk::AdaptiveView ad = c->adaptive_live ? adaptive_view(c) : rtk::AdaptiveView{};
 	const uint32_t packets = (c->W / 4u) * (c->H / 2u);
@@ -3175,21 +3230,12 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 			RF_TRY(dm::stream_wait_event(s, c->ev_resolve[prev]));
 		if (c->conn_used[i]) // the previous call's connection waves still use this sub-batch's counters and shadow buffers
 			RF_TRY(dm::stream_wait_event(s, c->ev_conn_last[i]));
-		if (c->adaptive_live && c->adaptive_seen[i] != c->adaptive_serial) // the mask this call reads: the state after the previous call
-		{
-			RF_TRY(dm::stream_wait_event(s, c->ev_adaptive));
-			c->adaptive_seen[i] = c->adaptive_serial;
-		}
-		if (ordered && c->order_seen[i] != c->order_serial) // the ordered table was rewritten since this stream last read it
-		{
-			RF_TRY(dm::stream_wait_event(s, c->ev_order));
-			c->order_seen[i] = c->order_serial;
-		}
-		if (entry && c->entry_seen[i] != c->entry_serial) // ... and so were the snapshot's records
-		{
-			RF_TRY(dm::stream_wait_event(s, c->ev_entry));
-			c->entry_seen[i] = c->entry_serial;
-		}
+		if (c->adaptive_live) // the mask this call reads: the state after the previous call
+			RF_TRY(c->adaptive_pub.acquire(i, s));
+		if (ordered) // the ordered table, if it was rewritten since this stream last read it
+			RF_TRY(c->order_pub.acquire(i, s));
+		if (entry) // ... and the snapshot's records
+			RF_TRY(c->entry_pub.acquire(i, s));
 		rtk::Params p = base;
 		const size_t off_rad = (size_t)c->fr.slots * s_begin; // this sub-batch's slice of the radiance buffers of the call
 		const size_t off = alternate ? (paths + pad) * par : off_rad + (size_t)k * pad; // and of every per-ray buffer (padded)
@@ -3261,9 +3307,9 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 				else
 					rtk::launch_extend(p, d == 0 ? rtk::GEN_PT : rtk::GEN_BUFFER, count, d == 0 ? n : n_ext, s, d == 0 ? ordered : nullptr);
 				if (d == 0 && ordered)
-					c->ord_reader[i] = true;
+					c->order_pub.read_by(i);
 				if (d == 0 && entry)
-					c->ent_reader[i] = true;
+					c->entry_pub.read_by(i);
 				pa_pending = false;
 				te.stop();
 				if (side && d >= 2 && d < c->max_depth) // connect(d - 2) read the buffers shade(d) is about to write
@@ -3374,8 +3420,7 @@ extern "C" int rfwhip_render(rfwhip_context *c, const rfwhip_camera *cam, int st
 			rtk::launch_noise_metric_adaptive(noise_view(c, c->d_noise.as<float>(), c->W, c->H, c->fr.local_rows, (uint32_t)c->rank, (uint32_t)c->world, 2u), ad.n_tile, false, s0);
 			tn.stop();
 			rtk::launch_adaptive_step(ad, 0u, true, s0);
-			RF_TRY(dm::event_record(c->ev_adaptive, s0));
-			c->adaptive_serial++;
+			RF_TRY(c->adaptive_pub.publish(s0));
 		}
 	}
 	c->resolve_recorded[par] = true;
@@ -3396,16 +3441,9 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 	// every render call ends with its resolve on the main stream, behind the events of all its sub-batch and connection
 	// streams: the main stream alone tells when the enqueued frames are done (one synchronisation instead of up to 17)
 	RF_TRY(dm::sync(c->stream));
-	if (c->present_pending)
-	{
-		RF_TRY(dm::event_sync(c->ev_present_out));
-		c->present_pending = false;
-	}
-	if (c->dn_pending && c->stage_timing) // (the denoiser's timed spans on a gather stream are read below)
-	{
-		RF_TRY(dm::event_sync(c->ev_dn));
-		c->dn_pending = false;
-	}
+	RF_TRY(c->marks[MK_PRESENT].sync());
+	if (c->stage_timing) // (the denoiser's timed spans on a gather stream are read below)
+		RF_TRY(c->marks[MK_DENOISE].sync());
 	// wave counters of the last frame, summed over its sub-batches.  A sub-batch's connection wave of depth d ran only
 	// if its depth d + 1 had extension rays (k_connect / k_trace_stream: connection_count)
 	rt::WaveCounters wc;
@@ -3448,8 +3486,8 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 			for (int d = 0; d < rt::MAX_DEPTH_SLOTS; d++)
 				for (int k = 0; k < 2; k++)
 				{
-					sums[d][k] += w.fused_ticks[d][k] - c->fused_ticks_seen[slot][d][k];
-					c->fused_ticks_seen[slot][d][k] = w.fused_ticks[d][k];
+					sums[d][k] += w.fused_ticks[d][k] - c->fused_ticks_at_wait[slot][d][k];
+					c->fused_ticks_at_wait[slot][d][k] = w.fused_ticks[d][k];
 				}
 		};
 		fold(c->subs_first, wc0);
@@ -3460,8 +3498,8 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 		// run, + 8 %; atrium (an interior lit from all sides) 5.5, + 0.6 %; the threshold, half of the 16 bins, is beyond what was measured
 		unsigned long long runs = 0, bins = 0;
 		auto fold_sp = [&](int slot, const rt::WaveCounters &w) {
-			runs += w.sp_runs - c->sp_seen[slot][0], bins += w.sp_bins - c->sp_seen[slot][1];
-			c->sp_seen[slot][0] = w.sp_runs, c->sp_seen[slot][1] = w.sp_bins;
+			runs += w.sp_runs - c->sp_at_wait[slot][0], bins += w.sp_bins - c->sp_at_wait[slot][1];
+			c->sp_at_wait[slot][0] = w.sp_runs, c->sp_at_wait[slot][1] = w.sp_bins;
 		};
 		fold_sp(c->subs_first, wc0);
 		for (size_t k = 0; k < more.size(); k++)
@@ -3530,32 +3568,19 @@ extern "C" int rfwhip_wait(rfwhip_context *c)
 		case KF_FINALIZE:
 			st.finalizeTime += ms;
 			break;
-		case KF_BLOOM:
-			if (sp.depth >= 0 && sp.depth < 4)
-				c->bloom_kind_ms[sp.depth] += ms, c->bloom_kind_launches[sp.depth]++;
-			break;
-		case KF_JPEG:
-			if (sp.depth >= 0 && sp.depth < 4)
-				c->jpeg_kind_ms[sp.depth] += ms, c->jpeg_kind_launches[sp.depth]++;
-			break;
-		case KF_TEXDEC:
-			if (sp.depth >= 0 && sp.depth < 6)
-				c->td_kind_ms[sp.depth] += ms, c->td_kind_launches[sp.depth]++;
-			break;
-		case KF_SKYLOAD:
-			if (sp.depth >= 0 && sp.depth < 9)
-				c->sl_kind_ms[sp.depth] += ms, c->sl_kind_launches[sp.depth]++;
-			break;
 		default:
+			if (KindTimes *kt = c->kind_times(sp.family)) // (the span's depth is the kernel's index in its family)
+				if (sp.depth >= 0 && sp.depth < kt->count)
+					kt->add(sp.depth, ms);
 			break;
 		}
 	}
 	c->spans.clear();
 	c->events_used = 0;
-	if (c->render_pending)
+	if (c->render_in_flight)
 	{
 		st.renderTime = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - c->render_t0).count();
-		c->render_pending = false;
+		c->render_in_flight = false;
 	}
 	// (reported last: the bookkeeping above is complete, so the context stays usable after the error)
 	if (stack_overflow)
@@ -3846,11 +3871,9 @@ int rfwhip_internal_denoise_stream(rfwhip_context *c, void *rgba_device, void *h
 	CTX_ENTER(c);
 	if (!c->denoise || !c->have_last_cam) // (nothing rendered yet: the accumulator is empty)
 		return RFWHIP_OK;
-	RF_TRY(ensure_sub_batches(c, 1)); // creates the hand-off events
+	RF_TRY(ensure_sub_batches(c, 1));
 	RF_TRY(dn_filter(c, (f4 *)rgba_device, (f4 *)rgba_device, hip_stream, true));
-	RF_TRY(dm::event_record(c->ev_dn, hip_stream));
-	c->dn_pending = true;
-	return RFWHIP_OK;
+	return c->marks[MK_DENOISE].record(hip_stream, true);
 }
 
 extern "C" int rfwhip_read_framebuffer_device(rfwhip_context *c, void *rgba_device)
@@ -3927,16 +3950,7 @@ static rtk::MeterParams meter_params(const rfwhip_context *c)
 // behind work on the record enqueued on `stream`: a caller's stream is remembered by an event (rfwhip_get_meter, sync_all)
 static int meter_mark(rfwhip_context *c, void *stream)
 {
-	if (stream == c->stream)
-		return 0;
-	if (!c->ev_meter_ready)
-	{
-		RF_TRY(dm::event_create(&c->ev_meter, false));
-		c->ev_meter_ready = true;
-	}
-	RF_TRY(dm::event_record(c->ev_meter, stream));
-	c->meter_pending = true;
-	return 0;
+	return stream == c->stream ? 0 : c->marks[MK_METER].record(stream, true);
 }
 // the reduce on `records` partial records in d_meter_part, enqueued on `stream`
 static int meter_reduce(rfwhip_context *c, uint32_t records, void *stream)
@@ -4009,8 +4023,8 @@ static int bloom_ensure(rfwhip_context *c)
 static int bloom_chain(rfwhip_context *c, const f4 *in, const float *E, void *stream)
 {
 	RF_TRY(bloom_ensure(c));
-	if (c->bloom_marked && c->bloom_stream != stream)
-		RF_TRY(dm::stream_wait_event(stream, c->ev_bloom));
+	if (c->marks[MK_BLOOM].stream != stream)
+		RF_TRY(c->marks[MK_BLOOM].wait_on(stream)); // (nothing before the first record)
 	rtk::BloomParams b;
 	b.intensity = c->bloom_intensity, b.threshold = c->bloom_threshold, b.knee = c->bloom_knee, b.scatter = c->bloom_scatter;
 	const uint32_t n = rtk::bloom_levels(c->W, c->H, (uint32_t)c->bloom_levels);
@@ -4049,18 +4063,9 @@ static int bloom_chain(rfwhip_context *c, const f4 *in, const float *E, void *st
 	c->bloom_ran = n;
 	return dm::last_launch_error();
 }
-// behind the last reader of d_bloom_out on `stream`
-static int bloom_mark(rfwhip_context *c, void *stream)
-{
-	if (!c->ev_bloom_ready)
-	{
-		RF_TRY(dm::event_create(&c->ev_bloom, false));
-		c->ev_bloom_ready = true;
-	}
-	RF_TRY(dm::event_record(c->ev_bloom, stream));
-	c->bloom_marked = true, c->bloom_stream = stream, c->bloom_pending = stream != c->stream;
-	return 0;
-}
+// behind the last reader of d_bloom_out on `stream` (the main stream too: the next chain may run elsewhere; sync_all waits for the
+// main stream itself)
+static int bloom_mark(rfwhip_context *c, void *stream) { return c->marks[MK_BLOOM].record(stream, stream != c->stream); }
 
 // ---- colour grading and dither (settings "display_grade*", "display_wb_temperature", "display_dither"; work items: display_grade.h) ----
 static void mat3_mul(const double a[9], const double b[9], double o[9])
@@ -4179,16 +4184,8 @@ static int display_enqueue(rfwhip_context *c, const f4 *in, void *out, float bri
 		t.stop(1);
 	}
 	RF_TRY(dm::last_launch_error());
-	if (c->grade_on && c->lut_n && stream != c->stream)
-	{
-		if (!c->ev_grade_ready)
-		{
-			RF_TRY(dm::event_create(&c->ev_grade, false));
-			c->ev_grade_ready = true;
-		}
-		RF_TRY(dm::event_record(c->ev_grade, stream));
-		c->grade_pending = true;
-	}
+	if (c->grade_on && c->lut_n && stream != c->stream) // (the kernel read the LUT on a caller's stream)
+		RF_TRY(c->marks[MK_GRADE].record(stream, true));
 	return c->bloom_on ? bloom_mark(c, stream) : 0;
 }
 // brightness and contrast of the presented image: the camera of the last render; before the first one the reference's defaults
@@ -4405,11 +4402,8 @@ static int jpeg_enqueue(rfwhip_context *c, const void *rgba8, void *out, size_t 
 	if (jpeg_bound(v) + 3ull * v.intervals > 0xFFFFFFFFull)
 		return set_error(RFWHIP_ERR_UNSUPPORTED, "display_jpeg: a %u x %u target is too large for the encoder's 32-bit offsets", c->W, c->H);
 	// one scratch: an encode on another stream has to be through with it
-	if (c->jpeg_pending && c->jpeg_stream != stream)
-	{
-		RF_TRY(dm::event_sync(c->ev_jpeg));
-		c->jpeg_pending = false;
-	}
+	if (c->marks[MK_JPEG].stream != stream)
+		RF_TRY(c->marks[MK_JPEG].sync());
 	if (!c->d_jpeg_tab.p)
 	{
 		rtk::JpegTables t;
@@ -4445,14 +4439,7 @@ static int jpeg_enqueue(rfwhip_context *c, const void *rgba8, void *out, size_t 
 		RF_TRY(dm::last_launch_error());
 	}
 	c->jpeg_coef_blocks = v.blocks;
-	if (!c->ev_jpeg_ready)
-	{
-		RF_TRY(dm::event_create(&c->ev_jpeg, false));
-		c->ev_jpeg_ready = true;
-	}
-	RF_TRY(dm::event_record(c->ev_jpeg, stream));
-	c->jpeg_pending = true, c->jpeg_stream = stream;
-	return 0;
+	return c->marks[MK_JPEG].record(stream, true);
 }
 
 extern "C" int rfwhip_display_jpeg_bound(rfwhip_context *c, size_t *bytes)
@@ -4497,7 +4484,7 @@ static int jpeg_read_back(rfwhip_context *c, const char *who, void *out_host, si
 	RF_TRY(jpeg_enqueue(c, c->d_display.p, c->d_jpeg_out.p, dev_cap, c->d_jpeg_rec.p, c->stream));
 	rtk::JpegRecord r;
 	RF_TRY(dm::d2h(&r, c->d_jpeg_rec.p, sizeof(r), c->stream));
-	c->jpeg_pending = false; // (the stream is idle)
+	c->marks[MK_JPEG].pending = false; // (the stream is idle)
 	c->jpeg_rec_host = r;
 	if (bytes)
 		*bytes = r.bytes;
@@ -5655,7 +5642,7 @@ extern "C" int rfwhip_read_local_framebuffer_stream(rfwhip_context *c, void *rgb
 		return set_error(RFWHIP_ERR_INVALID_ARGUMENT, "null destination");
 	if (!c->W)
 		return set_error(RFWHIP_ERR_STATE, "no render target");
-	RF_TRY(ensure_sub_batches(c, 1)); // creates the hand-off events
+	RF_TRY(ensure_sub_batches(c, 1)); // creates ev_present_in
 	RF_TRY(dm::event_record(c->ev_present_in, c->stream));
 	RF_TRY(dm::stream_wait_event(hip_stream, c->ev_present_in));
 	rtk::Params p;
@@ -5666,9 +5653,7 @@ extern "C" int rfwhip_read_local_framebuffer_stream(rfwhip_context *c, void *rgb
 	else
 		rtk::launch_present(p, (f4 *)rgba_device, scale, 0, hip_stream);
 	RF_TRY(dm::last_launch_error());
-	RF_TRY(dm::event_record(c->ev_present_out, hip_stream));
-	c->present_pending = true;
-	return RFWHIP_OK;
+	return c->marks[MK_PRESENT].record(hip_stream, true);
 }
 
 extern "C" int rfwhip_deinterleave_stream(rfwhip_context *c, const void *gathered_device, void *rgba_device, void *hip_stream)
@@ -5876,6 +5861,17 @@ static int put(char *out, size_t cap, const char *fmt, ...)
 	vsnprintf(out, cap, fmt, ap);
 	va_end(ap);
 	return RFWHIP_OK;
+}
+// a family's table as its *_time setting prints it: the milliseconds by kernel, then the launches, one space between any two
+static int put_kind_times(char *out, size_t cap, const KindTimes &t)
+{
+	char line[640]; // (9 floats of at most 47 characters, 9 counts of at most 10, the spaces)
+	int at = 0;
+	for (int k = 0; k < t.count; k++)
+		at += snprintf(line + at, sizeof(line) - (size_t)at, "%.6f ", t.ms[k]);
+	for (int k = 0; k < t.count; k++)
+		at += snprintf(line + at, sizeof(line) - (size_t)at, k + 1 < t.count ? "%u " : "%u", t.launches[k]);
+	return put(out, cap, "%s", line);
 }
 
 #define SET [](rfwhip_context * c, const char *key, const char *value) -> int
@@ -6089,8 +6085,7 @@ static const Setting k_settings[] = {
 	 GET_INT(bloom_levels), false},
 	// (read-only, stage_timing = 1) family 12 by kernel since its last reset: the milliseconds of k_bloom_down0, k_bloom_down,
 	// k_bloom_up, k_bloom_apply, then their launches
-	{"display_bloom_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %u %u %u %u", c->bloom_kind_ms[0], c->bloom_kind_ms[1], c->bloom_kind_ms[2], c->bloom_kind_ms[3],
-													  c->bloom_kind_launches[0], c->bloom_kind_launches[1], c->bloom_kind_launches[2], c->bloom_kind_launches[3]); }, false},
+	{"display_bloom_time", nullptr, GET { return put_kind_times(out, cap, c->bloom_times); }, false},
 	// colour grading and dither (display_grade.h): k_display_graded in place of the display kernel
 	{"display_grade", SET {
 		 bool on;
@@ -6132,8 +6127,7 @@ static const Setting k_settings[] = {
 	{"display_jpeg_bytes", nullptr, GET { return put(out, cap, "%u", c->jpeg_rec_host.bytes); }, false},
 	// (read-only, stage_timing = 1) family 14 by kernel since its last reset: the milliseconds of k_jpeg_blocks, k_jpeg_entropy,
 	// k_jpeg_offsets, k_jpeg_pack, then their launches
-	{"display_jpeg_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %u %u %u %u", c->jpeg_kind_ms[0], c->jpeg_kind_ms[1], c->jpeg_kind_ms[2], c->jpeg_kind_ms[3],
-													 c->jpeg_kind_launches[0], c->jpeg_kind_launches[1], c->jpeg_kind_launches[2], c->jpeg_kind_launches[3]); }, false},
+	{"display_jpeg_time", nullptr, GET { return put_kind_times(out, cap, c->jpeg_times); }, false},
 	// image textures (texture_decode.h): which side decodes the entropy data; auto = the device when the stream
 	// has restart intervals, the host when it has none
 	{"texture_entropy", SET {
@@ -6145,9 +6139,7 @@ static const Setting k_settings[] = {
 	 GET { return put(out, cap, "%s", c->td_entropy == 1 ? "host" : c->td_entropy == 2 ? "device" : "auto"); }, false},
 	// (read-only, stage_timing = 1) family 15 by kernel since its last reset: the milliseconds of k_texdec_zero, k_texdec_entropy,
 	// k_texdec_idct, k_texdec_color, k_tex_mips, k_texdec_finish, then their launches
-	{"texture_decode_time", nullptr, GET { return put(out, cap, "%.6f %.6f %.6f %.6f %.6f %.6f %u %u %u %u %u %u", c->td_kind_ms[0], c->td_kind_ms[1], c->td_kind_ms[2],
-													   c->td_kind_ms[3], c->td_kind_ms[4], c->td_kind_ms[5], c->td_kind_launches[0], c->td_kind_launches[1],
-													   c->td_kind_launches[2], c->td_kind_launches[3], c->td_kind_launches[4], c->td_kind_launches[5]); }, false},
+	{"texture_decode_time", nullptr, GET { return put_kind_times(out, cap, c->texdec_times); }, false},
 	// the sky's loaders (sky_load.h): who builds the alias table of sky_sampling; a change rebuilds it
 	{"sky_table", SET {
 		 const int k = !strcmp(value, "host") ? 0 : !strcmp(value, "device") ? 1 : -1;
@@ -6160,14 +6152,7 @@ static const Setting k_settings[] = {
 	// (read-only, stage_timing = 1) family 17 by kernel since its last reset: the milliseconds of k_skyhdr_planes, k_skyhdr_texels,
 	// k_skytab_weights, k_skytab_total, k_skytab_scan_block, k_skytab_scan_super, k_skytab_scan_top, k_skytab_scan_apply,
 	// k_skytab_assign, then their launches
-	{"sky_load_time", nullptr, GET {
-		 int at = 0;
-		 char line[512];
-		 for (int k = 0; k < 9; k++)
-			 at += snprintf(line + at, sizeof(line) - (size_t)at, "%.6f ", c->sl_kind_ms[k]);
-		 for (int k = 0; k < 9; k++)
-			 at += snprintf(line + at, sizeof(line) - (size_t)at, k < 8 ? "%u " : "%u", c->sl_kind_launches[k]);
-		 return put(out, cap, "%s", line); }, false},
+	{"sky_load_time", nullptr, GET { return put_kind_times(out, cap, c->skyload_times); }, false},
 	// the noise estimate (noise.h): the moments beside the accumulator and the two definitions of the metric
 	{"noise_estimate", SET {
 		 bool on;
@@ -6329,18 +6314,8 @@ extern "C" int rfwhip_get_kernel_time(rfwhip_context *c, int which, float *ms, u
 		*launches = c->kernel_launches[which];
 	if (reset)
 		c->kernel_ms[which] = 0.0f, c->kernel_launches[which] = 0;
-	if (reset && which == KF_BLOOM)
-		for (int k = 0; k < 4; k++)
-			c->bloom_kind_ms[k] = 0.0f, c->bloom_kind_launches[k] = 0;
-	if (reset && which == KF_JPEG)
-		for (int k = 0; k < 4; k++)
-			c->jpeg_kind_ms[k] = 0.0f, c->jpeg_kind_launches[k] = 0;
-	if (reset && which == KF_TEXDEC)
-		for (int k = 0; k < 6; k++)
-			c->td_kind_ms[k] = 0.0f, c->td_kind_launches[k] = 0;
-	if (reset && which == KF_SKYLOAD)
-		for (int k = 0; k < 9; k++)
-			c->sl_kind_ms[k] = 0.0f, c->sl_kind_launches[k] = 0;
+	if (KindTimes *kt = reset ? c->kind_times(which) : nullptr)
+		kt->reset();
 	return RFWHIP_OK;
 }
 
@@ -6373,6 +6348,23 @@ extern "C" int rfwhip_read_denoise_guides(rfwhip_context *c, float *albedo, floa
 	return RFWHIP_OK;
 }
 
+// What rfwhip_read_denoise_history / _motion run the presented frame's stage once more with, from the same history into the same set
+// (the bits it wrote): the presented image in d_present, the guides, the params of last_cam, the history sets (*rd -> *wr), the
+// instance versions and the view
+static int dn_replay_setup(rfwhip_context *c, rtk::Params &p, int *rd, int *wr, rtk::DnView &d)
+{
+	RF_TRY(sync_all(c));
+	RF_TRY(c->d_present.ensure((size_t)c->W * c->H * sizeof(f4)));
+	RF_TRY(present(c, c->d_present.as<f4>(), 1));
+	RF_TRY(dn_guides(c, c->stream));
+	fill_params(c, &c->last_cam, p);
+	*wr = c->dn_hist_cur, *rd = *wr ^ 1;
+	RF_TRY(dn_inst_ver_current(c, c->stream));
+	d = dn_view(c, c->d_present.as<f4>(), c->d_present.as<f4>());
+	d.hist = dn_hist_colour(c, *wr);
+	return 0;
+}
+
 extern "C" int rfwhip_read_denoise_history(rfwhip_context *c, float *pre_rgbl, float *var, float *hist_rgbl, float *moments, float *length)
 {
 	CTX_ENTER(c);
@@ -6383,18 +6375,12 @@ extern "C" int rfwhip_read_denoise_history(rfwhip_context *c, float *pre_rgbl, f
 	if (!c->denoise || !c->dn_temporal || !c->dn_have_pres || c->frame_serial != c->dn_pres_serial)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_denoise_history: the last render has not been presented with denoise and "
 											"denoise_temporal on");
-	RF_TRY(sync_all(c));
-	// the stage of the presented frame once more, from the same history into the same set (the bits it wrote), for I~ and var
+	// the stage of the presented frame once more, for I~ and var
 	const size_t px = (size_t)c->W * c->H;
-	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
-	RF_TRY(present(c, c->d_present.as<f4>(), 1));
-	RF_TRY(dn_guides(c, c->stream));
 	rtk::Params p;
-	fill_params(c, &c->last_cam, p);
-	const int wr = c->dn_hist_cur, rd = wr ^ 1;
-	RF_TRY(dn_inst_ver_current(c, c->stream));
-	rtk::DnView d = dn_view(c, c->d_present.as<f4>(), c->d_present.as<f4>());
-	d.hist = dn_hist_colour(c, wr);
+	rtk::DnView d;
+	int rd, wr;
+	RF_TRY(dn_replay_setup(c, p, &rd, &wr, d));
 	rtk::DnMotion mv;
 	if (c->dn_motion)
 		RF_TRY(dn_motion_view(c, false, c->stream, mv));
@@ -6446,18 +6432,12 @@ extern "C" int rfwhip_read_denoise_motion(rfwhip_context *c, int32_t *state, flo
 	if (!c->denoise || !c->dn_temporal || !c->dn_motion || !c->dn_have_pres || c->frame_serial != c->dn_pres_serial)
 		return set_error(RFWHIP_ERR_STATE, "rfwhip_read_denoise_motion: the last render has not been presented with denoise, "
 											"denoise_temporal and denoise_motion on");
-	RF_TRY(sync_all(c));
-	// the stage of the presented frame once more, from the same history into the same set, with the per-pixel record written
+	// the stage of the presented frame once more, with the per-pixel record written
 	const size_t px = (size_t)c->W * c->H;
-	RF_TRY(c->d_present.ensure(px * sizeof(f4)));
-	RF_TRY(present(c, c->d_present.as<f4>(), 1));
-	RF_TRY(dn_guides(c, c->stream));
 	rtk::Params p;
-	fill_params(c, &c->last_cam, p);
-	const int wr = c->dn_hist_cur, rd = wr ^ 1;
-	RF_TRY(dn_inst_ver_current(c, c->stream));
-	rtk::DnView d = dn_view(c, c->d_present.as<f4>(), c->d_present.as<f4>());
-	d.hist = dn_hist_colour(c, wr);
+	rtk::DnView d;
+	int rd, wr;
+	RF_TRY(dn_replay_setup(c, p, &rd, &wr, d));
 	rtk::DnMotion mv;
 	RF_TRY(dn_motion_view(c, false, c->stream, mv));
 	DevBuf dump;

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import display_model as dm
+import handoff_cases as H
 
 pytestmark = pytest.mark.gpu
 
@@ -133,3 +134,14 @@ def test_one_rank_comm_gather_then_display_on_the_callers_stream(pkg, make_hip):
     ref.read_display_device(dev.data_ptr(), "rgba8")
     assert np.array_equal(dev.cpu().numpy(), ref.display("rgba8"))
     comm.destroy()
+
+
+def test_one_context_on_two_streams(pkg):
+    """tests/test_schedule.py's case of the same name on the device: a group of one runs the meter, bloom, the graded display
+    kernel and the JPEG encoder on its gather stream and on the context's own stream within every frame."""
+    scene, extra = H.scene(pkg), {"display_exposure_ev": 0.5}
+    want = H.reference(pkg, pkg.RenderContext(device=0), scene, extra, 4)
+    g = pkg._binding.RenderGroup(pkg.load_library(), "rfwhip_", [0], "peer")
+    H.setup(g, scene, extra)
+    H.one_context_two_streams(pkg, g, scene, want)
+    g.destroy()

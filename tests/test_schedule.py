@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import denoise_temporal_model as M
+import handoff_cases as H
 
 INORDER, LATE, RANDOM, EAGER = 0, 1, 2, 3
 # (eager: latest first over everything enqueued, needed by the sync point or not — a reader that a later writer must wait for)
@@ -311,6 +312,37 @@ def test_temporal_denoised_groups_under_every_schedule(pkg, make_s, lib, n, poli
     # repeated reads of an unchanged scene (the two history sets)
     assert np.array_equal(_bits(g.framebuffer()), _bits(want[-1])), (name, n, "repeated read")
     assert np.array_equal(_bits(g.framebuffer()), _bits(want[-1])), (name, n, "third read")
+    g.destroy()
+
+
+@pytest.mark.parametrize("policy", POLICIES, ids=POLICY_IDS)
+@pytest.mark.parametrize("n", [2, 3])
+def test_displayed_groups_under_every_schedule(pkg, make_s, lib, n, policy):
+    """The display stage with auto exposure, bloom, grading through a LUT, and the JPEG encoder, enqueued on the root's gather
+    stream with two frames in flight: every image and every JPEG stream is the single context's for that frame."""
+    name, pol, seed = policy
+    scene, extra = H.scene(pkg), {"display_exposure": "auto"}
+    _schedule(lib, INORDER)
+    want = H.reference(pkg, make_s(), scene, extra, 6)
+    _schedule(lib, pol, seed)
+    g = _group(pkg, lib, n)
+    H.setup(g, scene, extra)
+    H.displayed_group(pkg, g, scene, want)
+    g.destroy()
+
+
+@pytest.mark.parametrize("policy", POLICIES, ids=POLICY_IDS)
+def test_one_context_on_two_streams_under_every_schedule(pkg, make_s, lib, policy):
+    """A group of one: the meter, bloom, the graded display kernel and the encoder of one context on its gather stream and on
+    its own stream in turn (manual exposure: under `auto` a stream call and a host read step the meter differently)."""
+    name, pol, seed = policy
+    scene, extra = H.scene(pkg), {"display_exposure_ev": 0.5}
+    _schedule(lib, INORDER)
+    want = H.reference(pkg, make_s(), scene, extra, 4)
+    _schedule(lib, pol, seed)
+    g = _group(pkg, lib, 1)
+    H.setup(g, scene, extra)
+    H.one_context_two_streams(pkg, g, scene, want)
     g.destroy()
 
 
